@@ -142,10 +142,40 @@ def parse_args():
     ap.add_argument("--no-kernel-timing", action="store_true", help="do not record HIP events inside the timed region")
     ap.add_argument("--cpu-size", type=int, default=128)
     ap.add_argument("--dump-kernels", default="", help="write the full per-launch-group timing table (TSV) here")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (loss, logits, gradients, updated parameters) "
+                         "as DIR/<name>.npy (float32, seeded samples of the large arrays, at most 40 MB in all)")
     ap.add_argument("--config", default="window512", choices=["", "none", "window512"],
                     help="window512 (default at N=1): also time BASELINE configs[3] (one 512^3 volume, 128^3 windows, stride 64, 343 "
                          "windows, forward only; ~3 s) and report it under `window512`; none: skip it")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+def dump_outputs(out_dir, loss, pred0, pred1, model):
+    """--dump-outputs: what one step handed its caller, as float32 DIR/<name>.npy -- the loss, both heads' logits, and every
+    parameter's gradient and updated value (flattened and concatenated in parameters() order; dc62 is dead in the forward and
+    has no gradient).  An array longer than its cap is replaced by its values at a fixed seeded sample of positions, so two
+    builds run with the same arguments dump the same elements (caps: 2 x 2^20 + 2 x 2^22 values, 40 MB)."""
+    import numpy as np
+    import torch
+
+    def sample(t, cap):
+        t = t.detach().reshape(-1).float()
+        if t.numel() > cap:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:cap].sort().values
+            t = t[idx.to(t.device)]
+        return t.cpu().numpy()
+
+    params = list(model.parameters())
+    arrays = {"loss": sample(loss, 1), "pred0": sample(pred0, 1 << 20), "pred1": sample(pred1, 1 << 20),
+              "grads": sample(torch.cat([p.grad.reshape(-1) for p in params if p.grad is not None]), 1 << 22),
+              "params": sample(torch.cat([p.reshape(-1) for p in params]), 1 << 22)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def self_launch(args):
@@ -226,7 +256,7 @@ def main():
                     ar_events.append((e0, e1))
             if opt is not None:
                 opt.step()
-            return loss
+            return loss, pe, pd
         return step
 
     def fence():
@@ -236,7 +266,8 @@ def main():
         torch.cuda.synchronize()
 
     def timed(step, k):
-        """k steps between two fences: (wall seconds, per-step milliseconds from events on the launch stream)."""
+        """k steps between two fences: (wall seconds, per-step milliseconds from events on the launch stream, what the last
+        step returned)."""
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(k + 1)]
         for e in ev:          # first use of an event allocates its completion signal: do that outside the timed region
             e.record()
@@ -246,7 +277,8 @@ def main():
         t0 = time.perf_counter()
         ev[0].record()
         for i in range(k):
-            loss = step()
+            res = None        # (a step's logits are released before the next step allocates its own)
+            res = step()
             ev[i + 1].record()
         fence()
         dt = time.perf_counter() - t0
@@ -255,7 +287,7 @@ def main():
             tt = torch.tensor([dt], dtype=torch.float64, device=dev)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt)
-        return dt, [ev[i].elapsed_time(ev[i + 1]) for i in range(k)], loss
+        return dt, [ev[i].elapsed_time(ev[i + 1]) for i in range(k)], res
 
     def make_opt(model):
         if args.no_optimizer:
@@ -311,12 +343,15 @@ def main():
         model.grad_sync.elapsed_ms()       # (drop the warm-up's marks)
     if dom_tag and not args.no_kernel_timing:
         lib.seunet_prof_enable_filtered(dom_tag.encode())
-    dt, per_step_ms, loss = timed(step, args.steps)
+    dt, per_step_ms, (loss, pred0, pred1) = timed(step, args.steps)
     dom_report = ""
     if dom_tag and not args.no_kernel_timing:
         lib.seunet_prof_report(buf, len(buf))
         lib.seunet_prof_enable(0)
         dom_report = buf.value.decode()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, pred0, pred1, model)
+    del pred0, pred1
     voxels_step = world * B * S ** 3
     value = voxels_step * args.steps / dt
     ms_step = 1e3 * dt / args.steps
