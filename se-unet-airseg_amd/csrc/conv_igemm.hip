@@ -30,6 +30,7 @@
 //                 the fused concatenation)
 //   grid          blockIdx.x is remapped so that each XCD (private L2) owns a contiguous run of tiles
 #include "seunet_common.h"
+#include "lds_dma.h"
 #include <utility>
 #include <type_traits>
 
@@ -200,14 +201,14 @@ conv_igemm_kernel(ConvKArgs a) {
     const T* base = reinterpret_cast<const T*>(sp) + (long long)n * V * sC + c;
     const long long avail = ch0 < a.cin ? ((long long)V * sC - c) * (long long)sizeof(T) : 0;   // 0 records: all zeros
     rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(uniform_ptr(base)), 0,
-                                              __builtin_amdgcn_readfirstlane((int)avail), 0x00020000);
+                                              __builtin_amdgcn_readfirstlane((int)avail), RSRC_WORD3);
     in_stride = __builtin_amdgcn_readfirstlane((unsigned)(sC * (int)sizeof(T)));
     if (pair) {
       pofs = (unsigned)piece * 16u;
       pbad = piece == 1 && chb + KC / 2 >= a.cin;
     }
     rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(uniform_ptr(wbase + (size_t)chunk * (W_TOTAL * 16))), 0,
-                                             W_TOTAL * 16, 0x00020000);
+                                             W_TOTAL * 16, RSRC_WORD3);
   };
   auto fetch_item = [&](auto item_c) __attribute__((always_inline)) {   // item: 0..IN_ITEMS-1 input pieces, then W_ITEMS weight pieces
     constexpr int item = decltype(item_c)::value;
@@ -472,7 +473,7 @@ conv_igemm_kernel(ConvKArgs a) {
         T* dbase = reinterpret_cast<T*>(dpv) + (long long)n * V * dC + cl;
         const long long davail = ((long long)V * dC - cl) * (long long)sizeof(T);
         const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<void*>(uniform_ptr(dbase)), 0, __builtin_amdgcn_readfirstlane((int)davail), 0x00020000);
+            const_cast<void*>(uniform_ptr(dbase)), 0, __builtin_amdgcn_readfirstlane((int)davail), RSRC_WORD3);
         const unsigned dstride = __builtin_amdgcn_readfirstlane((unsigned)(dC * (int)sizeof(T)));
         const unsigned hofs = (unsigned)(4 * h * (int)sizeof(T));
 #pragma unroll

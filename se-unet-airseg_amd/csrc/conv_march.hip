@@ -15,7 +15,7 @@
 //     groups, the rows of the patch.  No weight ever touches the LDS, no K-chunk loop, no weight staging;
 //   * every fragment read from the LDS (16 voxels x 32 channels) feeds 9 MFMAs (3 dz x up to 3 dy): 0.11 KB of LDS reads
 //     per MFMA instead of 1.25 KB;
-//   * input planes arrive by LDS-DMA (global_load_lds_dwordx4, counted vmcnt, one raw s_barrier per step) two steps ahead
+//   * input planes arrive by LDS-DMA (lds_dma.h; counted wait, one raw s_barrier per step) two steps ahead
 //     into a 3-slot ring.  LDS image of a plane: voxel-major [row][x][CIN x 2 B] (row pitch 36 voxels), so a DMA
 //     instruction reads whole 64 / 128-byte voxel records (full cache lines at 64 channels); the 16-byte pieces of a voxel
 //     are XOR-swizzled by x (on the SOURCE side of the DMA and on the read) so that the fragment reads stay (nearly)
@@ -28,6 +28,7 @@
 //     record per workgroup.
 // One workgroup per CU: a 4 x 128^3 batch at 64 -> 32 channels is exactly 256 marches of 128 planes.
 #include "seunet_common.h"
+#include "lds_dma.h"
 #include <utility>
 #include <type_traits>
 
@@ -83,7 +84,7 @@ struct MarchArgs {
   double* stats; const void* zero;
   int N, D, H, W;
   int nyb, nxb, nseg, zsteps, nblk;      // patches, z segments (per parity class), output planes per segment, N blocks
-  int buf;                               // the source(s) of a sample fit one 32-bit buffer descriptor (see march_dma16_buf)
+  int buf;                               // the source(s) of a sample fit one 32-bit buffer descriptor (BUF, see the kernel)
 };
 
 static constexpr int MA_TX = 32, MA_NW = 4, MA_HXP = 36, MA_PF = 2, MA_RING = 3;
@@ -100,9 +101,9 @@ template <int KS, int NGW, int RYW, int DIL, int MODE> struct MarchGeo {
   static constexpr int NI = (HY * MA_HXP * NP + 63) / 64;            // DMA wave-instructions per plane
   static constexpr int PLB = NI * 1024;
   static constexpr int ITEMS = (NI + MA_NW - 1) / MA_NW;             // per wave (padded: every wave issues the same count)
-  static constexpr int OLDN = MODE == 2 ? RYW : 0;                   // old-row DMA instructions per wave and step
-  static constexpr int STORES = RYW * 2;                             // store instructions per wave and step
-  static constexpr int TOT = ITEMS + OLDN + STORES;                  // vector-memory operations per wave and step
+  // plane DMA loads per wave and step (the old rows of MODE 2 go out before them in a step, and no counted wait leaves any of
+  // those in flight: see the march)
+  static constexpr int PLANE_LOADS = ITEMS;
   static constexpr int DUMP = MA_RING * PLB;                         // 1 KB landing area of the padding DMA instructions
   static constexpr int OLD = DUMP + 1024;                            // [2 slots][4 waves][RYW rows][32 voxels][32 B]
   static constexpr int STAT = OLD + (MODE == 2 ? 2 * MA_NW * RYW * 1024 : 0);   // forward: f64 march totals, [8 values][256 lanes]
@@ -111,24 +112,6 @@ template <int KS, int NGW, int RYW, int DIL, int MODE> struct MarchGeo {
   static_assert(LDS <= 160 * 1024, "LDS budget");
   static_assert((HYW - 1) * ROWB + 2 * 16 * VB < 65536, "fragment immediates must fit the 16-bit offset field");
 };
-
-__device__ __forceinline__ void march_dma16(const void* gsrc, unsigned lds_dst) {
-  // one LDS-DMA wave-instruction: 64 lanes x 16 B, LDS destination = lds_dst + 16 * lane (M0 carries the base)
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-// The same through a buffer descriptor (round 4, single-source launches): base + scalar offset + per-lane offset, and a lane whose
-// offset lies beyond num_records writes ZEROS into the LDS (probed on gfx950: scripts/probes/blds_oob.hip) -- the padding of a
-// plane image needs no zero page, no per-lane pointer select, no validity mask and no 64-bit address.  In the main loop of the
-// dc5 data gradient that is 1.25 -> 1.06 other instructions per MFMA and 65 -> 12 scalar-register spill reads.
-typedef unsigned int mu32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void march_dma16_buf(unsigned voff, mu32x4 rsrc, unsigned soff, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(rsrc), "s"(soff), "s"(lds_dst) : "memory");
-}
-template <int N> __device__ __forceinline__ void march_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
 
 template <int NP> __device__ __forceinline__ int march_swz(int hx) {
   // piece permutation of the voxel at halo column hx (an involution applied on the DMA source side and on the read)
@@ -143,7 +126,8 @@ template <int N, typename F> __device__ __forceinline__ void static_for(F&& f) {
 }
 
 // MODE 0: forward (bias + InstanceNorm partial sums); 1: data gradient; 2: data gradient with accumulation (+=)
-// BUF: one source tensor whose sample is < 4 GB: the plane DMA goes through a buffer descriptor (march_dma16_buf)
+// BUF: the source(s) of a sample fit one 32-bit buffer descriptor: the plane DMA goes through it (dma16_buf; in the main loop of the
+// dc5 data gradient 1.25 -> 1.06 other instructions per MFMA and 65 -> 12 scalar-register spill reads against dma16)
 template <typename T, int KS, int NGW, int RYW, int DIL, int MODE, bool BUF>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 conv_march_kernel(MarchArgs a) {
@@ -200,10 +184,10 @@ conv_march_kernel(MarchArgs a) {
   const unsigned char* zero_page = reinterpret_cast<const unsigned char*>(a.zero) + lane * 16;
   const unsigned char* src0_n = reinterpret_cast<const unsigned char*>(a.src0) + (long long)n * a.D * plane_bytes;
   const unsigned char* src1_n = reinterpret_cast<const unsigned char*>(a.nsrc > 1 ? a.src1 : a.src0) + (long long)n * a.D * plane_bytes;
-  // plane of step s -> ring slot; every wave issues exactly ITEMS instructions (the vmcnt arithmetic counts on it).  The
-  // plane-level part (validity, 64-bit plane bases, LDS slot base) is computed once per step (`plane_of`) and handed to the
-  // items: they sit in different scheduling regions, so the compiler recomputed it for each of them, and with one wave per
-  // SIMD every scalar instruction takes an issue slot from the MFMA stream
+  // plane of step s -> ring slot; every wave issues exactly ITEMS instructions (lds_dma.h (a)).  The plane-level part
+  // (validity, 64-bit plane bases, LDS slot base) is computed once per step (`plane_of`) and handed to the items: they sit in
+  // different scheduling regions, so the compiler recomputed it for each of them, and with one wave per SIMD every scalar
+  // instruction takes an issue slot from the MFMA stream
   // BUF: ONE descriptor for the sample -- base = the lower of the (one or two) source pointers, a lane of the other source adds the
   // distance between the two tensors (the launcher checked that distance + sample fit 32 bits; net.cpp keeps dc5's two sources
   // next to each other in the arena), num_records = everything up to the end of the upper tensor's sample
@@ -253,15 +237,14 @@ conv_march_kernel(MarchArgs a) {
     if constexpr (it < ITEMS) {
       const bool real = wave + MA_NW * it < NI;                     // wave-uniform
       if constexpr (BUF) {      // (doff: the lane's offset inside a plane, 0xFFFFFFFF for padding; a padding item reads zero records)
-        mu32x4 rs;
-        rs.x = s_lo; rs.y = s_hi; rs.z = real ? r.nrec : 0u; rs.w = 0x00020000u;
-        march_dma16_buf(doff[it], rs, r.soff, real ? r.lds + (unsigned)((wave + MA_NW * it) * 1024) : lds_base + (unsigned)Geo::DUMP);
+        dma16_buf(doff[it], dma_rsrc(s_lo, s_hi, real ? r.nrec : 0u), r.soff,
+                  real ? r.lds + (unsigned)((wave + MA_NW * it) * 1024) : lds_base + (unsigned)Geo::DUMP);
         return;
       }
       const unsigned d = doff[it];
       const unsigned char* gp = ((d & 0x80000000u) ? r.b1 : r.b0) + (d & 0x7FFFFFFFu);
       gp = (r.ok && real && d != 0xFFFFFFFFu) ? gp : zero_page;
-      march_dma16(gp, real ? r.lds + (unsigned)((wave + MA_NW * it) * 1024) : lds_base + (unsigned)Geo::DUMP);
+      dma16(gp, real ? r.lds + (unsigned)((wave + MA_NW * it) * 1024) : lds_base + (unsigned)Geo::DUMP);
     }
   };
 
@@ -294,7 +277,7 @@ conv_march_kernel(MarchArgs a) {
         const bool ok = jok && y < a.H && xx < a.W;
         const unsigned char* gp = ok ? dbase + (((long long)z * a.H + y) * a.W + xx) * dC * (long long)sizeof(T) + (dch + 8 * (lane & 1)) * (long long)sizeof(T)
                                      : zero_page;
-        march_dma16(gp, lds_base + (unsigned)(Geo::OLD + ((oslot * MA_NW + wave) * RYW + r) * 1024));
+        dma16(gp, lds_base + (unsigned)(Geo::OLD + ((oslot * MA_NW + wave) * RYW + r) * 1024));
       }
     }
   };
@@ -346,7 +329,7 @@ conv_march_kernel(MarchArgs a) {
     const int z = pz + DIL * (q0 + j);
     const int y = yrow0 + r;
     const bool rowok = jok && y < a.H;                                  // wave-uniform
-    const __amdgpu_buffer_rsrc_t rdr = __builtin_amdgcn_make_buffer_rsrc(dbase, 0, rowok ? dst_records : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rdr = __builtin_amdgcn_make_buffer_rsrc(dbase, 0, rowok ? dst_records : 0, RSRC_WORD3);
     const int soff = __builtin_amdgcn_readfirstlane(rowok ? (z * a.H + y) * row_pitch : 0);
     mf32x4 v = acc[AI][r][b];
     // the accumulator leaves the accumulator half HERE (one copy, at the epilogue's place in the unit): with several vector
@@ -464,28 +447,25 @@ conv_march_kernel(MarchArgs a) {
   };
 
   // ---- the march ----
-  // Vector-memory operations of a wave, in program order: [prologue: DMA(0), DMA(1)], then per step s exactly TOT of them:
-  // old rows (MODE 2, first), ITEMS plane instructions for plane s + 2, STORES stores.  At the top of step s >= 1 plane s
-  // (issued in step s - 2, or in the prologue) must have landed, with accumulation the old rows of step s (issued first in
-  // step s - 1) too: the only LOADS younger than those are the ITEMS plane instructions of step s - 1, so the wait allows
-  // ITEMS outstanding operations and counts NO store as outstanding (round 4: until then it allowed TOT - OLDN, i.e. also the
-  // stores of step s - 1 -- right only if stores and LDS-DMA loads retire in issue order, and they need not: the streaming conv's
-  // 16-byte-store experiments passed such a wait before their plane had landed, DESIGN 4.  Same speed here).  Then one barrier:
-  // every wave's part of the plane is in the LDS, and every wave has finished reading the slot (plane s - 1) that this step's
-  // prefetch overwrites.
+  // Vector-memory operations of a wave, in program order: [prologue: DMA(0), DMA(1)], then per step s: the old rows (MODE 2,
+  // first), the PLANE_LOADS plane instructions for plane s + 2, the stores of the lazy epilogue.  At the top of step s >= 1
+  // plane s (issued in step s - 2, or in the prologue) must have landed, with accumulation the old rows of step s (issued first
+  // in step s - 1) too: the only loads younger than those are the plane instructions of step s - 1, so the wait allows
+  // PLANE_LOADS, and no store is counted (lds_dma.h (c)).  Then one barrier: every wave's part of the plane is in the LDS, and
+  // every wave has finished reading the slot (plane s - 1) that this step's prefetch overwrites.
   static_for<MA_PF>([&](auto k_c) __attribute__((always_inline)) {
     constexpr int k = decltype(k_c)::value;
     const PlaneRef r = plane_of(k, k);
     static_for<ITEMS>([&](auto it_c) __attribute__((always_inline)) { dma_item(r, it_c); });
   });
-  march_wait_vm<(MA_PF - 1) * ITEMS>();    // plane 0 has landed (this wave's part)
+  wait_loads<(MA_PF - 1) * Geo::PLANE_LOADS>();    // plane 0 has landed (this wave's part)
   __builtin_amdgcn_s_barrier();
   // Every step of the loop is a compute step and the trip count is padded to whole 3-step rounds, so that the loop body has no
   // conditional path (the accumulator sets stay in place: no copies, no merges); steps beyond the last input plane march over
-  // zero planes (DMA from the zero page).  The rows 1.. of the LAST output plane Z - 1 (set (Z - 1) % 3) are written by the
-  // lazy epilogue of step Z + 2 when the padding reaches that step; when Z + 2 is a multiple of 3 the loop ends before it and a
-  // tail without MFMAs writes them (then (Z - 1) % 3 == 0: one variant of the tail).  launch_conv_march() prefers such
-  // segment lengths.
+  // zero planes (zero records with BUF, DMA from the zero page otherwise).  The rows 1.. of the LAST output plane Z - 1 (set
+  // (Z - 1) % 3) are written by the lazy epilogue of step Z + 2 when the padding reaches that step; when Z + 2 is a multiple
+  // of 3 the loop ends before it and a tail without MFMAs writes them (then (Z - 1) % 3 == 0: one variant of the tail).
+  // launch_conv_march() prefers such segment lengths.
   const int nrounds = (ncompute + 2) / 3;
   int slot = 0, slot_pf = MA_PF % MA_RING;
   for (int rd3 = 0; rd3 < nrounds; ++rd3) {
@@ -493,7 +473,7 @@ conv_march_kernel(MarchArgs a) {
       constexpr int PH = decltype(ph_c)::value;
       const int s = 3 * rd3 + PH;
       if (PH > 0 || rd3 > 0) {
-        march_wait_vm<ITEMS>();
+        wait_loads<Geo::PLANE_LOADS>();
         __builtin_amdgcn_s_barrier();
       }
       compute(s, slot, slot_pf, ph_c);
@@ -501,7 +481,7 @@ conv_march_kernel(MarchArgs a) {
       slot_pf = slot_pf == MA_RING - 1 ? 0 : slot_pf + 1;
     });
   }
-  march_wait_vm<0>();            // no DMA may outlive the workgroup's LDS allocation
+  wait_loads<0>();               // no DMA may outlive the workgroup's LDS allocation
   if (3 * nrounds == ncompute) {   // (wave-uniform) the tail: rows 1.. of output Z - 1, held in set 0, as step Z + 2 would have
     // (accumulation: a wave reads only the old rows it fetched itself, and they have landed: vmcnt(0) above)
     static_for<RYW - 1>([&](auto r_c) __attribute__((always_inline)) {

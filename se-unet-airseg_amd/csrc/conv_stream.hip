@@ -11,9 +11,9 @@
 //     output row each, two per SIMD.  (Round 4, measured: every variant but the 8-channel one needs > 128 registers per lane,
 //     so ONE workgroup is resident per CU and its two waves per SIMD run in phase -- the barrier lines them up -- and hide
 //     nothing of each other; hence marches as long as the volume allows, see stream_zsteps, and DESIGN 4 for the timeline);
-//   * the planes arrive by LDS-DMA (buffer_load_dwordx4 ... lds through one descriptor per sample, inline asm so that hipcc
-//     neither counts nor drains them; padding lanes and planes outside the march read as zeros) into a ring two or three
-//     steps ahead of their use: counted s_waitcnt vmcnt(N) + one raw s_barrier per step;
+//   * the planes arrive by LDS-DMA (lds_dma.h, the buffer form through one descriptor per sample; padding lanes and planes
+//     outside the march read as zeros) into a ring two or three steps ahead of their use: counted wait + one raw s_barrier
+//     per step;
 //   * weights live in registers for the whole march (27 taps x 16 B per lane), no weight LDS, no K-chunk loop;
 //   * InstanceNorm partial sums are carried per lane across the march (f32) and reduced once per workgroup (f64), not once
 //     per 512-voxel tile;
@@ -28,6 +28,7 @@
 // LDS image of a plane: planar [16-B piece of the channels][voxel of the halo patch][16 B]; fragment reads are ds_read_b128
 // of consecutive voxels (conflict-free), DMA instructions write 1 KB contiguous.
 #include "seunet_common.h"
+#include "lds_dma.h"
 #include <utility>
 #include <type_traits>
 
@@ -78,6 +79,7 @@ template <int CIN, int COUTP, bool XFOLD, int DIL, bool DACC = false> struct Str
   static constexpr int PF = (5 * PLANE + 1280 + ST_NW * STG + (DACC ? 5 * ST_NW * OLDI * 1024 : 0) <= 160 * 1024) ? 3 : 2;
   static constexpr int RING = PF + 2;
   static constexpr int ITEMS = (NP * G + ST_NW - 1) / ST_NW;     // DMA wave-instructions per wave and plane
+  static constexpr int LOADS_PER_STEP = ITEMS + (DACC ? OLDI : 0);   // DMA loads per wave and step: the plane (+ the old row)
   static constexpr int NB = COUTP == 32 ? 32 : 16, NBX = ST_TX / NB;
   static constexpr int STORES = COUTP == 32 ? 4 : NBX;           // store wave-instructions per wave and step (direct and staged form alike)
   static constexpr int BIAS = RING * PLANE + 1024;          // f32 bias table (32-channel tiles keep it here instead of 16 registers per lane)
@@ -86,23 +88,6 @@ template <int CIN, int COUTP, bool XFOLD, int DIL, bool DACC = false> struct Str
   static constexpr int LDS = OLD + (DACC ? RING * ST_NW * OLDI * 1024 : 0);   // ring + a 1-KB dump for the padding DMA instructions (+ old rows)
 };
 
-__device__ __forceinline__ void stream_dma16(const void* gsrc, unsigned lds_dst) {
-  // one LDS-DMA wave-instruction: 64 lanes x 16 B, LDS destination = lds_dst + 16 * lane (M0 carries the base)
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-// The same through a buffer descriptor (round 4): the 16 bytes of a lane come from base + soffset + voffset, and a lane whose
-// voffset lies beyond num_records writes ZEROS into the LDS (probed on gfx950: scripts/probes/blds_oob.hip).  So the padding of a
-// plane image needs neither a zero page nor a per-lane pointer select nor a 64-bit address: the lane's offset inside a plane is
-// a constant (0xFFFFFFFF for padding voxels), the plane's offset inside the sample a scalar, a plane outside the volume a
-// descriptor of zero records.  One vector register, no vector arithmetic per DMA instruction.
-typedef unsigned int u32x4s __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void stream_dma16_buf(unsigned voff, u32x4s rsrc, unsigned soff, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(rsrc), "s"(soff), "s"(lds_dst) : "memory");
-}
 // -DSEUNET_STREAM_PROBE=1: no statistics; 2: no stores; 3: no MFMAs; 4: no fragment reads (timing by elimination, never shipped)
 #ifndef SEUNET_STREAM_PROBE
 #define SEUNET_STREAM_PROBE 0
@@ -112,7 +97,6 @@ __device__ __forceinline__ void stream_dma16_buf(unsigned voff, u32x4s rsrc, uns
 #else
 #define SSTAMP(i) do {} while (0)
 #endif
-template <int N> __device__ __forceinline__ void stream_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
 
 // FWD: bias + InstanceNorm partial sums (forward); !FWD: data gradient, optionally accumulating into the destination (DACC)
 template <typename T, int CIN, int COUTP, bool XFOLD, int DIL, bool FWD, bool DACC>
@@ -189,12 +173,11 @@ conv_stream_kernel(StreamArgs a) {
   auto dma_item = [&](const PlaneRef& r, auto it_c) __attribute__((always_inline)) {
     constexpr int it = decltype(it_c)::value;
     if constexpr (it < ITEMS) {
-      // every wave issues exactly ITEMS instructions per plane (the vmcnt arithmetic of the march counts on it): an item
-      // number beyond the plane's NP * G pieces reads nothing (zero records) into the dump area
+      // every wave issues exactly ITEMS instructions per plane (lds_dma.h (a)): an item number beyond the plane's NP * G
+      // pieces reads nothing (zero records) into the dump area
       const bool real = wave + ST_NW * it < NP * G;                 // wave-uniform
-      u32x4s rs;
-      rs.x = src_lo; rs.y = src_hi; rs.z = real ? r.nrec : 0u; rs.w = 0x00020000u;
-      stream_dma16_buf(doff[it], rs, r.soff, real ? r.lds + dlds[it] : lds_base + (unsigned)(Geo::RING * PLANE));
+      dma16_buf(doff[it], dma_rsrc(src_lo, src_hi, real ? r.nrec : 0u), r.soff,
+                real ? r.lds + dlds[it] : lds_base + (unsigned)(Geo::RING * PLANE));
     }
   };
   auto dma_plane = [&](int s, int slot) __attribute__((always_inline)) {
@@ -218,7 +201,7 @@ conv_stream_kernel(StreamArgs a) {
         const int byte = k * 1024 + lane * 16;
         const int xv = x0 + byte / (a.dstC * (int)sizeof(T));
         const unsigned char* gp = (rok && byte < old_row_bytes && xv < a.W) ? row + byte : zero_page;
-        stream_dma16(gp, lds_base + (unsigned)(Geo::OLD + ((slot * ST_NW + wave) * Geo::OLDI + k) * 1024));
+        dma16(gp, lds_base + (unsigned)(Geo::OLD + ((slot * ST_NW + wave) * Geo::OLDI + k) * 1024));
       }
     }
   };
@@ -383,7 +366,7 @@ conv_stream_kernel(StreamArgs a) {
             for (int b = 0; b < NBX; ++b) {
               if constexpr (SEUNET_STREAM_PROBE == 3) {
                 if (first) acc[ai][b] = cinit;
-                acc[ai][b][0] += __builtin_bit_cast(float, __builtin_bit_cast(u32x4s, fr[ri & 1][dxi][b]).x);   // (keeps the reads alive)
+                acc[ai][b][0] += __builtin_bit_cast(f32x4, fr[ri & 1][dxi][b])[0];   // (keeps the reads alive)
               } else if constexpr (COUTP == 32) acc[ai][b] = st_mfma32<T>(wreg[tap], fr[ri & 1][dxi][b], first ? cinit : acc[ai][b]);
               else acc[ai][b] = st_mfma16<T>(wreg[tap], fr[ri & 1][dxi][b], first ? cinit : acc[ai][b]);
             }
@@ -400,7 +383,7 @@ conv_stream_kernel(StreamArgs a) {
     const int q = q0 + s - 2;                                       // parity-class plane index
     const int z = pz + DIL * q;
     const bool zok = q >= q0 && q < q1;                             // wave-uniform
-    const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(dst_n, 0, zok ? (int)dst_sample : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(dst_n, 0, zok ? (int)dst_sample : 0, RSRC_WORD3);
     const int soff = __builtin_amdgcn_readfirstlane(zok ? z * dst_plane : 0);
 #pragma unroll
     for (int b = 0; b < NBX; ++b) {
@@ -462,16 +445,13 @@ conv_stream_kernel(StreamArgs a) {
   };
 
   // ---- the march ----
-  // VMEM issue order of a wave: [prologue: DMA(0) .. DMA(PF-1)]  then per step s: DMA(s+PF) (inside compute), stores(s).
-  // At the top of step s >= 1 plane s must have landed; it was issued in step s - PF (or the prologue), and the only LOADS
-  // younger than it are DMA(s+1) .. DMA(s+PF-1): the wait allows (PF-1) * LW outstanding operations and counts NO store as
-  // outstanding.  Round 3 (and this round at first) added the stores issued since -- correct if operations retire in issue
-  // order, and they do not: with 16-byte stores about one launch in a hundred passed the wait before its plane had landed
-  // (wrong output rows, never reproducibly), because a store can retire ahead of an older LDS-DMA load and lower the count
-  // early.  The 8-byte stores never showed it in thousands of runs; the count no longer relies on it (same speed: the stores
-  // of the previous step are acknowledged within the step).  Then one barrier: every wave's part of the plane is in LDS, and
-  // every wave has finished reading the slot that this step's prefetch overwrites (ring = PF + 2 slots).
-  constexpr int LW = ITEMS + (DACC ? Geo::OLDI : 0);   // DMA instructions per wave and step (padded to the same count in every wave)
+  // VMEM issue order of a wave: [prologue: DMA(0) .. DMA(PF-1)]  then per step s: DMA(s+PF) (inside compute), stores(s), where
+  // DMA(j) = the LOADS_PER_STEP loads of plane j and of the old row finished at step j - 2 (DACC).  At the top of step s >= 1
+  // plane s must have landed; it was issued in step s - PF (or the prologue), and the only loads younger than it are
+  // DMA(s+1) .. DMA(s+PF-1): the wait allows (PF-1) * LOADS_PER_STEP, and the STORES stores of each step are not counted
+  // (lds_dma.h (c); same speed: the stores of the previous step are acknowledged within the step).  Then one barrier: every
+  // wave's part of the plane is in LDS, and every wave has finished reading the slot that this step's prefetch overwrites
+  // (ring = PF + 2 slots).
 #pragma unroll
   for (int k = 0; k < Geo::PF; ++k) { dma_plane(k, k); dma_old(k, k); }
   // The weight loads are ordinary (compiler-visible) loads, and the compiler waits for a load at its first use -- which is inside
@@ -482,7 +462,7 @@ conv_stream_kernel(StreamArgs a) {
 #pragma unroll
   for (int k = 0; k < NTAP; ++k) asm volatile("" :: "v"(wreg[k]));
   SSTAMP(10);      // (prologue) first planes requested, weights arrived
-  stream_wait_vm<(Geo::PF - 1) * LW>();    // plane 0 has landed (this wave's part)
+  wait_loads<(Geo::PF - 1) * Geo::LOADS_PER_STEP>();    // plane 0 has landed (this wave's part)
   __builtin_amdgcn_s_barrier();
   SSTAMP(0);   // prologue: plans, weights, first planes
   int slot = 0, slot_pf = Geo::PF;         // s % Geo::RING, (s + Geo::PF) % Geo::RING
@@ -492,7 +472,7 @@ conv_stream_kernel(StreamArgs a) {
         const int s = s0 + PH;
         if (s < nsteps) {
           if (s > 0) {
-            stream_wait_vm<(Geo::PF - 1) * LW>();
+            wait_loads<(Geo::PF - 1) * Geo::LOADS_PER_STEP>();
             SSTAMP(1);   // counted wait for the plane (and the stores of two steps ago)
             __builtin_amdgcn_s_barrier();
             SSTAMP(2);   // barrier
@@ -514,7 +494,7 @@ conv_stream_kernel(StreamArgs a) {
   // ---- InstanceNorm partial sums of this workgroup: un-shift in f64, reduce over the lanes that hold the same channels,
   //      then over the four waves (fixed order), one record per workgroup ----
   if (FWD && a.stats != nullptr) {
-    stream_wait_vm<0>();
+    wait_loads<0>();
     __syncthreads();             // the ring is dead: reuse its first bytes
     double* red = reinterpret_cast<double*>(smem);     // [8 waves][COUTP][2]
 #pragma unroll
@@ -543,7 +523,7 @@ conv_stream_kernel(StreamArgs a) {
       }
     }
   } else {
-    stream_wait_vm<0>();         // no DMA may outlive the workgroup's LDS allocation
+    wait_loads<0>();         // no DMA may outlive the workgroup's LDS allocation
   }
 #ifdef SEUNET_STAMP
   if (a.debug != nullptr && lane == 0) {

@@ -185,7 +185,7 @@ __device__ __forceinline__ void zero8p(Pack8<float>& k) { k.a = k.b = make_float
 // DPP stage looks at EXEC late: where the compiler placed an s_and_saveexec (the `if (cg == 0)` that follows a group sum) right
 // behind the last DPP instruction, the last 16 lanes of the wave occasionally saw the NARROWED mask -- their partner lanes read as
 // 0 and the side value lost half of its channels.  Seen only while a second process kept the chip busy (two ranks on one GPU in the
-// data-parallel tests; scripts/r4_stress3.py: 5 % of launches), never in the sums that are followed by more vector work.  The ISA
+// data-parallel tests; scripts/r4_stress3.py@b7b98f0: 5 % of launches), never in the sums that are followed by more vector work.  The ISA
 // lists the mirror case (a VALU write of EXEC needs 5 wait states before a DPP), not this one, and the hazard recognizer inserts
 // nothing.  `dpp_settle` makes a value that came through DPP the operand of a plain vector move: the move cannot issue before the
 // DPP instruction has completed, and a scalar write of EXEC behind it is ordered after it by the ordinary interlock.  Every
@@ -226,7 +226,7 @@ __device__ __forceinline__ double dpp_settle(double v) {
 // The same holds for the LDS cross-lane instructions (ds_bpermute behind __shfl_*, ds_swizzle): the compiler leaves them in
 // flight across the s_and_saveexec of the `if (lane == 0)` that follows a wave reduction (the s_waitcnt sinks into the branch), and
 // under the same conditions the first-layer block's statistics lost lanes (ec1.conv1.weight / ec1.conv_se.weight off by 1e-4 ..
-// 7e-3 in 1 % of the steps of scripts/r4_stress.py).  Every cross-lane value is settled before it is used: the move needs the
+// 7e-3 in 1 % of the steps of scripts/r4_stress.py@b7b98f0).  Every cross-lane value is settled before it is used: the move needs the
 // result, so the wait for it precedes any change of EXEC.
 template <typename V> __device__ __forceinline__ V shfl_xor_settled(V v, int off) { return dpp_settle(__shfl_xor(v, off, 64)); }
 template <int CTRL> __device__ __forceinline__ int dpp_fetch_bits(int v) {

@@ -13,6 +13,7 @@
 //     ds_read_b64_tr_b16; accumulators (<= 24 pairs per wave) live in registers for the whole launch;
 //   * one slab per workgroup, fixed-order f64 slab sum (deterministic, no atomics).
 #include "seunet_common.h"
+#include "lds_dma.h"
 #include <utility>
 #include <type_traits>
 #include <cstdlib>
@@ -34,13 +35,6 @@ struct W1Args {
 };
 
 static constexpr int W1_NW = 4;
-
-__device__ __forceinline__ void w1_dma16(const void* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-template <int N> __device__ __forceinline__ void w1_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
 
 // piece permutation of voxel v in a record of np 16-byte pieces (np = 4, 8, 16): a transposing read takes, per 16 lanes, 4
 // consecutive voxels x two adjacent pieces; 32 lanes = voxels v..v+3 and v+8..v+11 (see wgrad_march.hip).  XOR on the pair index.
@@ -113,7 +107,8 @@ wgrad_1x1_kernel(W1Args a) {
   // ---- DMA plan: instruction number id = wave + 4 * it of a stage image (1 KB each).  Per lane and instruction one packed word:
   //      bits 0-1 tensor (0..2 sources, 3 = dY), bits 4-19 byte offset of the 16-byte piece inside the tensor's chunk (pieces
   //      permuted), bits 20-27 voxel inside the chunk; ~0 = padding.  Every wave issues exactly LW instructions per chunk
-  //      (LW = 8, 16 or 24 >= the real count: the vmcnt literal of the loop), the surplus ones copy the zero page to a dump. ----
+  //      (LW = 8, 16 or 24 >= the real count, so that the loop's wait count is one of a few literals; lds_dma.h (a)), the
+  //      surplus ones copy the zero page to a dump. ----
   const int ni = stage / 1024;                               // (regions are multiples of 1 KB: channels % 32 == 0, CH >= 64)
   const int items = (ni + W1_NW - 1) / W1_NW;
   const int LW = items <= 8 ? 8 : (items <= 16 ? 16 : 24);   // (uniform)
@@ -152,7 +147,7 @@ wgrad_1x1_kernel(W1Args a) {
         const bool ok = cok && w != 0xFFFFFFFFu && v < left;
         const unsigned char* gp = ok ? base + ((w >> 4) & 0xFFFF) : zero_page;
         const int id = wave + W1_NW * it;
-        w1_dma16(gp, (it < items && id < ni) ? lds_base + (unsigned)(st * stage + id * 1024) : lds_base + (unsigned)dump);
+        dma16(gp, (it < items && id < ni) ? lds_base + (unsigned)(st * stage + id * 1024) : lds_base + (unsigned)dump);
       }
     }
   };
@@ -171,14 +166,15 @@ wgrad_1x1_kernel(W1Args a) {
   for (; chunk < a.nchunk; chunk += gridDim.x) {
     issue(chunk + PF * (int)gridDim.x, stp);                 // (beyond the last chunk: padding instructions, same count)
     stp = stp + 1 == nst ? 0 : stp + 1;
-    // the current chunk's LW instructions are older than the PF * LW issued after them
+    // the current chunk's LW loads are older than the PF * LW issued after them, and no stores are in flight.  wgrad_1x1_cfg
+    // gives PF * LW = 8, 16, 24, 32 or 48 (PF = nst - 1 = 1..3, LW = 8 / 16 / 24, product <= 48)
     switch (PF * LW) {
-      case 8: w1_wait_vm<8>(); break;
-      case 16: w1_wait_vm<16>(); break;
-      case 24: w1_wait_vm<24>(); break;
-      case 32: w1_wait_vm<32>(); break;
-      case 48: w1_wait_vm<48>(); break;
-      default: w1_wait_vm<0>(); break;                       // (72: beyond the 6-bit counter; the launcher never asks for it)
+      case 8: wait_loads<8>(); break;
+      case 16: wait_loads<16>(); break;
+      case 24: wait_loads<24>(); break;
+      case 32: wait_loads<32>(); break;
+      case 48: wait_loads<48>(); break;
+      default: wait_loads<0>(); break;                       // (72: beyond the 6-bit counter; the launcher never asks for it)
     }
     __builtin_amdgcn_s_barrier();
     const unsigned sb = lds_base + (unsigned)(st * stage);
@@ -197,7 +193,7 @@ wgrad_1x1_kernel(W1Args a) {
     __builtin_amdgcn_s_barrier();                            // every wave is done reading this stage before it is refilled
     st = st + 1 == nst ? 0 : st + 1;
   }
-  w1_wait_vm<0>();
+  wait_loads<0>();
 
   // ---- slab of this workgroup: [wave][c][k][lane][4] ----
   float* out = a.slab + ((size_t)blockIdx.x * W1_NW + wave) * (CIBW * NCOB * 256) + lane * 4;

@@ -14,11 +14,12 @@
 //     from the unmodified DMA image; an X row fragment (3 x-taps) feeds up to 9 x PW MFMAs, a dY row fragment 9 (3 dy x 3 dx
 //     of its dz): 0.19 KB of LDS reads per MFMA;
 //   * planes arrive by LDS-DMA two steps ahead (X: 3-slot ring, dY: 5-slot ring -- a dY plane is used by three steps),
-//     counted vmcnt, one raw s_barrier per step; 16-byte pieces XOR-swizzled by x on the DMA source side so that the
+//     counted wait (lds_dma.h), one raw s_barrier per step; 16-byte pieces XOR-swizzled by x on the DMA source side so that the
 //     transposing reads touch every bank once; a dY plane outside the march is a zero plane in the LDS (no branches);
 //   * workgroups are persistent over their (sample, patch, z-segment) items; one slab of accumulators per workgroup, summed
 //     by a second kernel in a fixed order in f64 (deterministic, no atomics) into the PyTorch (Cout, Cin, 3, 3, 3) layout.
 #include "seunet_common.h"
+#include "lds_dma.h"
 #include <utility>
 #include <type_traits>
 #include <cstdlib>
@@ -51,7 +52,7 @@ template <int NCB, int NOB, int DIL> struct WmGeo {
   static constexpr int ROWBX = WM_HXP * VBX, ROWBY = WM_TX * VBY;
   static constexpr int NIX = (HY * WM_HXP * NPX + 63) / 64, PLBX = NIX * 1024, ITEMSX = (NIX + WM_NW - 1) / WM_NW;
   static constexpr int NIY = WM_RY * WM_TX * NPY / 64, PLBY = NIY * 1024, ITEMSY = NIY / WM_NW;
-  static constexpr int TOT = ITEMSX + ITEMSY;                         // DMA instructions per wave and step
+  static constexpr int LOADS_PER_STEP = ITEMSX + ITEMSY;              // DMA loads per wave and step (the X and the dY plane)
   static constexpr int YOFF = WM_XRING * PLBX, ZERO = YOFF + WM_YRING * PLBY, DUMP = ZERO + PLBY, LDS = DUMP + 1024;
   static_assert(PW == 1 || PW == 2, "pairs per wave");
   static_assert(NIY % WM_NW == 0, "dY plane instructions split evenly");
@@ -59,21 +60,6 @@ template <int NCB, int NOB, int DIL> struct WmGeo {
   static_assert(LDS <= 160 * 1024, "LDS budget");
   static_assert((HY - 1) * ROWBX + WM_HXP * VBX < 65536 && (WM_RY - 1) * ROWBY + WM_TX * VBY < 65536, "immediates");
 };
-
-__device__ __forceinline__ void wm_dma16(const void* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-// through a buffer descriptor (round 4; see conv_march.hip march_dma16_buf): base + scalar plane offset + the lane's constant offset;
-// a lane beyond num_records -- a padding voxel, or any lane of a plane outside the march (zero records) -- writes ZEROS into the LDS
-typedef unsigned int wmu32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void wm_dma16_buf(unsigned voff, wmu32x4 rsrc, unsigned soff, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(rsrc), "s"(soff), "s"(lds_dst) : "memory");
-}
-template <int N> __device__ __forceinline__ void wm_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
 
 // piece permutation of the voxel at column v.  A transposing read takes, per 16 lanes, 4 consecutive voxels x 32 bytes (two
 // adjacent pieces); 32 lanes = the voxels v..v+3 and v+8..v+11.  64-byte records: the four voxels already sit in different
@@ -137,7 +123,7 @@ wgrad_march_kernel(WmArgs a) {
   using Geo = WmGeo<NCB, NOB, DIL>;
   constexpr int PW = Geo::PW, NPX = Geo::NPX, NPY = Geo::NPY, VBX = Geo::VBX, VBY = Geo::VBY, HX = Geo::HX, HY = Geo::HY;
   constexpr int RY = WM_RY, ROWBX = Geo::ROWBX, ROWBY = Geo::ROWBY, PLBX = Geo::PLBX, PLBY = Geo::PLBY;
-  constexpr int NIX = Geo::NIX, ITEMSX = Geo::ITEMSX, ITEMSY = Geo::ITEMSY, TOT = Geo::TOT;
+  constexpr int NIX = Geo::NIX, ITEMSX = Geo::ITEMSX, ITEMSY = Geo::ITEMSY, LOADS_PER_STEP = Geo::LOADS_PER_STEP;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem;
 
@@ -230,8 +216,9 @@ wgrad_march_kernel(WmArgs a) {
       doy[it] = (y < a.H && x < a.W) ? (unsigned)(((y * a.W + x) * a.cout + ch) * (int)sizeof(T)) : 0xFFFFFFFFu;
     }
 
-    // DMA instruction `it` of the planes of step s (X plane -> slot xs, dY plane s -> slot ys); every wave issues exactly TOT
-    // instructions per step (padding instructions land in the dump area)
+    // DMA instruction `it` of the planes of step s (X plane -> slot xs, dY plane s -> slot ys); every wave issues exactly
+    // LOADS_PER_STEP instructions per step (lds_dma.h (a), (b): padding instructions land in the dump area, padding voxels and
+    // planes outside the march read as zeros)
     // (the plane-level part -- validity, 64-bit plane base, LDS slot base -- is computed ONCE per step by `plane_of` and handed
     // to the items: with one wave per SIMD every scalar instruction takes an issue slot from the MFMA stream, and the items
     // sit in different scheduling regions, so the compiler recomputed it for each of them)
@@ -254,14 +241,12 @@ wgrad_march_kernel(WmArgs a) {
       constexpr int it = decltype(it_c)::value;
       if constexpr (it < ITEMSX) {
         const bool real = wave + WM_NW * it < NIX;                    // wave-uniform
-        wmu32x4 rs;
-        rs.x = xlo; rs.y = xhi; rs.z = real ? r.xrec : 0u; rs.w = 0x00020000u;
-        wm_dma16_buf(dox[it], rs, r.xsoff, real ? r.xlds + (unsigned)((wave + WM_NW * it) * 1024) : lds_base + (unsigned)Geo::DUMP);
+        dma16_buf(dox[it], dma_rsrc(xlo, xhi, real ? r.xrec : 0u), r.xsoff,
+                  real ? r.xlds + (unsigned)((wave + WM_NW * it) * 1024) : lds_base + (unsigned)Geo::DUMP);
       } else {
         constexpr int iy = it - ITEMSX;
-        wmu32x4 rs;
-        rs.x = ylo; rs.y = yhi; rs.z = r.yrec; rs.w = 0x00020000u;
-        wm_dma16_buf(doy[iy], rs, r.ysoff, r.yok ? r.ylds + (unsigned)((wave + WM_NW * iy) * 1024) : lds_base + (unsigned)Geo::DUMP);
+        dma16_buf(doy[iy], dma_rsrc(ylo, yhi, r.yrec), r.ysoff,
+                  r.yok ? r.ylds + (unsigned)((wave + WM_NW * iy) * 1024) : lds_base + (unsigned)Geo::DUMP);
       }
     };
 
@@ -322,21 +307,21 @@ wgrad_march_kernel(WmArgs a) {
       });
     };
 
-    // Vector-memory operations of a wave, in program order: [prologue: planes 0 and 1], then per step s exactly TOT: the planes
-    // of step s + 2 (issued during the rows of step s).  The step ends with the synchronisation FOR THE NEXT STEP, placed
-    // before the MFMAs of its last row: all LDS reads of the step are done (lgkmcnt(0)), at most the TOT instructions of this
-    // step are outstanding (planes s + 1 have landed), one barrier (every wave's part is in, every wave is done reading the
-    // slots of step s -- which the DMA of step s + 1 overwrites); then the first row of step s + 1 is requested and the last
-    // row's MFMAs cover its latency.
-    wm_wait_vm<0>();
+    // Vector-memory operations of a wave, in program order: [prologue: planes 0 and 1], then per step s exactly LOADS_PER_STEP
+    // loads: the planes of step s + 2 (issued during the rows of step s; no stores in the march).  The step ends with the
+    // synchronisation FOR THE NEXT STEP, placed before the MFMAs of its last row: all LDS reads of the step are done
+    // (lgkmcnt(0)), at most the LOADS_PER_STEP loads of this step are outstanding (planes s + 1 have landed), one barrier
+    // (every wave's part is in, every wave is done reading the slots of step s -- which the DMA of step s + 1 overwrites);
+    // then the first row of step s + 1 is requested and the last row's MFMAs cover its latency.
+    wait_loads<0>();
     __syncthreads();                     // the previous item's readers are done; the zero plane is written
     if (nsteps == 0) continue;           // (block-uniform)
     {
       const PlaneRef p0 = plane_of(0, 0, 0), p1 = plane_of(1, 1, 1);
-      wm_for<TOT>([&](auto it_c) __attribute__((always_inline)) { issue_item(p0, it_c); });
-      wm_for<TOT>([&](auto it_c) __attribute__((always_inline)) { issue_item(p1, it_c); });
+      wm_for<LOADS_PER_STEP>([&](auto it_c) __attribute__((always_inline)) { issue_item(p0, it_c); });
+      wm_for<LOADS_PER_STEP>([&](auto it_c) __attribute__((always_inline)) { issue_item(p1, it_c); });
     }
-    wm_wait_vm<TOT>();
+    wait_loads<LOADS_PER_STEP>();
     __builtin_amdgcn_s_barrier();
     int xs = 0, ys = 0;                  // ring slots of step s: s % 3, s % 5
     set_addr(0, 0, 0);
@@ -348,14 +333,14 @@ wgrad_march_kernel(WmArgs a) {
       wm_for<HY - 1>([&](auto i_c) __attribute__((always_inline)) {
         constexpr int i = decltype(i_c)::value;
         row(i_c, std::integral_constant<int, i + 1>{}, [&]() __attribute__((always_inline)) {
-          wm_for<TOT>([&](auto it_c) __attribute__((always_inline)) {
+          wm_for<LOADS_PER_STEP>([&](auto it_c) __attribute__((always_inline)) {
             constexpr int it = decltype(it_c)::value;
-            if constexpr ((it * (HY - 1)) / TOT == i) issue_item(pr, it_c);
+            if constexpr ((it * (HY - 1)) / LOADS_PER_STEP == i) issue_item(pr, it_c);
           });
         });
       });
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      wm_wait_vm<TOT>();
+      wait_loads<LOADS_PER_STEP>();
       __builtin_amdgcn_s_barrier();
       xs = xs + 1 == WM_XRING ? 0 : xs + 1;
       ys = ys + 1 == WM_YRING ? 0 : ys + 1;
@@ -365,7 +350,7 @@ wgrad_march_kernel(WmArgs a) {
   }
   // (wait states between the last MFMA and the reads of its result below)
   asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-  wm_wait_vm<0>();
+  wait_loads<0>();
 
   // ---- slab of this workgroup: [pair = wave * PW + k][tap][lane][4] ----
   float* out = a.slab + ((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * (WM_NW * PW) + wave * PW) * (27 * 256) + lane * 4;

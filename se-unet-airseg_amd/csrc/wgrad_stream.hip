@@ -6,14 +6,15 @@
 //   * v_mfma_f32_16x16x32_bf16 with K = the 32 voxels of one x-row: a 16 (ci) x 16 (co) tile per MFMA, no padding for 16/32
 //     channels; 8 input channels fold two x-taps into the 16 rows (voxels x, x+d are adjacent 16-byte pieces);
 //   * the same z-march as conv_stream.hip: a workgroup owns an 8 x 32 (y, x) patch, the X planes (with halo) and the dY
-//     planes arrive by LDS-DMA two steps ahead (counted vmcnt + one raw barrier per step); X plane s meets the dY planes
-//     s-1, s, s+1 (the three dz taps), so an X fragment is read once per (row, dy, dx) and feeds three MFMAs;
+//     planes arrive by LDS-DMA two steps ahead (lds_dma.h: counted wait + one raw barrier per step); X plane s meets the
+//     dY planes s-1, s, s+1 (the three dz taps), so an X fragment is read once per (row, dy, dx) and feeds three MFMAs;
 //   * both operands need "8 voxels of one channel" per lane while LDS holds [voxel][channel]: ds_read_b64_tr_b16 delivers
 //     exactly that from the unmodified images;
 //   * 8 waves = 2 groups of (dy, dx, channel-block) units x 4 row pairs; every wave keeps its 16 x 16 accumulators in
 //     registers for the whole march; at the end the four row-pair partials are summed through LDS in a fixed order and the
 //     workgroup writes ONE compact slab [27][ci][co]; a second kernel sums the slabs (f64, fixed order: deterministic).
 #include "seunet_common.h"
+#include "lds_dma.h"
 #include <utility>
 #include <type_traits>
 
@@ -40,7 +41,7 @@ template <int CIN, int COUT, int DIL> struct WsGeo {
   static constexpr int YPLANE = WS_TY * WS_TX * COUT * 2, NDY = YPLANE / 1024;   // dY plane: natural [row][x][co]
   static constexpr int RX = WS_PF + 2, RY = WS_PF + 4;
   static constexpr int XITEMS = (NP * G + WS_NW - 1) / WS_NW, YITEMS = (NDY + WS_NW - 1) / WS_NW;
-  static constexpr int LW = XITEMS + YITEMS;
+  static constexpr int LOADS_PER_STEP = XITEMS + YITEMS;        // DMA loads per wave and step (an X and a dY plane)
   static constexpr int CB = CIN >= 16 ? CIN / 16 : 1, OB = COUT >= 16 ? COUT / 16 : 1;
   static constexpr int AU = XF ? 6 : 9 * CB;                    // A-units: (dy, dx[, ci block]) or (dy, dx pair)
   static constexpr int AUG = (AU + 1) / 2;                      // per wave group
@@ -50,28 +51,13 @@ template <int CIN, int COUT, int DIL> struct WsGeo {
   static constexpr int SLAB = 27 * CIN * COUT;                  // floats per workgroup
 };
 
-__device__ __forceinline__ void ws_dma16(const void* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-// through a buffer descriptor (round 4; see conv_stream.hip stream_dma16_buf): base + scalar plane offset + the lane's constant
-// offset; a lane beyond num_records -- a padding voxel, or any lane of a plane outside the march (zero records) -- writes ZEROS
-typedef unsigned int wsu32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void ws_dma16_buf(unsigned voff, wsu32x4 rsrc, unsigned soff, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(rsrc), "s"(soff), "s"(lds_dst) : "memory");
-}
-template <int N> __device__ __forceinline__ void ws_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
-
 template <typename T, int CIN, int COUT, int DIL>
 __global__ void __launch_bounds__(512, 2)
 wgrad_stream_kernel(WsArgs a) {
   using Geo = WsGeo<CIN, COUT, DIL>;
   constexpr bool XF = Geo::XF;
   constexpr int NP = Geo::NP, HX = Geo::HX, NVP = Geo::NVP, G = Geo::G, PS = Geo::PS, XPLANE = Geo::XPLANE, YPLANE = Geo::YPLANE;
-  constexpr int NDY = Geo::NDY, RX = Geo::RX, RY = Geo::RY, XITEMS = Geo::XITEMS, YITEMS = Geo::YITEMS, LW = Geo::LW;
+  constexpr int NDY = Geo::NDY, RX = Geo::RX, RY = Geo::RY, XITEMS = Geo::XITEMS, YITEMS = Geo::YITEMS;
   constexpr int CB = Geo::CB, OB = Geo::OB, AU = Geo::AU, AUG = Geo::AUG;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   typedef __attribute__((address_space(3))) bf16x4w lds_b4;
@@ -127,25 +113,27 @@ wgrad_stream_kernel(WsArgs a) {
     const bool ok = id < NDY && y0 + row < a.H && x0 + xx < a.W;
     yoff[it] = ok ? (unsigned)((((y0 + row) * a.W + x0 + xx) * COUT) * 2 + cbyte) : 0xFFFFFFFFu;
   }
+  // (the two descriptors are built in place, not by dma_rsrc: through it the compiler orders two scalar instructions of the
+  // DMA issue differently)
   auto dma_x = [&](int s, int slot, auto it_c) __attribute__((always_inline)) {
     constexpr int it = decltype(it_c)::value;
     const bool real = wave + WS_NW * it < NP * G;
     const int pl = q0 - 1 + s, z = pz + DIL * pl;
     const bool zok = real && pl >= 0 && z < a.D && s < nsteps;
-    wsu32x4 rs;
-    rs.x = xlo; rs.y = xhi; rs.z = zok ? xspan : 0u; rs.w = 0x00020000u;
-    ws_dma16_buf(xoff[it], rs, (unsigned)((long long)(zok ? z : 0) * xplane_bytes),
-                 real ? lds_base + (unsigned)(slot * XPLANE) + xlds[it] : lds_base + (unsigned)Geo::DUMP);
+    rsrc_t rs;
+    rs.x = xlo; rs.y = xhi; rs.z = zok ? xspan : 0u; rs.w = RSRC_WORD3;
+    dma16_buf(xoff[it], rs, (unsigned)((long long)(zok ? z : 0) * xplane_bytes),
+              real ? lds_base + (unsigned)(slot * XPLANE) + xlds[it] : lds_base + (unsigned)Geo::DUMP);
   };
   auto dma_y = [&](int jd, int slot, auto it_c) __attribute__((always_inline)) {   // dY plane q0 - 2 + jd; zero outside [q0, q1)
     constexpr int it = decltype(it_c)::value;
     const bool real = wave + WS_NW * it < NDY;
     const int pl = q0 - 2 + jd, z = pz + DIL * pl;
     const bool zok = real && pl >= q0 && pl < q1;
-    wsu32x4 rs;
-    rs.x = ylo; rs.y = yhi; rs.z = zok ? yspan : 0u; rs.w = 0x00020000u;
-    ws_dma16_buf(yoff[it], rs, (unsigned)((long long)(zok ? z : 0) * yplane_bytes),
-                 real ? lds_base + (unsigned)(Geo::YOFF + slot * YPLANE + (wave + WS_NW * it) * 1024) : lds_base + (unsigned)Geo::DUMP);
+    rsrc_t rs;
+    rs.x = ylo; rs.y = yhi; rs.z = zok ? yspan : 0u; rs.w = RSRC_WORD3;
+    dma16_buf(yoff[it], rs, (unsigned)((long long)(zok ? z : 0) * yplane_bytes),
+              real ? lds_base + (unsigned)(Geo::YOFF + slot * YPLANE + (wave + WS_NW * it) * 1024) : lds_base + (unsigned)Geo::DUMP);
   };
   auto dma_group = [&](int s, int xslot, int jd, int yslot, int part) __attribute__((always_inline)) {
     // part 0 / 1: first / second half of the instructions (spread over the two rows of a step); part 2: everything
@@ -226,19 +214,20 @@ wgrad_stream_kernel(WsArgs a) {
     }
   };
 
-  // ---- the march (see conv_stream.hip for the vmcnt arithmetic; no stores in flight here) ----
+  // ---- the march: as in conv_stream.hip, at the top of step s the only loads younger than X plane s (and its dY plane) are
+  //      those of the WS_PF - 1 steps issued after it; no stores in flight here ----
   int ysl = 0;
   [&]<int... I>(std::integer_sequence<int, I...>) __attribute__((always_inline)) {   // the two dY planes ahead of group 0
     ((dma_y(0, 0, std::integral_constant<int, I>{}), dma_y(1, 1, std::integral_constant<int, I>{})), ...);
   }(std::make_integer_sequence<int, YITEMS>{});
 #pragma unroll
   for (int k = 0; k < WS_PF; ++k) dma_group(k, k, k + 2, k + 2, 2);
-  ws_wait_vm<(WS_PF - 1) * LW>();
+  wait_loads<(WS_PF - 1) * Geo::LOADS_PER_STEP>();
   __builtin_amdgcn_s_barrier();
   int xs = 0, xs_pf = WS_PF, ys_pf = 2 + WS_PF;
   for (int s = 0; s < nsteps; ++s) {
     if (s > 0) {
-      ws_wait_vm<(WS_PF - 1) * LW>();
+      wait_loads<(WS_PF - 1) * Geo::LOADS_PER_STEP>();
       __builtin_amdgcn_s_barrier();
     }
     compute(s, xs, ysl, xs_pf, ys_pf);
@@ -247,7 +236,7 @@ wgrad_stream_kernel(WsArgs a) {
     ysl = ysl == RY - 1 ? 0 : ysl + 1;
     ys_pf = ys_pf == RY - 1 ? 0 : ys_pf + 1;
   }
-  ws_wait_vm<0>();
+  wait_loads<0>();
   __syncthreads();          // every DMA has landed, every wave is done reading: the rings are dead
 
   // ---- sum the four row-pair partials of each group (fixed order) and write the workgroup's slab [27][CIN][COUT] ----
