@@ -351,6 +351,19 @@ int seunet_net_backward(const seunet_net_desc* desc, const float* const* params,
 int seunet_net_backward_ev(const seunet_net_desc* desc, const float* const* params, const float* g_pred0,
                            const float* g_pred1, const float* drop1, const float* drop2, float* const* grads,
                            void* workspace, size_t workspace_bytes, seunet_stream_t s, void* decoder_done_event);
+/* Opt-in gradient with respect to the network input x.  grad_x: NCDHW f32 [batch][in_channel][d][h][w], overwritten (not
+ * accumulated).  scratch: a separate caller-owned buffer of seunet_net_input_grad_bytes(desc) bytes, 256-byte aligned, for the
+ * per-level f32 x-branch terms (the workspace and seunet_net_workspace_bytes are unchanged).  The parameter gradients are the
+ * same bits as seunet_net_backward_ev's; grad_x == NULL IS seunet_net_backward_ev (same launches; scratch unused).
+ * dL/dx = convT_ec1(draw_ec1) + W_x33^T d2_x33 + unpool_0(W_x63^T d2_x63 + unpool_1(W_x93^T d2_x93)), max-pool routing to the first
+ * maximum of each window of the stored input copy.  In bf16 / fp16 storage it is the gradient with respect to the network's
+ * rounded copy of x (the rounding passed straight through).  seunet_net_input_grad_bytes returns 0 and sets
+ * seunet_last_error() for a bad descriptor. */
+size_t seunet_net_input_grad_bytes(const seunet_net_desc* desc);
+int seunet_net_backward_input(const seunet_net_desc* desc, const float* const* params, const float* g_pred0,
+                              const float* g_pred1, const float* drop1, const float* drop2, float* const* grads, float* grad_x,
+                              void* scratch, size_t scratch_bytes, void* workspace, size_t workspace_bytes, seunet_stream_t s,
+                              void* decoder_done_event);
 
 /* ---- opt-in timing of the launch groups inside seunet_net_forward/backward (HIP events on the caller's
  * stream; process-wide, meant for one benchmarking thread at a time).  seunet_prof_report writes "tag<TAB>ms<TAB>count" lines and resets; it waits on

@@ -205,6 +205,7 @@ class _SEUNetFunction(torch.autograd.Function):
         ctx.loss_scale = float(meta.get("loss_scale", 1.0))
         ctx.overflow = meta.get("overflow")
         ctx.names, ctx.grad_sync = meta.get("names"), meta.get("grad_sync")
+        ctx.input_grad = bool(meta.get("input_grad", False))
         return pred0, pred1
 
     @staticmethod
@@ -227,10 +228,24 @@ class _SEUNetFunction(torch.autograd.Function):
             parr = _lib.ptr_array(ctx.plist)
             sync = ctx.grad_sync
             ev = sync.decoder_event() if sync is not None else None
-            _lib.check(lib.seunet_net_backward_ev(C.byref(ctx.desc), parr, g0.data_ptr(), g1.data_ptr(),
-                                                  _lib.ptr(ctx.drop[0]), _lib.ptr(ctx.drop[1]), garr,
-                                                  ctx.ws.data_ptr(), ctx.ws_bytes, _lib.stream_ptr(),
-                                                  None if ev is None else ev.cuda_event), "net_backward")
+            grad_x = None
+            if ctx.input_grad and ctx.needs_input_grad[0]:
+                # opt-in input gradient (SE_UNet(input_grad=True)): per rank, never exchanged; its scratch is separate from the workspace
+                d = ctx.desc
+                grad_x = _fresh((d.batch, d.in_channel, d.d, d.h, d.w), torch.float32, dev)
+                sbytes = lib.seunet_net_input_grad_bytes(C.byref(d))
+                if sbytes == 0:
+                    raise RuntimeError("libseunet_hip net_input_grad_bytes: " + _lib.last_error())
+                scratch = _fresh(sbytes, torch.uint8, dev)
+                _lib.check(lib.seunet_net_backward_input(C.byref(d), parr, g0.data_ptr(), g1.data_ptr(), _lib.ptr(ctx.drop[0]),
+                                                         _lib.ptr(ctx.drop[1]), garr, grad_x.data_ptr(), scratch.data_ptr(), sbytes,
+                                                         ctx.ws.data_ptr(), ctx.ws_bytes, _lib.stream_ptr(),
+                                                         None if ev is None else ev.cuda_event), "net_backward_input")
+            else:
+                _lib.check(lib.seunet_net_backward_ev(C.byref(ctx.desc), parr, g0.data_ptr(), g1.data_ptr(),
+                                                      _lib.ptr(ctx.drop[0]), _lib.ptr(ctx.drop[1]), garr,
+                                                      ctx.ws.data_ptr(), ctx.ws_bytes, _lib.stream_ptr(),
+                                                      None if ev is None else ev.cuda_event), "net_backward")
             if sync is not None:      # data parallel: decoder bucket on the side stream (already under way), the rest here
                 # (with a loss scale the SCALED buffer is what is summed over the ranks; the finiteness test below then runs on the
                 # global sum: an inf / NaN on any one rank is an inf / NaN in every rank's sum, so all ranks drop the step together)
@@ -241,20 +256,29 @@ class _SEUNetFunction(torch.autograd.Function):
                 # ``model.overflow_steps`` when it wants to (and lowers ``model.loss_scale`` if it ever becomes non-zero).
                 # Without ``grad_sync`` (``ddp.allreduce_gradients`` after the backward) the decision is per rank: a rank that
                 # overflowed contributes zeros to the sum; the ranks still apply the same update.
+                # (with an input gradient the decision covers it too: both are kept, unscaled, or both zeroed.  grad_x is per rank,
+                # so under data parallelism an overflow of grad_x alone drops the step on that rank only)
                 ok = torch.isfinite(flat).all()
+                if grad_x is not None:
+                    ok = ok & torch.isfinite(grad_x).all()
+                    grad_x.copy_(torch.where(ok, grad_x * (1.0 / ctx.loss_scale), torch.zeros((), dtype=grad_x.dtype, device=dev)))
                 flat.copy_(torch.where(ok, flat * (1.0 / ctx.loss_scale), torch.zeros((), dtype=flat.dtype, device=dev)))
                 if ctx.overflow is not None:
                     ctx.overflow.add_((~ok).to(ctx.overflow.dtype))
         ctx.ws = None
-        return (None, None, None, None) + tuple(grads)
+        return (grad_x, None, None, None) + tuple(grads)
 
 
 class SE_UNet(nn.Module):
     """Drop-in for the reference ``SE_UNet`` (SE_UNet.py:99-238) on MI355X."""
 
     def __init__(self, in_channel=1, n_classes=1, width_mult=1, negative_slope=0.01,
-                 act_dtype: Optional[str] = None, conv_impl: Optional[int] = None):
+                 act_dtype: Optional[str] = None, conv_impl: Optional[int] = None, input_grad: bool = False):
         super().__init__()
+        # opt-in gradient with respect to the input (saliency maps, a learnable module in front, input optimisation): a plain
+        # attribute, not part of state_dict.  Off: a requires_grad input raises as before.  On: forward accepts it and the
+        # backward also returns x.grad (f32; in bf16 / fp16 storage the gradient with respect to the network's rounded copy of x).
+        self.input_grad = bool(input_grad)
         self.in_channel, self.n_classes = in_channel, n_classes
         self.width_mult, self.negative_slope = width_mult, negative_slope
         self.act_dtype = act_dtype or _default_dtype()
@@ -406,9 +430,9 @@ class SE_UNet(nn.Module):
                                "(the CPU oracle lives in oracle/seunet_oracle.py and is test infrastructure).")
         if x.dim() != 5 or x.shape[1] != self.in_channel:
             raise ValueError(f"expected input (B,{self.in_channel},D,H,W), got {tuple(x.shape)}")
-        if x.requires_grad:
-            raise NotImplementedError("SE_UNet (HIP path) computes no gradient with respect to its input (no reference "
-                                      "caller asks for one); detach() the input")
+        if x.requires_grad and not self.input_grad:
+            raise NotImplementedError("SE_UNet (HIP path) computes no gradient with respect to its input unless asked to "
+                                      "(construct with input_grad=True); detach() the input")
         x = x.contiguous().float()          # callers pass strided views
         b = x.shape[0]
         if drop_scales is not None:
@@ -422,7 +446,8 @@ class SE_UNet(nn.Module):
             d2 = d2.reshape(b, 12).to(x.device, torch.float32).contiguous()
         meta = {"in_channel": self.in_channel, "n_classes": self.n_classes, "width_mult": self.width_mult,
                 "dtype": _lib.dtype_code(self.act_dtype), "conv_impl": self.conv_impl,
-                "negative_slope": float(self.negative_slope), "dead": self._dead, "loss_scale": float(self.loss_scale)}
+                "negative_slope": float(self.negative_slope), "dead": self._dead, "loss_scale": float(self.loss_scale),
+                "input_grad": self.input_grad}
         meta["names"], meta["grad_sync"] = self._names, getattr(self, "grad_sync", None)
         if self.loss_scale != 1.0:
             if self.overflow_steps is None or self.overflow_steps.device != x.device:

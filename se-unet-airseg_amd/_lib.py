@@ -112,6 +112,8 @@ PROTOTYPES = {
     "seunet_net_read_tensor": (_i, [C.POINTER(NetDesc), _pp, _vp, _sz, C.c_char_p, _i, _vp, _ip, _vp]),
     "seunet_net_backward": (_i, [C.POINTER(NetDesc), _pp, _vp, _vp, _vp, _vp, _pp, _vp, _sz, _vp]),
     "seunet_net_backward_ev": (_i, [C.POINTER(NetDesc), _pp, _vp, _vp, _vp, _vp, _pp, _vp, _sz, _vp, _vp]),
+    "seunet_net_input_grad_bytes": (_sz, [C.POINTER(NetDesc)]),
+    "seunet_net_backward_input": (_i, [C.POINTER(NetDesc), _pp, _vp, _vp, _vp, _vp, _pp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

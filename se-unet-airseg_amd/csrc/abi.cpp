@@ -23,7 +23,7 @@ extern "C" {
 // diagnostic hook (not part of the public header): device buffer of 8 u64 that -DSEUNET_STAMP builds add cycle sums to
 int seunet_debug_set_buffer(void* p) { seunet::g_conv_debug = reinterpret_cast<unsigned long long*>(p); return 0; }
 
-int seunet_version(void) { return 200; }
+int seunet_version(void) { return 201; }
 const char* seunet_last_error(void) { return get_error(); }
 
 int seunet_init(int device) {

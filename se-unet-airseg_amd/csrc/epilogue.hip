@@ -647,7 +647,11 @@ __device__ __forceinline__ void pool_locate(const PoolRef& pr, unsigned v, unsig
 //     systematic offset times the voxel count) it was 4.6e-2 off at 1 x 128^3 in fp32 mode -- and so is the fp32 reference.
 //     Instead pass A also sums S_i[c] = sum_v dxhat2[v][c] * x_i[v] (dxhat2 = g * LeakyReLU'; one record per block), and
 //     xw_finalize_kernel forms the gradient in f64 from S_i, sum_v dxhat2 and the input's first / second moments.
-template <typename T, int LPV, bool TWO, bool APPLY, bool XW = false, bool XR = false>
+// XG (pass B of an XR block, only when the network input's gradient is requested): each lane also contracts its eight draw2
+//     values with the x-branch weight, p_k = sum_j draw2[c0 + j] * W2[c0 + j][k] (k < in_channel), the LPV lanes of the voxel add
+//     their p_k in a fixed butterfly order and lane 0 writes (or adds to) gx_out [N][V][in_channel] f32 -- the x-branch's
+//     contribution W2^T draw2 to the input gradient at this level (net.cpp, seunet_net_backward_input).
+template <typename T, int LPV, bool TWO, bool APPLY, bool XW = false, bool XR = false, bool XG = false>
 __global__ void __launch_bounds__(EPI_THREADS)
 cat_bwd_kernel(const T* g_out, const T* __restrict__ raw,
                const float* __restrict__ mean, const float* __restrict__ rstd,
@@ -658,7 +662,9 @@ cat_bwd_kernel(const T* g_out, const T* __restrict__ raw,
                T* dxhat2_out, double* __restrict__ stat_partial,
                double* __restrict__ stat_partial2, long long V,
                const T* __restrict__ xin = nullptr, double* __restrict__ xw_partial = nullptr,
-               const float* __restrict__ w2x = nullptr, int xic = 0, PoolRef pool = PoolRef{}) {
+               const float* __restrict__ w2x = nullptr, int xic = 0, PoolRef pool = PoolRef{},
+               float* __restrict__ gx_out = nullptr, int gx_acc = 0) {
+  static_assert(!XG || (APPLY && XR), "XG: pass B of an XR block only");
   const int n = blockIdx.y, P = gridDim.x;
   const int cg = threadIdx.x % LPV, vb = threadIdx.x / LPV;
   constexpr int VPB = EPI_THREADS / LPV;
@@ -741,6 +747,19 @@ cat_bwd_kernel(const T* g_out, const T* __restrict__ raw,
         else { s[2][j] += (SumT)d2[j]; s[3][j] += (SumT)d2[j] * (SumT)xh; }
       }
       if (APPLY && !XR) store8(dxhat2_out + o, d2);
+      if (XG) {
+        float pa = 0.f, pb = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { pa = fmaf(d2[j], wa[j], pa); pb = fmaf(d2[j], wb[j], pb); }
+        // (the LPV lanes of one voxel share v: all active or all inactive together; the shuffles stay inside the group)
+#pragma unroll
+        for (int off = 1; off < LPV; off <<= 1) { pa += shfl_xor_settled(pa, off); pb += shfl_xor_settled(pb, off); }
+        if (cg == 0) {
+          float* gp = gx_out + ((long long)n * V + v) * xic;
+          gp[0] = gx_acc ? gp[0] + pa : pa;
+          if (xic > 1) gp[1] = gx_acc ? gp[1] + pb : pb;
+        }
+      }
       if (XW && !APPLY) {
         float xi[8];
         if (XR) {
@@ -1110,7 +1129,8 @@ int launch_cat_fwd_x_pool(int dtype, const void* raw, const float* mean, const f
 int launch_cat_bwd_x(int dtype, const void* g_out, const void* raw, const float* mean, const float* rstd, const void* x_in,
                      const float* w2, int in_channel, const float* mean2, const float* rstd2, int C, float slope,
                      const float* m1, const float* m2, const float* m1b, const float* m2b, void* dx, double* stat_partial,
-                     double* stat_partial2, double* xw_partial, Dims d, hipStream_t s, const unsigned* pool_argmax, const void* pool_g) {
+                     double* stat_partial2, double* xw_partial, Dims d, hipStream_t s, const unsigned* pool_argmax, const void* pool_g,
+                     float* gx_out, int gx_acc) {
   if (int e = check_c(C)) return e;
   SEUNET_CHECK(in_channel >= 1 && in_channel <= 2, "cat_epilogue_bwd_x: in_channel %d (1 or 2)", in_channel);
   PoolRef pr{};
@@ -1125,10 +1145,12 @@ int launch_cat_bwd_x(int dtype, const void* g_out, const void* raw, const float*
   const bool apply = m1 != nullptr;
   if (!apply) SEUNET_CHECK(stat_partial && stat_partial2, "cat_epilogue_bwd_x pass A needs the partial buffers");
   else SEUNET_CHECK(m2 && m1b && m2b && dx, "cat_epilogue_bwd_x pass B: missing argument");
+  SEUNET_CHECK(gx_out == nullptr || apply, "cat_epilogue_bwd_x: the input-gradient term is formed in pass B");
   dim3 grid(epi_partials(d) * (apply ? 4 : 1), d.N);
   SEUNET_LPV_SWITCH(C / 8, {
     SEUNET_DTYPE_SWITCH(dtype, {
-      if (apply) cat_bwd_kernel<T, LPV, true, true, false, true><<<grid, EPI_THREADS, 0, s>>>((const T*)g_out, (const T*)raw, mean, rstd, (const T*)x_in, mean2, rstd2, C, slope, m1, m2, m1b, m2b, (T*)dx, nullptr, nullptr, nullptr, d.vox(), nullptr, nullptr, w2, in_channel, pr);
+      if (apply && gx_out) cat_bwd_kernel<T, LPV, true, true, false, true, true><<<grid, EPI_THREADS, 0, s>>>((const T*)g_out, (const T*)raw, mean, rstd, (const T*)x_in, mean2, rstd2, C, slope, m1, m2, m1b, m2b, (T*)dx, nullptr, nullptr, nullptr, d.vox(), nullptr, nullptr, w2, in_channel, pr, gx_out, gx_acc);
+      else if (apply) cat_bwd_kernel<T, LPV, true, true, false, true><<<grid, EPI_THREADS, 0, s>>>((const T*)g_out, (const T*)raw, mean, rstd, (const T*)x_in, mean2, rstd2, C, slope, m1, m2, m1b, m2b, (T*)dx, nullptr, nullptr, nullptr, d.vox(), nullptr, nullptr, w2, in_channel, pr);
       else if (xw_partial) cat_bwd_kernel<T, LPV, true, false, true, true><<<grid, EPI_THREADS, 0, s>>>((const T*)g_out, (const T*)raw, mean, rstd, (const T*)x_in, mean2, rstd2, C, slope, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stat_partial, stat_partial2, d.vox(), nullptr, xw_partial, w2, in_channel, pr);
       else cat_bwd_kernel<T, LPV, true, false, false, true><<<grid, EPI_THREADS, 0, s>>>((const T*)g_out, (const T*)raw, mean, rstd, (const T*)x_in, mean2, rstd2, C, slope, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stat_partial, stat_partial2, d.vox(), nullptr, nullptr, w2, in_channel, pr);
     });

@@ -162,6 +162,14 @@ struct Plan {
   size_t wgrad_ws_bytes;
   size_t total;
   int stat_slots_max;
+  // input gradient (seunet_net_backward_input): a SEPARATE caller-owned scratch buffer, laid out here so that the workspace (and
+  // seunet_net_workspace_bytes) stays what it is -- the per-level x-branch terms gx_l = W_xl^T d2_xl, f32 [N][V_l][in_channel]
+  size_t ig_gx[3] = {0, 0, 0}, ig_total = 0;
+  void plan_input_grad() {
+    size_t c = 0;
+    for (int l = 0; l < 3; ++l) { ig_gx[l] = c; c = align_up(c + (size_t)d.batch * dims[l].vox() * d.in_channel * 4, 256); }
+    ig_total = c;
+  }
 
   size_t cur = 0;
   size_t take(size_t bytes) { size_t o = cur; cur = align_up(cur + bytes, 256); return o; }
@@ -299,6 +307,7 @@ struct Plan {
     xwp = take(xw_max);
     xmom = take(xmom_max);
     total = cur;
+    plan_input_grad();
     return 0;
   }
 };
@@ -309,7 +318,10 @@ struct Exec {
   unsigned char* ws = nullptr;
   const float* const* params = nullptr;
   hipStream_t s = nullptr;
+  float* grad_x = nullptr;             // seunet_net_backward_input: NCDHW f32 input gradient (null = not requested)
+  unsigned char* igs = nullptr;        // its scratch buffer (Plan::ig_gx)
 
+  float* gxl(int l) const { return reinterpret_cast<float*>(igs + p.ig_gx[l]); }
   void mark(const std::string& tag) const { if (prof_on()) prof_mark(tag.c_str(), s); }
   void* at(size_t off) const { return ws + off; }
   float* fat(size_t off) const { return reinterpret_cast<float*>(ws + off); }
@@ -624,6 +636,11 @@ struct Exec {
       }
       if (o.kind == OP_POOL || o.kind == OP_UP) {
         const int t = o.src[0];
+        if (grad_x && o.dst == T_X2) {
+          // pool1x: gx_1 = unpool_1(gx_2), arg-max of the stored X1 (ec63's pass B then adds its own term)
+          mark("input_grad:unpool1");
+          if (int e = launch_xgrad_unpool(p.d.dtype, at(p.feat[T_X1]), p.d.in_channel, gxl(2), gxl(1), p.dims[1], s)) return e;
+        }
         if (is_input(t)) continue;
         SEUNET_CHECK(written[o.dst], "net: internal: gradient of %s output missing", o.name);
         mark((o.kind == OP_POOL ? "pool_bwd:" : "up_bwd:") + n);
@@ -715,7 +732,8 @@ struct Exec {
           mark("in_bwd:" + n);    // pass B
           if (int e = launch_cat_bwd_x(p.d.dtype, at(p.grad[o.dst]), at(r.raw), fat(r.mean), fat(r.rstd), xin, w2, p.d.in_channel, mu2, rs2,
                                        r.cout, p.d.negative_slope, fat(p.m1), fat(p.m2), fat(p.m1b), fat(p.m2b), at(p.grad[o.dst]), nullptr,
-                                       nullptr, nullptr, dm, s, pool_am[o.dst], pool_g[o.dst])) return e;
+                                       nullptr, nullptr, dm, s, pool_am[o.dst], pool_g[o.dst], grad_x ? gxl(lv) : nullptr,
+                                       lv == 1 ? 1 : 0)) return e;
         } else {
           const void* r2 = o.xname ? at(r.raw2) : nullptr;
           if (int e = launch_cat_bwd(p.d.dtype, at(p.grad[o.dst]), at(r.raw), fat(r.mean), fat(r.rstd), r2, mu2, rs2, r.cout,
@@ -730,6 +748,11 @@ struct Exec {
                                      p.d.negative_slope, fat(p.m1), fat(p.m2), o.xname ? fat(p.m1b) : nullptr,
                                      o.xname ? fat(p.m2b) : nullptr, at(p.grad[o.dst]), o.xname ? at(p.gx) : nullptr, nullptr, nullptr,
                                      dm, s)) return e;
+          if (o.xname && grad_x) {   // gx_l (+)= W_x^T d2 from the stored d2 (level 1: on top of unpool_1(gx_2))
+            mark(std::string("input_grad:") + o.xname);
+            if (int e = launch_xgrad_contract(p.d.dtype, at(p.gx), r.cout, P(std::string(o.xname) + ".conv1.weight"), p.d.in_channel,
+                                              gxl(lv), lv == 1 ? 1 : 0, dm, s)) return e;
+          }
           if (o.xname && grads[xi]) {
             mark(std::string("wgrad:") + o.xname);
             SrcList xs{};
@@ -748,6 +771,12 @@ struct Exec {
     if (!zero_ptrs.empty()) {
       mark("stats");
       if (int e = launch_multi_zero(zero_ptrs.data(), zero_counts.data(), (int)zero_ptrs.size(), s)) return e;
+    }
+    if (grad_x) {
+      // grad_x = convT_ec1(draw_ec1) + gx_0 + unpool_0(gx_1); ec1's pass B left draw_ec1 in grad[T_E0]
+      mark("input_grad:ec1");
+      if (int e = launch_input_grad(p.d.dtype, at(p.grad[T_E0]), p.C[T_E0], P("ec1.conv1.weight"), at(p.feat[T_X0]), p.d.in_channel,
+                                    gxl(0), gxl(1), grad_x, p.dims[0], s)) return e;
     }
     mark("outside");
     return 0;
@@ -901,6 +930,30 @@ int seunet_net_backward_ev(const seunet_net_desc* desc, const float* const* para
   Exec ex;
   if (int e = ex.setup(desc, params, workspace, workspace_bytes, (hipStream_t)s)) return e;
   ex.decoder_done = reinterpret_cast<hipEvent_t>(decoder_done_event);
+  return ex.backward(g_pred0, g_pred1, drop1, drop2, grads);
+}
+
+size_t seunet_net_input_grad_bytes(const seunet_net_desc* desc) {
+  if (!desc) { (void)fail("net_input_grad_bytes: null descriptor"); return 0; }
+  Plan p;
+  if (p.init(*desc)) return 0;
+  return p.ig_total;
+}
+
+int seunet_net_backward_input(const seunet_net_desc* desc, const float* const* params, const float* g_pred0, const float* g_pred1,
+                              const float* drop1, const float* drop2, float* const* grads, float* grad_x, void* scratch,
+                              size_t scratch_bytes, void* workspace, size_t workspace_bytes, seunet_stream_t s,
+                              void* decoder_done_event) {
+  if (grad_x == nullptr)
+    return seunet_net_backward_ev(desc, params, g_pred0, g_pred1, drop1, drop2, grads, workspace, workspace_bytes, s, decoder_done_event);
+  SEUNET_CHECK(g_pred0 && g_pred1 && grads && scratch, "net_backward_input: null tensor");
+  Exec ex;
+  if (int e = ex.setup(desc, params, workspace, workspace_bytes, (hipStream_t)s)) return e;
+  SEUNET_CHECK(scratch_bytes >= ex.p.ig_total, "net_backward_input: scratch too small (%zu < %zu bytes)", scratch_bytes, ex.p.ig_total);
+  SEUNET_CHECK((reinterpret_cast<uintptr_t>(scratch) & 255) == 0, "net_backward_input: scratch must be 256-byte aligned");
+  ex.decoder_done = reinterpret_cast<hipEvent_t>(decoder_done_event);
+  ex.grad_x = grad_x;
+  ex.igs = reinterpret_cast<unsigned char*>(scratch);
   return ex.backward(g_pred0, g_pred1, drop1, drop2, grads);
 }
 

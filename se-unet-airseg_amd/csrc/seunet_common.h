@@ -384,7 +384,14 @@ int launch_cat_bwd_x(int dtype, const void* g_out, const void* raw, const float*
                      const float* w2, int in_channel, const float* mean2, const float* rstd2, int C, float slope,
                      const float* m1, const float* m2, const float* m1b, const float* m2b, void* dx, double* stat_partial,
                      double* stat_partial2, double* xw_partial, Dims d, hipStream_t s, const unsigned* pool_argmax = nullptr,
-                     const void* pool_g = nullptr);   // pool_*: gradient of the max-pool consuming the block's output, added on the fly
+                     const void* pool_g = nullptr,    // pool_*: gradient of the max-pool consuming the block's output, added on the fly
+                     float* gx_out = nullptr, int gx_acc = 0);   // pass B: + the x-branch's input-gradient term (XG), [N][V][in_channel] f32
+// input gradient of the network (input_grad.hip; net.cpp seunet_net_backward_input)
+int launch_xgrad_contract(int dtype, const void* d2, int C, const float* w2, int in_channel, float* gx, int accumulate, Dims d,
+                          hipStream_t s);
+int launch_xgrad_unpool(int dtype, const void* x_fine, int in_channel, const float* gx_coarse, float* gx_fine, Dims fine, hipStream_t s);
+int launch_input_grad(int dtype, const void* draw, int ce, const float* w_ec1, const void* x0, int in_channel, const float* gx0,
+                      const float* gx1, float* grad_x, Dims d, hipStream_t s);
 int launch_cat_xgrad_finalize(const double* xw_partial, const double* stat_partial2, int slots, const double* moments, const float* w2,
                               int C, int in_channel, int N, float eps, float* dw, hipStream_t s);
 int launch_xbranch_values(int dtype, const void* x_in, const float* w2, int C, int in_channel, float* out_ncdhw, Dims d, hipStream_t s);   // diagnostic
