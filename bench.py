@@ -12,11 +12,14 @@ train.py:594-599, HIP) -> backward (HIP) -> one flat-bucket RCCL all-reduce of t
 AdamW step (train.py:569,603).  Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
 
 `value` is the conservative whole step (optimizer and all-reduce included).  The same line also carries
-  * `fwd_bwd_only`: SURVEY.md 8(d)'s metric as stated (forward + loss + backward, no optimizer), its own timed loop;
   * `hbm_model_frac` / `mfma_frac`: the step against the 8(d) byte model at 8 TB/s and the FLOP count at the dense MFMA peak;
   * `roofline`: the dominant launch group (chosen from a full per-launch table taken during warm-up), timed with HIP
-    events on the launch stream inside the timed region;
+    events on the launch stream inside the timed region.
+A plain run stops there: set-up, warm-up, the timed steps, `--dump-outputs`, the line.  `--full` adds the legs that take
+runs of their own, after the timed region:
+  * `fwd_bwd_only`: SURVEY.md 8(d)'s metric as stated (forward + loss + backward, no optimizer), its own timed loop;
   * `parity_mode` (N=1): ms/step of the fp32 activation mode, the one that meets north_star's 1e-3 tolerance;
+  * `window512` (N=1): BASELINE configs[3], sliding-window inference over one 512^3 volume, with its own roofline;
   * `fp16_mode` (N=1): ms/step with fp16 activation storage (same bytes / MFMA rate as bf16, 8 x smaller gradient error);
   * `cpu_baseline` (N=1): the CPU oracle (oracle/, torch fp32, the reference's op sequence), 1 warm-up + 3 timed steps.
 
@@ -137,17 +140,20 @@ def parse_args():
     ap.add_argument("--train-mode", action="store_true", help="model.train(): DropLayer active (the reference's training callers)")
     ap.add_argument("--no-optimizer", action="store_true")
     ap.add_argument("--torch-optimizer", action="store_true", help="torch.optim.AdamW instead of the fused seunet AdamW (SURVEY 8(f1))")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the fwd_bwd_only and parity_mode legs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps also run the legs that take runs of their own: fwd_bwd_only, and at N=1 "
+                         "parity_mode, window512, fp16_mode and cpu_baseline (about 40 s more); a plain run ends after the timed steps")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the fwd_bwd_only, parity_mode, window512 and fp16_mode legs")
     ap.add_argument("--no-kernel-timing", action="store_true", help="do not record HIP events inside the timed region")
-    ap.add_argument("--cpu-size", type=int, default=128)
+    ap.add_argument("--cpu-size", type=int, default=128, help="with --full: edge of the cpu_baseline volume")
     ap.add_argument("--dump-kernels", default="", help="write the full per-launch-group timing table (TSV) here")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="after the timed steps, write what the last one computed (loss, logits, gradients, updated parameters) "
                          "as DIR/<name>.npy (float32, seeded samples of the large arrays, at most 40 MB in all)")
     ap.add_argument("--config", default="window512", choices=["", "none", "window512"],
-                    help="window512 (default at N=1): also time BASELINE configs[3] (one 512^3 volume, 128^3 windows, stride 64, 343 "
-                         "windows, forward only; ~3 s) and report it under `window512`; none: skip it")
+                    help="window512 (default; with --full at N=1): also time BASELINE configs[3] (one 512^3 volume, 128^3 windows, stride "
+                         "64, 343 windows, forward only; ~3 s) and report it under `window512`; none: skip it")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
@@ -444,8 +450,9 @@ def main():
                     out["roofline"]["traffic"] = t["hbm_bytes_per_launch"]
                     out["roofline"]["traffic_source"] = os.path.relpath(tpath, ROOT) + " (rocprofv3 --pmc over bench.py, per launch)"
 
+    # the legs from here on take runs of their own and the headline needs none of them: --full only
     # ---- SURVEY 8(d)'s metric as stated: forward + loss + backward (+ the gradient all-reduce for N > 1), no optimizer
-    if not args.no_secondary and not args.no_optimizer:
+    if args.full and not args.no_secondary and not args.no_optimizer:
         step2 = make_step(model, None)
         step2()
         dt2, per2, _ = timed(step2, args.steps)
@@ -454,7 +461,7 @@ def main():
                                "what": "forward + stage-1 loss + backward" + (" + gradient all-reduce" if world > 1 else "") + ", no optimizer step (SURVEY.md 8(d))"}
 
     # ---- the 1e-3-parity mode (fp32 activations, f64 InstanceNorm sums): a driver-timed number for it (N=1 only)
-    if not args.no_secondary and world == 1 and args.dtype != "fp32":
+    if args.full and not args.no_secondary and world == 1 and args.dtype != "fp32":
         del model, opt, step
         torch.cuda.empty_cache()
         m32 = make_model("fp32")
@@ -512,7 +519,7 @@ def main():
             del m16, s16
             torch.cuda.empty_cache()
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import seunet_oracle as orc
         cores = host_cores()
