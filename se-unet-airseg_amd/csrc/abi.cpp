@@ -132,10 +132,11 @@ int seunet_conv3d_wgrad(int dtype, int impl, int taps, int dilation, int nsrc, c
   SEUNET_CHECK(dy && dw, "conv3d_wgrad: null tensor");
   if (impl == SEUNET_CONV_NAIVE) return launch_wgrad_naive(dtype, taps, dilation, sl, cin, dy, cout, dw, D(dims), S(s));
   SEUNET_CHECK(workspace, "conv3d_wgrad: null workspace");
-  if (impl == SEUNET_CONV_MARCH)
-    return taps == 1 ? launch_wgrad_1x1(dtype, sl, cin, dy, cout, dw, workspace, workspace_bytes, D(dims), S(s))
-                     : launch_wgrad_march(dtype, taps, dilation, sl, cin, dy, cout, dw, workspace, workspace_bytes, D(dims), S(s));
-  return launch_wgrad(dtype, taps, dilation, sl, cin, dy, cout, dw, workspace, workspace_bytes, D(dims), S(s), impl != SEUNET_CONV_TILED);
+  // SEUNET_CONV_MARCH / SEUNET_CONV_TILED force a kernel; anything else picks by size, as the network's plan does
+  const ConvKernel k = impl == SEUNET_CONV_MARCH ? (taps == 1 ? ConvKernel::Wgrad1x1 : ConvKernel::March)
+                       : impl == SEUNET_CONV_TILED ? ConvKernel::Tiled
+                                                   : wgrad_kernel(dtype, taps, dilation, sl, cin, cout, D(dims), sl.gap());
+  return run_wgrad(k, dtype, taps, dilation, sl, cin, dy, cout, dw, workspace, workspace_bytes, D(dims), S(s));
 }
 
 int seunet_epilogue_slots(seunet_dims dims) { return epi_partials(D(dims)); }

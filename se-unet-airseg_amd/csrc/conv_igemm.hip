@@ -7,7 +7,7 @@
 //                 accumulators hold the transposed tile: a lane owns one voxel (x = lane % 32) and runs of 4
 //                 consecutive output channels -- what a channels-last store wants
 //   workgroup     256 threads = 4 waves; output tile 4(z) x 4(y) x 32(x) voxels; wave w owns z-slice w,
-//                 i.e. four 32-voxel x-rows, times all output-channel columns of the tile (32 or 64)
+//                 i.e. four 32-voxel x-rows, times the 32 output-channel columns of the tile
 //   dilation 2    decomposes into 8 independent dilation-1 problems on the parity sub-lattices
 //                 (voxel = 2*lattice + parity): the tile lives on one sub-lattice, so the halo is 1 lattice
 //                 voxel (39 KB tile) instead of 2 voxels (74 KB), and the rest of the kernel is unchanged
@@ -102,8 +102,8 @@ __device__ __forceinline__ double xlane_swz16(double v) {
 #define STAMP(i) do {} while (0)
 #endif
 
-template <typename T, int NSUB, int TAPS, int DIL>
-__global__ void __launch_bounds__(256, (TAPS == 1 && NSUB == 1) ? 3 : 1)   // 1x1x1 is bandwidth bound: keep 3 workgroups per CU
+template <typename T, int TAPS, int DIL>
+__global__ void __launch_bounds__(256, TAPS == 1 ? 3 : 1)   // 1x1x1 is bandwidth bound: keep 3 workgroups per CU
 conv_igemm_kernel(ConvKArgs a) {
 #ifdef SEUNET_STAMP
   unsigned long long ph[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -114,7 +114,7 @@ conv_igemm_kernel(ConvKArgs a) {
   constexpr int STEP = (TAPS == 27) ? DIL : 1;              // voxel stride of the (sub-)lattice
   constexpr int HZ = CV_TZ + 2 * HALO, HY = CV_TY + 2 * HALO, HX = CV_TX + 2 * HALO;
   constexpr int NVH = HZ * HY * HX;
-  constexpr int NCOL = 32 * NSUB;
+  constexpr int NCOL = 32;
   constexpr int T3 = (TAPS == 27) ? 3 : 1;
   constexpr int IN_ITEMS = (NVH * 2 + 255) / 256;           // 16-B pieces per thread (LDS region padded to IN_ITEMS*4 KB)
   constexpr int W_TOTAL = TAPS * NCOL * 2;                  // 16-byte pieces of one weight slab
@@ -185,9 +185,7 @@ conv_igemm_kernel(ConvKArgs a) {
     const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
     return reinterpret_cast<const void*>(((unsigned long long)hi << 32) | lo);
   };
-  // The fetch of one chunk is split into its descriptors (scalar work, once per chunk) and IN_ITEMS + W_ITEMS single
-  // wave-instructions, so that the K loop can issue them one per tap between the MFMAs: issued as one block they
-  // hold the wave for ~1.5k cycles (the texture path takes 16+ cycles per 1-KB instruction) with the matrix pipe idle.
+  // The fetch of one chunk: its descriptors (scalar work, once per chunk), then IN_ITEMS + W_ITEMS single wave-instructions.
   __amdgpu_buffer_rsrc_t rs_in, rs_w;
   unsigned in_stride = 0;
   unsigned pofs = 0;        // paired mode: byte offset of this lane's piece inside the chunk
@@ -227,21 +225,12 @@ conv_igemm_kernel(ConvKArgs a) {
     }
   };
   constexpr int F_ITEMS = IN_ITEMS + W_ITEMS;
-  constexpr int F_PER_TAP = (F_ITEMS + TAPS - 1) / TAPS;
-  auto fetch_range = [&](auto first_c) __attribute__((always_inline)) {   // items [first, first + F_PER_TAP)
-    constexpr int first = decltype(first_c)::value;
-    [&]<int... I>(std::integer_sequence<int, I...>) __attribute__((always_inline)) {
-      (fetch_item(std::integral_constant<int, first + I>{}), ...);
-    }(std::make_integer_sequence<int, F_PER_TAP>{});
-  };
 
-  f32x16 acc[4][NSUB];
+  f32x16 acc[4];
 #pragma unroll
   for (int ms = 0; ms < 4; ++ms)
 #pragma unroll
-    for (int ns = 0; ns < NSUB; ++ns)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[ms][ns][r] = 0.f;
+    for (int r = 0; r < 16; ++r) acc[ms][r] = 0.f;
 
   fetch_setup(0);
   [&]<int... I>(std::integer_sequence<int, I...>) __attribute__((always_inline)) {
@@ -258,32 +247,27 @@ conv_igemm_kernel(ConvKArgs a) {
     STAMP(2);   // wait for the fetched registers + LDS writes
     __syncthreads();
     STAMP(3);   // barrier 2
-    // Next chunk's fetch.  64 columns (one workgroup per CU, nothing else to fill the matrix pipe): issued one item
-    // per tap between the MFMAs below (measured -9..-11 % on 128->64 @64^3).  32 columns (two workgroups per CU): as
-    // one block here -- interleaved it ran 20 % slower (a wave blocked on a full vector-memory queue cannot issue
-    // its MFMAs either, while as a block the other workgroup's MFMAs cover the issue time).
-    constexpr bool INTERLEAVE = NSUB == 2;
-    const bool has_next = chunk + 1 < a.nchunks;
-    if (has_next) {
+    // Next chunk's fetch, as one block (two workgroups per CU): interleaved one item per tap between the MFMAs below it
+    // ran 20 % slower -- a wave blocked on a full vector-memory queue cannot issue its MFMAs either, while as a block the
+    // other workgroup's MFMAs cover the issue time.
+    if (chunk + 1 < a.nchunks) {
       fetch_setup(chunk + 1);
-      if constexpr (!INTERLEAVE) {
-        [&]<int... I>(std::integer_sequence<int, I...>) __attribute__((always_inline)) {
-          (fetch_item(std::integral_constant<int, I>{}), ...);
-        }(std::make_integer_sequence<int, F_ITEMS>{});
-      }
+      [&]<int... I>(std::integer_sequence<int, I...>) __attribute__((always_inline)) {
+        (fetch_item(std::integral_constant<int, I>{}), ...);
+      }(std::make_integer_sequence<int, F_ITEMS>{});
     }
     STAMP(4);   // prefetch issue
 
     // ---- MFMA over taps, software-pipelined by hand ----
-    // One step = one tap (bf16) or one (tap, 2-channel K-step) (f32): 1 + ... fragments of weights (NSUB) and voxels (4
-    // y-rows), 4 * NSUB MFMAs.  The fragments of step s + 1 are requested before the MFMAs of step s issue (two
+    // One step = one tap (bf16) or one (tap, 2-channel K-step) (f32): 1 + 4 fragments of weights and voxels (4
+    // y-rows), 4 MFMAs.  The fragments of step s + 1 are requested before the MFMAs of step s issue (two
     // register sets, compile-time indices); __builtin_amdgcn_sched_barrier keeps that order, so the live set is what is
     // written here -- left to the scheduler the loop either waited for each read (lgkmcnt(0) before most MFMAs) or, fully
     // unrolled, hoisted reads until the kernel no longer fitted two workgroups per CU.
     {
       constexpr int NST = TAPS * KSTEPS;
       typedef typename std::conditional<sizeof(T) == 2, bf16x8, float>::type FragT;
-      FragT wf[2][NSUB], af[2][4];
+      FragT wf[2], af[2][4];
       auto load_step = [&](auto st_c) __attribute__((always_inline)) {
         constexpr int st = decltype(st_c)::value;
         if constexpr (st < NST) {
@@ -291,16 +275,12 @@ conv_igemm_kernel(ConvKArgs a) {
           constexpr int tz3 = tap / (T3 * T3), ty3 = (tap / T3) % T3, tx3 = tap % T3;
           constexpr int voff = ((tz3 * HALO) * HY + ty3 * HALO) * HX + tx3 * HALO;
           if constexpr (sizeof(T) == 2) {
-#pragma unroll
-            for (int ns = 0; ns < NSUB; ++ns)
-              wf[b][ns] = *reinterpret_cast<const bf16x8*>(wfrag0 + (tap * 2 * NCOL + ns * 32) * 16);
+            wf[b] = *reinterpret_cast<const bf16x8*>(wfrag0 + tap * 2 * NCOL * 16);
 #pragma unroll
             for (int ms = 0; ms < 4; ++ms)
               af[b][ms] = *reinterpret_cast<const bf16x8*>(afrag0 + (voff + ms * HX) * 16);
           } else {
-#pragma unroll
-            for (int ns = 0; ns < NSUB; ++ns)
-              wf[b][ns] = *reinterpret_cast<const float*>(wfrag0 + ((tap * 4 + ks) * 2 * NCOL + ns * 32) * 4);
+            wf[b] = *reinterpret_cast<const float*>(wfrag0 + (tap * 4 + ks) * 2 * NCOL * 4);
 #pragma unroll
             for (int ms = 0; ms < 4; ++ms)
               af[b][ms] = *reinterpret_cast<const float*>(afrag0 + (ks >> 1) * PLANE + 8 * (ks & 1) + (voff + ms * HX) * 16);
@@ -313,18 +293,13 @@ conv_igemm_kernel(ConvKArgs a) {
           constexpr int b = ST & 1;
           load_step(std::integral_constant<int, ST + 1>{});
           __builtin_amdgcn_sched_barrier(0);   // (the reads stay ahead of this step's MFMAs)
-          if constexpr (INTERLEAVE && (ST % KSTEPS) == 0) {
-            if (has_next) fetch_range(std::integral_constant<int, (ST / KSTEPS) * F_PER_TAP>{});   // wave-uniform
+#pragma unroll
+          for (int ms = 0; ms < 4; ++ms) {
+            if constexpr (sizeof(T) == 2)
+              acc[ms] = mfma32_16bit<T>(wf[b], af[b][ms], acc[ms]);
+            else
+              acc[ms] = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[b], af[b][ms], acc[ms], 0, 0, 0);
           }
-#pragma unroll
-          for (int ms = 0; ms < 4; ++ms)
-#pragma unroll
-            for (int ns = 0; ns < NSUB; ++ns) {
-              if constexpr (sizeof(T) == 2)
-                acc[ms][ns] = mfma32_16bit<T>(wf[b][ns], af[b][ms], acc[ms][ns]);
-              else
-                acc[ms][ns] = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[b][ns], af[b][ms], acc[ms][ns], 0, 0, 0);
-            }
           __builtin_amdgcn_sched_barrier(0);
         }(), ...);
       }(std::make_integer_sequence<int, NST>{});
@@ -334,8 +309,8 @@ conv_igemm_kernel(ConvKArgs a) {
 
   // ---- epilogue ----
   // The MFMAs ran with the weights as the A operand, so the accumulators are the TRANSPOSED tile: lane (col, h) holds
-  // voxel x = col of the four y-rows ms, and register r of acc[ms][ns] is output channel
-  //     ch(ns, r, h) = ns*32 + (r & 3) + 8*(r >> 2) + 4*h,
+  // voxel x = col of the four y-rows ms, and register r of acc[ms] is output channel
+  //     ch(r, h) = (r & 3) + 8*(r >> 2) + 4*h,
   // i.e. four runs of 4 consecutive channels per lane: exactly what a channels-last store wants (8-B / 16-B pieces,
   // the h = 0 / 1 lanes writing adjacent pieces), with no transposition through LDS and no workgroup barrier between
   // the K loop and the stores.
@@ -352,14 +327,12 @@ conv_igemm_kernel(ConvKArgs a) {
   // (1) bias
   if (a.bias != nullptr) {
 #pragma unroll
-    for (int ns = 0; ns < NSUB; ++ns)
+    for (int r = 0; r < 16; ++r) {
+      const int co = ntile * NCOL + (r & 3) + 8 * (r >> 2) + 4 * h;
+      const float bias = co < a.cout ? a.bias[co] : 0.f;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int co = ntile * NCOL + ns * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-        const float bias = co < a.cout ? a.bias[co] : 0.f;
-#pragma unroll
-        for (int ms = 0; ms < 4; ++ms) acc[ms][ns][r] += bias;
-      }
+      for (int ms = 0; ms < 4; ++ms) acc[ms][r] += bias;
+    }
   }
   // (2) InstanceNorm partial sums of this wave's 128 voxels (fixed order, hence deterministic).  Per channel the
   //     deviations from one of its values (the wave's first voxel) are summed in f32 -- they are of the order of the
@@ -382,17 +355,17 @@ conv_igemm_kernel(ConvKArgs a) {
     // parity mode, whose gradients are ill-conditioned enough to see an f32 reduction tree
     typedef typename std::conditional<sizeof(T) == 4, double, float>::type R;
 #pragma unroll
-    for (int ns = 0; ns < NSUB; ++ns) {
+    for (int once = 0; once < 1; ++once) {   // (one trip: without the loop the compiler schedules this epilogue differently)
       float v0[16];
       R val[32];   // val[0..15] sums, val[16..31] sums of squares
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         // the shift: this channel's value at the half-wave's first lane, y-row 0 (any value of the channel will do)
-        v0[r] = dpp_settle(__builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((lane & 32) * 4, __builtin_bit_cast(int, acc[0][ns][r]))));
+        v0[r] = dpp_settle(__builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((lane & 32) * 4, __builtin_bit_cast(int, acc[0][r]))));
         R p1 = 0, p2 = 0;
 #pragma unroll
         for (int ms = 0; ms < 4; ++ms) {
-          const R dv = vok[ms] ? (R)acc[ms][ns][r] - (R)v0[r] : (R)0;   // (exact in the f64 mode)
+          const R dv = vok[ms] ? (R)acc[ms][r] - (R)v0[r] : (R)0;   // (exact in the f64 mode)
           p1 += dv;
           p2 += dv * dv;
         }
@@ -434,7 +407,7 @@ conv_igemm_kernel(ConvKArgs a) {
       const double d0 = (double)sh, dc = (double)cntf;
       const double tot = j < 16 ? (double)mine + dc * d0
                                 : (double)mine + 2.0 * d0 * (double)s_of_q + dc * d0 * d0;
-      const int cl = ns * 32 + (rj & 3) + 8 * (rj >> 2) + 4 * h;
+      const int cl = (rj & 3) + 8 * (rj >> 2) + 4 * h;
       red[(wave * NCOL + cl) * 2 + (j >> 4)] = tot;
     }
   }
@@ -456,10 +429,10 @@ conv_igemm_kernel(ConvKArgs a) {
     const unsigned long long dp0 = reinterpret_cast<unsigned long long>(a.dst0), dp1 = reinterpret_cast<unsigned long long>(a.dst1),
                              dp2 = reinterpret_cast<unsigned long long>(a.dst2);
 #pragma unroll
-    for (int ns = 0; ns < NSUB; ++ns) {
+    for (int once = 0; once < 1; ++once) {   // (one trip, as above)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const int co8 = ntile * NCOL + ns * 32 + 8 * q;
+        const int co8 = ntile * NCOL + 8 * q;
         if (co8 >= a.cout) continue;
         // which destination: by arithmetic, not select chains over the argument struct's fields -- those the compiler
         // turns into a scratch lookup table whose reload waits (s_waitcnt vmcnt(0)) for every store issued so far
@@ -481,7 +454,7 @@ conv_igemm_kernel(ConvKArgs a) {
           const unsigned off = vok[ms] ? vlin[ms] * dstride + hofs : 0x80000000u;   // beyond any admitted sample: dropped
           float v[4];
 #pragma unroll
-          for (int i = 0; i < 4; ++i) v[i] = acc[ms][ns][4 * q + i];
+          for (int i = 0; i < 4; ++i) v[i] = acc[ms][4 * q + i];
           if constexpr (sizeof(T) == 2) {
             typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
             if (dacc) {
@@ -514,25 +487,23 @@ conv_igemm_kernel(ConvKArgs a) {
     constexpr int CPP = 16 / (int)sizeof(T);                  // channels per piece
     unsigned char* stage = smem + wave * (128 * ROWB);
 #pragma unroll
-    for (int ns = 0; ns < NSUB; ++ns)
+    for (int ms = 0; ms < 4; ++ms)
 #pragma unroll
-      for (int ms = 0; ms < 4; ++ms)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          unsigned char* sp = stage + (ms * 32 + col) * ROWB + (ns * 32 + 8 * q + 4 * h) * (int)sizeof(T);
-          if constexpr (sizeof(T) == 2) {
-            typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-            u32x2 u;
-            u.x = pack2<T>(acc[ms][ns][4 * q], acc[ms][ns][4 * q + 1]);
-            u.y = pack2<T>(acc[ms][ns][4 * q + 2], acc[ms][ns][4 * q + 3]);
-            *reinterpret_cast<u32x2*>(sp) = u;
-          } else {
-            u32x4 u;
-            u.x = __float_as_uint(acc[ms][ns][4 * q]); u.y = __float_as_uint(acc[ms][ns][4 * q + 1]);
-            u.z = __float_as_uint(acc[ms][ns][4 * q + 2]); u.w = __float_as_uint(acc[ms][ns][4 * q + 3]);
-            *reinterpret_cast<u32x4*>(sp) = u;
-          }
+      for (int q = 0; q < 4; ++q) {
+        unsigned char* sp = stage + (ms * 32 + col) * ROWB + (8 * q + 4 * h) * (int)sizeof(T);
+        if constexpr (sizeof(T) == 2) {
+          typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+          u32x2 u;
+          u.x = pack2<T>(acc[ms][4 * q], acc[ms][4 * q + 1]);
+          u.y = pack2<T>(acc[ms][4 * q + 2], acc[ms][4 * q + 3]);
+          *reinterpret_cast<u32x2*>(sp) = u;
+        } else {
+          u32x4 u;
+          u.x = __float_as_uint(acc[ms][4 * q]); u.y = __float_as_uint(acc[ms][4 * q + 1]);
+          u.z = __float_as_uint(acc[ms][4 * q + 2]); u.w = __float_as_uint(acc[ms][4 * q + 3]);
+          *reinterpret_cast<u32x4*>(sp) = u;
         }
+      }
     __builtin_amdgcn_wave_barrier();   // LDS operations of one wave complete in order
     STAMP(9);   // stage writes
     {
@@ -654,27 +625,24 @@ __global__ void conv_pack_multi_kernel(PackList l) {
 // >= 64 -> > 32 channel layers (128 -> 64 ran 10 % faster that way).  Since the column blocks of one tile run back to back on
 // one XCD (the second finds the input tile in that L2), two 32-column workgroups per CU win everywhere: dc3 forward 0.47 ->
 // 0.45 ms, data gradient 0.52 -> 0.47 ms, the 128 -> 64 1x1x1 blocks 0.14 -> 0.12 ms, the 16^3-level layers 0.033 -> 0.022 ms
-// (17.53 -> 17.20 ms per step).  SEUNET_CONV_NCOL=64 restores the old rule for A/B timing.
-static inline int conv_ncol(int cin_e, int cout_e) {
-  static const bool wide = [] { const char* e = getenv("SEUNET_CONV_NCOL"); return e && atoi(e) == 64; }();
-  return (wide && cout_e > 32 && cin_e >= 64) ? 64 : 32;
-}
+// (17.53 -> 17.20 ms per step).
+static constexpr int CV_NCOL = 32;
 unsigned long long* g_conv_debug = nullptr;   // set by seunet_debug_set_buffer (diagnostic builds)
 static inline int conv_kc(int dtype) { return dtype_size(dtype) == 2 ? 16 : 8; }
 
 size_t conv_wpack_bytes(int dtype, int taps, int cin, int cout) {
-  const int ncol = conv_ncol(cin, cout), ntiles = cdiv(cout, ncol), nchunks = cdiv(cin, conv_kc(dtype));
-  return (size_t)ntiles * nchunks * taps * ncol * 32;
+  const int ntiles = cdiv(cout, CV_NCOL), nchunks = cdiv(cin, conv_kc(dtype));
+  return (size_t)ntiles * nchunks * taps * CV_NCOL * 32;
 }
 
 int launch_conv_pack_weights(int dtype, const float* w, int taps, int cin_w, int cout_w, int tflip,
                              void* wpack, hipStream_t s) {
   SEUNET_CHECK(taps == 27 || taps == 1, "conv pack: taps=%d unsupported", taps);
   const int cin_e = tflip ? cout_w : cin_w, cout_e = tflip ? cin_w : cout_w;
-  const int ncol = conv_ncol(cin_e, cout_e), nchunks = cdiv(cin_e, conv_kc(dtype));
+  const int nchunks = cdiv(cin_e, conv_kc(dtype));
   const long long total = (long long)(conv_wpack_bytes(dtype, taps, cin_e, cout_e) / dtype_size(dtype));
   const int grid = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
-  SEUNET_DTYPE_SWITCH(dtype, conv_pack_kernel<T><<<grid, 256, 0, s>>>(w, taps, cin_w, cout_w, tflip, (T*)wpack, cin_e, cout_e, nchunks, ncol, total));
+  SEUNET_DTYPE_SWITCH(dtype, conv_pack_kernel<T><<<grid, 256, 0, s>>>(w, taps, cin_w, cout_w, tflip, (T*)wpack, cin_e, cout_e, nchunks, CV_NCOL, total));
   SEUNET_LAUNCH_CHECK();
   return 0;
 }
@@ -689,7 +657,7 @@ int launch_conv_pack_weights_multi(int dtype, const ConvPackJob* jobs, int n, hi
       PackEntry& e = l.e[i];
       e.w = j.w; e.out = j.wpack; e.taps = j.taps; e.cin_w = j.cin_w; e.cout_w = j.cout_w; e.tflip = j.tflip;
       e.cin_e = j.tflip ? j.cout_w : j.cin_w; e.cout_e = j.tflip ? j.cin_w : j.cout_w;
-      e.ncol = conv_ncol(e.cin_e, e.cout_e); e.nchunks = cdiv(e.cin_e, conv_kc(dtype));
+      e.ncol = CV_NCOL; e.nchunks = cdiv(e.cin_e, conv_kc(dtype));
       e.total = (long long)(conv_wpack_bytes(dtype, j.taps, e.cin_e, e.cout_e) / dtype_size(dtype));
     }
     SEUNET_DTYPE_SWITCH(dtype, conv_pack_multi_kernel<T><<<dim3(64, m), 256, 0, s>>>(l));
@@ -704,25 +672,25 @@ int conv_stats_tiles(Dims d, int taps, int dil) {
   return cdiv(cdiv(d.D, st), CV_TZ) * cdiv(cdiv(d.H, st), CV_TY) * cdiv(cdiv(d.W, st), CV_TX) * st * st * st;
 }
 
-template <typename T, int NSUB, int TAPS, int DIL>
+template <typename T, int TAPS, int DIL>
 static int launch_one(const ConvKArgs& a, dim3 grid, hipStream_t s) {
   constexpr int HALO = (TAPS == 27) ? 1 : 0;
   constexpr int NVH = (CV_TZ + 2 * HALO) * (CV_TY + 2 * HALO) * (CV_TX + 2 * HALO);
-  constexpr int LDS_K = ((NVH * 2 + 255) / 256 + (TAPS * 64 * NSUB + 255) / 256) * 4096 + 128;   // K-loop tiles, padded to whole staging rounds
-  constexpr int LDS_E = 4 * 128 * (32 * NSUB * (int)sizeof(T) + 16);                       // the four waves' store stages
-  constexpr int LDS = (LDS_K > LDS_E ? LDS_K : LDS_E) + 4 * 32 * NSUB * 16;                // + the statistics partials
+  constexpr int LDS_K = ((NVH * 2 + 255) / 256 + (TAPS * 64 + 255) / 256) * 4096 + 128;   // K-loop tiles, padded to whole staging rounds
+  constexpr int LDS_E = 4 * 128 * (32 * (int)sizeof(T) + 16);                       // the four waves' store stages
+  constexpr int LDS = (LDS_K > LDS_E ? LDS_K : LDS_E) + 4 * 32 * 16;                // + the statistics partials
   static unsigned long long configured = 0;   // per instantiation: devices on which the LDS limit was raised
-  if (int e = configure_kernel_lds(configured, reinterpret_cast<const void*>(&conv_igemm_kernel<T, NSUB, TAPS, DIL>), LDS)) return e;
-  conv_igemm_kernel<T, NSUB, TAPS, DIL><<<grid, 256, LDS, s>>>(a);
+  if (int e = configure_kernel_lds(configured, reinterpret_cast<const void*>(&conv_igemm_kernel<T, TAPS, DIL>), LDS)) return e;
+  conv_igemm_kernel<T, TAPS, DIL><<<grid, 256, LDS, s>>>(a);
   SEUNET_LAUNCH_CHECK();
   return 0;
 }
 
 template <typename T>
-static int launch_t(int taps, int dil, int nsub, const ConvKArgs& a, dim3 grid, hipStream_t s) {
-  if (taps == 1) return nsub == 1 ? launch_one<T, 1, 1, 1>(a, grid, s) : launch_one<T, 2, 1, 1>(a, grid, s);
-  if (dil == 1) return nsub == 1 ? launch_one<T, 1, 27, 1>(a, grid, s) : launch_one<T, 2, 27, 1>(a, grid, s);
-  return nsub == 1 ? launch_one<T, 1, 27, 2>(a, grid, s) : launch_one<T, 2, 27, 2>(a, grid, s);
+static int launch_t(int taps, int dil, const ConvKArgs& a, dim3 grid, hipStream_t s) {
+  if (taps == 1) return launch_one<T, 1, 1>(a, grid, s);
+  if (dil == 1) return launch_one<T, 27, 1>(a, grid, s);
+  return launch_one<T, 27, 2>(a, grid, s);
 }
 
 static int check_lists(const SrcList& src, const DstList& dst) {
@@ -766,8 +734,7 @@ int launch_conv_igemm(int dtype, int taps, int dil, const SrcList& src, int cin_
   a.direct = 1;   // voxel pitch of every destination <= 32 B (dilation 2 writes every other voxel: pitch doubles)
   for (int i = 0; i < dst.n; ++i) if (dst.C[i] * st > 16) a.direct = 0;
   a.debug = g_conv_debug;
-  const int ncol = conv_ncol(a.cin, a.cout);
-  a.ncb = cdiv(a.cout, ncol);
+  a.ncb = cdiv(a.cout, CV_NCOL);
   dim3 grid(a.tx * a.ty * a.tz * st * st * st * a.ncb, 1, d.N);
   SEUNET_CHECK(d.N <= 65535, "conv: batch too large");
   // the staging loads use 32-bit byte offsets inside one sample of one source tensor
@@ -779,7 +746,7 @@ int launch_conv_igemm(int dtype, int taps, int dil, const SrcList& src, int cin_
     SEUNET_CHECK((long long)d.vox() * dst.C[i] * (long long)dtype_size(dtype) < (1LL << 31),
                  "conv: one sample of destination %d is %lld bytes; the MFMA path addresses < 2^31 bytes per sample",
                  i, (long long)d.vox() * dst.C[i] * (long long)dtype_size(dtype));
-  SEUNET_DTYPE_SWITCH(dtype, return (launch_t<T>(taps, dil, ncol / 32, a, grid, s)));
+  SEUNET_DTYPE_SWITCH(dtype, return (launch_t<T>(taps, dil, a, grid, s)));
   return 1;
 }
 

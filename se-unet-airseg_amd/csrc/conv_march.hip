@@ -39,32 +39,6 @@ typedef f16_t mf16x8 __attribute__((ext_vector_type(8)));
 typedef float mf32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int mu32x2 __attribute__((ext_vector_type(2)));
 
-// The matrix instruction as inline asm with the accumulator pinned to the accumulator half of the register file ("+a": D = C,
-// in place) and the weights / voxels in the other half.  Through the builtin the register allocator moved accumulator sets
-// between the two halves (D != C, copies through v_accvgpr_*) until a 377-register kernel no longer fitted 512.  Hazards: the
-// asm's operands are ordinary data dependencies (the compiler still waits for the LDS reads that produce them); an accumulator
-// is read by vector instructions (the lazy epilogue) a whole step after its last MFMA, and re-initialised after that read.
-// WA = 1: the weight fragment lives in the accumulator half too (K-step 1 of the 64-channel layers: 216 weight registers).
-template <typename T, int WA> __device__ __forceinline__ void mm16_acc(mf32x4& c, mbf16x8 a, mbf16x8 b) {
-  if constexpr (std::is_same<T, f16_t>::value) {
-    if constexpr (WA) asm("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(c) : "a"(a), "v"(b));
-    else asm("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
-  } else {
-    if constexpr (WA) asm("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(c) : "a"(a), "v"(b));
-    else asm("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
-  }
-}
-// first MFMA of an accumulator: C = the bias vector (accumulator half, like D) or the constant 0
-template <typename T, int WA, bool BIAS> __device__ __forceinline__ void mm16_init(mf32x4& c, mbf16x8 a, mbf16x8 b, const mf32x4& c0) {
-  if constexpr (std::is_same<T, f16_t>::value) {
-    if constexpr (BIAS) asm("v_mfma_f32_16x16x32_f16 %0, %1, %2, %3" : "=&a"(c) : "v"(a), "v"(b), "a"(c0));
-    else asm("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=a"(c) : "v"(a), "v"(b));
-  } else {
-    if constexpr (BIAS) asm("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %3" : "=&a"(c) : "v"(a), "v"(b), "a"(c0));
-    else asm("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=a"(c) : "v"(a), "v"(b));
-  }
-}
-
 template <typename T> __device__ __forceinline__ mf32x4 mm16b(mbf16x8 a, mbf16x8 b, mf32x4 c) {
   if constexpr (std::is_same<T, f16_t>::value)
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(mf16x8, a), __builtin_bit_cast(mf16x8, b), c, 0, 0, 0);
@@ -88,10 +62,7 @@ struct MarchArgs {
 };
 
 static constexpr int MA_TX = 32, MA_NW = 4, MA_HXP = 36, MA_PF = 2, MA_RING = 3;
-#ifndef SEUNET_MARCH_PFD
-#define SEUNET_MARCH_PFD 1
-#endif
-static constexpr int MA_PFD = SEUNET_MARCH_PFD;   // fragment prefetch distance in units
+static constexpr int MA_PFD = 1;   // fragment prefetch distance in units
 
 template <int KS, int NGW, int RYW, int DIL, int MODE> struct MarchGeo {
   static constexpr int RGW = MA_NW / NGW, RY = RYW * RGW;
@@ -407,9 +378,6 @@ conv_march_kernel(MarchArgs a) {
           finish_blk(s, s - 2, std::integral_constant<int, (PH + 1) % 3>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, dx - 1>{});
       }
       if constexpr (hi == RYW && ks == 0 && dx == 0) flush_stats();
-#ifdef SEUNET_MARCH_ASM_MFMA
-      __builtin_amdgcn_sched_barrier(0);                 // (the next unit's reads stay ahead of this unit's MFMAs)
-#endif
 #pragma unroll
       for (int b = 0; b < 2; ++b)
 #pragma unroll
@@ -420,16 +388,10 @@ conv_march_kernel(MarchArgs a) {
           for (int dz = 0; dz < 3; ++dz) {                // output plane s - dz
             const int ai = (PH - dz + 3) % 3;
             const int tap = (dz * 3 + dy) * 3 + dx;
-#ifndef SEUNET_MARCH_ASM_MFMA
             if (dz == 0 && dy == 0 && dx == 0 && ks == 0) acc[ai][r][b] = mm16b<T>(wreg[tap * KS + ks], fr[u % (PFD + 1)][b], cinit);
             else acc[ai][r][b] = mm16b<T>(wreg[tap * KS + ks], fr[u % (PFD + 1)][b], acc[ai][r][b]);
-#else
-            if (dz == 0 && dy == 0 && dx == 0 && ks == 0) mm16_init<T, 0, MODE == 0>(acc[ai][r][b], wreg[tap * KS + ks], fr[u % (PFD + 1)][b], cinit);
-            else mm16_acc<T, (ks == 1)>(acc[ai][r][b], wreg[tap * KS + ks], fr[u % (PFD + 1)][b]);
-#endif
           }
         }
-#ifndef SEUNET_MARCH_ASM_MFMA
       // one scheduling region per unit: the next unit's two fragment reads first, then the unit's MFMAs with the vector work of
       // the epilogue / DMA addressing dealt between them (an MFMA holds the SIMD's issue for 8 of its 16 cycles)
       {
@@ -441,7 +403,6 @@ conv_march_kernel(MarchArgs a) {
           __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
         }
       }
-#endif
       __builtin_amdgcn_sched_barrier(0);
     });
   };
@@ -523,7 +484,6 @@ conv_march_kernel(MarchArgs a) {
   }
 }
 
-#ifndef SEUNET_MARCH_PROBE   /* (scripts/march_probe.sh compiles single instantiations of the kernel above) */
 // ------------------------------------------------------------------------------------------------------------------
 // weight packing: PyTorch (Cout, Cin, 3, 3, 3) f32 -> [16-channel group][tap][K-step][lane][8] MFMA A-operand fragments
 // ------------------------------------------------------------------------------------------------------------------
@@ -740,7 +700,5 @@ int launch_conv_march(int dtype, int dil, const SrcList& src, const void* wpack,
   if (dtype == SEUNET_F16) return dil == 1 ? march_launch_cfg<f16_t, 1>(c, mode, a, grid, s) : march_launch_cfg<f16_t, 2>(c, mode, a, grid, s);
   return dil == 1 ? march_launch_cfg<bf16_t, 1>(c, mode, a, grid, s) : march_launch_cfg<bf16_t, 2>(c, mode, a, grid, s);
 }
-
-#endif  // SEUNET_MARCH_PROBE
 
 }  // namespace seunet

@@ -53,17 +53,14 @@ template <typename T> __device__ __forceinline__ f32x4 st_mfma16(bf16x8 a, bf16x
 
 struct StreamArgs {
   const void* src; const void* wpack; const float* bias;
-  void* dst; int dstC; int dacc; int cout; int stage;
+  void* dst; int dstC; int dacc; int cout;
   double* stats; const void* zero;
   unsigned long long* debug;       // diagnostic builds only (-DSEUNET_STAMP): [workgroup][wave][12] cycle sums per phase
   int N, D, H, W;
   int nyb, nxb, nzseg, zsteps;      // patches, z segments (per parity class), output planes per segment
 };
 
-#ifndef SEUNET_STREAM_ROWS
-#define SEUNET_STREAM_ROWS 8
-#endif
-static constexpr int ST_TY = SEUNET_STREAM_ROWS, ST_TX = 32, ST_NW = SEUNET_STREAM_ROWS;   // 8 waves: one output row each, two waves per SIMD
+static constexpr int ST_TY = 8, ST_TX = 32, ST_NW = 8;   // 8 waves: one output row each, two waves per SIMD
 
 template <int CIN, int COUTP, bool XFOLD, int DIL, bool DACC = false> struct StreamGeo {
   static constexpr int NP = CIN / 8;
@@ -88,10 +85,6 @@ template <int CIN, int COUTP, bool XFOLD, int DIL, bool DACC = false> struct Str
   static constexpr int LDS = OLD + (DACC ? RING * ST_NW * OLDI * 1024 : 0);   // ring + a 1-KB dump for the padding DMA instructions (+ old rows)
 };
 
-// -DSEUNET_STREAM_PROBE=1: no statistics; 2: no stores; 3: no MFMAs; 4: no fragment reads (timing by elimination, never shipped)
-#ifndef SEUNET_STREAM_PROBE
-#define SEUNET_STREAM_PROBE 0
-#endif
 #ifdef SEUNET_STAMP
 #define SSTAMP(i) do { const unsigned long long _t = __builtin_readcyclecounter(); ph[i] += _t - t_last; t_last = _t; } while (0)
 #else
@@ -283,7 +276,7 @@ conv_stream_kernel(StreamArgs a) {
   // registers after a v_permlane32_swap exchange and from this buffer with ds_read_b128; both wrote wrong rows now and then, which
   // turned out to be the counted wait of the march, not the stores: see there.  With the wait fixed they are correct and no faster
   // than the four 8-byte stores, which stay.)
-  const bool staged = COUTP == 32 && a.stage != 0 && a.dstC == COUTP && a.cout == COUTP;         // wave-uniform
+  const bool staged = COUTP == 32 && a.dstC == COUTP && a.cout == COUTP;         // wave-uniform
   constexpr int NSTG = COUTP == 32 ? 4 : 2, SPB = 8; // 8-byte pieces per lane of the row image
   const unsigned stg_base = (unsigned)(Geo::STAGE + wave * Geo::STG);
   unsigned stg_w[NBX][ACCR / 4];      // LDS byte address of the lane's 8-byte pieces
@@ -326,8 +319,7 @@ conv_stream_kernel(StreamArgs a) {
 #pragma unroll
           for (int b = 0; b < NBX; ++b) {
             const int off = frag0 + ((DIL * ri) * HX + b * NB + DIL * Geo::VPK * dxi) * 16;
-            if constexpr (SEUNET_STREAM_PROBE == 4) fr[ri & 1][dxi][b] = wreg[(ri * NDX + dxi) % NTAP];
-            else fr[ri & 1][dxi][b] = *reinterpret_cast<const bf16x8*>(pl + off);
+            fr[ri & 1][dxi][b] = *reinterpret_cast<const bf16x8*>(pl + off);
           }
       }
     };
@@ -364,10 +356,7 @@ conv_stream_kernel(StreamArgs a) {
             const bool first = dz == -1 && ri == 0 && dxi == 0;
 #pragma unroll
             for (int b = 0; b < NBX; ++b) {
-              if constexpr (SEUNET_STREAM_PROBE == 3) {
-                if (first) acc[ai][b] = cinit;
-                acc[ai][b][0] += __builtin_bit_cast(f32x4, fr[ri & 1][dxi][b])[0];   // (keeps the reads alive)
-              } else if constexpr (COUTP == 32) acc[ai][b] = st_mfma32<T>(wreg[tap], fr[ri & 1][dxi][b], first ? cinit : acc[ai][b]);
+              if constexpr (COUTP == 32) acc[ai][b] = st_mfma32<T>(wreg[tap], fr[ri & 1][dxi][b], first ? cinit : acc[ai][b]);
               else acc[ai][b] = st_mfma16<T>(wreg[tap], fr[ri & 1][dxi][b], first ? cinit : acc[ai][b]);
             }
           }
@@ -390,7 +379,7 @@ conv_stream_kernel(StreamArgs a) {
       float v[ACCR];
 #pragma unroll
       for (int e = 0; e < ACCR; ++e) v[e] = acc[ai][b][e];       // (bias included: it was the C operand of the set's first MFMA)
-      if constexpr (FWD && SEUNET_STREAM_PROBE != 1) {
+      if constexpr (FWD) {
         // branch-free (a lane outside the volume or a plane outside the march adds v * 0; a.stats == nullptr: the sums are simply
         // never stored): fma(v, 1, s) and fma(v * 1, v, s) round exactly like s + v and fma(v, v, s)
         const float m = zok ? mk[b] : 0.f;
@@ -419,10 +408,7 @@ conv_stream_kernel(StreamArgs a) {
       }
       if (!staged) {
 #pragma unroll
-        for (int pc = 0; pc < ACCR / 4; ++pc) {
-          if constexpr (SEUNET_STREAM_PROBE == 2) asm volatile("" :: "v"(u[pc]));
-          else __builtin_amdgcn_raw_buffer_store_b64(u[pc], rd, lofs[b][pc], soff, 0);
-        }
+        for (int pc = 0; pc < ACCR / 4; ++pc) __builtin_amdgcn_raw_buffer_store_b64(u[pc], rd, lofs[b][pc], soff, 0);
       } else {
 #pragma unroll
         for (int pc = 0; pc < ACCR / 4; ++pc)
@@ -437,8 +423,7 @@ conv_stream_kernel(StreamArgs a) {
 #pragma unroll
       for (int k = 0; k < NSTG; ++k) {
         const u32x2s qv = *reinterpret_cast<const u32x2s*>(smem + stg_r[k]);
-        if constexpr (SEUNET_STREAM_PROBE == 2) asm volatile("" :: "v"(qv));
-        else __builtin_amdgcn_raw_buffer_store_b64(qv, rd, stg_o[k], soff, 0);
+        __builtin_amdgcn_raw_buffer_store_b64(qv, rd, stg_o[k], soff, 0);
       }
       asm volatile("" ::: "memory");
     }
@@ -596,7 +581,7 @@ static int stream_zsteps(Dims d, int dil) {
   // at dilation 1, 512 of 66 at dilation 2.  At least 8 planes per march.  The split is a function of the SAMPLE's extents only:
   // the statistics records, hence the bits of a sample's result, must not depend on the batch it sits in (the data-parallel
   // equivalence tests and the window loop rely on that), so a batch of one 128^3 sample fills a quarter of the chip here.
-  static const int target = [] { const char* e = std::getenv("SEUNET_STREAM_WGS"); const int v = e ? std::atoi(e) : 0; return v > 0 ? v : 256; }();
+  constexpr int target = 256;
   const int planes = cdiv(d.D, dil);
   const long long base = (long long)cdiv(d.H, ST_TY) * cdiv(d.W, ST_TX) * dil * 4;
   long long segs = (target + base - 1) / base;
@@ -684,8 +669,6 @@ int launch_conv_stream(int dtype, int dil, const void* src, int src_c, const voi
   a.src = src; a.wpack = wpack; a.bias = bias; a.dst = dst; a.dstC = dst_c; a.dacc = dst_accumulate; a.cout = dst_c;
   a.stats = stats; a.zero = device_zero_page();
   a.debug = g_conv_debug;
-  static const bool no_stage = std::getenv("SEUNET_STREAM_NO_STAGE") != nullptr;     // (diagnostic switch for A/B timing)
-  a.stage = no_stage ? 0 : 1;
   SEUNET_CHECK(a.zero != nullptr, "conv_stream: no zero page on this device");
   a.N = d.N; a.D = d.D; a.H = d.H; a.W = d.W;
   const int planes = cdiv(d.D, dil);

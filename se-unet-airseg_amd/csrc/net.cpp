@@ -122,15 +122,65 @@ const OpDesc kOps[] = {
 constexpr int kNumOps = sizeof(kOps) / sizeof(kOps[0]);
 
 inline bool is_input(int t) { return t <= T_X2; }
+
+// ---------------------------------------------------------------------------------------------------
+// kernel routing: which kernel runs each pass of each conv (Plan::route, and wgrad_kernel below for the non-streaming weight
+// gradient).  The packed weights, the statistics slots, the workspace and the dispatch all follow from that one choice.
+// ---------------------------------------------------------------------------------------------------
 // levels on which the marching conv pays: full 32-voxel rows and enough (y, x) patches x planes for one workgroup per CU
 // (dilation 2 already at 32^3: the tiled kernel runs it on eight 16^3 parity sub-lattices, where its tiles are mostly halo --
 // measured on 4 x 32^3, 64 -> 64 channels: forward 0.043 vs 0.057 ms, data gradient 0.039 vs 0.059 ms; dilation 1 at that size
 // stays on the tiled kernel, 0.036 vs 0.041 ms)
 inline bool march_level(const Dims& d, int dil) {
-  static const long long minvox = [] { const char* e = getenv("SEUNET_MARCH_MINVOX"); return e ? atoll(e) : 48LL * 48 * 48; }();
-  static const bool no_coarse = getenv("SEUNET_MARCH_NO_COARSE") != nullptr;   // (diagnostic switch for A/B timing)
-  return d.W >= 32 && (d.vox() >= minvox || (!no_coarse && dil == 2 && d.vox() >= 32LL * 32 * 32));
+  return d.W >= 32 && (d.vox() >= 48LL * 48 * 48 || (dil == 2 && d.vox() >= 32LL * 32 * 32));
 }
+
+// statistics slots per sample of a forward conv on kernel k
+int conv_slots(ConvKernel k, const Dims& dm, int taps, int dil, int cin, int cout) {
+  switch (k) {
+    case ConvKernel::Stream: return conv_stream_slots(dm, dil);
+    case ConvKernel::March: return conv_march_slots(dm, dil, cin, cout);
+    case ConvKernel::Naive: return epi_partials(dm);
+    default: return conv_stats_tiles(dm, taps, dil);
+  }
+}
+
+}  // namespace
+
+ConvKernel wgrad_kernel(int dtype, int taps, int dil, const SrcList& x, int cin_logical, int cout, Dims d, long long src_dist) {
+  if (taps == 1) {
+    // where the whole-GEMM 1x1x1 kernel beats the tiled kernel (isolated launches): many (ci, co) combos there, i.e. many
+    // re-reads -- ec63 (8 combos, 1 M voxels) 0.104 vs 0.165 ms, ec93 (24 combos, 131 k voxels) 0.051 vs 0.085 ms; not dc42
+    // (2 combos: 0.059 vs 0.039 ms) nor dc22 (8 combos but 131 k voxels: 0.033 vs 0.023 ms, four chunks per workgroup do not
+    // amortise the pipeline fill)
+    const int combos = cdiv(cin_logical, 32) * cdiv(cout, 32);
+    const long long nv = (long long)d.N * d.vox();
+    const bool pays = combos >= 16 || (combos >= 8 && nv >= 500000);
+    return pays && wgrad_1x1_supported(dtype, x, cin_logical, cout) ? ConvKernel::Wgrad1x1 : ConvKernel::Tiled;
+  }
+  // where the marching kernel beats the tiled kernel (isolated launches, 4 samples): the fine levels (rows of >= 32 voxels,
+  // >= 48^3); every dilation-2 layer down to 16^3 (the tiled kernel works on parity sub-lattices there: 32^3 64 -> 64 0.057 vs
+  // 0.080 ms, 16^3 128 -> 128 0.058 vs 0.075 ms); 256-channel inputs (dc1: 0.118 vs 0.134 ms).  Dilation 1 with <= 128 input
+  // channels on the coarse levels is a tie and stays where it was.
+  const bool fine = d.W >= 32 && (long long)d.D * d.H * d.W >= 48LL * 48 * 48;
+  const bool pays = fine || dil == 2 || cin_logical >= 256;
+  return pays && wgrad_march_supported(dtype, taps, dil, x, cin_logical, cout, d, src_dist) ? ConvKernel::March : ConvKernel::Tiled;
+}
+
+int run_wgrad(ConvKernel k, int dtype, int taps, int dil, const SrcList& x, int cin_logical, const void* dy, int cout, float* dw,
+              void* workspace, size_t ws_bytes, Dims d, hipStream_t s) {
+  switch (k) {
+    case ConvKernel::Naive: return launch_wgrad_naive(dtype, taps, dil, x, cin_logical, dy, cout, dw, d, s);
+    case ConvKernel::Tiled: return launch_wgrad(dtype, taps, dil, x, cin_logical, dy, cout, dw, workspace, ws_bytes, d, s);
+    case ConvKernel::Stream:
+      return launch_wgrad_stream(dtype, dil, x.ptr[0], x.C[0], cin_logical, dy, cout, cout, dw, workspace, ws_bytes, d, s);
+    case ConvKernel::March: return launch_wgrad_march(dtype, taps, dil, x, cin_logical, dy, cout, dw, workspace, ws_bytes, d, s);
+    case ConvKernel::Wgrad1x1: return launch_wgrad_1x1(dtype, x, cin_logical, dy, cout, dw, workspace, ws_bytes, d, s);
+  }
+  return fail("wgrad: unknown kernel %d", (int)k);
+}
+
+namespace {
 
 // ---------------------------------------------------------------------------------------------------
 // workspace plan
@@ -139,8 +189,10 @@ struct OpRes {
   size_t raw = 0, raw2 = 0, mean = 0, rstd = 0, mean2 = 0, rstd2 = 0, xtot = 0, wp_f = 0, wp_d = 0, wp_x = 0;
   int cin = 0, cout = 0, taps = 0;
   bool need_dgrad = false;
-  bool stream_f = false, stream_d = false, stream_w = false;   // forward / data gradient / weight gradient on the streaming kernels
-  bool march_f = false, march_d = false;                       // forward / data gradient on the marching kernel (conv_march.hip)
+  // the kernel of each pass (Plan::route): the block conv's forward / data gradient / weight gradient, and the forward / weight
+  // gradient of a materialised x-branch (in_channel > 2)
+  ConvKernel fwd = ConvKernel::Tiled, dgrad = ConvKernel::Tiled, wgrad = ConvKernel::Tiled;
+  ConvKernel x_fwd = ConvKernel::Tiled, x_wgrad = ConvKernel::Tiled;
   size_t pool_idx = 0; bool has_pool_idx = false;              // OP_POOL behind a fused aggregation block: arg-max words of the forward
   size_t side = 0;                                             // n_classes > 1: the block's 2-channel side map, f32 [N][V][2] (classes.hip)
 };
@@ -157,8 +209,6 @@ struct Plan {
   size_t gside = 0, cls_part = 0, cls_bias = 0;                // n_classes > 1: side-map gradient of one block, head-gradient records, per-(sample, class) bias sums
   // x-branches (x33 / x63 / x93) recomputed from the <= 2-channel input instead of materialised (csrc/epilogue.hip, XR)
   bool fuse_x = false;
-  bool use_stream = true;
-  bool use_march = true;
   size_t wgrad_ws_bytes;
   size_t total;
   int stat_slots_max;
@@ -173,6 +223,51 @@ struct Plan {
 
   size_t cur = 0;
   size_t take(size_t bytes) { size_t o = cur; cur = align_up(cur + bytes, 256); return o; }
+
+  // The kernel of every conv pass of op i (OpRes::fwd .. x_wgrad).
+  void route(int i) {
+    const OpDesc& o = kOps[i];
+    OpRes& r = op[i];
+    if (d.conv_impl == SEUNET_CONV_NAIVE) { r.fwd = r.dgrad = r.wgrad = r.x_fwd = r.x_wgrad = ConvKernel::Naive; return; }
+    const Dims& dm = dims[kT[o.dst].level];
+    SrcList x{}, gy{};   // the forward's sources and the data gradient's
+    DstList y{}, gx{};   // and their destinations
+    x.n = gx.n = o.nsrc;
+    for (int k = 0; k < o.nsrc; ++k) x.C[k] = gx.C[k] = C[o.src[k]];
+    y.n = gy.n = 1;
+    y.C[0] = gy.C[0] = r.cout;
+    const int c0 = C[o.src[0]];
+    // small-channel 3x3x3 layers with one source tensor (ec1 / ec2 / ec3 / dc6 at width 1) run on the streaming kernel
+    // (the streaming kernels address one sample through 32-bit buffer offsets; a sample of 4 GB or more takes the general kernels)
+    const bool stream_ok = o.kind == OP_GATED && o.nsrc == 1 && (long long)dm.D * dm.H * dm.W * 32 * (long long)esz < 0xFFFFFFFFll;
+    const bool stream_f = stream_ok && conv_stream_supported(d.dtype, 27, o.dil, c0, r.cout);
+    const bool stream_d = stream_ok && conv_stream_supported(d.dtype, 27, o.dil, r.cout, c0);
+    // 32 / 64-input-channel 3x3x3 layers of the levels that fill the chip with 32-voxel rows run on the marching kernel
+    // (one workgroup per CU, weights in registers): dc5, dc4, ec4..ec6 and the data gradients of those and of dc3
+    const bool march_ok = o.kind == OP_GATED && !stream_f && march_level(dm, o.dil);
+    r.fwd = stream_f ? ConvKernel::Stream
+          : march_ok && conv_march_supported(d.dtype, 27, o.dil, x, y) ? ConvKernel::March : ConvKernel::Tiled;
+    r.dgrad = stream_d ? ConvKernel::Stream
+            : march_ok && conv_march_supported(d.dtype, 27, o.dil, gy, gx) ? ConvKernel::March : ConvKernel::Tiled;
+    // (the marching weight gradient reaches both sources of dc5 through one 32-bit descriptor: their distance counts)
+    const long long src_dist = o.nsrc == 2 ? (long long)feat[o.src[1]] - (long long)feat[o.src[0]] : 0;
+    r.wgrad = stream_ok && wgrad_stream_supported(d.dtype, 27, o.dil, c0, r.cout)
+                  ? ConvKernel::Stream : wgrad_kernel(d.dtype, r.taps, o.dil, x, r.cin, r.cout, dm, src_dist);
+    if (o.xname) {   // the x-branch: 1x1x1 conv of the 8-channel padded input
+      SrcList xs{};
+      xs.n = 1; xs.C[0] = 8;
+      r.x_fwd = ConvKernel::Tiled;
+      r.x_wgrad = wgrad_kernel(d.dtype, 1, 1, xs, d.in_channel, r.cout, dm, 0);
+    }
+  }
+  // bytes of a packed weight for kernel k: src_c channels in the single source tensor (Stream), cin -> cout channels
+  size_t wpack_bytes(ConvKernel k, int taps, int src_c, int cin, int cout) const {
+    switch (k) {
+      case ConvKernel::Stream: return conv_stream_wpack_bytes(src_c);
+      case ConvKernel::March: return conv_march_wpack_bytes(cin, cout);
+      default: return conv_wpack_bytes(d.dtype, taps, cin, cout);   // (the naive kernels read the PyTorch weight: same slot)
+    }
+  }
 
   int init(const seunet_net_desc& desc) {
     d = desc;
@@ -203,14 +298,12 @@ struct Plan {
     }
     size_t gx_max = 0, wg_max = 0, xw_max = 0, xmom_max = 0;
     fuse_x = d.in_channel <= 2 && d.conv_impl != SEUNET_CONV_NAIVE;
-    use_stream = getenv("SEUNET_NO_STREAM") == nullptr;   // (diagnostic switch for A/B timing; the default is on)
-    use_march = getenv("SEUNET_NO_MARCH") == nullptr;     // (likewise)
     int slots_max = 1, cmax = 8;
     for (int i = 0; i < kNumOps; ++i) {
       const OpDesc& o = kOps[i];
       OpRes& r = op[i];
       if (o.kind == OP_POOL && i > 0 && kOps[i - 1].kind == OP_CAT && kOps[i - 1].xname && kOps[i - 1].dst == o.src[0] &&
-          d.in_channel <= 2 && d.conv_impl != SEUNET_CONV_NAIVE && !is_input(o.src[0])) {
+          fuse_x && !is_input(o.src[0])) {
         // the aggregation block's forward writes this pool (and the position of each maximum, which the backward pass then
         // reads instead of the block output and the pooled tensor)
         const Dims& dl = dims[kT[o.dst].level];
@@ -231,36 +324,11 @@ struct Plan {
       r.raw = take(act);
       r.mean = take((size_t)d.batch * r.cout * 4);
       r.rstd = take((size_t)d.batch * r.cout * 4);
-      // small-channel 3x3x3 layers with one source tensor (ec1 / ec2 / ec3 / dc6 at width 1) run on the streaming kernel
-      // (the streaming kernels address one sample through 32-bit buffer offsets; a sample of 4 GB or more takes the general kernels)
-      const bool stream_ok = use_stream && o.kind == OP_GATED && o.nsrc == 1 && d.conv_impl != SEUNET_CONV_NAIVE &&
-                             (long long)dims[kT[o.dst].level].D * dims[kT[o.dst].level].H * dims[kT[o.dst].level].W * 32 * (long long)esz < 0xFFFFFFFFll;
-      r.stream_f = stream_ok && conv_stream_supported(d.dtype, 27, o.dil, C[o.src[0]], r.cout);
-      r.stream_d = stream_ok && r.need_dgrad && conv_stream_supported(d.dtype, 27, o.dil, r.cout, C[o.src[0]]);
-      // 32 / 64-input-channel 3x3x3 layers of the levels that fill the chip with 32-voxel rows run on the marching kernel
-      // (one workgroup per CU, weights in registers): dc5, dc4, ec4..ec6 and the data gradients of those and of dc3
-      if (use_march && o.kind == OP_GATED && d.conv_impl != SEUNET_CONV_NAIVE && !r.stream_f && march_level(dims[lv], o.dil)) {
-        SrcList sl{}; DstList dl{};
-        sl.n = o.nsrc;
-        for (int k = 0; k < o.nsrc; ++k) sl.C[k] = C[o.src[k]];
-        dl.n = 1; dl.C[0] = r.cout;
-        r.march_f = conv_march_supported(d.dtype, 27, o.dil, sl, dl);
-        if (r.need_dgrad && !r.stream_d) {
-          SrcList gs{}; DstList gd{};
-          gs.n = 1; gs.C[0] = r.cout;
-          gd.n = o.nsrc;
-          for (int k = 0; k < o.nsrc; ++k) gd.C[k] = C[o.src[k]];
-          r.march_d = conv_march_supported(d.dtype, 27, o.dil, gs, gd);
-        }
-      }
-      r.wp_f = take(r.stream_f ? conv_stream_wpack_bytes(C[o.src[0]])
-                               : (r.march_f ? conv_march_wpack_bytes(cin, r.cout) : conv_wpack_bytes(d.dtype, r.taps, r.cin, r.cout)));
-      if (r.need_dgrad) r.wp_d = take(r.stream_d ? conv_stream_wpack_bytes(r.cout)
-                                                 : (r.march_d ? conv_march_wpack_bytes(r.cout, cin) : conv_wpack_bytes(d.dtype, r.taps, r.cout, r.cin)));
-      if (r.stream_f) slots_max = std::max(slots_max, conv_stream_slots(dims[lv], o.dil));
-      if (r.march_f) slots_max = std::max(slots_max, conv_march_slots(dims[lv], o.dil, cin, r.cout));
-      r.stream_w = stream_ok && wgrad_stream_supported(d.dtype, 27, o.dil, C[o.src[0]], r.cout);
-      if (r.stream_w) wg_max = std::max(wg_max, wgrad_stream_workspace_bytes(C[o.src[0]], r.cout, o.dil, dims[lv]));
+      route(i);
+      r.wp_f = take(wpack_bytes(r.fwd, r.taps, C[o.src[0]], r.cin, r.cout));
+      if (r.need_dgrad) r.wp_d = take(wpack_bytes(r.dgrad, r.taps, r.cout, r.cout, r.cin));
+      slots_max = std::max(slots_max, conv_slots(r.fwd, dims[lv], r.taps, o.dil, cin, r.cout));
+      if (r.wgrad == ConvKernel::Stream) wg_max = std::max(wg_max, wgrad_stream_workspace_bytes(C[o.src[0]], r.cout, o.dil, dims[lv]));
       wg_max = std::max(wg_max, wgrad_workspace_bytes(r.taps, r.cin, r.cout));
       if (o.xname) {
         r.mean2 = take((size_t)d.batch * r.cout * 4);
@@ -271,7 +339,7 @@ struct Plan {
           xmom_max = std::max(xmom_max, (size_t)d.batch * xbranch_moment_slots(dims[lv]) * 5 * 8);
         } else {
           r.raw2 = take(act);
-          r.wp_x = take(conv_wpack_bytes(d.dtype, 1, d.in_channel, r.cout));
+          r.wp_x = take(wpack_bytes(r.x_fwd, 1, 8, d.in_channel, r.cout));
           gx_max = std::max(gx_max, act);
           wg_max = std::max(wg_max, wgrad_workspace_bytes(1, d.in_channel, r.cout));
         }
@@ -352,33 +420,34 @@ struct Exec {
     return l;
   }
 
+  // one forward or data-gradient conv on kernel k.  w: the PyTorch weight (naive kernels, tflip 1 = data gradient); wp: the weight
+  // packed for k by pack_all_weights
+  int run_conv(ConvKernel k, int taps, int dil, const SrcList& src, int cin, const float* w, int tflip, const void* wp,
+               const float* bias, const DstList& dst, double* stats, const Dims& dm) const {
+    switch (k) {
+      case ConvKernel::Naive: return launch_conv_naive(p.d.dtype, taps, dil, src, cin, w, tflip, bias, dst, dm, s);
+      case ConvKernel::Tiled: return launch_conv_igemm(p.d.dtype, taps, dil, src, cin, wp, bias, dst, stats, dm, s);
+      case ConvKernel::Stream:
+        return launch_conv_stream(p.d.dtype, dil, src.ptr[0], src.C[0], wp, bias, dst.ptr[0], dst.C[0], dst.acc[0], stats, dm, s);
+      case ConvKernel::March: return launch_conv_march(p.d.dtype, dil, src, wp, bias, dst, stats, dm, s);
+      default: return fail("net: internal: kernel %d runs no convolution", (int)k);
+    }
+  }
+
   // conv (+ InstanceNorm statistics) of one block: raw <- conv(src), (mean, rstd) <- stats(raw)
-  int conv_and_stats(const std::string& nm, int taps, int dil, const SrcList& src, int cin, const float* w, const float* bias, size_t wp_off,
-                     size_t raw_off, int cout, size_t mean_off, size_t rstd_off, const Dims& dm, bool stream = false, bool march = false) {
+  int conv_and_stats(const std::string& nm, ConvKernel k, int taps, int dil, const SrcList& src, int cin, const float* w,
+                     const float* bias, size_t wp_off, size_t raw_off, int cout, size_t mean_off, size_t rstd_off, const Dims& dm) {
     DstList dst{};
     dst.n = 1; dst.ptr[0] = at(raw_off); dst.C[0] = cout; dst.acc[0] = 0;
-    int slots;
-    if (march) {
-      mark("conv_fwd:" + nm);   // (weights were packed by pack_all_weights)
-      if (int e = launch_conv_march(p.d.dtype, dil, src, at(wp_off), bias, dst, dat(p.stats), dm, s)) return e;
-      slots = conv_march_slots(dm, dil, src.total(), cout);
-    } else if (stream) {
-      mark("conv_fwd:" + nm);   // (weights were packed by pack_all_weights)
-      if (int e = launch_conv_stream(p.d.dtype, dil, src.ptr[0], src.C[0], at(wp_off), bias, at(raw_off), cout, 0, dat(p.stats), dm, s)) return e;
-      slots = conv_stream_slots(dm, dil);
-    } else if (p.d.conv_impl == SEUNET_CONV_NAIVE) {
-      mark("conv_fwd:" + nm);
-      if (int e = launch_conv_naive(p.d.dtype, taps, dil, src, cin, w, 0, bias, dst, dm, s)) return e;
+    mark("conv_fwd:" + nm);
+    if (int e = run_conv(k, taps, dil, src, cin, w, 0, at(wp_off), bias, dst, dat(p.stats), dm)) return e;
+    if (k == ConvKernel::Naive) {   // (the naive conv leaves the statistics to a pass of their own)
       mark("stats");
       if (int e = launch_channel_stats(p.d.dtype, at(raw_off), cout, dat(p.stats), dm, s)) return e;
-      slots = epi_partials(dm);
-    } else {
-      mark("conv_fwd:" + nm);   // (weights were packed by pack_all_weights)
-      if (int e = launch_conv_igemm(p.d.dtype, taps, dil, src, cin, at(wp_off), bias, dst, dat(p.stats), dm, s)) return e;
-      slots = conv_stats_tiles(dm, taps, dil);
     }
     mark("stats");
-    return launch_stats_finalize(dat(p.stats), slots, cout, dm.N, dm.vox(), p.d.eps, 0, fat(mean_off), fat(rstd_off), s);
+    return launch_stats_finalize(dat(p.stats), conv_slots(k, dm, taps, dil, src.total(), cout), cout, dm.N, dm.vox(), p.d.eps, 0,
+                                 fat(mean_off), fat(rstd_off), s);
   }
 
   SseParams sse_params(const OpDesc& o) const {
@@ -419,29 +488,26 @@ struct Exec {
     std::vector<ConvPackJob> jobs;
     std::vector<MarchPackJob> mjobs;
     std::vector<StreamPackJob> sjobs;
+    // PyTorch weight w (cout, cin, k,k,k), read transposed / mirrored by the data gradient; src_c -> dst_c: the channels of the
+    // conv's source and destination tensors
+    const int tf = dgrad ? 1 : 0;
+    auto add = [&](ConvKernel k, const float* w, size_t wp, int taps, int cin, int cout, int src_c, int dst_c) {
+      if (k == ConvKernel::Stream) sjobs.push_back({w, at(wp), cin, cout, tf, src_c, dst_c});
+      else if (k == ConvKernel::March) mjobs.push_back({w, at(wp), cin, cout, tf, src_c, dst_c});
+      else jobs.push_back({w, at(wp), taps, cin, cout, tf});
+    };
     for (int i = 0; i < kNumOps; ++i) {
       const OpDesc& o = kOps[i];
       if (o.kind != OP_GATED && o.kind != OP_CAT) continue;
       const OpRes& r = p.op[i];
       const std::string n = o.name;
-      if ((!dgrad && r.stream_f) || (dgrad && r.stream_d)) {
-        // PyTorch weight (cout, cin, 3,3,3); the data gradient reads it transposed / mirrored
-        const int src_c = dgrad ? r.cout : p.C[o.src[0]], dst_c = dgrad ? p.C[o.src[0]] : r.cout;
-        sjobs.push_back({P(n + ".conv1.weight"), at(dgrad ? r.wp_d : r.wp_f), r.cin, r.cout, dgrad ? 1 : 0, src_c, dst_c});
-        continue;
-      }
-      if ((!dgrad && r.march_f) || (dgrad && r.march_d)) {
-        int ctot = 0;
-        for (int k = 0; k < o.nsrc; ++k) ctot += p.C[o.src[k]];
-        mjobs.push_back({P(n + ".conv1.weight"), at(dgrad ? r.wp_d : r.wp_f), r.cin, r.cout, dgrad ? 1 : 0, dgrad ? r.cout : ctot,
-                         dgrad ? ctot : r.cout});
-        continue;
-      }
+      int ctot = 0;
+      for (int k = 0; k < o.nsrc; ++k) ctot += p.C[o.src[k]];
       if (!dgrad) {
-        jobs.push_back({P(n + ".conv1.weight"), at(r.wp_f), r.taps, r.cin, r.cout, 0});
-        if (o.kind == OP_CAT && o.xname && !p.fuse_x) jobs.push_back({P(std::string(o.xname) + ".conv1.weight"), at(r.wp_x), 1, p.d.in_channel, r.cout, 0});
+        add(r.fwd, P(n + ".conv1.weight"), r.wp_f, r.taps, r.cin, r.cout, ctot, r.cout);
+        if (o.xname && !p.fuse_x) add(r.x_fwd, P(std::string(o.xname) + ".conv1.weight"), r.wp_x, 1, p.d.in_channel, r.cout, 8, r.cout);
       } else if (r.need_dgrad) {
-        jobs.push_back({P(n + ".conv1.weight"), at(r.wp_d), r.taps, r.cin, r.cout, 1});
+        add(r.dgrad, P(n + ".conv1.weight"), r.wp_d, r.taps, r.cin, r.cout, r.cout, ctot);
       }
     }
     if (!sjobs.empty())
@@ -471,8 +537,8 @@ struct Exec {
         if (int e = launch_upsample2_fwd(p.d.dtype, at(p.feat[o.src[0]]), p.C[o.src[0]], at(p.feat[o.dst]), p.dims[kT[o.src[0]].level], s)) return e;
       } else if (o.kind == OP_GATED) {
         const int lv = kT[o.dst].level;
-        if (int e = conv_and_stats(n, 27, o.dil, srcs(o), r.cin, P(n + ".conv1.weight"), P(n + ".conv1.bias"), r.wp_f, r.raw,
-                                   r.cout, r.mean, r.rstd, p.dims[lv], r.stream_f, r.march_f)) return e;
+        if (int e = conv_and_stats(n, r.fwd, 27, o.dil, srcs(o), r.cin, P(n + ".conv1.weight"), P(n + ".conv1.bias"), r.wp_f, r.raw,
+                                   r.cout, r.mean, r.rstd, p.dims[lv])) return e;
         const SseHead hd = sse_head(o, drop1, drop2, !lvl_written[o.head][lv]);
         lvl_written[o.head][lv] = true;
         mark("epi_fwd:" + n);
@@ -486,7 +552,7 @@ struct Exec {
         }
       } else {  // OP_CAT
         const int lv = kT[o.dst].level;
-        if (int e = conv_and_stats(n, 1, 1, srcs(o), r.cin, P(n + ".conv1.weight"), nullptr, r.wp_f, r.raw, r.cout, r.mean,
+        if (int e = conv_and_stats(n, r.fwd, 1, 1, srcs(o), r.cin, P(n + ".conv1.weight"), nullptr, r.wp_f, r.raw, r.cout, r.mean,
                                    r.rstd, p.dims[lv])) return e;
         if (o.xname && p.fuse_x) {
           // x-branch: statistics from the input's moments, values recomputed inside the epilogue (never stored)
@@ -496,22 +562,20 @@ struct Exec {
           if (int e = launch_xbranch_stats(dat(p.xmom), xbranch_moment_slots(p.dims[lv]), w2, r.cout, p.d.in_channel, p.dims[lv].N,
                                            p.dims[lv].vox(), p.d.eps, fat(r.mean2), fat(r.rstd2), dat(r.xtot), s)) return e;
           mark("cat_fwd:" + n);
-          // the max-pool that consumes this block (ec33 -> pool0, ec63 -> pool1, ec93 -> pool2) is written by the same kernel
-          const bool pool_next = i + 1 < kNumOps && kOps[i + 1].kind == OP_POOL && kOps[i + 1].src[0] == o.dst &&
-                                 getenv("SEUNET_NO_POOL_FUSE") == nullptr;
-          if (pool_next) {
-            if (int e = launch_cat_fwd_x_pool(p.d.dtype, at(r.raw), fat(r.mean), fat(r.rstd), at(p.feat[o.xsrc]), w2, p.d.in_channel,
-                                              fat(r.mean2), fat(r.rstd2), r.cout, p.d.negative_slope, at(p.feat[o.dst]),
-                                              at(p.feat[kOps[i + 1].dst]), p.dims[lv], s,
-                                              p.op[i + 1].has_pool_idx ? reinterpret_cast<unsigned*>(at(p.op[i + 1].pool_idx)) : nullptr)) return e;
-            pool_done[i + 1] = true;
-          } else if (int e = launch_cat_fwd_x(p.d.dtype, at(r.raw), fat(r.mean), fat(r.rstd), at(p.feat[o.xsrc]), w2, p.d.in_channel,
-                                       fat(r.mean2), fat(r.rstd2), r.cout, p.d.negative_slope, at(p.feat[o.dst]), p.dims[lv], s)) return e;
+          // the max-pool that consumes this block (ec33 -> pool0, ec63 -> pool1, ec93 -> pool2) is written by the same kernel,
+          // with the position of each maximum for the backward pass
+          const OpDesc& pool = kOps[i + 1];
+          SEUNET_CHECK(pool.kind == OP_POOL && pool.src[0] == o.dst && p.op[i + 1].has_pool_idx,
+                       "net: internal: %s is not followed by its max-pool", o.name);
+          if (int e = launch_cat_fwd_x_pool(p.d.dtype, at(r.raw), fat(r.mean), fat(r.rstd), at(p.feat[o.xsrc]), w2, p.d.in_channel,
+                                            fat(r.mean2), fat(r.rstd2), r.cout, p.d.negative_slope, at(p.feat[o.dst]),
+                                            at(p.feat[pool.dst]), p.dims[lv], s, reinterpret_cast<unsigned*>(at(p.op[i + 1].pool_idx)))) return e;
+          pool_done[i + 1] = true;
         } else {
           if (o.xname) {
             SrcList xs{};
             xs.n = 1; xs.ptr[0] = at(p.feat[o.xsrc]); xs.C[0] = 8;
-            if (int e = conv_and_stats(o.xname, 1, 1, xs, p.d.in_channel, P(std::string(o.xname) + ".conv1.weight"), nullptr, r.wp_x,
+            if (int e = conv_and_stats(o.xname, r.x_fwd, 1, 1, xs, p.d.in_channel, P(std::string(o.xname) + ".conv1.weight"), nullptr, r.wp_x,
                                        r.raw2, r.cout, r.mean2, r.rstd2, p.dims[lv])) return e;
           }
           mark("cat_fwd:" + n);
@@ -557,15 +621,8 @@ struct Exec {
     const int wi = find_param(reg, n + ".conv1.weight");
     if (grads[wi]) {
       mark("wgrad:" + n);
-      if (r.stream_w) {
-        if (int e = launch_wgrad_stream(p.d.dtype, o.dil, x.ptr[0], x.C[0], r.cin, at(p.grad[o.dst]), r.cout, r.cout, grads[wi],
-                                        at(p.wgrad_ws), p.wgrad_ws_bytes, p.dims[lv], s)) return e;
-      } else if (p.d.conv_impl == SEUNET_CONV_NAIVE) {
-        if (int e = launch_wgrad_naive(p.d.dtype, r.taps, o.dil, x, r.cin, at(p.grad[o.dst]), r.cout, grads[wi], p.dims[lv], s)) return e;
-      } else {
-        if (int e = launch_wgrad(p.d.dtype, r.taps, o.dil, x, r.cin, at(p.grad[o.dst]), r.cout, grads[wi], at(p.wgrad_ws),
-                                 p.wgrad_ws_bytes, p.dims[lv], s)) return e;
-      }
+      if (int e = run_wgrad(r.wgrad, p.d.dtype, r.taps, o.dil, x, r.cin, at(p.grad[o.dst]), r.cout, grads[wi], at(p.wgrad_ws),
+                            p.wgrad_ws_bytes, p.dims[lv], s)) return e;
     }
     if (!r.need_dgrad) return 0;
     SrcList gsrc{};
@@ -579,15 +636,8 @@ struct Exec {
       gd.acc[k] = (!is_input(t) && written[t]) ? 1 : 0;
       if (!is_input(t)) written[t] = true;
     }
-    const float* w = P(n + ".conv1.weight");
     mark("dgrad:" + n);
-    if (r.stream_d)
-      return launch_conv_stream(p.d.dtype, o.dil, at(p.grad[o.dst]), r.cout, at(r.wp_d), nullptr, gd.ptr[0], gd.C[0], gd.acc[0], nullptr,
-                                p.dims[lv], s);
-    if (r.march_d) return launch_conv_march(p.d.dtype, o.dil, gsrc, at(r.wp_d), nullptr, gd, nullptr, p.dims[lv], s);
-    if (p.d.conv_impl == SEUNET_CONV_NAIVE)
-      return launch_conv_naive(p.d.dtype, r.taps, o.dil, gsrc, r.cout, w, 1, nullptr, gd, p.dims[lv], s);
-    return launch_conv_igemm(p.d.dtype, r.taps, o.dil, gsrc, r.cout, at(r.wp_d), nullptr, gd, nullptr, p.dims[lv], s);
+    return run_conv(r.dgrad, r.taps, o.dil, gsrc, r.cout, P(n + ".conv1.weight"), 1, at(r.wp_d), nullptr, gd, nullptr, p.dims[lv]);
   }
 
   hipEvent_t decoder_done = nullptr;   // recorded once every gradient of the decoder blocks (dc1 .. dc6, dc22, dc42) is final
@@ -645,20 +695,17 @@ struct Exec {
         SEUNET_CHECK(written[o.dst], "net: internal: gradient of %s output missing", o.name);
         mark((o.kind == OP_POOL ? "pool_bwd:" : "up_bwd:") + n);
         if (o.kind == OP_POOL) {
-          // (the index is valid when the fused forward wrote it: same condition as in the forward walk)
-          static const bool no_fuse = getenv("SEUNET_NO_POOL_FUSE") != nullptr, no_defer = getenv("SEUNET_NO_POOL_DEFER") != nullptr;
-          if (r.has_pool_idx && !no_fuse && !no_defer && written[t] && p.fuse_x) {
+          if (r.has_pool_idx) {
             // nothing to launch: the aggregation block that produced tensor t adds this gradient on the fly in both of its
-            // backward passes (launch_cat_bwd_x, pool_* arguments) -- no read-modify-write of the full-resolution gradient
+            // backward passes (launch_cat_bwd_x, pool_* arguments) -- no read-modify-write of the full-resolution gradient.
+            // (dc5, dc3 and dc1 have already differentiated E1, E3 and E5, the tensors these pools read)
+            SEUNET_CHECK(written[t], "net: internal: gradient of %s input missing before its deferred pool gradient", o.name);
             pool_am[t] = reinterpret_cast<const unsigned*>(at(r.pool_idx));
             pool_g[t] = at(p.grad[o.dst]);
             continue;
           }
-          if (r.has_pool_idx && !no_fuse) {
-            if (int e = launch_maxpool_bwd_idx(p.d.dtype, reinterpret_cast<const unsigned*>(at(r.pool_idx)), at(p.grad[o.dst]), p.C[t],
-                                               at(p.grad[t]), written[t] ? 1 : 0, p.dims[kT[t].level], s)) return e;
-          } else if (int e = launch_maxpool_bwd(p.d.dtype, at(p.feat[t]), at(p.grad[o.dst]), p.C[t], at(p.grad[t]), written[t] ? 1 : 0,
-                                                p.dims[kT[t].level], s)) return e;
+          if (int e = launch_maxpool_bwd(p.d.dtype, at(p.feat[t]), at(p.grad[o.dst]), p.C[t], at(p.grad[t]), written[t] ? 1 : 0,
+                                         p.dims[kT[t].level], s)) return e;
         } else {
           if (int e = launch_upsample2_bwd(p.d.dtype, at(p.grad[o.dst]), p.C[t], at(p.grad[t]), written[t] ? 1 : 0,
                                            p.dims[kT[t].level], s)) return e;
@@ -757,12 +804,8 @@ struct Exec {
             mark(std::string("wgrad:") + o.xname);
             SrcList xs{};
             xs.n = 1; xs.ptr[0] = at(p.feat[o.xsrc]); xs.C[0] = 8;
-            if (p.d.conv_impl == SEUNET_CONV_NAIVE) {
-              if (int e = launch_wgrad_naive(p.d.dtype, 1, 1, xs, p.d.in_channel, at(p.gx), r.cout, grads[xi], dm, s)) return e;
-            } else {
-              if (int e = launch_wgrad(p.d.dtype, 1, 1, xs, p.d.in_channel, at(p.gx), r.cout, grads[xi], at(p.wgrad_ws),
-                                       p.wgrad_ws_bytes, dm, s)) return e;
-            }
+            if (int e = run_wgrad(r.x_wgrad, p.d.dtype, 1, 1, xs, p.d.in_channel, at(p.gx), r.cout, grads[xi], at(p.wgrad_ws),
+                                  p.wgrad_ws_bytes, dm, s)) return e;
           }
         }
         if (int e = conv_backward(i, srcs(o), grads, written)) return e;

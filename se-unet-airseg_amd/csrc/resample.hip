@@ -142,45 +142,6 @@ __global__ void maxpool_bwd_kernel(const T* __restrict__ in, const T* __restrict
   }
 }
 
-// The same from the arg-max words the fused forward wrote (epilogue.hip cat_fwd_pool_kernel: 3 bits per channel, position of the
-// first maximum of the stored values): the backward pass reads 4 bytes per window and 8 channels instead of the eight input
-// voxels and the pooled output (pool0 at 4 x 128^3 x 32 channels: 0.60 GB less traffic of 1.75 GB).
-template <typename T>
-__global__ void maxpool_bwd_idx_kernel(const unsigned* __restrict__ argmax, const T* __restrict__ g_out, int C,
-                                       T* g_in, int accumulate, int D, int H, int W, long long total) {
-  const int G = C / 8, Do = D / 2, Ho = H / 2, Wo = W / 2;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
-       i += (long long)gridDim.x * blockDim.x) {
-    const int g = (int)(i % G);
-    long long r = i / G;
-    const int xo = (int)(r % Wo); r /= Wo;
-    const int yo = (int)(r % Ho); r /= Ho;
-    const int zo = (int)(r % Do);
-    const long long n = r / Do;
-    const unsigned am = argmax[i];
-    float gy[8];
-    load8(g_out + ((((n * Do + zo) * Ho + yo) * Wo + xo) * (long long)C) + g * 8, gy);
-    Pack8<T> old[8];
-    if (accumulate) {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {     // the eight old values in flight together
-        const int z = 2 * zo + (k >> 2), y = 2 * yo + ((k >> 1) & 1), x = 2 * xo + (k & 1);
-        load8p(g_in + ((((n * D + z) * H + y) * W + x) * (long long)C) + g * 8, old[k]);
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int z = 2 * zo + (k >> 2), y = 2 * yo + ((k >> 1) & 1), x = 2 * xo + (k & 1);
-      T* p = g_in + ((((n * D + z) * H + y) * W + x) * (long long)C) + g * 8;
-      float v[8];
-      if (accumulate) unpack8(old[k], v);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = (accumulate ? v[j] : 0.f) + (((am >> (3 * j)) & 7u) == (unsigned)k ? gy[j] : 0.f);
-      store8(p, v);
-    }
-  }
-}
-
 // ---------------- x2 trilinear up-sampling of feature maps ------------------------------------
 template <typename T>
 __global__ void upsample2_fwd_kernel(const T* __restrict__ in, int C, T* __restrict__ out, int D, int H,
@@ -1184,18 +1145,10 @@ int launch_maxpool_bwd(int dtype, const void* in, const void* g_out, int C, void
   return 0;
 }
 
-int launch_maxpool_bwd_idx(int dtype, const unsigned* argmax, const void* g_out, int C, void* g_in, int accumulate, Dims d, hipStream_t s) {
-  SEUNET_CHECK(C % 8 == 0 && d.D % 2 == 0 && d.H % 2 == 0 && d.W % 2 == 0 && argmax, "maxpool_bwd_idx: bad argument");
-  const long long total = (long long)d.N * (d.D / 2) * (d.H / 2) * (d.W / 2) * (C / 8);
-  SEUNET_DTYPE_SWITCH(dtype, maxpool_bwd_idx_kernel<T><<<grid_for(total), 256, 0, s>>>(argmax, (const T*)g_out, C, (T*)g_in, accumulate, d.D, d.H, d.W, total));
-  SEUNET_LAUNCH_CHECK();
-  return 0;
-}
-
 int launch_upsample2_fwd(int dtype, const void* in, int C, void* out, Dims d, hipStream_t s) {
   SEUNET_CHECK(C % 8 == 0, "upsample2: C=%d must be a multiple of 8", C);
   const long long total = (long long)d.N * d.vox() * 8 * (C / 8);
-  if ((C == 32 || C == 64 || C == 128) && d.D >= 2 && d.H >= 2 && d.W >= 2 && getenv("SEUNET_UP_TILED") == nullptr) {
+  if ((C == 32 || C == 64 || C == 128) && d.D >= 2 && d.H >= 2 && d.W >= 2) {
     const int XF = 4096 / C;                               // fine columns per block: four (row, column, 8-channel) items per thread
     const int nseg = (2 * d.D + UFM_ZSF - 1) / UFM_ZSF;
     const size_t lds_m = (size_t)2 * 3 * UFM_XC * C * dtype_size(dtype);   // <= 102 KB except 128 channels in f32 (tiled kernel)
@@ -1247,7 +1200,7 @@ int launch_upsample2_bwd(int dtype, const void* g_out, int C, void* g_in, int ac
   // z-marching kernel: TY * C = 128 (256 phase-2 items of 8 channels = 1 per thread), LDS = 2 x 128 * 40 floats = 40 KB
   // (16-bit storage only: the f32 parity mode would hold 200 registers of fetched rows; it stays on the tiled kernel)
   if (dtype_size(dtype) == 2 && (C == 32 || C == 64 || C == 128) && d.D >= 4 && d.H >= 4 && d.W >= 4 &&
-      (long long)4 * d.H * d.W * C < (1LL << 31) && getenv("SEUNET_UP_TILED") == nullptr) {
+      (long long)4 * d.H * d.W * C < (1LL << 31)) {
     const int ZS = d.D >= 32 ? 8 : 4;
     const int nseg = (d.D + ZS - 1) / ZS;
     SEUNET_CHECK((long long)d.N * nseg <= 65535, "upsample2_bwd: batch too large");

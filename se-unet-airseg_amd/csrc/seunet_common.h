@@ -66,6 +66,9 @@ struct SrcList {           // virtual channel concatenation of up to 3 tensors
   int C[3];
   int n;
   int total() const { int t = 0; for (int i = 0; i < n; ++i) t += C[i]; return t; }
+  long long gap() const {  // byte distance between the first two tensors (0 with one)
+    return n < 2 ? 0 : reinterpret_cast<const unsigned char*>(ptr[1]) - reinterpret_cast<const unsigned char*>(ptr[0]);
+  }
 };
 
 struct DstList {           // channel split of an output over up to 3 tensors
@@ -307,18 +310,24 @@ int launch_wgrad_stream(int dtype, int dil, const void* x, int x_c, int cin_w, c
 // weight gradient (wgrad.hip)
 size_t wgrad_workspace_bytes(int taps, int cin, int cout);
 int launch_wgrad(int dtype, int taps, int dil, const SrcList& x, int cin_logical, const void* dy,
-                 int cout, float* dw_torch, void* workspace, size_t ws_bytes, Dims d,
-                 hipStream_t s, bool allow_march = true);
-// marching weight gradient (wgrad_march.hip); `supported` includes the size gate launch_wgrad dispatches on
-bool wgrad_march_supported(int dtype, int taps, int dil, const SrcList& x, int cin_logical, int cout, Dims d);
+                 int cout, float* dw_torch, void* workspace, size_t ws_bytes, Dims d, hipStream_t s);
+// marching weight gradient (wgrad_march.hip); src_dist: byte distance between the two sources of x (32-bit reach)
+bool wgrad_march_supported(int dtype, int taps, int dil, const SrcList& x, int cin_logical, int cout, Dims d, long long src_dist);
 int launch_wgrad_march(int dtype, int taps, int dil, const SrcList& x, int cin_logical, const void* dy, int cout,
                        float* dw, void* workspace, size_t ws_bytes, Dims d, hipStream_t s);
 // 1x1x1 weight gradient of the aggregation convolutions (wgrad_1x1.hip)
-bool wgrad_1x1_supported(int dtype, const SrcList& x, int cin_logical, int cout, Dims d);
+bool wgrad_1x1_supported(int dtype, const SrcList& x, int cin_logical, int cout);
 int launch_wgrad_1x1(int dtype, const SrcList& x, int cin_logical, const void* dy, int cout, float* dw, void* workspace,
                      size_t ws_bytes, Dims d, hipStream_t s);
 int launch_wgrad_naive(int dtype, int taps, int dil, const SrcList& x, int cin_logical,
                        const void* dy, int cout, float* dw_torch, Dims d, hipStream_t s);
+// the kernel of each conv pass: chosen in one place, net.cpp (kernel routing)
+enum class ConvKernel { Naive, Tiled, Stream, March, Wgrad1x1 };
+// the non-streaming weight gradient's choice by size (the network plan and seunet_conv3d_wgrad); src_dist as above
+ConvKernel wgrad_kernel(int dtype, int taps, int dil, const SrcList& x, int cin_logical, int cout, Dims d, long long src_dist);
+// weight gradient on kernel k (Stream: one source, dy with cout channels)
+int run_wgrad(ConvKernel k, int dtype, int taps, int dil, const SrcList& x, int cin_logical, const void* dy, int cout, float* dw,
+              void* workspace, size_t ws_bytes, Dims d, hipStream_t s);
 
 // normalisation / gates / cat (epilogue.hip)
 int epi_partials(Dims d);         // partial slots per sample used by the epilogue kernels
@@ -396,8 +405,6 @@ int launch_cat_xgrad_finalize(const double* xw_partial, const double* stat_parti
                               int C, int in_channel, int N, float eps, float* dw, hipStream_t s);
 int launch_xbranch_values(int dtype, const void* x_in, const float* w2, int C, int in_channel, float* out_ncdhw, Dims d, hipStream_t s);   // diagnostic
 int launch_maxpool_fwd(int dtype, const void* in, int C, void* out, Dims din, hipStream_t s);
-// max-pool backward from the arg-max words written by launch_cat_fwd_x_pool ([N][Vo][C/8] uint32, 3 bits per channel)
-int launch_maxpool_bwd_idx(int dtype, const unsigned* argmax, const void* g_out, int C, void* g_in, int accumulate, Dims d, hipStream_t s);
 int launch_maxpool_bwd(int dtype, const void* in, const void* g_out, int C, void* g_in,
                        int accumulate, Dims din, hipStream_t s);
 int launch_upsample2_fwd(int dtype, const void* in, int C, void* out, Dims din, hipStream_t s);

@@ -418,14 +418,12 @@ wgrad_reduce_kernel(const float* __restrict__ slab, int nslab, int taps, int cin
 }
 
 // persistent workgroups per (ci, co) combo == slabs the reduce kernel has to sum; ~2 resident workgroups per CU in total
-static inline int wgrad_groups(int taps, int combos, int total_tiles) {
-  static const int per_chip = [] { const char* e = getenv("SEUNET_WGRAD_WGS"); return e ? atoi(e) : 512; }();   // (diagnostic)
-  int g = per_chip / combos;   // two resident workgroups per CU
+static inline int wgrad_groups(int combos, int total_tiles) {
+  int g = 512 / combos;   // two resident workgroups per CU
   if (g < 16) g = 16;
   if (g > 512) g = 512;
   if (g > total_tiles) g = total_tiles;
   if (g < 1) g = 1;
-  (void)taps;
   return g;
 }
 
@@ -457,16 +455,12 @@ static int wgrad_launch_one(const WgArgs& a, dim3 grid, hipStream_t s) {
 // x: input activation (may be a concatenation), cin_logical leading channels carry weights;
 // dy: gradient w.r.t. the raw conv output, [N][V][cout]; dw: (cout, cin_logical, taps) f32, overwritten.
 int launch_wgrad(int dtype, int taps, int dil, const SrcList& x, int cin_logical, const void* dy, int cout,
-                 float* dw, void* workspace, size_t ws_bytes, Dims d, hipStream_t s, bool allow_march) {
+                 float* dw, void* workspace, size_t ws_bytes, Dims d, hipStream_t s) {
   SEUNET_CHECK(taps == 27 || taps == 1, "wgrad: taps=%d unsupported", taps);
   SEUNET_CHECK(taps == 1 || dil == 1 || dil == 2, "wgrad: dilation %d unsupported", dil);
   SEUNET_CHECK(x.n >= 1 && x.n <= 3, "wgrad: 1..3 sources");
   SEUNET_CHECK(cout % 8 == 0 && cin_logical >= 1 && cin_logical <= x.total(), "wgrad: bad channel counts");
   SEUNET_CHECK(ws_bytes >= wgrad_workspace_bytes(taps, cin_logical, cout), "wgrad: workspace too small");
-  if (allow_march && taps == 1 && wgrad_1x1_supported(dtype, x, cin_logical, cout, d))   // aggregation convs: wgrad_1x1.hip
-    return launch_wgrad_1x1(dtype, x, cin_logical, dy, cout, dw, workspace, ws_bytes, d, s);
-  if (allow_march && wgrad_march_supported(dtype, taps, dil, x, cin_logical, cout, d))     // wide layers of the fine levels: wgrad_march.hip
-    return launch_wgrad_march(dtype, taps, dil, x, cin_logical, dy, cout, dw, workspace, ws_bytes, d, s);
   WgArgs a{};
   a.src0 = x.ptr[0]; a.srcC0 = x.C[0];
   a.src1 = x.n > 1 ? x.ptr[1] : nullptr; a.srcC1 = x.n > 1 ? x.C[1] : 0;
@@ -486,7 +480,7 @@ int launch_wgrad(int dtype, int taps, int dil, const SrcList& x, int cin_logical
   a.co_tiles = cdiv(cout, 32);
   a.debug = g_conv_debug;
   const int combos = cdiv(cin_logical, 32) * a.co_tiles;
-  const int G = wgrad_groups(taps, combos, a.tx * a.ty * a.tz * st * st * st * d.N);
+  const int G = wgrad_groups(combos, a.tx * a.ty * a.tz * st * st * st * d.N);
   dim3 grid(G, combos);
   int e;
   SEUNET_DTYPE_SWITCH(dtype, {

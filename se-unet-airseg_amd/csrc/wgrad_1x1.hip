@@ -233,7 +233,7 @@ wgrad_1x1_reduce_kernel(const float* __restrict__ slab, int nslab, int cibw, int
 }
 
 struct W1Cfg { int cibw, ncob, ch, nst; };
-static bool wgrad_1x1_cfg(int dtype, const SrcList& x, int cin_logical, int cout, Dims d, bool size_gate, W1Cfg& c) {
+static bool wgrad_1x1_cfg(int dtype, const SrcList& x, int cin_logical, int cout, W1Cfg& c) {
   if (dtype_size(dtype) != 2 || x.n < 1 || x.n > 3 || cin_logical != x.total()) return false;
   for (int i = 0; i < x.n; ++i) if (x.C[i] != 32 && x.C[i] != 64) return false;
   if (cout != 32 && cout != 64 && cout != 128) return false;
@@ -254,22 +254,11 @@ static bool wgrad_1x1_cfg(int dtype, const SrcList& x, int cin_logical, int cout
     while (nst > 2 && (nst - 1) * lw > 48) --nst;
     if (nst >= 2 && nst > c.nst) { c.nst = nst; c.ch = ch; }
   }
-  if (c.nst < 2) return false;
-  if (size_gate) {
-    static const bool off = std::getenv("SEUNET_NO_WGRAD_1X1") != nullptr;   // (diagnostic switch for A/B timing)
-    // where it beats the tiled kernel (isolated launches): many (ci, co) combos there, i.e. many re-reads -- ec63 (8 combos, 1 M
-    // voxels) 0.104 vs 0.165 ms, ec93 (24 combos, 131 k voxels) 0.051 vs 0.085 ms; not dc42 (2 combos: 0.059 vs 0.039 ms) nor
-    // dc22 (8 combos but 131 k voxels: 0.033 vs 0.023 ms, four chunks per workgroup do not amortise the pipeline fill)
-    const int combos = cdiv(cin_logical, 32) * cdiv(cout, 32);
-    const long long nv = (long long)d.N * d.vox();
-    static const bool all = std::getenv("SEUNET_WGRAD_1X1_ALL") != nullptr;   // (diagnostic: every layer the kernel serves)
-    if (off || !(all || combos >= 16 || (combos >= 8 && nv >= 500000))) return false;
-  }
-  return true;
+  return c.nst >= 2;
 }
-bool wgrad_1x1_supported(int dtype, const SrcList& x, int cin_logical, int cout, Dims d) {
+bool wgrad_1x1_supported(int dtype, const SrcList& x, int cin_logical, int cout) {
   W1Cfg c;
-  return wgrad_1x1_cfg(dtype, x, cin_logical, cout, d, true, c);
+  return wgrad_1x1_cfg(dtype, x, cin_logical, cout, c);
 }
 
 template <typename T, int CIBW, int NCOB, int CH>
@@ -284,7 +273,7 @@ static int wgrad_1x1_launch(const W1Args& a, int grid, int lds, hipStream_t s) {
 int launch_wgrad_1x1(int dtype, const SrcList& x, int cin_logical, const void* dy, int cout, float* dw, void* workspace,
                      size_t ws_bytes, Dims d, hipStream_t s) {
   W1Cfg c;
-  SEUNET_CHECK(wgrad_1x1_cfg(dtype, x, cin_logical, cout, d, false, c),
+  SEUNET_CHECK(wgrad_1x1_cfg(dtype, x, cin_logical, cout, c),
                "wgrad_1x1: 16-bit tensors, 1..3 sources of 32 or 64 channels (64, 128 or 192 together), 32 / 64 / 128 output channels only");
   SEUNET_CHECK(ws_bytes >= 256, "wgrad_1x1: workspace too small");
   W1Args a{};

@@ -393,7 +393,7 @@ wgrad_march_reduce_kernel(const float* __restrict__ slab, int nslab, int ncb, in
 }
 
 struct WmCfg { int ncb, nob; };
-static bool wgrad_march_cfg(int dtype, int taps, int dil, const SrcList& x, int cin_logical, int cout, Dims d, bool size_gate, WmCfg& c) {
+static bool wgrad_march_cfg(int dtype, int taps, int dil, const SrcList& x, int cin_logical, int cout, Dims d, long long src_dist, WmCfg& c) {
   if (dtype_size(dtype) != 2 || taps != 27 || (dil != 1 && dil != 2)) return false;
   if (x.n < 1 || x.n > 2 || (x.n == 2 && x.C[0] != x.C[1])) return false;
   if (cin_logical != x.total() || cin_logical % 32 || cout % 32 || x.C[0] % 8) return false;
@@ -402,22 +402,8 @@ static bool wgrad_march_cfg(int dtype, int taps, int dil, const SrcList& x, int 
     // INCLUDING the distance between them, must fit (the network's plan places the halves of a concatenation next to each other;
     // anything larger goes to the tiled kernel)
     const long long esz = 2, xs = (long long)d.D * d.H * d.W * x.C[0] * esz, ys = (long long)d.D * d.H * d.W * cout * esz;
-    long long dist = 0;
-    if (x.n == 2) {
-      dist = reinterpret_cast<const unsigned char*>(x.ptr[1]) - reinterpret_cast<const unsigned char*>(x.ptr[0]);
-      if (dist < 0) dist = -dist;
-    }
+    const long long dist = x.n == 2 ? (src_dist < 0 ? -src_dist : src_dist) : 0;
     if (dist + xs >= 0xFFFFFFFFll || ys >= 0xFFFFFFFFll) return false;
-  }
-  if (size_gate) {
-    // where it beats the tiled kernel (isolated launches, 4 samples): the fine levels (rows of >= 32 voxels, >= 48^3); every
-    // dilation-2 layer down to 16^3 (the tiled kernel works on parity sub-lattices there: 32^3 64 -> 64 0.057 vs 0.080 ms, 16^3
-    // 128 -> 128 0.058 vs 0.075 ms); 256-channel inputs (dc1: 0.118 vs 0.134 ms).  Dilation 1 with <= 128 input channels on the
-    // coarse levels is a tie and stays where it was.
-    static const bool off = std::getenv("SEUNET_NO_WGRAD_MARCH") != nullptr;
-    const bool fine = d.W >= 32 && (long long)d.D * d.H * d.W >= 48LL * 48 * 48;
-    static const bool no_coarse = std::getenv("SEUNET_MARCH_NO_COARSE") != nullptr;   // (diagnostic switch for A/B timing)
-    if (off || !(fine || (!no_coarse && (dil == 2 || cin_logical >= 256)))) return false;
   }
   if (cin_logical % 64 == 0) c = {4, 2};
   else if (cout % 64 == 0) c = {2, 4};
@@ -425,9 +411,9 @@ static bool wgrad_march_cfg(int dtype, int taps, int dil, const SrcList& x, int 
   return true;
 }
 
-bool wgrad_march_supported(int dtype, int taps, int dil, const SrcList& x, int cin_logical, int cout, Dims d) {
+bool wgrad_march_supported(int dtype, int taps, int dil, const SrcList& x, int cin_logical, int cout, Dims d, long long src_dist) {
   WmCfg c;
-  return wgrad_march_cfg(dtype, taps, dil, x, cin_logical, cout, d, true, c);
+  return wgrad_march_cfg(dtype, taps, dil, x, cin_logical, cout, d, src_dist, c);
 }
 
 template <typename T, int NCB, int NOB, int DIL>
@@ -443,7 +429,7 @@ static int wgrad_march_launch(const WmArgs& a, dim3 grid, hipStream_t s) {
 int launch_wgrad_march(int dtype, int taps, int dil, const SrcList& x, int cin_logical, const void* dy, int cout,
                        float* dw, void* workspace, size_t ws_bytes, Dims d, hipStream_t s) {
   WmCfg c;
-  SEUNET_CHECK(wgrad_march_cfg(dtype, taps, dil, x, cin_logical, cout, d, false, c),
+  SEUNET_CHECK(wgrad_march_cfg(dtype, taps, dil, x, cin_logical, cout, d, x.gap(), c),
                "wgrad_march: 16-bit 3x3x3 layers with 32k input and 32k output channels (one tensor or two equal halves) only");
   SEUNET_CHECK(ws_bytes >= 256, "wgrad_march: workspace too small");
   const int xc = 16 * c.ncb, yc = 16 * c.nob, pw = c.ncb * c.nob / WM_NW;
