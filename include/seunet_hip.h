@@ -294,6 +294,37 @@ size_t seunet_metric_out_bytes(int nbins);
 int seunet_metric_sums(const unsigned char* pred, const unsigned char* label, const unsigned char* skeleton, const int* parsing,
                        long long n, int nbins, void* out, size_t out_bytes, seunet_stream_t s);
 
+/* ---- stage-2/3 preparation: exact EDT, hard-mining candidates, LIB weight, break weight -------------------------------
+ * Volumes are C-contiguous (n0, n1, n2) on the device, axis 2 contiguous; masks are bytes with non-zero = 1.  Extents up to
+ * 32767 per axis and fewer than 2^31 voxels (anything else: error).  workspaces: the *_workspace_bytes of the same extents.
+ *
+ * seunet_edt: scipy.ndimage.distance_transform_edt(volume, return_indices=...) with unit sampling: for every voxel the nearest
+ *   ZERO voxel.  Outputs (each optional, NULL = skip): sqdist int32 squared distance; dist float64 = the correctly rounded sqrt
+ *   (bitwise scipy's); indices int32 (3, n0, n1, n2), the feature transform, bitwise scipy's, ties included.  A volume with no
+ *   zero voxel is an error (scipy's values are meaningless there): status_dev (device int, optional) is 1 then, 0 otherwise,
+ *   and the outputs are -1.
+ * seunet_hard_mining_masks: the candidate lists of data.py:305-306 / :457-458 as bit masks (bit j of word w = voxel 64 w + j in
+ *   raster order, ceil(n0 n1 n2 / 64) words each): skeleton_bits = skeleton != 0 and pred != 1 (where(skeleton * (1 - pred)));
+ *   small_bits = skeleton == 0 or EDT(label)^2 < 4 (where(dis * skeleton < 2)).  seunet_mask_bits packs any mask the same way
+ *   (loc_break = where(br_skel == 1)).
+ * seunet_lib_weight: lib_weight.py:36-53 (save_lib_weight, no ** 2.5): out = float16 (raw 16-bit) table[c] * label, c the 7x7x7
+ *   count of label voxels with mode 'mirror'; table: 344 host floats, table[k] = -log10(float32(k) / 343), table[0] = -log10(1).
+ * seunet_break_weight: weight_br.py:113-177 (save_weight_break) with the skeleton given: w_br float16 (raw 16-bit) and br_skel
+ *   bytes.  When the reference's maxf is 0 both are all zeros.  An empty skeleton is an error (status_dev 1). */
+size_t seunet_edt_workspace_bytes(int n0, int n1, int n2);
+int seunet_edt(const unsigned char* volume, int n0, int n1, int n2, int* sqdist, double* dist, int* indices, int* status_dev,
+               void* workspace, size_t workspace_bytes, seunet_stream_t s);
+int seunet_mask_bits(const unsigned char* mask, long long n, unsigned long long* bits, seunet_stream_t s);
+int seunet_hard_mining_masks(const unsigned char* label, const unsigned char* skeleton, const unsigned char* pred, int n0, int n1,
+                             int n2, unsigned long long* skeleton_bits, unsigned long long* small_bits, seunet_stream_t s);
+size_t seunet_lib_weight_workspace_bytes(int n0, int n1, int n2);
+int seunet_lib_weight(const unsigned char* label, int n0, int n1, int n2, const float* table, void* out, void* workspace,
+                      size_t workspace_bytes, seunet_stream_t s);
+size_t seunet_break_weight_workspace_bytes(int n0, int n1, int n2);
+int seunet_break_weight(const unsigned char* label, const unsigned char* pred, const unsigned char* skeleton, int n0, int n1, int n2,
+                        void* w_br, unsigned char* br_skel, int* status_dev, void* workspace, size_t workspace_bytes,
+                        seunet_stream_t s);
+
 /* ---- whole network: SE_UNet.forward (SE_UNet.py:181-238) and its backward ------------------------------- */
 typedef struct seunet_net_desc {
   int batch, in_channel, n_classes;

@@ -97,6 +97,14 @@ PROTOTYPES = {
     "seunet_window_finalize": (_i, [_vp, _i, _i, _i, _i, _i, _ip, _i, _ip, _i, _ip, _i, _vp, _vp]),
     "seunet_dti_workspace_bytes": (_sz, [_i, _i, _i]),
     "seunet_dti": (_i, [_vp, _i, _i, _i, C.c_double, C.c_double, _i, _vp, _vp, _sz, _vp]),
+    "seunet_edt_workspace_bytes": (_sz, [_i, _i, _i]),
+    "seunet_edt": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "seunet_mask_bits": (_i, [_vp, _ll, _vp, _vp]),
+    "seunet_hard_mining_masks": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "seunet_lib_weight_workspace_bytes": (_sz, [_i, _i, _i]),
+    "seunet_lib_weight": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "seunet_break_weight_workspace_bytes": (_sz, [_i, _i, _i]),
+    "seunet_break_weight": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "seunet_adamw_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _i, _i, _vp]),
     "seunet_net_param_count": (_i, [C.POINTER(NetDesc)]),
     "seunet_net_param_info": (_i, [C.POINTER(NetDesc), _i, C.c_char_p, _i, _ip, _ip]),

@@ -291,6 +291,39 @@ int seunet_metric_sums(const unsigned char* pred, const unsigned char* label, co
   return launch_metric_sums(pred, label, skeleton, parsing, n, nbins, out, out_bytes, S(s));
 }
 
+size_t seunet_edt_workspace_bytes(int n0, int n1, int n2) {
+  if (n0 < 1 || n1 < 1 || n2 < 1) { fail("edt_workspace_bytes: bad dimensions"); return 0; }
+  return edt_workspace_bytes(n0, n1, n2);
+}
+int seunet_edt(const unsigned char* volume, int n0, int n1, int n2, int* sqdist, double* dist, int* indices, int* status_dev,
+               void* workspace, size_t workspace_bytes, seunet_stream_t s) {
+  return launch_edt(volume, n0, n1, n2, sqdist, dist, indices, status_dev, workspace, workspace_bytes, S(s));
+}
+int seunet_mask_bits(const unsigned char* mask, long long n, unsigned long long* bits, seunet_stream_t s) {
+  return launch_mask_bits(mask, n, bits, S(s));
+}
+int seunet_hard_mining_masks(const unsigned char* label, const unsigned char* skeleton, const unsigned char* pred, int n0, int n1,
+                             int n2, unsigned long long* skeleton_bits, unsigned long long* small_bits, seunet_stream_t s) {
+  return launch_hm_candidates(label, skeleton, pred, n0, n1, n2, skeleton_bits, small_bits, S(s));
+}
+size_t seunet_lib_weight_workspace_bytes(int n0, int n1, int n2) {
+  if (n0 < 1 || n1 < 1 || n2 < 1) { fail("lib_weight_workspace_bytes: bad dimensions"); return 0; }
+  return lib_weight_workspace_bytes(n0, n1, n2);
+}
+int seunet_lib_weight(const unsigned char* label, int n0, int n1, int n2, const float* table, void* out, void* workspace,
+                      size_t workspace_bytes, seunet_stream_t s) {
+  return launch_lib_weight(label, n0, n1, n2, table, out, workspace, workspace_bytes, S(s));
+}
+size_t seunet_break_weight_workspace_bytes(int n0, int n1, int n2) {
+  if (n0 < 1 || n1 < 1 || n2 < 1) { fail("break_weight_workspace_bytes: bad dimensions"); return 0; }
+  return break_weight_workspace_bytes(n0, n1, n2);
+}
+int seunet_break_weight(const unsigned char* label, const unsigned char* pred, const unsigned char* skeleton, int n0, int n1, int n2,
+                        void* w_br, unsigned char* br_skel, int* status_dev, void* workspace, size_t workspace_bytes,
+                        seunet_stream_t s) {
+  return launch_break_weight(label, pred, skeleton, n0, n1, n2, w_br, br_skel, status_dev, workspace, workspace_bytes, S(s));
+}
+
 int seunet_crop_batch(const void* img, int img_dtype, const unsigned char* label, const void* weight, int weight_dtype,
                       const unsigned char* skeleton, int d, int h, int w, int cube, int ncrop, const int* starts, const int* aug,
                       double weight_exponent, int f64_math, float* data_out, float* label_out, float* weight_out, float* skel_out,

@@ -189,6 +189,16 @@ cc_fill_kernel(const int* __restrict__ L, const unsigned int* __restrict__ flag,
   if (L[i] >= 0 && flag[L[i]] == 0u) out[i] = 1;      // enclosed background becomes foreground
 }
 
+// L[i] = minimum linear index of the 26-connected component of foreground voxel i, -1 for background (also used by the break
+// weight, edt.hip).  Stream-ordered launches only.
+void cc_label26(const unsigned char* vol, int H, int W, int Z, int* L, hipStream_t s) {
+  const long long n = (long long)H * W * Z;
+  const unsigned blocks = (unsigned)((n + 255) / 256);
+  cc_init_kernel<false><<<blocks, 256, 0, s>>>(vol, n, Z, L);
+  cc_merge_kernel<true><<<blocks, 256, 0, s>>>(L, n, H, W, Z);
+  cc_compress_kernel<<<blocks, 256, 0, s>>>(L, n);
+}
+
 size_t cc_workspace_bytes(int H, int W, int Z) {
   const size_t n = (size_t)H * W * Z;
   return align_up(n * 4, 256) * 2 + 256;               // labels, counts / border flags, CcSel
@@ -208,9 +218,7 @@ int launch_largest_component(const unsigned char* vol, int H, int W, int Z, int 
   const unsigned blocks = (unsigned)((n + 255) / 256);
   SEUNET_HIP(hipMemsetAsync(cnt, 0, (size_t)n * 4, s));
   SEUNET_HIP(hipMemsetAsync(sel, 0, sizeof(CcSel), s));
-  cc_init_kernel<false><<<blocks, 256, 0, s>>>(vol, n, Z, L);
-  cc_merge_kernel<true><<<blocks, 256, 0, s>>>(L, n, H, W, Z);
-  cc_compress_kernel<<<blocks, 256, 0, s>>>(L, n);
+  cc_label26(vol, H, W, Z, L, s);
   cc_count_kernel<<<blocks, 256, 0, s>>>(L, n, cnt);
   cc_select_kernel<<<blocks, 256, 0, s>>>(L, cnt, n, 0, sel);
   if (rule == 1) {

@@ -422,11 +422,25 @@ int launch_level_to_side_grad(const float* glev, long long cstride, long long ns
 int launch_class_bias_grad(const float* per_sample, int N, int K, float* out, hipStream_t s);
 // connected components / metrics (components.hip)
 size_t cc_workspace_bytes(int H, int W, int Z);
+void cc_label26(const unsigned char* vol, int H, int W, int Z, int* L, hipStream_t s);   // component labels (minimum index), -1 off
 int launch_largest_component(const unsigned char* vol, int H, int W, int Z, int rule, unsigned char* out, int* status_dev,
                              void* workspace, size_t ws_bytes, hipStream_t s);
 size_t metric_out_bytes(int nbins);
 int launch_metric_sums(const unsigned char* pred, const unsigned char* label, const unsigned char* skel, const int* parsing, long long n,
                        int nbins, void* out, size_t out_bytes, hipStream_t s);
+// stage-2/3 preparation (edt.hip): exact EDT / feature transform, candidate bit masks, LIB weight, break weight
+size_t edt_workspace_bytes(int n0, int n1, int n2);
+int launch_edt(const unsigned char* vol, int n0, int n1, int n2, int* sqdist, double* dist, int* indices, int* status_dev,
+               void* workspace, size_t ws_bytes, hipStream_t s);
+int launch_mask_bits(const unsigned char* mask, long long n, unsigned long long* bits, hipStream_t s);
+int launch_hm_candidates(const unsigned char* label, const unsigned char* skel, const unsigned char* pred, int n0, int n1, int n2,
+                         unsigned long long* skel_bits, unsigned long long* small_bits, hipStream_t s);
+size_t lib_weight_workspace_bytes(int n0, int n1, int n2);
+int launch_lib_weight(const unsigned char* label, int n0, int n1, int n2, const float* table, void* out, void* workspace,
+                      size_t ws_bytes, hipStream_t s);
+size_t break_weight_workspace_bytes(int n0, int n1, int n2);
+int launch_break_weight(const unsigned char* label, const unsigned char* pred, const unsigned char* skel, int n0, int n1, int n2,
+                        void* w_br, unsigned char* br_skel, int* status_dev, void* workspace, size_t ws_bytes, hipStream_t s);
 // input pipeline (pipeline.hip)
 int launch_crop_batch(const void* img, int img_dtype, const unsigned char* label, const void* weight, int w_dtype,
                       const unsigned char* skel, int D, int H, int W, int cube, int ncrop, const int* starts, const int* aug,

@@ -240,6 +240,14 @@ class AirwayHMDataGPU:
         self.batch_size, self.aug_flag, self.cube = batch_size, aug_flag, cube
         self.random_ratio, self.hard_ratio = 0.6, 0.4
 
+    @classmethod
+    def from_case(cls, img, label, weight, skeleton, pred, batch_size: int, aug_flag: int = 1, cube: int = 128) -> "AirwayHMDataGPU":
+        """The sampler of one case fed entirely from device volumes: the two candidate lists are computed on the GPU from
+        uint8 ``label`` / ``skeleton`` / ``pred`` (``prep.hard_mining_candidates``, data.py:304-306) instead of by the caller."""
+        from .prep import hard_mining_candidates
+        loc_skeleton, loc_small = hard_mining_candidates(label, skeleton, pred)
+        return cls(img, label, weight, loc_skeleton, loc_small, batch_size, aug_flag, cube)
+
     def sample(self) -> Dict[str, torch.Tensor]:
         plan = draw_stage2_plan(self.img.shape, self.batch_size, self.loc_skeleton, self.loc_small, self.cube, self.hard_ratio,
                                 self.aug_flag)
@@ -258,6 +266,16 @@ class AirwayHMData3GPU:
         self.loc_skeleton, self.loc_small, self.loc_break = loc_skeleton, loc_small, loc_break
         self.batch_size, self.aug_flag, self.cube = batch_size, aug_flag, cube
         self.hard_ratio, self.break_ratio = 0.8, 0.625      # (set by the caller's curriculum between epochs)
+
+    @classmethod
+    def from_case(cls, img, label, weight, skeleton, pred, batch_size: int, aug_flag: int = 1, cube: int = 128, *,
+                  br_skel) -> "AirwayHMData3GPU":
+        """As ``AirwayHMDataGPU.from_case`` (data.py:455-458), plus ``loc_break = where(br_skel == 1)`` from the device
+        ``br_skel`` volume (``prep.break_weight``, weight_br.py:171)."""
+        from .prep import CandidateSet, hard_mining_candidates
+        loc_skeleton, loc_small = hard_mining_candidates(label, skeleton, pred)
+        loc_break = CandidateSet.from_mask(br_skel)
+        return cls(img, label, weight, skeleton, loc_skeleton, loc_small, loc_break, batch_size, aug_flag, cube)
 
     def sample(self) -> Dict[str, torch.Tensor]:
         plan = draw_stage3_plan(self.img.shape, self.batch_size, self.loc_skeleton, self.loc_small, self.loc_break, self.cube,
