@@ -279,9 +279,13 @@ int seunet_dti(const double* pred, int h, int w, int z, double h_thresh, double 
  *        does not reach the border becomes foreground).
  * out: h*w*z bytes of 0/1.  status_dev (device int, optional): 0 ok, 1 no component, 2 no second component (the reference
  * raises IndexError in both cases under maximum_3d).  Union-find with atomics on labels = minimum linear index: the
- * result is deterministic.  workspace: seunet_cc_workspace_bytes(h, w, z), caller-owned. */
+ * result is deterministic.  workspace: seunet_cc_workspace_bytes(h, w, z), caller-owned.
+ *   rule SEUNET_CC_LARGEST_FILLED (util.py:156-165, large_connected_domain26): the component of SEUNET_CC_EVALUATION (ties:
+ *        the highest label, as the reference's argsort gives with a stable sort), then the binary_fill_holes of
+ *        SEUNET_CC_MAXIMUM_3D; status 1 for an empty volume (the reference raises IndexError). */
 #define SEUNET_CC_EVALUATION 0
 #define SEUNET_CC_MAXIMUM_3D 1
+#define SEUNET_CC_LARGEST_FILLED 2
 size_t seunet_cc_workspace_bytes(int h, int w, int z);
 int seunet_largest_component(const unsigned char* volume, int h, int w, int z, int rule, unsigned char* out, int* status_dev,
                              void* workspace, size_t workspace_bytes, seunet_stream_t s);
@@ -324,6 +328,31 @@ size_t seunet_break_weight_workspace_bytes(int n0, int n1, int n2);
 int seunet_break_weight(const unsigned char* label, const unsigned char* pred, const unsigned char* skeleton, int n0, int n1, int n2,
                         void* w_br, unsigned char* br_skel, int* status_dev, void* workspace, size_t workspace_bytes,
                         seunet_stream_t s);
+
+/* ---- CT preprocessing: preprocessing.py:26-130 with util.py:95-152 -----------------------------
+ * CT volumes are int16, C-contiguous (h, w, z) on the device (the reference's orientation after its transposes), fewer than 2^31
+ * voxels; masks are bytes, non-zero = 1.
+ * seunet_value_counts: counts[(uint16)(int16)(ct[i] + shift)] += 1 over the n voxels; counts = 65536 device uint32 (zeroed
+ *   here).  Bin b holds the value (int16)b.  The 300-bin histograms of preprocessing.py:51 and util.py:99 follow on the host.
+ * seunet_shift_clamp: out[i] = (int16)(ct[i] + shift) (numpy's wrapping int16 sum); with clamp != 0, values <= clamp_le
+ *   become clamp_to (preprocessing.py:69-71: clamp_le = -800, clamp_to = int16(aaa)).  out may alias ct.
+ * seunet_get_l: util.py:120-152 (get_l) for every slice n of range(int(0.05 z) - 1, int(0.95 z)) (n = -1: the last slice):
+ *   ct >= T (float64), its largest 8-connected component (ties: first in raster order), that component's 4-connected
+ *   holes, relabelled 8-connected, and the largest two of those written as 1 when they have more than min_area pixels (the
+ *   reference: 2000).  Every other slice is 0.  workspace: seunet_get_l_workspace_bytes(h, w, z), caller-owned.
+ * seunet_mask_combine: out = (a != 0) ^ (b != 0) (op 0) or (a != 0) | (b != 0) (op 1), as 0/1 bytes.
+ * seunet_mask_box: box_dev (6 device ints) = {min, max} of the coordinates of the non-zero voxels along axes 0, 1, 2;
+ *   {INT_MAX, -1} for an axis of an empty mask.
+ * seunet_crop3d: dst = src[box[0]:box[1], box[2]:box[3], box[4]:box[5]] (box: 6 HOST ints, half-open, inside the volume),
+ *   elements of elem_bytes = 1 or 2 bytes, dst C-contiguous. */
+int seunet_value_counts(const short* ct, long long n, int shift, unsigned int* counts, seunet_stream_t s);
+int seunet_shift_clamp(const short* ct, long long n, int shift, int clamp, int clamp_le, int clamp_to, short* out, seunet_stream_t s);
+size_t seunet_get_l_workspace_bytes(int h, int w, int z);
+int seunet_get_l(const short* ct, int h, int w, int z, double T, int min_area, unsigned char* out, void* workspace,
+                 size_t workspace_bytes, seunet_stream_t s);
+int seunet_mask_combine(const unsigned char* a, const unsigned char* b, long long n, int op, unsigned char* out, seunet_stream_t s);
+int seunet_mask_box(const unsigned char* mask, int h, int w, int z, int* box_dev, seunet_stream_t s);
+int seunet_crop3d(const void* src, int elem_bytes, int h, int w, int z, const int* box, void* dst, seunet_stream_t s);
 
 /* ---- whole network: SE_UNet.forward (SE_UNet.py:181-238) and its backward ------------------------------- */
 typedef struct seunet_net_desc {

@@ -16,7 +16,7 @@ F32, BF16, F16 = 0, 1, 2
 CONV_MFMA, CONV_NAIVE, CONV_MARCH, CONV_TILED = 0, 1, 2, 3
 LOSS_NSUMS = 7
 DTI_F64, DTI_F32 = 0, 1
-CC_EVALUATION, CC_MAXIMUM_3D = 0, 1
+CC_EVALUATION, CC_MAXIMUM_3D, CC_LARGEST_FILLED = 0, 1, 2
 
 
 class Dims(C.Structure):
@@ -90,6 +90,13 @@ PROTOTYPES = {
     "seunet_largest_component": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "seunet_metric_out_bytes": (_sz, [_i]),
     "seunet_metric_sums": (_i, [_vp, _vp, _vp, _vp, _ll, _i, _vp, _sz, _vp]),
+    "seunet_value_counts": (_i, [_vp, _ll, _i, _vp, _vp]),
+    "seunet_shift_clamp": (_i, [_vp, _ll, _i, _i, _i, _i, _vp, _vp]),
+    "seunet_get_l_workspace_bytes": (_sz, [_i, _i, _i]),
+    "seunet_get_l": (_i, [_vp, _i, _i, _i, _d, _i, _vp, _vp, _sz, _vp]),
+    "seunet_mask_combine": (_i, [_vp, _vp, _ll, _i, _vp, _vp]),
+    "seunet_mask_box": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "seunet_crop3d": (_i, [_vp, _i, _i, _i, _i, _ip, _vp, _vp]),
     "seunet_crop_batch": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _ip, _ip, C.c_double, _i, _vp, _vp, _vp, _vp, _vp]),
     "seunet_hu_two_channel": (_i, [_vp, _i, _ll, _i, _vp, _vp]),
     "seunet_window_gather": (_i, [_vp, _i, _i, _i, _i, _i, _i, _ip, _vp, _vp]),

@@ -324,6 +324,30 @@ int seunet_break_weight(const unsigned char* label, const unsigned char* pred, c
   return launch_break_weight(label, pred, skeleton, n0, n1, n2, w_br, br_skel, status_dev, workspace, workspace_bytes, S(s));
 }
 
+int seunet_value_counts(const short* ct, long long n, int shift, unsigned int* counts, seunet_stream_t s) {
+  return launch_value_counts(ct, n, shift, counts, S(s));
+}
+int seunet_shift_clamp(const short* ct, long long n, int shift, int clamp, int clamp_le, int clamp_to, short* out, seunet_stream_t s) {
+  return launch_shift_clamp(ct, n, shift, clamp, clamp_le, clamp_to, out, S(s));
+}
+size_t seunet_get_l_workspace_bytes(int h, int w, int z) {
+  if (h < 1 || w < 1 || z < 1) { fail("get_l_workspace_bytes: bad dimensions"); return 0; }
+  return get_l_workspace_bytes(h, w, z);
+}
+int seunet_get_l(const short* ct, int h, int w, int z, double T, int min_area, unsigned char* out, void* workspace,
+                 size_t workspace_bytes, seunet_stream_t s) {
+  return launch_get_l(ct, h, w, z, T, min_area, out, workspace, workspace_bytes, S(s));
+}
+int seunet_mask_combine(const unsigned char* a, const unsigned char* b, long long n, int op, unsigned char* out, seunet_stream_t s) {
+  return launch_mask_combine(a, b, n, op, out, S(s));
+}
+int seunet_mask_box(const unsigned char* mask, int h, int w, int z, int* box_dev, seunet_stream_t s) {
+  return launch_mask_box(mask, h, w, z, box_dev, S(s));
+}
+int seunet_crop3d(const void* src, int elem_bytes, int h, int w, int z, const int* box, void* dst, seunet_stream_t s) {
+  return launch_crop3d(src, elem_bytes, h, w, z, box, dst, S(s));
+}
+
 int seunet_crop_batch(const void* img, int img_dtype, const unsigned char* label, const void* weight, int weight_dtype,
                       const unsigned char* skeleton, int d, int h, int w, int cube, int ncrop, const int* starts, const int* aug,
                       double weight_exponent, int f64_math, float* data_out, float* label_out, float* weight_out, float* skel_out,

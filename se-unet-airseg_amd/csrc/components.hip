@@ -7,6 +7,8 @@
 //                   scipy.ndimage.binary_fill_holes (background = 6-connected, holes = background not reaching the border)
 //   train.py:749-757 evaluation_case: the same largest-component rule without the slice test and without hole filling;
 //                   an empty prediction stays empty
+//   util.py:156-165 large_connected_domain26 (rule 2): evaluation_case's selection (`argsort(volume)[-1]`; on equal counts the
+//                   highest label, as a stable sort gives), then maximum_3d's binary_fill_holes; an empty mask is status 1
 //   metrics.py:14-78 sums over pred / label / skeleton and per-branch counts (bincount of skeleton * parsing)
 // cc3d numbers components in order of first appearance in memory order, so "highest label number" = the component whose
 // first voxel comes LAST in raster order = the largest minimum linear index.
@@ -33,22 +35,7 @@ struct CcSel {            // device-side scalars of one call
   int pad;
 };
 
-__device__ __forceinline__ int cc_find(const int* L, int i) {
-  int p = L[i];
-  while (p != i) { i = p; p = L[i]; }      // strictly decreasing chain: terminates even on stale reads
-  return i;
-}
-
-__device__ __forceinline__ void cc_union(int* L, int a, int b) {
-  bool done;
-  do {
-    a = cc_find(L, a);
-    b = cc_find(L, b);
-    if (a < b) { const int old = atomicMin(&L[b], a); done = old == b; b = old; }
-    else if (b < a) { const int old = atomicMin(&L[a], b); done = old == a; a = old; }
-    else done = true;
-  } while (!done);
-}
+// cc_find / cc_union: seunet_common.h (shared with the per-slice labelling of lung.hip)
 
 // L[i] = start of the z-run of voxel i inside its wave span (foreground), -1 (background).  INVERT labels the complement.
 template <bool INVERT>
@@ -207,7 +194,8 @@ size_t cc_workspace_bytes(int H, int W, int Z) {
 int launch_largest_component(const unsigned char* vol, int H, int W, int Z, int rule, unsigned char* out, int* status_dev,
                              void* workspace, size_t ws_bytes, hipStream_t s) {
   SEUNET_CHECK(vol && out && workspace && H >= 1 && W >= 1 && Z >= 1, "largest_component: bad argument");
-  SEUNET_CHECK(rule == 0 || rule == 1, "largest_component: rule %d (0 = evaluation_case, train.py:749-757; 1 = maximum_3d, util.py:58-75)", rule);
+  SEUNET_CHECK(rule >= 0 && rule <= 2, "largest_component: rule %d (0 = evaluation_case, train.py:749-757; 1 = maximum_3d, util.py:58-75; "
+               "2 = large_connected_domain26, util.py:156-165)", rule);
   const long long n = (long long)H * W * Z;
   SEUNET_CHECK(n < (1ll << 31), "largest_component: %lld voxels exceed the 32-bit label range", n);
   SEUNET_CHECK(ws_bytes >= cc_workspace_bytes(H, W, Z), "largest_component: workspace too small");
@@ -228,7 +216,7 @@ int launch_largest_component(const unsigned char* vol, int H, int W, int Z, int 
   }
   cc_choose_kernel<<<1, 64, 0, s>>>(sel, rule);
   cc_mask_kernel<<<blocks, 256, 0, s>>>(L, n, sel, out);
-  if (rule == 1) {   // binary_fill_holes (util.py:73): label the complement with 6-connectivity, keep what reaches the border
+  if (rule >= 1) {   // binary_fill_holes (util.py:73, :163): label the complement with 6-connectivity, keep what reaches the border
     SEUNET_HIP(hipMemsetAsync(cnt, 0, (size_t)n * 4, s));
     cc_init_kernel<true><<<blocks, 256, 0, s>>>(out, n, Z, L);
     cc_merge_kernel<false><<<blocks, 256, 0, s>>>(L, n, H, W, Z);

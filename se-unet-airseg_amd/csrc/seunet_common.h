@@ -421,6 +421,24 @@ int launch_level_to_side_grad(const float* glev, long long cstride, long long ns
                               hipStream_t s);
 int launch_class_bias_grad(const float* per_sample, int N, int K, float* out, hipStream_t s);
 // connected components / metrics (components.hip)
+// Union-find on labels = minimum linear index (every element points to a smaller index of its set, roots to themselves; a union
+// is an atomicMin on the larger root).  Parents only decrease, so a stale read is still an ancestor and cc_find terminates.
+__device__ __forceinline__ int cc_find(const int* L, int i) {
+  int p = L[i];
+  while (p != i) { i = p; p = L[i]; }      // strictly decreasing chain: terminates even on stale reads
+  return i;
+}
+
+__device__ __forceinline__ void cc_union(int* L, int a, int b) {
+  bool done;
+  do {
+    a = cc_find(L, a);
+    b = cc_find(L, b);
+    if (a < b) { const int old = atomicMin(&L[b], a); done = old == b; b = old; }
+    else if (b < a) { const int old = atomicMin(&L[a], b); done = old == a; a = old; }
+    else done = true;
+  } while (!done);
+}
 size_t cc_workspace_bytes(int H, int W, int Z);
 void cc_label26(const unsigned char* vol, int H, int W, int Z, int* L, hipStream_t s);   // component labels (minimum index), -1 off
 int launch_largest_component(const unsigned char* vol, int H, int W, int Z, int rule, unsigned char* out, int* status_dev,
@@ -441,6 +459,15 @@ int launch_lib_weight(const unsigned char* label, int n0, int n1, int n2, const 
 size_t break_weight_workspace_bytes(int n0, int n1, int n2);
 int launch_break_weight(const unsigned char* label, const unsigned char* pred, const unsigned char* skel, int n0, int n1, int n2,
                         void* w_br, unsigned char* br_skel, int* status_dev, void* workspace, size_t ws_bytes, hipStream_t s);
+// CT preprocessing (lung.hip): value counts, shift + clamp, per-slice lung field, mask combination, bounding box, crop
+int launch_value_counts(const short* ct, long long n, int shift, unsigned int* counts, hipStream_t s);
+int launch_shift_clamp(const short* ct, long long n, int shift, int clamp, int clamp_le, int clamp_to, short* out, hipStream_t s);
+size_t get_l_workspace_bytes(int H, int W, int Z);
+int launch_get_l(const short* ct, int H, int W, int Z, double T, int min_area, unsigned char* out, void* workspace, size_t ws_bytes,
+                 hipStream_t s);
+int launch_mask_combine(const unsigned char* a, const unsigned char* b, long long n, int op, unsigned char* out, hipStream_t s);
+int launch_mask_box(const unsigned char* mask, int H, int W, int Z, int* box, hipStream_t s);
+int launch_crop3d(const void* src, int elem_bytes, int H, int W, int Z, const int* box, void* dst, hipStream_t s);
 // input pipeline (pipeline.hip)
 int launch_crop_batch(const void* img, int img_dtype, const unsigned char* label, const void* weight, int w_dtype,
                       const unsigned char* skel, int D, int H, int W, int cube, int ncrop, const int* starts, const int* aug,
