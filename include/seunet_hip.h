@@ -398,6 +398,34 @@ int seunet_graph_destroy(void* graph);
  * NULL otherwise).  The product path does not call this (tests/flip_census.py and the same-choice gradient gate do). */
 int seunet_net_read_tensor(const seunet_net_desc* desc, const float* const* params, const void* workspace, size_t workspace_bytes,
                            const char* name, int which, float* out, int* channels, seunet_stream_t s);
+/* Host-only description of the plan's convolutions (no GPU, like seunet_net_workspace_bytes): the index-th convolution block of
+ * the network in execution order (the 18 gated 3x3x3 blocks and the 6 aggregation 1x1x1 blocks; dc62 is dead), with the kernel
+ * the plan routes each of its passes to.  Returns non-zero past the last convolution (and for a bad descriptor).
+ *   dims: the block's level extents, n = batch.  src_c: stored channels of each source tensor; src_is_input: 1 where the source is
+ *   the packed network input (it takes no data gradient: a null destination).  cin: logical input channels (in_channel for ec1).
+ *   fwd / dgrad / wgrad: SEUNET_KERNEL_* of the forward, data-gradient (meaningful when need_dgrad) and weight-gradient pass.
+ *   x_name: the raw-input branch of an aggregation block (x33 / x63 / x93; "" = none), a 1x1x1 conv of the 8-channel packed
+ *   input; x_materialised: 1 when it runs as a convolution of its own (in_channel > 2, or the naive path), on x_fwd / x_wgrad;
+ *   0 when the aggregation epilogue recomputes it.  src_dist: for a two-source block the byte distance source[1] - source[0]
+ *   inside the workspace (what the marching kernels' 32-bit buffer descriptor has to span), 0 otherwise. */
+#define SEUNET_KERNEL_NAIVE 0
+#define SEUNET_KERNEL_TILED 1     /* implicit GEMM, conv_igemm.hip / wgrad.hip */
+#define SEUNET_KERNEL_STREAM 2    /* conv_stream.hip / wgrad_stream.hip */
+#define SEUNET_KERNEL_MARCH 3     /* conv_march.hip / wgrad_march.hip */
+#define SEUNET_KERNEL_WGRAD1X1 4  /* wgrad_1x1.hip (weight gradient only) */
+typedef struct seunet_conv_info {
+  char name[16];
+  int taps, dilation, level;
+  seunet_dims dims;
+  int nsrc, src_c[3], src_is_input[3];
+  int cin, cout;
+  int need_dgrad;
+  int fwd, dgrad, wgrad;
+  char x_name[16];
+  int x_materialised, x_fwd, x_wgrad;
+  long long src_dist;
+} seunet_conv_info;
+int seunet_net_conv_info(const seunet_net_desc* desc, int index, seunet_conv_info* out);
 /* grads: device pointers in registry order, each overwritten (NULL = skip).  The dead block dc62
  * (SE_UNet.py:148,230) receives no gradient: its entry is never written. */
 int seunet_net_backward(const seunet_net_desc* desc, const float* const* params, const float* g_pred0,

@@ -152,6 +152,34 @@ def registry(desc: _lib.NetDesc) -> List[Tuple[str, Tuple[int, ...]]]:
     return out
 
 
+def conv_plan(desc: _lib.NetDesc) -> List[dict]:
+    """The native plan's convolution blocks in execution order, one dict each (``seunet_net_conv_info``; needs no GPU): name,
+    taps, dilation, level, dims (n, d, h, w), src_c / src_is_input per source, cin, cout, need_dgrad, the kernel of the
+    ``fwd`` / ``dgrad`` / ``wgrad`` pass (``_lib.KERNEL_NAMES``), the raw-input branch (``x_name`` or None, ``x_materialised``,
+    ``x_fwd``, ``x_wgrad``) and ``src_dist``, the byte distance of a two-source block's sources in the workspace."""
+    lib = _lib.load()
+    if lib.seunet_net_workspace_bytes(C.byref(desc)) == 0:     # a bad descriptor: report it instead of an empty plan
+        raise RuntimeError(f"libseunet_hip conv_plan: {_lib.last_error()}")
+    out = []
+    info = _lib.ConvInfo()
+    while lib.seunet_net_conv_info(C.byref(desc), len(out), C.byref(info)) == 0:
+        k = lambda code: _lib.KERNEL_NAMES[code]
+        x_name = info.x_name.decode() or None
+        out.append({
+            "name": info.name.decode(), "taps": info.taps, "dilation": info.dilation, "level": info.level,
+            "dims": (info.dims.n, info.dims.d, info.dims.h, info.dims.w),
+            "src_c": [info.src_c[i] for i in range(info.nsrc)],
+            "src_is_input": [bool(info.src_is_input[i]) for i in range(info.nsrc)],
+            "cin": info.cin, "cout": info.cout, "need_dgrad": bool(info.need_dgrad),
+            "fwd": k(info.fwd), "dgrad": k(info.dgrad) if info.need_dgrad else None, "wgrad": k(info.wgrad),
+            "x_name": x_name, "x_materialised": bool(info.x_materialised),
+            "x_fwd": k(info.x_fwd) if x_name and info.x_materialised else None,
+            "x_wgrad": k(info.x_wgrad) if x_name and info.x_materialised else None,
+            "src_dist": info.src_dist,
+        })
+    return out
+
+
 def _is_decoder(name: str) -> bool:
     return name.startswith("dc") and not name.startswith("dc0_")
 
@@ -327,6 +355,8 @@ class SE_UNet(nn.Module):
         self._dead = [n.startswith("dc62.") for n in self._names]
         self._registry_checked = False
         self._arena = {}              # inference workspaces by (shape, dtype, device): predict_logits()
+
+    conv_plan = staticmethod(conv_plan)
 
     def _check_registry(self, desc):
         if self._registry_checked:

@@ -30,7 +30,19 @@ class NetDesc(C.Structure):
                 ("negative_slope", C.c_float), ("eps", C.c_float)]
 
 
-_vp, _i, _f, _ll, _sz, _d = C.c_void_p, C.c_int, C.c_float, C.c_longlong, C.c_size_t, C.c_double
+KERNEL_NAIVE, KERNEL_TILED, KERNEL_STREAM, KERNEL_MARCH, KERNEL_WGRAD1X1 = range(5)
+KERNEL_NAMES = ("Naive", "Tiled", "Stream", "March", "Wgrad1x1")
+
+
+class ConvInfo(C.Structure):
+    _fields_ = [("name", C.c_char * 16), ("taps", C.c_int), ("dilation", C.c_int), ("level", C.c_int), ("dims", Dims),
+                ("nsrc", C.c_int), ("src_c", C.c_int * 3), ("src_is_input", C.c_int * 3), ("cin", C.c_int), ("cout", C.c_int),
+                ("need_dgrad", C.c_int), ("fwd", C.c_int), ("dgrad", C.c_int), ("wgrad", C.c_int),
+                ("x_name", C.c_char * 16), ("x_materialised", C.c_int), ("x_fwd", C.c_int), ("x_wgrad", C.c_int),
+                ("src_dist", C.c_longlong)]
+
+
+_vp, _i, _f, _ll, _sz, _d =C.c_void_p, C.c_int, C.c_float, C.c_longlong, C.c_size_t, C.c_double
 _pp = C.POINTER(C.c_void_p)
 _ip = C.POINTER(C.c_int)
 
@@ -125,6 +137,7 @@ PROTOTYPES = {
     "seunet_graph_launch": (_i, [_vp, _vp]),
     "seunet_graph_destroy": (_i, [_vp]),
     "seunet_net_read_tensor": (_i, [C.POINTER(NetDesc), _pp, _vp, _sz, C.c_char_p, _i, _vp, _ip, _vp]),
+    "seunet_net_conv_info": (_i, [C.POINTER(NetDesc), _i, C.POINTER(ConvInfo)]),
     "seunet_net_backward": (_i, [C.POINTER(NetDesc), _pp, _vp, _vp, _vp, _vp, _pp, _vp, _sz, _vp]),
     "seunet_net_backward_ev": (_i, [C.POINTER(NetDesc), _pp, _vp, _vp, _vp, _vp, _pp, _vp, _sz, _vp, _vp]),
     "seunet_net_input_grad_bytes": (_sz, [C.POINTER(NetDesc)]),

@@ -423,6 +423,12 @@ conv_igemm_kernel(ConvKArgs a) {
   //    its 128 voxels through LDS -- cheaply, because the transposed accumulators already hold runs of 4 channels: one
   //    ds_write_b64 / b128 per run into [voxel][NCOL channels] rows (row pitch +16 B: conflict-free) -- and stores whole
   //    16-B pieces, 4-8 adjacent lanes covering one voxel's contiguous channels.
+  //  `+=` in 16-bit storage: the direct path adds the old value to the f32 accumulator and rounds once (as the marching and
+  //  streaming kernels do); the staged path has only the ROUNDED new value in its stage, so it stores
+  //  round(round(new) + old): one storage ulp from round(new + old) on a few per cent of the elements (in the network: the
+  //  data gradients of ec11, ec12 and dc2).  Sending accumulating launches down the direct path removes the second rounding
+  //  and costs 0.3-0.6 % of the training step (14.31-14.35 -> 14.35-14.44 ms, same box, alternating runs), so it stays;
+  //  tests/test_ops_gpu.py and tests/test_conv_layers_gpu.py pin both forms bitwise.
   if (a.direct) {
     const int daccmask = a.dacc0 | (a.dacc1 << 1) | (a.dacc2 << 2);
     const int dC0 = a.dstC0, dC1 = a.dstC1, dC2 = a.dstC2;

@@ -150,9 +150,10 @@ int conv_slots(ConvKernel k, const Dims& dm, int taps, int dil, int cin, int cou
 ConvKernel wgrad_kernel(int dtype, int taps, int dil, const SrcList& x, int cin_logical, int cout, Dims d, long long src_dist) {
   if (taps == 1) {
     // where the whole-GEMM 1x1x1 kernel beats the tiled kernel (isolated launches): many (ci, co) combos there, i.e. many
-    // re-reads -- ec63 (8 combos, 1 M voxels) 0.104 vs 0.165 ms, ec93 (24 combos, 131 k voxels) 0.051 vs 0.085 ms; not dc42
-    // (2 combos: 0.059 vs 0.039 ms) nor dc22 (8 combos but 131 k voxels: 0.033 vs 0.023 ms, four chunks per workgroup do not
-    // amortise the pipeline fill)
+    // re-reads -- ec63 (8 combos, 1 M voxels) 0.104 vs 0.165 ms, 192 -> 128 channels (24 combos, 131 k voxels) 0.051 vs 0.085 ms;
+    // not dc42 (2 combos: 0.059 vs 0.039 ms) nor dc22 (8 combos but 131 k voxels: 0.033 vs 0.023 ms, four chunks per workgroup do
+    // not amortise the pipeline fill).  (ec93 is 192 -> 64 at width 1: 12 combos on 131 k voxels, on dc22's side, and not a form
+    // wgrad_1x1.hip instantiates.)
     const int combos = cdiv(cin_logical, 32) * cdiv(cout, 32);
     const long long nv = (long long)d.N * d.vox();
     const bool pays = combos >= 16 || (combos >= 8 && nv >= 500000);
@@ -160,7 +161,7 @@ ConvKernel wgrad_kernel(int dtype, int taps, int dil, const SrcList& x, int cin_
   }
   // where the marching kernel beats the tiled kernel (isolated launches, 4 samples): the fine levels (rows of >= 32 voxels,
   // >= 48^3); every dilation-2 layer down to 16^3 (the tiled kernel works on parity sub-lattices there: 32^3 64 -> 64 0.057 vs
-  // 0.080 ms, 16^3 128 -> 128 0.058 vs 0.075 ms); 256-channel inputs (dc1: 0.118 vs 0.134 ms).  Dilation 1 with <= 128 input
+  // 0.080 ms, 16^3 128 -> 128 0.058 vs 0.075 ms); 256-channel inputs (dc1 at width 2: 0.118 vs 0.134 ms; 128 at width 1).  Dilation 1 with <= 128 input
   // channels on the coarse levels is a tie and stays where it was.
   const bool fine = d.W >= 32 && (long long)d.D * d.H * d.W >= 48LL * 48 * 48;
   const bool pays = fine || dil == 2 || cin_logical >= 256;
@@ -958,6 +959,49 @@ int seunet_net_read_tensor(const seunet_net_desc* desc, const float* const* para
     return 0;
   }
   return fail("net_read_tensor: no block named %s", name);
+}
+
+static_assert((int)ConvKernel::Naive == SEUNET_KERNEL_NAIVE && (int)ConvKernel::Tiled == SEUNET_KERNEL_TILED &&
+                  (int)ConvKernel::Stream == SEUNET_KERNEL_STREAM && (int)ConvKernel::March == SEUNET_KERNEL_MARCH &&
+                  (int)ConvKernel::Wgrad1x1 == SEUNET_KERNEL_WGRAD1X1,
+              "SEUNET_KERNEL_* are the values of ConvKernel");
+
+int seunet_net_conv_info(const seunet_net_desc* desc, int index, seunet_conv_info* out) {
+  SEUNET_CHECK(desc && out, "net_conv_info: null argument");
+  Plan p;
+  if (int e = p.init(*desc)) return e;
+  SEUNET_CHECK(index >= 0, "net_conv_info: index %d out of range", index);
+  int seen = 0;
+  for (int i = 0; i < kNumOps; ++i) {
+    const OpDesc& o = kOps[i];
+    if (o.kind != OP_GATED && o.kind != OP_CAT) continue;
+    if (seen++ != index) continue;
+    const OpRes& r = p.op[i];
+    const int lv = kT[o.dst].level;
+    *out = seunet_conv_info{};
+    snprintf(out->name, sizeof out->name, "%s", o.name);
+    out->taps = r.taps;
+    out->dilation = o.kind == OP_GATED ? o.dil : 1;
+    out->level = lv;
+    out->dims = seunet_dims{p.dims[lv].N, p.dims[lv].D, p.dims[lv].H, p.dims[lv].W};
+    out->nsrc = o.nsrc;
+    for (int k = 0; k < o.nsrc; ++k) { out->src_c[k] = p.C[o.src[k]]; out->src_is_input[k] = is_input(o.src[k]) ? 1 : 0; }
+    out->cin = r.cin;
+    out->cout = r.cout;
+    out->need_dgrad = r.need_dgrad ? 1 : 0;
+    out->fwd = (int)r.fwd;
+    out->dgrad = (int)r.dgrad;
+    out->wgrad = (int)r.wgrad;
+    if (o.xname) {
+      snprintf(out->x_name, sizeof out->x_name, "%s", o.xname);
+      out->x_materialised = p.fuse_x ? 0 : 1;
+      out->x_fwd = (int)r.x_fwd;
+      out->x_wgrad = (int)r.x_wgrad;
+    }
+    out->src_dist = o.nsrc == 2 ? (long long)p.feat[o.src[1]] - (long long)p.feat[o.src[0]] : 0;
+    return 0;
+  }
+  return fail("net_conv_info: index %d is past the last convolution (%d)", index, seen);
 }
 
 int seunet_net_backward(const seunet_net_desc* desc, const float* const* params, const float* g_pred0,

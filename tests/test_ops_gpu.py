@@ -146,6 +146,42 @@ def test_conv_data_gradient(S, dtype, impl, case):
         o += c
 
 
+@pytest.mark.parametrize("dtype", ["bf16", "fp16"])
+@pytest.mark.parametrize("case", [([64], 64, 1, 27), ([32, 32], 32, 1, 27), ([32], 64, 2, 27), ([64, 64, 64], 64, 1, 1),   # staged stores
+                                  ([16], 32, 1, 27), ([8], 32, 2, 27), ([16, 8], 32, 1, 1)])                             # direct stores
+def test_conv_data_gradient_accumulation_rounding(S, dtype, case):
+    """`+=` into 16-bit destinations on the tiled kernel, bitwise.  Small integer operands make every f32 sum exact, so what
+    is stored is decided by the roundings alone: round(new + old) on the direct store path (every destination <= 16 channels
+    per written voxel pitch), round(round(new) + old) on the staged path, whose LDS stage holds the new values already
+    rounded (csrc/conv_igemm.hip, comment on the store paths; found at the network's shapes by
+    tests/test_conv_layers_gpu.py).  The weights are scaled by an odd factor so that many results leave the range in which
+    the storage type holds every integer; the two forms then differ on some elements, which the test requires."""
+    split, cout, dil, taps = case
+    k = 3 if taps == 27 else 1
+    st = dil if k == 3 else 1
+    staged = any(c * st > 16 for c in split)
+    n, d, h, w = 1, 5, 6, 36
+    cin = sum(split)
+    g = torch.Generator().manual_seed(60)
+    scale = {("bf16", 27): 3.0, ("bf16", 1): 15.0, ("fp16", 27): 15.0, ("fp16", 1): 75.0}[(dtype, taps)]
+    wt = torch.randint(-3, 4, (cout, cin, k, k, k), generator=g).float() * scale
+    dy = torch.randint(-3, 4, (n, cout, d, h, w), generator=g).float()
+    prev = torch.randint(-3, 4, (n, cin, d, h, w), generator=g).float()
+    ref = F.conv3d(dy, wt.transpose(0, 1).flip(2, 3, 4).contiguous(), padding=dil if k == 3 else 0, dilation=dil if k == 3 else 1)
+    once, twice = rnd(dtype, ref + prev), rnd(dtype, rnd(dtype, ref) + prev)
+    assert float((once != twice).float().mean()) > 0.005 and float(ref.abs().max()) < 60000     # the case tells the two forms apart
+    dsts, o = [], 0
+    for c in split:
+        dsts.append(S.to_cl(prev[:, o:o + c].cuda(), dtype))
+        o += c
+    S.conv3d([S.to_cl(dy.cuda(), dtype)], wt.cuda(), None, dil, 0, transpose_flip=True, dsts=dsts, accumulate=[1] * len(split))
+    want, o = twice if staged else once, 0
+    for i, c in enumerate(split):
+        got = S.from_cl(dsts[i]).cpu()
+        assert torch.equal(got, want[:, o:o + c]), (i, int((got != want[:, o:o + c]).sum()), got.numel(), int((got != (once if staged else twice)[:, o:o + c]).sum()))
+        o += c
+
+
 @pytest.mark.parametrize("dtype", DT)
 @pytest.mark.parametrize("impl", IMPL)
 @pytest.mark.parametrize("case", [([8], 2, 8, 1, 27), ([16], 16, 32, 2, 27), ([32, 32], 64, 32, 1, 27),
