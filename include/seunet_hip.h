@@ -131,6 +131,13 @@ int seunet_gate_epilogue_bwd(int dtype, const void* raw, const float* mean, cons
                              float* pgrad_partial, seunet_dims dims, seunet_stream_t s);
 int seunet_pgrad_reduce(const float* pgrad_partial, int records, int c, float* dw_se, float* dw_se2, float* dw_side,
                         float* db_side, float* dhead_w, seunet_stream_t s);
+/* What the network runs between pass A and pass B, in one launch: seunet_stats_finalize(mode 1) -> m1, m2 [n][c] and
+ * seunet_pgrad_reduce over the block records.  Preconditions (checked): c a power of two in [8, 128]; slots =
+ * seunet_epilogue_slots(dims) of the pass-A call and records == n * slots, so that stat_partial holds n * slots * c * 2
+ * doubles and pgrad_partial records * (4c + 4) floats.  Any parameter-gradient pointer may be NULL (not written). */
+int seunet_gate_bwd_finalize(const double* stat_partial, int slots, int c, int n, long long count, float* m1, float* m2,
+                             const float* pgrad_partial, int records, float* dw_se, float* dw_se2, float* dw_side,
+                             float* db_side, float* dhead_w, seunet_stream_t s);
 
 /* ---- aggregation block: conv1x1 -> IN -> LeakyReLU (+ x-branch); SE_UNet.py:45-49,187,196,205 -------- */
 int seunet_cat_epilogue_fwd(int dtype, const void* raw, const float* mean, const float* rstd, const void* raw2,
@@ -165,6 +172,20 @@ int seunet_cat_epilogue_bwd_x(int dtype, const void* g_out, const void* raw, con
                               int c, float slope, const float* m1, const float* m2, const float* m1b, const float* m2b,
                               void* dx, double* stat_partial, double* stat_partial2, double* xw_partial, seunet_dims dims,
                               seunet_stream_t s);
+/* The same block followed by nn.MaxPool3d(2,2) (ec33 -> pool0, ec63 -> pool1, ec93 -> pool2; even extents), as the network
+ * runs it: one kernel writes out, pooled [n][d/2][h/2][w/2][c] and, when argmax is not NULL, one 32-bit word per pooling
+ * window and group of 8 channels, argmax [n][vox/8][c/8]: bits [3j, 3j+3) of word (window, g) hold, for channel 8g + j, the
+ * position k = 4*(z&1) + 2*(y&1) + (x&1) of the FIRST maximum, in that z-y-x order, of the window's values AS STORED in out
+ * (bits 24-31 are zero).  The backward takes the pooled gradient pool_g [n][vox/8][c] (storage type) with those words and
+ * adds it on the fly, in both passes, to g_out at the voxel each word names; pool_argmax == NULL is seunet_cat_epilogue_bwd_x. */
+int seunet_cat_epilogue_fwd_x_pool(int dtype, const void* raw, const float* mean, const float* rstd, const void* x_in,
+                                   const float* w2, int in_channel, const float* mean2, const float* rstd2, int c, float slope,
+                                   void* out, void* pooled, unsigned int* argmax, seunet_dims dims, seunet_stream_t s);
+int seunet_cat_epilogue_bwd_x_pool(int dtype, const void* g_out, const void* raw, const float* mean, const float* rstd,
+                                   const void* x_in, const float* w2, int in_channel, const float* mean2, const float* rstd2,
+                                   int c, float slope, const float* m1, const float* m2, const float* m1b, const float* m2b,
+                                   void* dx, double* stat_partial, double* stat_partial2, double* xw_partial,
+                                   const unsigned int* pool_argmax, const void* pool_g, seunet_dims dims, seunet_stream_t s);
 int seunet_cat_xgrad_finalize(const double* xw_partial, const double* stat_partial2, int slots, const double* moments,
                               const float* w2, int c, int in_channel, int n, float eps, float* dw, seunet_stream_t s);
 

@@ -4,6 +4,7 @@ timeout -k 10 700 python -m pytest tests/test_ops_gpu.py -m gpu -q -p no:cachepr
 rc=$?
 rc2=0
 rc3=0
+rc4=0
 echo "ops rc=$rc"; tail -3 gpurun_out/ops.log
 if [ $rc -le 1 ]; then
   timeout -k 10 900 python -m pytest tests/test_net_gpu.py -m gpu -q -s -p no:cacheprovider > gpurun_out/net.log 2>&1
@@ -18,13 +19,26 @@ if [ $rc -le 1 ]; then
     echo "layers rc=$rc3"; grep -E -A12 "not bitwise equal" "$layers_log" | cut -c1-200 | head -60
     grep -E "passed|failed|FAILED|Error" "$layers_log" | tail -20
     rm -f "$layers_log"
+    if [ $rc3 -le 1 ]; then
+      # every epilogue / pooling / up-sampling / head pass at its benchmark shape against float64 under derived bounds, and one
+      # forward of the network block by block (measured: 19-20 s on an MI355X box, the float64 references included)
+      epi_log=$(mktemp)
+      timeout -k 10 45 python -m pytest tests/test_epilogue_layers_gpu.py -m gpu -q -s -p no:cacheprovider > "$epi_log" 2>&1
+      rc4=$?
+      echo "epilogue layers rc=$rc4"; grep -E -A8 "beyond the bound|not bitwise equal" "$epi_log" | cut -c1-200 | head -60
+      grep -E "passed|failed|FAILED|Error" "$epi_log" | tail -20
+      rm -f "$epi_log"
+    else
+      echo "layer run crashed or timed out (rc=$rc3): epilogue layer tests skipped"
+    fi
   else
     echo "net run crashed or timed out (rc=$rc2): layer tests skipped"
   fi
 else
   echo "ops run crashed or timed out (rc=$rc): net and layer tests skipped"
 fi
-# exit status = the worst of the three runs (a crash / timeout / GPU fault is a failure, not a skip)
+# exit status = the worst of the four runs (a crash / timeout / GPU fault is a failure, not a skip)
 [ $rc2 -gt $rc ] && rc=$rc2
 [ $rc3 -gt $rc ] && rc=$rc3
+[ $rc4 -gt $rc ] && rc=$rc4
 exit $rc

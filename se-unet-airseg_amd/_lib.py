@@ -78,6 +78,7 @@ PROTOTYPES = {
     "seunet_gate_epilogue_fwd": (_i, [_i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _i, _vp, _vp, _i, Dims, _vp]),
     "seunet_gate_epilogue_bwd": (_i, [_i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, Dims, _vp]),
     "seunet_pgrad_reduce": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "seunet_gate_bwd_finalize": (_i, [_vp, _i, _i, _i, _ll, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "seunet_cat_epilogue_fwd": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _vp, Dims, _vp]),
     "seunet_cat_epilogue_bwd": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, Dims, _vp]),
     "seunet_maxpool_fwd": (_i, [_i, _vp, _i, _vp, Dims, _vp]),
@@ -97,6 +98,8 @@ PROTOTYPES = {
     "seunet_xbranch_stats": (_i, [_vp, _i, _vp, _i, _i, _i, _ll, _f, _vp, _vp, _vp, _vp]),
     "seunet_cat_epilogue_fwd_x": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _f, _vp, Dims, _vp]),
     "seunet_cat_epilogue_bwd_x": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, Dims, _vp]),
+    "seunet_cat_epilogue_fwd_x_pool": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _f, _vp, _vp, _vp, Dims, _vp]),
+    "seunet_cat_epilogue_bwd_x_pool": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, Dims, _vp]),
     "seunet_cat_xgrad_finalize": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _f, _vp, _vp]),
     "seunet_cc_workspace_bytes": (_sz, [_i, _i, _i]),
     "seunet_largest_component": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),

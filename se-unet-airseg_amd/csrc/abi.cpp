@@ -177,6 +177,15 @@ int seunet_pgrad_reduce(const float* pgrad_partial, int records, int c, float* d
   SEUNET_CHECK(pgrad_partial && records >= 1, "pgrad_reduce: bad argument");
   return launch_pgrad_reduce(pgrad_partial, records, c, dw_se, dw_se2, dw_side, db_side, dhead_w, S(s));
 }
+int seunet_gate_bwd_finalize(const double* stat_partial, int slots, int c, int n, long long count, float* m1, float* m2,
+                             const float* pgrad_partial, int records, float* dw_se, float* dw_se2, float* dw_side,
+                             float* db_side, float* dhead_w, seunet_stream_t s) {
+  SEUNET_CHECK(stat_partial && m1 && m2 && pgrad_partial && slots >= 1 && n >= 1 && count >= 1, "gate_bwd_finalize: bad argument");
+  SEUNET_CHECK(c % 8 == 0 && c >= 8 && c <= 128 && (c & (c - 1)) == 0, "channel count %d must be a power of two in [8,128]", c);
+  SEUNET_CHECK(records == n * slots, "gate_bwd_finalize: records=%d, pass A wrote n * slots = %d", records, n * slots);
+  return launch_gate_bwd_finalize(stat_partial, slots, c, n, count, m1, m2, pgrad_partial, records, dw_se, dw_se2, dw_side,
+                                  db_side, dhead_w, S(s));
+}
 int seunet_cat_epilogue_fwd(int dtype, const void* raw, const float* mean, const float* rstd, const void* raw2,
                             const float* mean2, const float* rstd2, int c, float slope, void* out, seunet_dims dims,
                             seunet_stream_t s) {
@@ -270,6 +279,23 @@ int seunet_cat_epilogue_bwd_x(int dtype, const void* g_out, const void* raw, con
   SEUNET_CHECK(g_out && raw && mean && rstd && x_in && w2 && mean2 && rstd2, "cat_epilogue_bwd_x: null argument");
   return launch_cat_bwd_x(dtype, g_out, raw, mean, rstd, x_in, w2, in_channel, mean2, rstd2, c, slope, m1, m2, m1b, m2b, dx,
                           stat_partial, stat_partial2, xw_partial, D(dims), S(s));
+}
+int seunet_cat_epilogue_fwd_x_pool(int dtype, const void* raw, const float* mean, const float* rstd, const void* x_in,
+                                   const float* w2, int in_channel, const float* mean2, const float* rstd2, int c, float slope,
+                                   void* out, void* pooled, unsigned int* argmax, seunet_dims dims, seunet_stream_t s) {
+  SEUNET_CHECK(raw && mean && rstd && x_in && w2 && mean2 && rstd2 && out && pooled, "cat_epilogue_fwd_x_pool: null argument");
+  return launch_cat_fwd_x_pool(dtype, raw, mean, rstd, x_in, w2, in_channel, mean2, rstd2, c, slope, out, pooled, D(dims), S(s),
+                               argmax);
+}
+int seunet_cat_epilogue_bwd_x_pool(int dtype, const void* g_out, const void* raw, const float* mean, const float* rstd,
+                                   const void* x_in, const float* w2, int in_channel, const float* mean2, const float* rstd2,
+                                   int c, float slope, const float* m1, const float* m2, const float* m1b, const float* m2b,
+                                   void* dx, double* stat_partial, double* stat_partial2, double* xw_partial,
+                                   const unsigned int* pool_argmax, const void* pool_g, seunet_dims dims, seunet_stream_t s) {
+  SEUNET_CHECK(g_out && raw && mean && rstd && x_in && w2 && mean2 && rstd2, "cat_epilogue_bwd_x_pool: null argument");
+  SEUNET_CHECK((pool_argmax == nullptr) == (pool_g == nullptr), "cat_epilogue_bwd_x_pool: pool_argmax and pool_g go together");
+  return launch_cat_bwd_x(dtype, g_out, raw, mean, rstd, x_in, w2, in_channel, mean2, rstd2, c, slope, m1, m2, m1b, m2b, dx,
+                          stat_partial, stat_partial2, xw_partial, D(dims), S(s), pool_argmax, pool_g);
 }
 int seunet_cat_xgrad_finalize(const double* xw_partial, const double* stat_partial2, int slots, const double* moments, const float* w2,
                               int c, int in_channel, int n, float eps, float* dw, seunet_stream_t s) {

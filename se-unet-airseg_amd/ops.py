@@ -240,8 +240,10 @@ def gate_epilogue_fwd(raw, mean, rstd, w_se, w_se2, w_side, b_side, slope=0.01, 
 
 
 def gate_epilogue_bwd(raw, mean, rstd, w_se, w_se2, w_side, b_side, slope=0.01, g_e=None, g_side=None, g_level=None,
-                      head_w=None, drop=None, drop_stride=0):
-    """Both backward passes.  Returns dict with draw (gradient w.r.t. the raw conv output) and the parameter gradients."""
+                      head_w=None, drop=None, drop_stride=0, fused_finalize=False):
+    """Both backward passes.  Returns dict with draw (gradient w.r.t. the raw conv output), the parameter gradients and the two
+    InstanceNorm-backward means m1, m2.  fused_finalize: what follows pass A is the one launch the network uses
+    (``seunet_gate_bwd_finalize``) instead of ``seunet_stats_finalize`` + ``seunet_pgrad_reduce``."""
     lib = _lib.load()
     n, d, h, w, c = raw.shape
     dims = _dims_cl(raw)
@@ -259,15 +261,25 @@ def gate_epilogue_bwd(raw, mean, rstd, w_se, w_se2, w_side, b_side, slope=0.01, 
                                                 _lib.ptr(m1), _lib.ptr(m2), _lib.ptr(out), _lib.ptr(st), _lib.ptr(pgp), dims, _s()),
                    "gate_epilogue_bwd")
     call(None, None, None, stat, pg)
-    m1, m2 = stats_finalize(stat, slots, d * h * w, 0.0, 1)
     dev = raw.device
     out = {"dw_se": torch.empty(c, device=dev), "dw_se2": torch.empty(c, device=dev), "dw_side": torch.empty(2 * c, device=dev),
            "db_side": torch.empty(2, device=dev), "dhead_w": torch.empty(2, device=dev)}
-    _lib.check(lib.seunet_pgrad_reduce(pg.data_ptr(), n * slots, c, out["dw_se"].data_ptr(), out["dw_se2"].data_ptr(),
-                                       out["dw_side"].data_ptr(), out["db_side"].data_ptr(), out["dhead_w"].data_ptr(), _s()),
-               "pgrad_reduce")
+    if fused_finalize:
+        m1 = torch.empty((n, c), dtype=torch.float32, device=dev)
+        m2 = torch.empty_like(m1)
+        _lib.check(lib.seunet_gate_bwd_finalize(stat.data_ptr(), slots, c, n, d * h * w, m1.data_ptr(), m2.data_ptr(), pg.data_ptr(),
+                                                n * slots, out["dw_se"].data_ptr(), _lib.ptr(None if ws2 is None else out["dw_se2"]),
+                                                out["dw_side"].data_ptr(), out["db_side"].data_ptr(), out["dhead_w"].data_ptr(), _s()),
+                   "gate_bwd_finalize")
+        if ws2 is None:      # (the network has no conv_se2 gradient to write for a one-gate block)
+            out["dw_se2"].zero_()
+    else:
+        m1, m2 = stats_finalize(stat, slots, d * h * w, 0.0, 1)
+        _lib.check(lib.seunet_pgrad_reduce(pg.data_ptr(), n * slots, c, out["dw_se"].data_ptr(), out["dw_se2"].data_ptr(),
+                                           out["dw_side"].data_ptr(), out["db_side"].data_ptr(), out["dhead_w"].data_ptr(), _s()),
+                   "pgrad_reduce")
     call(m1, m2, dx, None, None)
-    out["draw"] = dx
+    out["draw"], out["m1"], out["m2"] = dx, m1, m2
     return out
 
 
@@ -301,28 +313,60 @@ def cat_epilogue_bwd(g_out, raw, mean, rstd, raw2=None, mean2=None, rstd2=None, 
     return dx, dx2
 
 
-def cat_epilogue_x(g_out, raw, mean, rstd, x_in, w2, in_channel, slope=0.01, eps=1e-5):
-    """Two-branch aggregation block whose second branch (the 1x1x1 conv ``w2`` of the <= 2-channel network input) is
-    recomputed instead of stored (``seunet_xbranch_*``, ``seunet_cat_epilogue_fwd_x / bwd_x``).
-    x_in: packed 8-channel input [N, D, H, W, 8]; w2: (C, in_channel, 1, 1, 1) f32.
-    Returns (out, dx, dW2): forward output, gradient w.r.t. ``raw`` for the upstream ``g_out``, gradient of ``w2``."""
+def xbranch_stats(x_in, w2, in_channel, eps=1e-5):
+    """(mean2, rstd2, moments) of the recomputed x-branch ``w2 . x``: ``seunet_xbranch_moments`` -> ``seunet_xbranch_stats``.
+    x_in: packed 8-channel input [N, D, H, W, 8]; moments: f64 [N, 5] per-voxel means of x0, x1, x0^2, x0 x1, x1^2."""
+    lib = _lib.load()
+    n, d, h, w, _ = x_in.shape
+    dims = _dims_cl(x_in)
+    c = w2.shape[0]
+    w2f = w2.contiguous().float().reshape(c, in_channel)
+    mslots = lib.seunet_xbranch_moment_slots(dims)
+    mom = torch.zeros((n, mslots, 5), dtype=torch.float64, device=x_in.device)
+    _lib.check(lib.seunet_xbranch_moments(_code(x_in), x_in.data_ptr(), mom.data_ptr(), dims, _s()), "xbranch_moments")
+    mean2 = torch.empty((n, c), dtype=torch.float32, device=x_in.device)
+    rstd2 = torch.empty_like(mean2)
+    tot = torch.empty((n, 5), dtype=torch.float64, device=x_in.device)
+    _lib.check(lib.seunet_xbranch_stats(mom.data_ptr(), mslots, w2f.data_ptr(), c, in_channel, n, d * h * w, eps, mean2.data_ptr(),
+                                        rstd2.data_ptr(), tot.data_ptr(), _s()), "xbranch_stats")
+    return mean2, rstd2, tot
+
+
+def cat_epilogue_fwd_x(raw, mean, rstd, x_in, w2, in_channel, mean2, rstd2, slope=0.01):
+    """Forward of the two-branch block with the recomputed x-branch (``seunet_cat_epilogue_fwd_x``): out."""
+    c = raw.shape[4]
+    w2f = w2.contiguous().float().reshape(c, in_channel)
+    out = torch.empty_like(raw)
+    _lib.check(_lib.load().seunet_cat_epilogue_fwd_x(_code(raw), raw.data_ptr(), mean.data_ptr(), rstd.data_ptr(), x_in.data_ptr(),
+                                                     w2f.data_ptr(), in_channel, mean2.data_ptr(), rstd2.data_ptr(), c, slope,
+                                                     out.data_ptr(), _dims_cl(raw), _s()), "cat_epilogue_fwd_x")
+    return out
+
+
+def cat_epilogue_fwd_x_pool(raw, mean, rstd, x_in, w2, in_channel, mean2, rstd2, slope=0.01):
+    """The same forward in the form the network runs when a 2x2x2 max-pool consumes the block
+    (``seunet_cat_epilogue_fwd_x_pool``): (out, pooled, arg-max words [N, Vo, C/8] int32)."""
+    n, d, h, w, c = raw.shape
+    w2f = w2.contiguous().float().reshape(c, in_channel)
+    out = torch.empty_like(raw)
+    pooled = torch.empty((n, d // 2, h // 2, w // 2, c), dtype=raw.dtype, device=raw.device)
+    words = torch.empty((n, (d // 2) * (h // 2) * (w // 2), c // 8), dtype=torch.int32, device=raw.device)
+    _lib.check(_lib.load().seunet_cat_epilogue_fwd_x_pool(_code(raw), raw.data_ptr(), mean.data_ptr(), rstd.data_ptr(), x_in.data_ptr(),
+                                                          w2f.data_ptr(), in_channel, mean2.data_ptr(), rstd2.data_ptr(), c, slope,
+                                                          out.data_ptr(), pooled.data_ptr(), words.data_ptr(), _dims_cl(raw), _s()),
+               "cat_epilogue_fwd_x_pool")
+    return out, pooled, words
+
+
+def cat_epilogue_bwd_x(g_out, raw, mean, rstd, x_in, w2, in_channel, mean2, rstd2, moments, slope=0.01, eps=1e-5,
+                       pool_argmax=None, pool_g=None):
+    """Both backward passes of that block as the network runs them (``seunet_cat_epilogue_bwd_x``); with pool_argmax / pool_g
+    the gradient of the consuming max-pool is added on the fly (``seunet_cat_epilogue_bwd_x_pool``).
+    Returns dict: dx, dw2 and the four means of the InstanceNorm backward."""
     lib = _lib.load()
     n, d, h, w, c = raw.shape
     dims = _dims_cl(raw)
-    code = _code(raw)
     w2f = w2.contiguous().float().reshape(c, in_channel)
-    mslots = lib.seunet_xbranch_moment_slots(dims)
-    mom = torch.zeros((n, mslots, 5), dtype=torch.float64, device=raw.device)
-    _lib.check(lib.seunet_xbranch_moments(code, x_in.data_ptr(), mom.data_ptr(), dims, _s()), "xbranch_moments")
-    mean2 = torch.empty((n, c), dtype=torch.float32, device=raw.device)
-    rstd2 = torch.empty_like(mean2)
-    tot = torch.empty((n, 5), dtype=torch.float64, device=raw.device)
-    _lib.check(lib.seunet_xbranch_stats(mom.data_ptr(), mslots, w2f.data_ptr(), c, in_channel, n, d * h * w, eps, mean2.data_ptr(),
-                                        rstd2.data_ptr(), tot.data_ptr(), _s()), "xbranch_stats")
-    out = torch.empty_like(raw)
-    _lib.check(lib.seunet_cat_epilogue_fwd_x(code, raw.data_ptr(), mean.data_ptr(), rstd.data_ptr(), x_in.data_ptr(), w2f.data_ptr(),
-                                             in_channel, mean2.data_ptr(), rstd2.data_ptr(), c, slope, out.data_ptr(), dims, _s()),
-               "cat_epilogue_fwd_x")
     slots = lib.seunet_epilogue_slots(dims)
     st = torch.zeros((n, slots, c, 2), dtype=torch.float64, device=raw.device)
     st2 = torch.zeros_like(st)
@@ -330,18 +374,33 @@ def cat_epilogue_x(g_out, raw, mean, rstd, x_in, w2, in_channel, slope=0.01, eps
     dx = torch.empty_like(raw)
 
     def bwd(m1, m2, m1b, m2b, o, s1, s2, xp):
-        _lib.check(lib.seunet_cat_epilogue_bwd_x(code, g_out.data_ptr(), raw.data_ptr(), mean.data_ptr(), rstd.data_ptr(), x_in.data_ptr(),
-                                                 w2f.data_ptr(), in_channel, mean2.data_ptr(), rstd2.data_ptr(), c, slope, _lib.ptr(m1),
-                                                 _lib.ptr(m2), _lib.ptr(m1b), _lib.ptr(m2b), _lib.ptr(o), _lib.ptr(s1), _lib.ptr(s2),
-                                                 _lib.ptr(xp), dims, _s()), "cat_epilogue_bwd_x")
+        head = (_code(raw), g_out.data_ptr(), raw.data_ptr(), mean.data_ptr(), rstd.data_ptr(), x_in.data_ptr(), w2f.data_ptr(),
+                in_channel, mean2.data_ptr(), rstd2.data_ptr(), c, slope, _lib.ptr(m1), _lib.ptr(m2), _lib.ptr(m1b), _lib.ptr(m2b),
+                _lib.ptr(o), _lib.ptr(s1), _lib.ptr(s2), _lib.ptr(xp))
+        if pool_argmax is None:
+            _lib.check(lib.seunet_cat_epilogue_bwd_x(*head, dims, _s()), "cat_epilogue_bwd_x")
+        else:
+            _lib.check(lib.seunet_cat_epilogue_bwd_x_pool(*head, pool_argmax.data_ptr(), _lib.ptr(pool_g), dims, _s()),
+                       "cat_epilogue_bwd_x_pool")
     bwd(None, None, None, None, None, st, st2, part)
     m1, m2 = stats_finalize(st, slots, d * h * w, 0.0, 1)
     m1b, m2b = stats_finalize(st2, slots, d * h * w, 0.0, 1)
     bwd(m1, m2, m1b, m2b, dx, None, None, None)
     dw = torch.zeros((c, in_channel, 1, 1, 1), dtype=torch.float32, device=raw.device)
-    _lib.check(lib.seunet_cat_xgrad_finalize(part.data_ptr(), st2.data_ptr(), slots, tot.data_ptr(), w2f.data_ptr(), c, in_channel, n,
-                                             eps, dw.data_ptr(), _s()), "cat_xgrad_finalize")
-    return out, dx, dw
+    _lib.check(lib.seunet_cat_xgrad_finalize(part.data_ptr(), st2.data_ptr(), slots, moments.data_ptr(), w2f.data_ptr(), c,
+                                             in_channel, n, eps, dw.data_ptr(), _s()), "cat_xgrad_finalize")
+    return {"dx": dx, "dw2": dw, "m1": m1, "m2": m2, "m1b": m1b, "m2b": m2b}
+
+
+def cat_epilogue_x(g_out, raw, mean, rstd, x_in, w2, in_channel, slope=0.01, eps=1e-5):
+    """Two-branch aggregation block whose second branch (the 1x1x1 conv ``w2`` of the <= 2-channel network input) is
+    recomputed instead of stored (``seunet_xbranch_*``, ``seunet_cat_epilogue_fwd_x / bwd_x``).
+    x_in: packed 8-channel input [N, D, H, W, 8]; w2: (C, in_channel, 1, 1, 1) f32.
+    Returns (out, dx, dW2): forward output, gradient w.r.t. ``raw`` for the upstream ``g_out``, gradient of ``w2``."""
+    mean2, rstd2, moments = xbranch_stats(x_in, w2, in_channel, eps)
+    out = cat_epilogue_fwd_x(raw, mean, rstd, x_in, w2, in_channel, mean2, rstd2, slope)
+    res = cat_epilogue_bwd_x(g_out, raw, mean, rstd, x_in, w2, in_channel, mean2, rstd2, moments, slope, eps)
+    return out, res["dx"], res["dw2"]
 
 
 # ---- pooling / interpolation / heads ---------------------------------------------------------------------
