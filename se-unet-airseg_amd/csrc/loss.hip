@@ -20,19 +20,22 @@ int loss_partials() { return LOSS_BLOCKS; }
 template <int TERMS>
 __device__ __forceinline__ void loss_terms(float p, int apply_sigmoid, float t, float w, float sk, float (&s)[SEUNET_LOSS_NSUMS]) {
   if (apply_sigmoid) p = 1.f / (1.f + expf(-p));
+  // Every multiply-add is an explicit fmaf.  Left to the compiler the contraction differed between the instantiations (<2>
+  // formed 0.2 p + 0.8 t from a packed multiply and an addition, <6> and <7> from a multiply and an fma), and a sum depended in
+  // its last bits on which OTHER sums were asked for.
   if (TERMS & 1) {
-    s[0] += p * t;
+    s[0] = fmaf(p, t, s[0]);
     s[1] += p;
     s[2] += t;
   }
   if (TERMS & 2) {
-    if (t != 0.f) s[3] += w * powf(p + 1e-4f, 0.7f) * t;   // (the label is sparse: the pow is skipped where it is multiplied by 0)
-    s[4] += w * (0.2f * p + 0.8f * t);
+    if (t != 0.f) s[3] = fmaf(w * powf(p + 1e-4f, 0.7f), t, s[3]);   // (the label is sparse: the pow is skipped where it is multiplied by 0)
+    s[4] = fmaf(w, fmaf(0.2f, p, 0.8f * t), s[4]);
   }
   if (TERMS & 4) {
     const float ps = p * sk;
-    s[5] += w * ps * sk;
-    s[6] += w * (ps + sk);
+    s[5] = fmaf(w * ps, sk, s[5]);
+    s[6] = fmaf(w, ps + sk, s[6]);
   }
 }
 

@@ -3,6 +3,9 @@
 f32 kernels must agree to ~1e-5 relative; bf16 kernels are compared against the fp32 op applied to
 bf16-rounded inputs (so what is measured is the kernel, not input quantisation) with a tolerance of a few
 bf16 ulps of the output range.  Shapes are deliberately not multiples of the tile sizes (masking)."""
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
@@ -464,14 +467,28 @@ def test_side_upsample(S):
 
 
 def test_losses_match_oracle(S):
+    """The fp32 oracle under the fixed tolerances this test has always had, and float64 autograd of the oracle under the derived
+    bounds of tests/loss_ref.py (value: the sum bound carried through the ratio; gradient: the element bound plus what the sum
+    bound propagates).  The benchmark shapes and the edge inputs are in tests/test_loss_layers_gpu.py."""
     import seunet_oracle as orc
     import seunet_amd as A
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import loss_ref as R
     g = torch.Generator().manual_seed(5)
     logit = torch.randn(2, 1, 12, 12, 12, generator=g)
     t = (torch.rand(2, 1, 12, 12, 12, generator=g) > 0.9).float()
     wt = 1 + torch.rand(2, 1, 12, 12, 12, generator=g)
     sk = t * (torch.rand(2, 1, 12, 12, 12, generator=g) > 0.5).float()
-    for name, args in (("dice_loss", (t,)), ("general_union_loss_lib", (t, wt)), ("atr_loss", (t, sk, wt))):
+    n = logit.numel()
+    assert n % 4 == 0                                   # the 16-byte path (torch's allocations are aligned)
+
+    def within(got, ref, lim, what):
+        err = (got.double() - ref).abs()
+        assert bool((err <= lim).all()), f"{what}: worst {float((err / lim).max()):.2f} x bound"
+
+    for name, args, coef, (w_, s_) in (("dice_loss", (t,), (1.0, 0.0, 0.0), (None, None)),
+                                       ("general_union_loss_lib", (t, wt), (0.0, 1.0, 0.0), (wt, None)),
+                                       ("atr_loss", (t, sk, wt), (0.0, 0.0, 1.0), (wt, sk))):
         p = torch.sigmoid(logit).requires_grad_(True)
         l_ref = getattr(orc, name)(p, *args)
         l_ref.backward()
@@ -480,12 +497,23 @@ def test_losses_match_oracle(S):
         (3.0 * l).backward()
         assert abs(float(l) - float(l_ref)) < 2e-6, name
         np.testing.assert_allclose(pg.grad.cpu().numpy() / 3.0, p.grad.numpy(), rtol=2e-4, atol=1e-9, err_msg=name)
+        # float64 autograd of the oracle on the same f32 probabilities, derived bounds
+        p64 = torch.sigmoid(logit).double().requires_grad_(True)
+        l64 = getattr(orc, name)(p64, *[a.double() for a in args])
+        (3.0 * l64).backward()
+        w64, s64 = (None if w_ is None else w_.double()), (None if s_ is None else s_.double())
+        S64 = R.sums(p64.detach(), t.double(), w64, s64)
+        eS = R.sum_bound(S64, n, True, False)
+        assert abs(float(l) - float(l64)) <= R.value_bound(S64, eS, coef), name
+        _, mag, prop = R.grad_pred(p64.detach(), t.double(), w64, s64, S64, coef, 3.0, eS)
+        within(pg.grad.cpu(), p64.grad, R.grad_bound_pred(mag, coef) + prop, name)
     # the one-launch value kernel == the scalar arithmetic it replaces, to the bit
     from seunet_amd.losses import _value, _value_dev
     sums = (torch.rand(2, 7, dtype=torch.float64, generator=g) * 1000).cuda()
     for c0, c1 in (((1.0, 0.0, 0.0), (1.0, 0.0, 0.0)), ((0.0, 1.0, 0.5), (0.0, 0.5, 0.5)), ((0.3, 0.0, 2.0), (0.0, 0.0, 0.0))):
         assert torch.equal(_value_dev(sums[0], c0), _value(sums[0], *c0))
         assert torch.equal(_value_dev(sums[0], c0, sums[1], c1), _value(sums[0], *c0) + _value(sums[1], *c1))
+    stage_coef = {1: ((1.0, 0.0, 0.0), (1.0, 0.0, 0.0)), 2: ((0.0, 1.0, 0.0), (0.0, 0.5, 0.0)), 3: ((0.0, 1.0, 0.5), (0.0, 0.5, 0.5))}
     for stage in (1, 2, 3):
         a = logit.clone().requires_grad_(True)
         b = (logit * 0.5 + 0.1).clone().requires_grad_(True)
@@ -497,6 +525,19 @@ def test_losses_match_oracle(S):
         assert abs(float(l) - float(l_ref)) < 5e-6, stage
         np.testing.assert_allclose(ag.grad.cpu().numpy(), a.grad.numpy(), rtol=3e-4, atol=1e-9)
         np.testing.assert_allclose(bg.grad.cpu().numpy(), b.grad.numpy(), rtol=3e-4, atol=1e-9)
+        # float64 autograd of the oracle, derived bounds; a is the encoder head, b the decoder head (head 0 of the kernels)
+        a64, b64 = a.detach().double().requires_grad_(True), b.detach().double().requires_grad_(True)
+        l64 = orc.stage_loss(stage, a64, b64, t.double(), wt.double(), sk.double())
+        l64.backward()
+        s64 = None if stage == 2 else sk.double()
+        lim = 0.0
+        for x64, got, coef in ((b64, bg.grad, stage_coef[stage][0]), (a64, ag.grad, stage_coef[stage][1])):
+            S64 = R.sums(R.sigmoid(x64.detach()), t.double(), wt.double(), s64)
+            eS = R.sum_bound(S64, n, True, True)
+            lim += R.value_bound(S64, eS, coef)
+            _, mag, prop, pp, ds = R.grad_logit(x64.detach(), t.double(), wt.double(), s64, S64, coef, 1.0, eS)
+            within(got.cpu(), x64.grad, R.grad_bound_logit(mag, pp, ds, coef) + prop, f"stage {stage}")
+        assert abs(float(l) - float(l64)) <= lim + R.U * (abs(float(l64)) + lim), stage
 
 
 # ---- streaming small-channel convolution (csrc/conv_stream.hip): the full-resolution layers ec1 / ec2 / ec3 / dc6 ----
