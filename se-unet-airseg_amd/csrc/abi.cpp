@@ -156,9 +156,9 @@ int seunet_gate_epilogue_fwd(int dtype, const void* raw, const float* mean, cons
                              int drop_stride, seunet_dims dims, seunet_stream_t s) {
   SEUNET_CHECK(raw && mean && rstd && w_se && w_side && b_side && e_out, "gate_epilogue_fwd: null tensor");
   SEUNET_CHECK(!level_map || head_w, "gate_epilogue_fwd: level_map needs head_w");
-  SseParams p{w_se, w_se2, w_side, b_side, slope};
+  const GateBlock b{{raw, mean, rstd}, c, {w_se, w_se2, w_side, b_side, slope}};
   SseHead h{side_out, level_map, level_accumulate, head_w, drop, drop_stride};
-  return launch_sse_fwd(dtype, raw, mean, rstd, c, p, e_out, h, D(dims), S(s));
+  return launch_sse_fwd(dtype, b, e_out, h, D(dims), S(s));
 }
 int seunet_gate_epilogue_bwd(int dtype, const void* raw, const float* mean, const float* rstd, int c, const float* w_se,
                              const float* w_se2, const float* w_side, const float* b_side, float slope, const void* g_e,
@@ -167,10 +167,11 @@ int seunet_gate_epilogue_bwd(int dtype, const void* raw, const float* mean, cons
                              seunet_dims dims, seunet_stream_t s) {
   SEUNET_CHECK(raw && mean && rstd && w_se && w_side && b_side, "gate_epilogue_bwd: null tensor");
   SEUNET_CHECK(!g_level || head_w, "gate_epilogue_bwd: g_level needs head_w");
-  SseParams p{w_se, w_se2, w_side, b_side, slope};
+  const GateBlock b{{raw, mean, rstd}, c, {w_se, w_se2, w_side, b_side, slope}};
   SseBwdIn g{g_e, g_side, g_level};
   SseHead h{nullptr, nullptr, 0, head_w, drop, drop_stride};
-  return launch_sse_bwd(dtype, raw, mean, rstd, c, p, g, h, m1, m2, draw_out, stat_partial, pgrad_partial, D(dims), S(s));
+  if (m1 == nullptr) return launch_sse_bwd_sums(dtype, b, g, h, {stat_partial, pgrad_partial}, D(dims), S(s));   // pass A
+  return launch_sse_bwd_apply(dtype, b, g, h, {m1, m2, draw_out}, D(dims), S(s));
 }
 int seunet_pgrad_reduce(const float* pgrad_partial, int records, int c, float* dw_se, float* dw_se2, float* dw_side,
                         float* db_side, float* dhead_w, seunet_stream_t s) {
@@ -186,11 +187,19 @@ int seunet_gate_bwd_finalize(const double* stat_partial, int slots, int c, int n
   return launch_gate_bwd_finalize(stat_partial, slots, c, n, count, m1, m2, pgrad_partial, records, dw_se, dw_se2, dw_side,
                                   db_side, dhead_w, S(s));
 }
+// the C ABI of the aggregation block's backward: m1 == nullptr asks for pass A (the sums), anything else for pass B
+static int cat_epilogue_bwd(int dtype, const CatBlock& b, const void* g_out, const PoolGrad& pool, const float* m1, const float* m2,
+                            const float* m1b, const float* m2b, void* dx, void* dx2, double* stat_partial, double* stat_partial2,
+                            double* xw_partial, seunet_dims dims, seunet_stream_t s) {
+  if (m1 == nullptr) return launch_cat_bwd_sums(dtype, b, g_out, pool, {stat_partial, stat_partial2, xw_partial}, D(dims), S(s));
+  return launch_cat_bwd_apply(dtype, b, g_out, pool, {m1, m2, m1b, m2b, dx, dx2, nullptr, 0}, D(dims), S(s));
+}
 int seunet_cat_epilogue_fwd(int dtype, const void* raw, const float* mean, const float* rstd, const void* raw2,
                             const float* mean2, const float* rstd2, int c, float slope, void* out, seunet_dims dims,
                             seunet_stream_t s) {
   SEUNET_CHECK(raw && mean && rstd && out && (!raw2 || (mean2 && rstd2)), "cat_epilogue_fwd: null tensor");
-  return launch_cat_fwd(dtype, raw, mean, rstd, raw2, mean2, rstd2, c, slope, out, D(dims), S(s));
+  const CatBlock b{{raw, mean, rstd}, {raw2 ? Branch2::Stored : Branch2::None, raw2, mean2, rstd2, nullptr, 0}, c, slope};
+  return launch_cat_fwd(dtype, b, out, PoolOut{}, D(dims), S(s));
 }
 int seunet_cat_epilogue_bwd(int dtype, const void* g_out, const void* raw, const float* mean, const float* rstd,
                             const void* raw2, const float* mean2, const float* rstd2, int c, float slope, const float* m1,
@@ -198,8 +207,8 @@ int seunet_cat_epilogue_bwd(int dtype, const void* g_out, const void* raw, const
                             double* stat_partial2, seunet_dims dims, seunet_stream_t s) {
   SEUNET_CHECK(g_out && raw && mean && rstd, "cat_epilogue_bwd: null tensor");
   SEUNET_CHECK(!raw2 || (mean2 && rstd2), "cat_epilogue_bwd: second branch incomplete");
-  return launch_cat_bwd(dtype, g_out, raw, mean, rstd, raw2, mean2, rstd2, c, slope, m1, m2, m1b, m2b, dx, dx2, stat_partial,
-                        stat_partial2, D(dims), S(s));
+  const CatBlock b{{raw, mean, rstd}, {raw2 ? Branch2::Stored : Branch2::None, raw2, mean2, rstd2, nullptr, 0}, c, slope};
+  return cat_epilogue_bwd(dtype, b, g_out, PoolGrad{}, m1, m2, m1b, m2b, dx, dx2, stat_partial, stat_partial2, nullptr, dims, s);
 }
 
 int seunet_maxpool_fwd(int dtype, const void* in, int c, void* out, seunet_dims d, seunet_stream_t s) {
@@ -269,7 +278,8 @@ int seunet_cat_epilogue_fwd_x(int dtype, const void* raw, const float* mean, con
                               const float* w2, int in_channel, const float* mean2, const float* rstd2, int c, float slope,
                               void* out, seunet_dims dims, seunet_stream_t s) {
   SEUNET_CHECK(raw && mean && rstd && x_in && w2 && mean2 && rstd2 && out, "cat_epilogue_fwd_x: null argument");
-  return launch_cat_fwd_x(dtype, raw, mean, rstd, x_in, w2, in_channel, mean2, rstd2, c, slope, out, D(dims), S(s));
+  const CatBlock b{{raw, mean, rstd}, {Branch2::Recomputed, x_in, mean2, rstd2, w2, in_channel}, c, slope};
+  return launch_cat_fwd(dtype, b, out, PoolOut{}, D(dims), S(s));
 }
 int seunet_cat_epilogue_bwd_x(int dtype, const void* g_out, const void* raw, const float* mean, const float* rstd,
                               const void* x_in, const float* w2, int in_channel, const float* mean2, const float* rstd2,
@@ -277,15 +287,15 @@ int seunet_cat_epilogue_bwd_x(int dtype, const void* g_out, const void* raw, con
                               void* dx, double* stat_partial, double* stat_partial2, double* xw_partial, seunet_dims dims,
                               seunet_stream_t s) {
   SEUNET_CHECK(g_out && raw && mean && rstd && x_in && w2 && mean2 && rstd2, "cat_epilogue_bwd_x: null argument");
-  return launch_cat_bwd_x(dtype, g_out, raw, mean, rstd, x_in, w2, in_channel, mean2, rstd2, c, slope, m1, m2, m1b, m2b, dx,
-                          stat_partial, stat_partial2, xw_partial, D(dims), S(s));
+  const CatBlock b{{raw, mean, rstd}, {Branch2::Recomputed, x_in, mean2, rstd2, w2, in_channel}, c, slope};
+  return cat_epilogue_bwd(dtype, b, g_out, PoolGrad{}, m1, m2, m1b, m2b, dx, nullptr, stat_partial, stat_partial2, xw_partial, dims, s);
 }
 int seunet_cat_epilogue_fwd_x_pool(int dtype, const void* raw, const float* mean, const float* rstd, const void* x_in,
                                    const float* w2, int in_channel, const float* mean2, const float* rstd2, int c, float slope,
                                    void* out, void* pooled, unsigned int* argmax, seunet_dims dims, seunet_stream_t s) {
   SEUNET_CHECK(raw && mean && rstd && x_in && w2 && mean2 && rstd2 && out && pooled, "cat_epilogue_fwd_x_pool: null argument");
-  return launch_cat_fwd_x_pool(dtype, raw, mean, rstd, x_in, w2, in_channel, mean2, rstd2, c, slope, out, pooled, D(dims), S(s),
-                               argmax);
+  const CatBlock b{{raw, mean, rstd}, {Branch2::Recomputed, x_in, mean2, rstd2, w2, in_channel}, c, slope};
+  return launch_cat_fwd(dtype, b, out, PoolOut{pooled, argmax}, D(dims), S(s));
 }
 int seunet_cat_epilogue_bwd_x_pool(int dtype, const void* g_out, const void* raw, const float* mean, const float* rstd,
                                    const void* x_in, const float* w2, int in_channel, const float* mean2, const float* rstd2,
@@ -294,8 +304,9 @@ int seunet_cat_epilogue_bwd_x_pool(int dtype, const void* g_out, const void* raw
                                    const unsigned int* pool_argmax, const void* pool_g, seunet_dims dims, seunet_stream_t s) {
   SEUNET_CHECK(g_out && raw && mean && rstd && x_in && w2 && mean2 && rstd2, "cat_epilogue_bwd_x_pool: null argument");
   SEUNET_CHECK((pool_argmax == nullptr) == (pool_g == nullptr), "cat_epilogue_bwd_x_pool: pool_argmax and pool_g go together");
-  return launch_cat_bwd_x(dtype, g_out, raw, mean, rstd, x_in, w2, in_channel, mean2, rstd2, c, slope, m1, m2, m1b, m2b, dx,
-                          stat_partial, stat_partial2, xw_partial, D(dims), S(s), pool_argmax, pool_g);
+  const CatBlock b{{raw, mean, rstd}, {Branch2::Recomputed, x_in, mean2, rstd2, w2, in_channel}, c, slope};
+  return cat_epilogue_bwd(dtype, b, g_out, PoolGrad{pool_argmax, pool_g}, m1, m2, m1b, m2b, dx, nullptr, stat_partial, stat_partial2,
+                          xw_partial, dims, s);
 }
 int seunet_cat_xgrad_finalize(const double* xw_partial, const double* stat_partial2, int slots, const double* moments, const float* w2,
                               int c, int in_channel, int n, float eps, float* dw, seunet_stream_t s) {

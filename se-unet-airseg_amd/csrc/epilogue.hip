@@ -665,6 +665,7 @@ cat_bwd_kernel(const T* g_out, const T* __restrict__ raw,
                const float* __restrict__ w2x = nullptr, int xic = 0, PoolRef pool = PoolRef{},
                float* __restrict__ gx_out = nullptr, int gx_acc = 0) {
   static_assert(!XG || (APPLY && XR), "XG: pass B of an XR block only");
+  static_assert(!XW || XR, "XW: the weight-gradient sums are formed from the recomputed branch's own input voxel");
   const int n = blockIdx.y, P = gridDim.x;
   const int cg = threadIdx.x % LPV, vb = threadIdx.x / LPV;
   constexpr int VPB = EPI_THREADS / LPV;
@@ -848,15 +849,14 @@ int launch_stats_finalize(const double* partial, int slots, int C, int N, long l
   return 0;
 }
 
-int launch_sse_fwd(int dtype, const void* raw, const float* mean, const float* rstd, int C,
-                   const SseParams& p, void* e_out, const SseHead& head, Dims d, hipStream_t s) {
-  if (int e = check_c(C)) return e;
+int launch_sse_fwd(int dtype, const GateBlock& b, void* e_out, const SseHead& head, Dims d, hipStream_t s) {
+  if (int e = check_c(b.C)) return e;
   dim3 grid(epi_partials(d) * 4, d.N);   // nothing is reduced here: enough blocks for full occupancy
-  const bool g2 = p.w_se2 != nullptr;
-  SEUNET_LPV_SWITCH(C / 8, {
+  const bool g2 = b.p.w_se2 != nullptr;
+  SEUNET_LPV_SWITCH(b.C / 8, {
     SEUNET_DTYPE_SWITCH(dtype, {
-      if (g2) sse_fwd_kernel<T, LPV, true><<<grid, EPI_THREADS, 0, s>>>((const T*)raw, mean, rstd, C, p, (T*)e_out, head, d.vox());
-      else sse_fwd_kernel<T, LPV, false><<<grid, EPI_THREADS, 0, s>>>((const T*)raw, mean, rstd, C, p, (T*)e_out, head, d.vox());
+      if (g2) sse_fwd_kernel<T, LPV, true><<<grid, EPI_THREADS, 0, s>>>((const T*)b.a.raw, b.a.mean, b.a.rstd, b.C, b.p, (T*)e_out, head, d.vox());
+      else sse_fwd_kernel<T, LPV, false><<<grid, EPI_THREADS, 0, s>>>((const T*)b.a.raw, b.a.mean, b.a.rstd, b.C, b.p, (T*)e_out, head, d.vox());
     });
   });
   SEUNET_LAUNCH_CHECK();
@@ -864,14 +864,13 @@ int launch_sse_fwd(int dtype, const void* raw, const float* mean, const float* r
 }
 
 template <typename T, bool APPLY>
-static int sse_bwd_t(const void* raw, const float* mean, const float* rstd, int C, const SseParams& p, const SseBwdIn& g,
-                     const SseHead& head, const float* m1, const float* m2, void* out, double* stat_partial,
-                     float* pgrad_partial, Dims d, hipStream_t s) {
+static int sse_bwd_t(const GateBlock& b, const SseBwdIn& g, const SseHead& head, const SseSums& o, const SseApply& a, Dims d,
+                     hipStream_t s) {
   dim3 grid(epi_partials(d) * (APPLY ? 4 : 1), d.N);
-  const bool g2 = p.w_se2 != nullptr;
+  const bool g2 = b.p.w_se2 != nullptr;
   const bool level = g.g_level != nullptr;
-#define SEUNET_SSE_BWD(G2V, LV) sse_bwd_kernel<T, LPV, G2V, APPLY, LV><<<grid, EPI_THREADS, 0, s>>>((const T*)raw, mean, rstd, C, p, g, head, m1, m2, (T*)out, stat_partial, pgrad_partial, d.vox())
-  SEUNET_LPV_SWITCH(C / 8, {
+#define SEUNET_SSE_BWD(G2V, LV) sse_bwd_kernel<T, LPV, G2V, APPLY, LV><<<grid, EPI_THREADS, 0, s>>>((const T*)b.a.raw, b.a.mean, b.a.rstd, b.C, b.p, g, head, a.m1, a.m2, (T*)a.draw_out, o.stat_partial, o.pgrad_partial, d.vox())
+  SEUNET_LPV_SWITCH(b.C / 8, {
     if (g2) { if (level) SEUNET_SSE_BWD(true, true); else SEUNET_SSE_BWD(true, false); }
     else { if (level) SEUNET_SSE_BWD(false, true); else SEUNET_SSE_BWD(false, false); }
   });
@@ -880,17 +879,19 @@ static int sse_bwd_t(const void* raw, const float* mean, const float* rstd, int 
   return 0;
 }
 
-// m1 == nullptr: pass A (sums + parameter-gradient records); otherwise pass B (writes draw_out)
-int launch_sse_bwd(int dtype, const void* raw, const float* mean, const float* rstd, int C,
-                   const SseParams& p, const SseBwdIn& g, const SseHead& head, const float* m1, const float* m2,
-                   void* draw_out, double* stat_partial, float* pgrad_partial, Dims d, hipStream_t s) {
-  if (int e = check_c(C)) return e;
-  if (m1 == nullptr) {
-    SEUNET_CHECK(stat_partial && pgrad_partial, "gate_epilogue_bwd pass A needs the partial buffers");
-    SEUNET_DTYPE_SWITCH(dtype, return (sse_bwd_t<T, false>(raw, mean, rstd, C, p, g, head, nullptr, nullptr, nullptr, stat_partial, pgrad_partial, d, s)));
-  }
-  SEUNET_CHECK(m2 && draw_out, "gate_epilogue_bwd pass B needs m2 and the output tensor");
-  SEUNET_DTYPE_SWITCH(dtype, return (sse_bwd_t<T, true>(raw, mean, rstd, C, p, g, head, m1, m2, draw_out, nullptr, nullptr, d, s)));
+int launch_sse_bwd_sums(int dtype, const GateBlock& b, const SseBwdIn& g, const SseHead& head, const SseSums& out, Dims d,
+                        hipStream_t s) {
+  if (int e = check_c(b.C)) return e;
+  SEUNET_CHECK(out.stat_partial && out.pgrad_partial, "gate_epilogue_bwd_sums needs the partial buffers");
+  SEUNET_DTYPE_SWITCH(dtype, return (sse_bwd_t<T, false>(b, g, head, out, SseApply{}, d, s)));
+  return 1;
+}
+
+int launch_sse_bwd_apply(int dtype, const GateBlock& b, const SseBwdIn& g, const SseHead& head, const SseApply& io, Dims d,
+                         hipStream_t s) {
+  if (int e = check_c(b.C)) return e;
+  SEUNET_CHECK(io.m1 && io.m2 && io.draw_out, "gate_epilogue_bwd_apply needs m1, m2 and the output tensor");
+  SEUNET_DTYPE_SWITCH(dtype, return (sse_bwd_t<T, true>(b, g, head, SseSums{}, io, d, s)));
   return 1;
 }
 
@@ -1024,19 +1025,6 @@ int launch_xbranch_stats(const double* partial, int slots, const float* w2, int 
   return 0;
 }
 
-int launch_cat_fwd_x(int dtype, const void* raw, const float* mean, const float* rstd, const void* x_in, const float* w2,
-                     int in_channel, const float* mean2, const float* rstd2, int C, float slope, void* out, Dims d,
-                     hipStream_t s) {
-  if (int e = check_c(C)) return e;
-  SEUNET_CHECK(in_channel >= 1 && in_channel <= 2, "cat_epilogue_fwd_x: in_channel %d (1 or 2)", in_channel);
-  dim3 grid(epi_partials(d) * 4, d.N);
-  SEUNET_LPV_SWITCH(C / 8, {
-    SEUNET_DTYPE_SWITCH(dtype, cat_fwd_kernel<T, LPV, true, true><<<grid, EPI_THREADS, 0, s>>>((const T*)raw, mean, rstd, (const T*)x_in, mean2, rstd2, C, slope, (T*)out, d.vox(), w2, in_channel));
-  });
-  SEUNET_LAUNCH_CHECK();
-  return 0;
-}
-
 // The aggregation block's forward with the 2x2x2 max-pool that follows it in the encoder (SE_UNet.py:188-189, 197-198,
 // 206-207: ec33 -> pool0, ec63 -> pool1, ec93 -> pool2) written by the same kernel: a thread owns one pooling window x 8
 // channels, computes the block output of its eight voxels (same arithmetic as cat_fwd_kernel<.., true, true>), stores them and
@@ -1110,98 +1098,99 @@ cat_fwd_pool_kernel(const T* __restrict__ raw, const float* __restrict__ mean, c
   }
 }
 
-int launch_cat_fwd_x_pool(int dtype, const void* raw, const float* mean, const float* rstd, const void* x_in, const float* w2,
-                          int in_channel, const float* mean2, const float* rstd2, int C, float slope, void* out, void* pooled,
-                          Dims d, hipStream_t s, unsigned* argmax) {
-  if (int e = check_c(C)) return e;
-  SEUNET_CHECK(in_channel >= 1 && in_channel <= 2, "cat_epilogue_fwd_x_pool: in_channel %d (1 or 2)", in_channel);
-  SEUNET_CHECK(d.D % 2 == 0 && d.H % 2 == 0 && d.W % 2 == 0, "cat_epilogue_fwd_x_pool: odd extent");
+int launch_cat_fwd(int dtype, const CatBlock& b, void* out, const PoolOut& pool, Dims d, hipStream_t s) {
+  if (int e = check_c(b.C)) return e;
+  const Branch2 x = b.b.kind == Branch2::None ? Branch2{} : b.b;
+  const bool xr = x.kind == Branch2::Recomputed;
+  SEUNET_CHECK(!xr || (x.in_channel >= 1 && x.in_channel <= 2), "cat_epilogue_fwd: in_channel %d (1 or 2)", x.in_channel);
+  SEUNET_CHECK(!pool.pooled || (xr && d.D % 2 == 0 && d.H % 2 == 0 && d.W % 2 == 0),
+               "cat_epilogue_fwd: the fused max-pool needs a recomputed second branch and even extents");
   dim3 grid(epi_partials(d) * 4, d.N);
-  SEUNET_LPV_SWITCH(C / 8, {
-    SEUNET_DTYPE_SWITCH(dtype, cat_fwd_pool_kernel<T, LPV><<<grid, EPI_THREADS, 0, s>>>((const T*)raw, mean, rstd, (const T*)x_in, mean2, rstd2, C, slope, (T*)out, (T*)pooled, d.D, d.H, d.W, w2, in_channel, argmax));
+#define SEUNET_CAT_FWD(...) <<<grid, EPI_THREADS, 0, s>>>((const T*)b.a.raw, b.a.mean, b.a.rstd, (const T*)x.src, x.mean2, x.rstd2, b.C, b.slope, (T*)out, __VA_ARGS__)
+  SEUNET_LPV_SWITCH(b.C / 8, {
+    SEUNET_DTYPE_SWITCH(dtype, {
+      if (pool.pooled) cat_fwd_pool_kernel<T, LPV> SEUNET_CAT_FWD((T*)pool.pooled, d.D, d.H, d.W, x.w2, x.in_channel, pool.argmax);
+      else if (xr) cat_fwd_kernel<T, LPV, true, true> SEUNET_CAT_FWD(d.vox(), x.w2, x.in_channel);
+      else if (x.kind == Branch2::Stored) cat_fwd_kernel<T, LPV, true> SEUNET_CAT_FWD(d.vox());
+      else cat_fwd_kernel<T, LPV, false> SEUNET_CAT_FWD(d.vox());
+    });
   });
+#undef SEUNET_CAT_FWD
   SEUNET_LAUNCH_CHECK();
   return 0;
 }
 
-// m1 == nullptr: pass A (f64 sums of both branches and, if xw_partial is given, one record of the x-branch weight-gradient sums per
-// block, see cat_bwd_kernel XW / XR); otherwise pass B: writes dx (may alias g_out)
-int launch_cat_bwd_x(int dtype, const void* g_out, const void* raw, const float* mean, const float* rstd, const void* x_in,
-                     const float* w2, int in_channel, const float* mean2, const float* rstd2, int C, float slope,
-                     const float* m1, const float* m2, const float* m1b, const float* m2b, void* dx, double* stat_partial,
-                     double* stat_partial2, double* xw_partial, Dims d, hipStream_t s, const unsigned* pool_argmax, const void* pool_g,
-                     float* gx_out, int gx_acc) {
-  if (int e = check_c(C)) return e;
-  SEUNET_CHECK(in_channel >= 1 && in_channel <= 2, "cat_epilogue_bwd_x: in_channel %d (1 or 2)", in_channel);
-  PoolRef pr{};
-  if (pool_argmax != nullptr) {
-    SEUNET_CHECK(pool_g != nullptr && d.D % 2 == 0 && d.H % 2 == 0 && d.W % 2 == 0 && d.vox() < (1ll << 31),
-                 "cat_epilogue_bwd_x: pooled gradient needs even extents below 2^31 voxels");
-    pr.argmax = pool_argmax; pr.g_pool = pool_g;
-    pr.W = (unsigned)d.W; pr.H = (unsigned)d.H; pr.Wo = (unsigned)d.W / 2; pr.Ho = (unsigned)d.H / 2;
-    pr.mW = (unsigned)((1ull << 32) / (unsigned)d.W); pr.mH = (unsigned)((1ull << 32) / (unsigned)d.H);
-    pr.Vo = d.vox() / 8;
-  }
-  const bool apply = m1 != nullptr;
-  if (!apply) SEUNET_CHECK(stat_partial && stat_partial2, "cat_epilogue_bwd_x pass A needs the partial buffers");
-  else SEUNET_CHECK(m2 && m1b && m2b && dx, "cat_epilogue_bwd_x pass B: missing argument");
-  SEUNET_CHECK(gx_out == nullptr || apply, "cat_epilogue_bwd_x: the input-gradient term is formed in pass B");
-  dim3 grid(epi_partials(d) * (apply ? 4 : 1), d.N);
-  SEUNET_LPV_SWITCH(C / 8, {
+// what both backward passes check, and the host side of PoolRef; `who` names the entry point
+static int cat_bwd_setup(const char* who, const CatBlock& b, const PoolGrad& pool, Dims d, PoolRef& pr) {
+  if (int e = check_c(b.C)) return e;
+  const bool xr = b.b.kind == Branch2::Recomputed;
+  SEUNET_CHECK(!xr || (b.b.in_channel >= 1 && b.b.in_channel <= 2), "%s: in_channel %d (1 or 2)", who, b.b.in_channel);
+  pr = PoolRef{};
+  if (pool.argmax == nullptr) return 0;
+  SEUNET_CHECK(xr && pool.g_pool != nullptr && d.D % 2 == 0 && d.H % 2 == 0 && d.W % 2 == 0 && d.vox() < (1ll << 31),
+               "%s: pooled gradient needs a recomputed second branch and even extents below 2^31 voxels", who);
+  pr.argmax = pool.argmax; pr.g_pool = pool.g_pool;
+  pr.W = (unsigned)d.W; pr.H = (unsigned)d.H; pr.Wo = (unsigned)d.W / 2; pr.Ho = (unsigned)d.H / 2;
+  pr.mW = (unsigned)((1ull << 32) / (unsigned)d.W); pr.mH = (unsigned)((1ull << 32) / (unsigned)d.H);
+  pr.Vo = d.vox() / 8;
+  return 0;
+}
+
+// one argument list for every instantiation: x is the second branch (all null for Branch2::None), o / a the pass's own struct
+// and a null one for the other pass
+#define SEUNET_CAT_BWD(TWO, APPLY, XW, XR, XG)                                                                                   \
+  cat_bwd_kernel<T, LPV, TWO, APPLY, XW, XR, XG><<<grid, EPI_THREADS, 0, s>>>(                                                    \
+      (const T*)g_out, (const T*)b.a.raw, b.a.mean, b.a.rstd, (const T*)x.src, x.mean2, x.rstd2, b.C, b.slope, a.m1, a.m2, a.m1b, \
+      a.m2b, (T*)a.dx, (T*)a.dx2, o.stat_partial, o.stat_partial2, d.vox(), nullptr, o.xw_partial, x.w2, x.in_channel, pr,        \
+      a.gx_out, a.gx_acc)
+
+int launch_cat_bwd_sums(int dtype, const CatBlock& b, const void* g_out, const PoolGrad& pool, const CatSums& out, Dims d,
+                        hipStream_t s) {
+  PoolRef pr;
+  if (int e = cat_bwd_setup("cat_epilogue_bwd_sums", b, pool, d, pr)) return e;
+  const Branch2 x = b.b.kind == Branch2::None ? Branch2{} : b.b;
+  const bool two = x.kind != Branch2::None, xr = x.kind == Branch2::Recomputed;
+  SEUNET_CHECK(out.stat_partial && (!two || out.stat_partial2), "cat_epilogue_bwd_sums needs the partial buffers");
+  SEUNET_CHECK(!out.xw_partial || xr, "cat_epilogue_bwd_sums: the weight-gradient sums belong to a recomputed second branch");
+  const CatSums o{out.stat_partial, two ? out.stat_partial2 : nullptr, out.xw_partial};
+  const CatApply a{};
+  dim3 grid(epi_partials(d), d.N);
+  SEUNET_LPV_SWITCH(b.C / 8, {
     SEUNET_DTYPE_SWITCH(dtype, {
-      if (apply && gx_out) cat_bwd_kernel<T, LPV, true, true, false, true, true><<<grid, EPI_THREADS, 0, s>>>((const T*)g_out, (const T*)raw, mean, rstd, (const T*)x_in, mean2, rstd2, C, slope, m1, m2, m1b, m2b, (T*)dx, nullptr, nullptr, nullptr, d.vox(), nullptr, nullptr, w2, in_channel, pr, gx_out, gx_acc);
-      else if (apply) cat_bwd_kernel<T, LPV, true, true, false, true><<<grid, EPI_THREADS, 0, s>>>((const T*)g_out, (const T*)raw, mean, rstd, (const T*)x_in, mean2, rstd2, C, slope, m1, m2, m1b, m2b, (T*)dx, nullptr, nullptr, nullptr, d.vox(), nullptr, nullptr, w2, in_channel, pr);
-      else if (xw_partial) cat_bwd_kernel<T, LPV, true, false, true, true><<<grid, EPI_THREADS, 0, s>>>((const T*)g_out, (const T*)raw, mean, rstd, (const T*)x_in, mean2, rstd2, C, slope, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stat_partial, stat_partial2, d.vox(), nullptr, xw_partial, w2, in_channel, pr);
-      else cat_bwd_kernel<T, LPV, true, false, false, true><<<grid, EPI_THREADS, 0, s>>>((const T*)g_out, (const T*)raw, mean, rstd, (const T*)x_in, mean2, rstd2, C, slope, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stat_partial, stat_partial2, d.vox(), nullptr, nullptr, w2, in_channel, pr);
+      if (xr && o.xw_partial) SEUNET_CAT_BWD(true, false, true, true, false);
+      else if (xr) SEUNET_CAT_BWD(true, false, false, true, false);
+      else if (two) SEUNET_CAT_BWD(true, false, false, false, false);
+      else SEUNET_CAT_BWD(false, false, false, false, false);
     });
   });
   SEUNET_LAUNCH_CHECK();
   return 0;
 }
 
-int launch_cat_fwd(int dtype, const void* raw, const float* mean, const float* rstd, const void* raw2,
-                   const float* mean2, const float* rstd2, int C, float slope, void* out, Dims d,
-                   hipStream_t s) {
-  if (int e = check_c(C)) return e;
+int launch_cat_bwd_apply(int dtype, const CatBlock& b, const void* g_out, const PoolGrad& pool, const CatApply& io, Dims d,
+                         hipStream_t s) {
+  PoolRef pr;
+  if (int e = cat_bwd_setup("cat_epilogue_bwd_apply", b, pool, d, pr)) return e;
+  const Branch2 x = b.b.kind == Branch2::None ? Branch2{} : b.b;
+  const bool two = x.kind != Branch2::None, xr = x.kind == Branch2::Recomputed;
+  SEUNET_CHECK(io.m1 && io.m2 && io.dx && (!two || (io.m1b && io.m2b)) && (!two || xr || io.dx2),
+               "cat_epilogue_bwd_apply: missing argument");
+  SEUNET_CHECK(!io.gx_out || xr, "cat_epilogue_bwd_apply: the input-gradient term belongs to a recomputed second branch");
+  const CatApply a{io.m1, io.m2, two ? io.m1b : nullptr, two ? io.m2b : nullptr, io.dx, two && !xr ? io.dx2 : nullptr,
+                   io.gx_out, io.gx_out ? io.gx_acc : 0};
+  const CatSums o{};
   dim3 grid(epi_partials(d) * 4, d.N);
-  const bool two = raw2 != nullptr;
-  SEUNET_LPV_SWITCH(C / 8, {
+  SEUNET_LPV_SWITCH(b.C / 8, {
     SEUNET_DTYPE_SWITCH(dtype, {
-      if (two) cat_fwd_kernel<T, LPV, true><<<grid, EPI_THREADS, 0, s>>>((const T*)raw, mean, rstd, (const T*)raw2, mean2, rstd2, C, slope, (T*)out, d.vox());
-      else cat_fwd_kernel<T, LPV, false><<<grid, EPI_THREADS, 0, s>>>((const T*)raw, mean, rstd, nullptr, nullptr, nullptr, C, slope, (T*)out, d.vox());
+      if (xr && a.gx_out) SEUNET_CAT_BWD(true, true, false, true, true);
+      else if (xr) SEUNET_CAT_BWD(true, true, false, true, false);
+      else if (two) SEUNET_CAT_BWD(true, true, false, false, false);
+      else SEUNET_CAT_BWD(false, true, false, false, false);
     });
   });
   SEUNET_LAUNCH_CHECK();
   return 0;
 }
-
-template <typename T, bool APPLY>
-static int cat_bwd_t(const void* g_out, const void* raw, const float* mean, const float* rstd, const void* raw2,
-                     const float* mean2, const float* rstd2, int C, float slope, const float* m1, const float* m2,
-                     const float* m1b, const float* m2b, void* dx, void* dx2, double* st, double* st2, Dims d, hipStream_t s) {
-  dim3 grid(epi_partials(d) * (APPLY ? 4 : 1), d.N);
-  const bool two = raw2 != nullptr;
-  SEUNET_LPV_SWITCH(C / 8, {
-    if (two) cat_bwd_kernel<T, LPV, true, APPLY><<<grid, EPI_THREADS, 0, s>>>((const T*)g_out, (const T*)raw, mean, rstd, (const T*)raw2, mean2, rstd2, C, slope, m1, m2, m1b, m2b, (T*)dx, (T*)dx2, st, st2, d.vox());
-    else cat_bwd_kernel<T, LPV, false, APPLY><<<grid, EPI_THREADS, 0, s>>>((const T*)g_out, (const T*)raw, mean, rstd, nullptr, nullptr, nullptr, C, slope, m1, m2, nullptr, nullptr, (T*)dx, nullptr, st, nullptr, d.vox());
-  });
-  SEUNET_LAUNCH_CHECK();
-  return 0;
-}
-
-// m1 == nullptr: pass A (f64 sums into stat_partial[2]); otherwise pass B (writes draw into dx / dx2)
-int launch_cat_bwd(int dtype, const void* g_out, const void* raw, const float* mean, const float* rstd,
-                   const void* raw2, const float* mean2, const float* rstd2, int C, float slope, const float* m1,
-                   const float* m2, const float* m1b, const float* m2b, void* dx, void* dx2, double* stat_partial,
-                   double* stat_partial2, Dims d, hipStream_t s) {
-  if (int e = check_c(C)) return e;
-  if (m1 == nullptr) {
-    SEUNET_CHECK(stat_partial && (!raw2 || stat_partial2), "cat_epilogue_bwd pass A needs the partial buffers");
-    SEUNET_DTYPE_SWITCH(dtype, return (cat_bwd_t<T, false>(g_out, raw, mean, rstd, raw2, mean2, rstd2, C, slope, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stat_partial, stat_partial2, d, s)));
-  }
-  SEUNET_CHECK(m2 && dx && (!raw2 || (m1b && m2b && dx2)), "cat_epilogue_bwd pass B: missing argument");
-  SEUNET_DTYPE_SWITCH(dtype, return (cat_bwd_t<T, true>(g_out, raw, mean, rstd, raw2, mean2, rstd2, C, slope, m1, m2, m1b, m2b, dx, dx2, nullptr, nullptr, d, s)));
-  return 1;
-}
+#undef SEUNET_CAT_BWD
 
 }  // namespace seunet

@@ -32,33 +32,40 @@ const BlockDesc kBlocks[] = {
 constexpr int kNumBlocks = sizeof(kBlocks) / sizeof(kBlocks[0]);
 
 struct ParamInfo { std::string name; int shape[5]; int ndim; };
+// registry indices of a block's parameters, -1 = none; xw: for an op, the weight of its aggregation block's x-branch (x33 / x63 / x93)
+struct BlockParams { int conv1_w = -1, conv1_b = -1, conv2_w = -1, conv2_b = -1, se = -1, se2 = -1, xw = -1; };
 
-std::vector<ParamInfo> build_registry(const seunet_net_desc& d) {
+// blocks / head_w / head_b (optional): where the parameters of kBlocks[i] and of the two heads (dc0_0, dc0_1) are in the registry
+std::vector<ParamInfo> build_registry(const seunet_net_desc& d, BlockParams* blocks = nullptr, int* head_w = nullptr,
+                                      int* head_b = nullptr) {
   std::vector<ParamInfo> r;
-  auto add5 = [&](const std::string& n, int a, int b, int k) { r.push_back({n, {a, b, k, k, k}, 5}); };
-  auto add1 = [&](const std::string& n, int a) { r.push_back({n, {a, 0, 0, 0, 0}, 1}); };
+  auto add5 = [&](const std::string& n, int a, int b, int k) { r.push_back({n, {a, b, k, k, k}, 5}); return (int)r.size() - 1; };
+  auto add1 = [&](const std::string& n, int a) { r.push_back({n, {a, 0, 0, 0, 0}, 1}); return (int)r.size() - 1; };
   for (int i = 0; i < kNumBlocks; ++i) {
     const BlockDesc& b = kBlocks[i];
     const int ci = b.cin < 0 ? d.in_channel : b.cin * d.width_mult, co = b.cout * d.width_mult;
     const std::string n = b.name;
-    if (b.kind == 'c') { add5(n + ".conv1.weight", co, ci, 1); continue; }
-    add5(n + ".conv1.weight", co, ci, 3);
-    add1(n + ".conv1.bias", co);
-    add5(n + ".conv2.weight", 2, co, 1);
-    add1(n + ".conv2.bias", 2);
-    add5(n + ".conv_se.weight", 1, co, 1);
-    if (b.kind == 'G') add5(n + ".conv_se2.weight", 1, co, 1);
+    BlockParams bp;
+    bp.conv1_w = add5(n + ".conv1.weight", co, ci, b.kind == 'c' ? 1 : 3);
+    if (b.kind != 'c') {
+      bp.conv1_b = add1(n + ".conv1.bias", co);
+      bp.conv2_w = add5(n + ".conv2.weight", 2, co, 1);
+      bp.conv2_b = add1(n + ".conv2.bias", 2);
+      bp.se = add5(n + ".conv_se.weight", 1, co, 1);
+      if (b.kind == 'G') bp.se2 = add5(n + ".conv_se2.weight", 1, co, 1);
+    }
+    if (blocks) blocks[i] = bp;
   }
-  add5("dc0_0.weight", d.n_classes, 24, 1);
-  add1("dc0_0.bias", d.n_classes);
-  add5("dc0_1.weight", d.n_classes, 12, 1);
-  add1("dc0_1.bias", d.n_classes);
+  const int hw0 = add5("dc0_0.weight", d.n_classes, 24, 1), hb0 = add1("dc0_0.bias", d.n_classes);
+  const int hw1 = add5("dc0_1.weight", d.n_classes, 12, 1), hb1 = add1("dc0_1.bias", d.n_classes);
+  if (head_w) { head_w[0] = hw0; head_w[1] = hw1; }
+  if (head_b) { head_b[0] = hb0; head_b[1] = hb1; }
   return r;
 }
 
-int find_param(const std::vector<ParamInfo>& reg, const std::string& name) {
-  for (size_t i = 0; i < reg.size(); ++i)
-    if (reg[i].name == name) return (int)i;
+int find_block(const char* name) {
+  for (int i = 0; i < kNumBlocks; ++i)
+    if (strcmp(kBlocks[i].name, name) == 0) return i;
   return -1;
 }
 
@@ -383,29 +390,38 @@ struct Plan {
 
 struct Exec {
   Plan p;
-  std::vector<ParamInfo> reg;
   unsigned char* ws = nullptr;
   const float* const* params = nullptr;
   hipStream_t s = nullptr;
   float* grad_x = nullptr;             // seunet_net_backward_input: NCDHW f32 input gradient (null = not requested)
   unsigned char* igs = nullptr;        // its scratch buffer (Plan::ig_gx)
 
+  BlockParams opp[kNumOps];            // parameter indices of each op's block and of the two heads, resolved once in setup
+  int head_w[2], head_b[2];
+  const float* drops[2] = {nullptr, nullptr};   // DropLayer scales of the encoder / decoder head, or null
+
   float* gxl(int l) const { return reinterpret_cast<float*>(igs + p.ig_gx[l]); }
-  void mark(const std::string& tag) const { if (prof_on()) prof_mark(tag.c_str(), s); }
+  void mark(const char* tag, const char* name = "") const { if (prof_on()) prof_mark((std::string(tag) + name).c_str(), s); }
   void* at(size_t off) const { return ws + off; }
   float* fat(size_t off) const { return reinterpret_cast<float*>(ws + off); }
   double* dat(size_t off) const { return reinterpret_cast<double*>(ws + off); }
-  const float* P(const std::string& name) const {
-    const int i = find_param(reg, name);
-    return i < 0 ? nullptr : params[i];
-  }
+  const float* par(int i) const { return i < 0 ? nullptr : params[i]; }
 
   int setup(const seunet_net_desc* desc, const float* const* prm, void* workspace, size_t bytes, hipStream_t st) {
     SEUNET_CHECK(desc && prm && workspace, "net: null argument");
     if (int e = p.init(*desc)) return e;
     SEUNET_CHECK(bytes >= p.total, "net: workspace too small (%zu < %zu bytes)", bytes, p.total);
     SEUNET_CHECK((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "net: workspace must be 256-byte aligned");
-    reg = build_registry(p.d);
+    BlockParams blocks[kNumBlocks];
+    const std::vector<ParamInfo> reg = build_registry(p.d, blocks, head_w, head_b);
+    for (int i = 0; i < kNumOps; ++i) {
+      const OpDesc& o = kOps[i];
+      if (o.kind != OP_GATED && o.kind != OP_CAT) continue;
+      const int b = find_block(o.name), bx = o.xname ? find_block(o.xname) : -1;
+      SEUNET_CHECK(b >= 0 && (!o.xname || bx >= 0), "net: internal: no parameters for %s", o.name);
+      opp[i] = blocks[b];
+      if (bx >= 0) opp[i].xw = blocks[bx].conv1_w;
+    }
     ws = reinterpret_cast<unsigned char*>(workspace);
     params = prm;
     s = st;
@@ -436,11 +452,11 @@ struct Exec {
   }
 
   // conv (+ InstanceNorm statistics) of one block: raw <- conv(src), (mean, rstd) <- stats(raw)
-  int conv_and_stats(const std::string& nm, ConvKernel k, int taps, int dil, const SrcList& src, int cin, const float* w,
+  int conv_and_stats(const char* nm, ConvKernel k, int taps, int dil, const SrcList& src, int cin, const float* w,
                      const float* bias, size_t wp_off, size_t raw_off, int cout, size_t mean_off, size_t rstd_off, const Dims& dm) {
     DstList dst{};
     dst.n = 1; dst.ptr[0] = at(raw_off); dst.C[0] = cout; dst.acc[0] = 0;
-    mark("conv_fwd:" + nm);
+    mark("conv_fwd:", nm);
     if (int e = run_conv(k, taps, dil, src, cin, w, 0, at(wp_off), bias, dst, dat(p.stats), dm)) return e;
     if (k == ConvKernel::Naive) {   // (the naive conv leaves the statistics to a pass of their own)
       mark("stats");
@@ -451,35 +467,40 @@ struct Exec {
                                  fat(mean_off), fat(rstd_off), s);
   }
 
-  SseParams sse_params(const OpDesc& o) const {
-    const std::string n = o.name;
-    SseParams sp{};
-    sp.w_se = P(n + ".conv_se.weight");
-    sp.w_se2 = o.gates == 2 ? P(n + ".conv_se2.weight") : nullptr;
-    sp.w_side = P(n + ".conv2.weight");
-    sp.b_side = P(n + ".conv2.bias");
-    sp.slope = p.d.negative_slope;
-    return sp;
+  // a block's epilogue, described once from its OpRes offsets for the forward and both backward passes
+  GateBlock gate_block(int i) const {
+    const OpRes& r = p.op[i];
+    const BlockParams& bp = opp[i];
+    return GateBlock{{at(r.raw), fat(r.mean), fat(r.rstd)}, r.cout,
+                     {par(bp.se), par(bp.se2), par(bp.conv2_w), par(bp.conv2_b), p.d.negative_slope}};
   }
+  CatBlock cat_block(int i) const {
+    const OpDesc& o = kOps[i];
+    const OpRes& r = p.op[i];
+    Branch2 x{};
+    if (o.xname && p.fuse_x) x = {Branch2::Recomputed, at(p.feat[o.xsrc]), fat(r.mean2), fat(r.rstd2), par(opp[i].xw), p.d.in_channel};
+    else if (o.xname) x = {Branch2::Stored, at(r.raw2), fat(r.mean2), fat(r.rstd2), nullptr, 0};
+    return CatBlock{{at(r.raw), fat(r.mean), fat(r.rstd)}, x, r.cout, p.d.negative_slope};
+  }
+  // the source of a materialised x-branch conv: the padded network input
+  SrcList xbranch_src(const OpDesc& o) const { return SrcList{{at(p.feat[o.xsrc])}, {8}, 1}; }
   bool skip_enc_head = false;   // inference (prediction.py:102-103 discards pred0): the encoder head and its side maps are not evaluated
 
-  SseHead sse_head(const OpDesc& o, const float* drop1, const float* drop2, bool first_of_level) const {
-    SseHead h{};
-    const int lv = kT[o.dst].level;
-    h.side_out = nullptr;
-    if (o.head == 0 && skip_enc_head) return h;     // (no level map: the epilogue skips the side conv altogether)
-    if (p.d.n_classes > 1) {                        // general head path (classes.hip): the epilogue leaves the side map
-      h.side_out = fat(p.op[&o - kOps].side);
-      h.level_accumulate = first_of_level ? 0 : 1;    // (consumed by launch_side_to_level)
-      return h;
-    }
-    h.level_map = fat(p.lvl[o.head][lv]);
-    h.level_accumulate = first_of_level ? 0 : 1;
-    h.head_w = (o.head == 0 ? P("dc0_0.weight") : P("dc0_1.weight")) + 2 * o.m;
-    const float* dr = o.head == 0 ? drop1 : drop2;
-    h.drop = dr ? dr + 2 * o.m : nullptr;
-    h.drop_stride = o.head == 0 ? 24 : 12;
-    return h;
+  // the slice of its head (dc0_0: 24 side channels, dc0_1: 12) that a gated block's two side channels feed
+  struct HeadSlice { const float* w; const float* drop; int stride; float* gw; };
+  HeadSlice head_slice(const OpDesc& o, float* const* grads = nullptr) const {
+    const float* dr = drops[o.head];
+    float* g = grads ? grads[head_w[o.head]] : nullptr;
+    return HeadSlice{params[head_w[o.head]] + 2 * o.m, dr ? dr + 2 * o.m : nullptr, o.head == 0 ? 24 : 12, g ? g + 2 * o.m : nullptr};
+  }
+
+  SseHead sse_head(const OpDesc& o, bool first_of_level) const {
+    if (o.head == 0 && skip_enc_head) return SseHead{};   // (no level map: the epilogue skips the side conv altogether)
+    const int acc = first_of_level ? 0 : 1;
+    // general head path (classes.hip): the epilogue leaves the side map (acc: consumed by launch_side_to_level)
+    if (p.d.n_classes > 1) return SseHead{fat(p.op[&o - kOps].side), nullptr, acc, nullptr, nullptr, 0};
+    const HeadSlice hs = head_slice(o);
+    return SseHead{nullptr, fat(p.lvl[o.head][kT[o.dst].level]), acc, hs.w, hs.drop, hs.stride};
   }
 
   // every conv weight of a pass repacked into its MFMA layout by one or two launches (the parameters change every step)
@@ -501,14 +522,13 @@ struct Exec {
       const OpDesc& o = kOps[i];
       if (o.kind != OP_GATED && o.kind != OP_CAT) continue;
       const OpRes& r = p.op[i];
-      const std::string n = o.name;
       int ctot = 0;
       for (int k = 0; k < o.nsrc; ++k) ctot += p.C[o.src[k]];
       if (!dgrad) {
-        add(r.fwd, P(n + ".conv1.weight"), r.wp_f, r.taps, r.cin, r.cout, ctot, r.cout);
-        if (o.xname && !p.fuse_x) add(r.x_fwd, P(std::string(o.xname) + ".conv1.weight"), r.wp_x, 1, p.d.in_channel, r.cout, 8, r.cout);
+        add(r.fwd, par(opp[i].conv1_w), r.wp_f, r.taps, r.cin, r.cout, ctot, r.cout);
+        if (o.xname && !p.fuse_x) add(r.x_fwd, par(opp[i].xw), r.wp_x, 1, p.d.in_channel, r.cout, 8, r.cout);
       } else if (r.need_dgrad) {
-        add(r.dgrad, P(n + ".conv1.weight"), r.wp_d, r.taps, r.cin, r.cout, r.cout, ctot);
+        add(r.dgrad, par(opp[i].conv1_w), r.wp_d, r.taps, r.cin, r.cout, r.cout, ctot);
       }
     }
     if (!sjobs.empty())
@@ -520,6 +540,7 @@ struct Exec {
 
   int forward(const float* x, const float* drop1, const float* drop2, float* pred0, float* pred1) {
     skip_enc_head = pred0 == nullptr;
+    drops[0] = drop1; drops[1] = drop2;
     if (int e = pack_all_weights(false)) return e;
     mark("pack_input");
     if (int e = launch_pack_input(p.d.dtype, x, p.d.in_channel, at(p.feat[T_X0]), p.dims[0], s)) return e;
@@ -528,62 +549,52 @@ struct Exec {
     for (int i = 0; i < kNumOps; ++i) {
       const OpDesc& o = kOps[i];
       const OpRes& r = p.op[i];
-      const std::string n = o.name;
+      const BlockParams& bp = opp[i];
+      const int lv = kT[o.dst].level;
+      const Dims& dm = p.dims[lv];
       if (o.kind == OP_POOL) {
         if (pool_done[i]) continue;          // written by the aggregation block's epilogue (below)
-        mark("pool_fwd:" + n);
+        mark("pool_fwd:", o.name);
         if (int e = launch_maxpool_fwd(p.d.dtype, at(p.feat[o.src[0]]), p.C[o.src[0]], at(p.feat[o.dst]), p.dims[kT[o.src[0]].level], s)) return e;
       } else if (o.kind == OP_UP) {
-        mark("up_fwd:" + n);
+        mark("up_fwd:", o.name);
         if (int e = launch_upsample2_fwd(p.d.dtype, at(p.feat[o.src[0]]), p.C[o.src[0]], at(p.feat[o.dst]), p.dims[kT[o.src[0]].level], s)) return e;
       } else if (o.kind == OP_GATED) {
-        const int lv = kT[o.dst].level;
-        if (int e = conv_and_stats(n, r.fwd, 27, o.dil, srcs(o), r.cin, P(n + ".conv1.weight"), P(n + ".conv1.bias"), r.wp_f, r.raw,
-                                   r.cout, r.mean, r.rstd, p.dims[lv])) return e;
-        const SseHead hd = sse_head(o, drop1, drop2, !lvl_written[o.head][lv]);
+        if (int e = conv_and_stats(o.name, r.fwd, 27, o.dil, srcs(o), r.cin, par(bp.conv1_w), par(bp.conv1_b), r.wp_f, r.raw,
+                                   r.cout, r.mean, r.rstd, dm)) return e;
+        const SseHead hd = sse_head(o, !lvl_written[o.head][lv]);
         lvl_written[o.head][lv] = true;
-        mark("epi_fwd:" + n);
-        if (int e = launch_sse_fwd(p.d.dtype, at(r.raw), fat(r.mean), fat(r.rstd), r.cout, sse_params(o), at(p.feat[o.dst]), hd,
-                                   p.dims[lv], s)) return e;
+        mark("epi_fwd:", o.name);
+        if (int e = launch_sse_fwd(p.d.dtype, gate_block(i), at(p.feat[o.dst]), hd, dm, s)) return e;
         if (p.d.n_classes > 1 && hd.side_out != nullptr) {
-          const float* dr = o.head == 0 ? drop1 : drop2;
-          if (int e = launch_side_to_level(fat(r.side), (o.head == 0 ? P("dc0_0.weight") : P("dc0_1.weight")) + 2 * o.m, o.head == 0 ? 24 : 12,
-                                           dr ? dr + 2 * o.m : nullptr, o.head == 0 ? 24 : 12, p.d.n_classes, fat(p.lvl[o.head][lv]),
-                                           hd.level_accumulate, p.dims[lv], s)) return e;
+          const HeadSlice hs = head_slice(o);
+          if (int e = launch_side_to_level(fat(r.side), hs.w, hs.stride, hs.drop, hs.stride, p.d.n_classes, fat(p.lvl[o.head][lv]),
+                                           hd.level_accumulate, dm, s)) return e;
         }
       } else {  // OP_CAT
-        const int lv = kT[o.dst].level;
-        if (int e = conv_and_stats(n, r.fwd, 1, 1, srcs(o), r.cin, P(n + ".conv1.weight"), nullptr, r.wp_f, r.raw, r.cout, r.mean,
-                                   r.rstd, p.dims[lv])) return e;
-        if (o.xname && p.fuse_x) {
+        const CatBlock blk = cat_block(i);
+        if (int e = conv_and_stats(o.name, r.fwd, 1, 1, srcs(o), r.cin, par(bp.conv1_w), nullptr, r.wp_f, r.raw, r.cout, r.mean,
+                                   r.rstd, dm)) return e;
+        PoolOut pool_out{};
+        if (blk.b.kind == Branch2::Recomputed) {
           // x-branch: statistics from the input's moments, values recomputed inside the epilogue (never stored)
-          const float* w2 = P(std::string(o.xname) + ".conv1.weight");
           mark("stats");
-          if (int e = launch_xbranch_moments(p.d.dtype, at(p.feat[o.xsrc]), dat(p.xmom), p.dims[lv], s)) return e;
-          if (int e = launch_xbranch_stats(dat(p.xmom), xbranch_moment_slots(p.dims[lv]), w2, r.cout, p.d.in_channel, p.dims[lv].N,
-                                           p.dims[lv].vox(), p.d.eps, fat(r.mean2), fat(r.rstd2), dat(r.xtot), s)) return e;
-          mark("cat_fwd:" + n);
+          if (int e = launch_xbranch_moments(p.d.dtype, blk.b.src, dat(p.xmom), dm, s)) return e;
+          if (int e = launch_xbranch_stats(dat(p.xmom), xbranch_moment_slots(dm), blk.b.w2, r.cout, p.d.in_channel, dm.N, dm.vox(),
+                                           p.d.eps, fat(r.mean2), fat(r.rstd2), dat(r.xtot), s)) return e;
           // the max-pool that consumes this block (ec33 -> pool0, ec63 -> pool1, ec93 -> pool2) is written by the same kernel,
           // with the position of each maximum for the backward pass
           const OpDesc& pool = kOps[i + 1];
           SEUNET_CHECK(pool.kind == OP_POOL && pool.src[0] == o.dst && p.op[i + 1].has_pool_idx,
                        "net: internal: %s is not followed by its max-pool", o.name);
-          if (int e = launch_cat_fwd_x_pool(p.d.dtype, at(r.raw), fat(r.mean), fat(r.rstd), at(p.feat[o.xsrc]), w2, p.d.in_channel,
-                                            fat(r.mean2), fat(r.rstd2), r.cout, p.d.negative_slope, at(p.feat[o.dst]),
-                                            at(p.feat[pool.dst]), p.dims[lv], s, reinterpret_cast<unsigned*>(at(p.op[i + 1].pool_idx)))) return e;
+          pool_out = PoolOut{at(p.feat[pool.dst]), reinterpret_cast<unsigned*>(at(p.op[i + 1].pool_idx))};
           pool_done[i + 1] = true;
-        } else {
-          if (o.xname) {
-            SrcList xs{};
-            xs.n = 1; xs.ptr[0] = at(p.feat[o.xsrc]); xs.C[0] = 8;
-            if (int e = conv_and_stats(o.xname, r.x_fwd, 1, 1, xs, p.d.in_channel, P(std::string(o.xname) + ".conv1.weight"), nullptr, r.wp_x,
-                                       r.raw2, r.cout, r.mean2, r.rstd2, p.dims[lv])) return e;
-          }
-          mark("cat_fwd:" + n);
-          if (int e = launch_cat_fwd(p.d.dtype, at(r.raw), fat(r.mean), fat(r.rstd), o.xname ? at(r.raw2) : nullptr,
-                                     o.xname ? fat(r.mean2) : nullptr, o.xname ? fat(r.rstd2) : nullptr, r.cout,
-                                     p.d.negative_slope, at(p.feat[o.dst]), p.dims[lv], s)) return e;
+        } else if (blk.b.kind == Branch2::Stored) {
+          if (int e = conv_and_stats(o.xname, r.x_fwd, 1, 1, xbranch_src(o), p.d.in_channel, par(bp.xw), nullptr, r.wp_x, r.raw2,
+                                     r.cout, r.mean2, r.rstd2, dm)) return e;
         }
+        mark("cat_fwd:", o.name);
+        if (int e = launch_cat_fwd(p.d.dtype, blk, at(p.feat[o.dst]), pool_out, dm, s)) return e;
       }
     }
     const float* enc[4] = {fat(p.lvl[0][0]), fat(p.lvl[0][1]), fat(p.lvl[0][2]), fat(p.lvl[0][3])};
@@ -600,15 +611,15 @@ struct Exec {
           for (int c = 0; c < K; ++c) {
             const float* lm[4] = {nullptr, nullptr, nullptr, nullptr};
             for (int l = 0; l < nl; ++l) lm[l] = fat(p.lvl[hd][l]) + ((size_t)c * N + n) * p.dims[l].vox();
-            if (int e = launch_head_fwd(lm, nl, (hd == 0 ? P("dc0_0.bias") : P("dc0_1.bias")) + c, pred + ((size_t)n * K + c) * d1.vox(), d1, s)) return e;
+            if (int e = launch_head_fwd(lm, nl, par(head_b[hd]) + c, pred + ((size_t)n * K + c) * d1.vox(), d1, s)) return e;
           }
       }
       mark("outside");
       return 0;
     }
     if (!skip_enc_head)
-      if (int e = launch_head_fwd(enc, 4, P("dc0_0.bias"), pred0, p.dims[0], s)) return e;
-    if (int e = launch_head_fwd(dec, 3, P("dc0_1.bias"), pred1, p.dims[0], s)) return e;
+      if (int e = launch_head_fwd(enc, 4, par(head_b[0]), pred0, p.dims[0], s)) return e;
+    if (int e = launch_head_fwd(dec, 3, par(head_b[1]), pred1, p.dims[0], s)) return e;
     mark("outside");
     return 0;
   }
@@ -618,10 +629,9 @@ struct Exec {
     const OpDesc& o = kOps[i];
     const OpRes& r = p.op[i];
     const int lv = kT[o.dst].level;
-    const std::string n = o.name;
-    const int wi = find_param(reg, n + ".conv1.weight");
+    const int wi = opp[i].conv1_w;
     if (grads[wi]) {
-      mark("wgrad:" + n);
+      mark("wgrad:", o.name);
       if (int e = run_wgrad(r.wgrad, p.d.dtype, r.taps, o.dil, x, r.cin, at(p.grad[o.dst]), r.cout, grads[wi], at(p.wgrad_ws),
                             p.wgrad_ws_bytes, p.dims[lv], s)) return e;
     }
@@ -637,13 +647,14 @@ struct Exec {
       gd.acc[k] = (!is_input(t) && written[t]) ? 1 : 0;
       if (!is_input(t)) written[t] = true;
     }
-    mark("dgrad:" + n);
-    return run_conv(r.dgrad, r.taps, o.dil, gsrc, r.cout, P(n + ".conv1.weight"), 1, at(r.wp_d), nullptr, gd, nullptr, p.dims[lv]);
+    mark("dgrad:", o.name);
+    return run_conv(r.dgrad, r.taps, o.dil, gsrc, r.cout, params[wi], 1, at(r.wp_d), nullptr, gd, nullptr, p.dims[lv]);
   }
 
   hipEvent_t decoder_done = nullptr;   // recorded once every gradient of the decoder blocks (dc1 .. dc6, dc22, dc42) is final
 
   int backward(const float* g_pred0, const float* g_pred1, const float* drop1, const float* drop2, float* const* grads) {
+    drops[0] = drop1; drops[1] = drop2;
     if (int e = pack_all_weights(true)) return e;
     bool written[T_COUNT];
     for (int t = 0; t < T_COUNT; ++t) written[t] = false;
@@ -664,23 +675,22 @@ struct Exec {
               for (int l = 1; l < nl; ++l) gl[l] = fat(p.glvl[hd][l]) + ((size_t)c * N + n) * p.dims[l].vox();
               if (int e = launch_head_bwd(gp + ((size_t)n * K + c) * d1.vox(), gl, nl, fat(p.head_tmp), fat(p.cls_bias) + n * K + c, d1, s)) return e;
             }
-          if (float* gb = grads[find_param(reg, hd == 0 ? "dc0_0.bias" : "dc0_1.bias")])
+          if (float* gb = grads[head_b[hd]])
             if (int e = launch_class_bias_grad(fat(p.cls_bias), N, K, gb, s)) return e;
         }
       } else {
-      if (int e = launch_head_bwd(g_pred0, ge, 4, fat(p.head_tmp), grads[find_param(reg, "dc0_0.bias")], p.dims[0], s)) return e;
-      if (int e = launch_head_bwd(g_pred1, gd, 3, fat(p.head_tmp), grads[find_param(reg, "dc0_1.bias")], p.dims[0], s)) return e;
+      if (int e = launch_head_bwd(g_pred0, ge, 4, fat(p.head_tmp), grads[head_b[0]], p.dims[0], s)) return e;
+      if (int e = launch_head_bwd(g_pred1, gd, 3, fat(p.head_tmp), grads[head_b[1]], p.dims[0], s)) return e;
       }
     }
     std::vector<float*> zero_ptrs;
     std::vector<int> zero_counts;
-    const unsigned* pool_am[T_COUNT] = {};     // per tensor: a max-pool gradient still to be added by its producer's backward
-    const void* pool_g[T_COUNT] = {};
+    PoolGrad pool_grad[T_COUNT] = {};          // per tensor: a max-pool gradient still to be added by its producer's backward
     for (int i = kNumOps - 1; i >= 0; --i) {
       const OpDesc& o = kOps[i];
       const OpRes& r = p.op[i];
-      const std::string n = o.name;
-      if (decoder_done && std::string(o.name) == "up0") {
+      const BlockParams& bp = opp[i];
+      if (decoder_done && strcmp(o.name, "up0") == 0) {
         // the walk is in reverse forward order: everything after up0 (the decoder) has been differentiated.  Its parameter
         // gradients are final from here on (the heads' weights are not: the encoder blocks still add to dc0_0)
         SEUNET_HIP(hipEventRecord(decoder_done, s));
@@ -694,15 +704,14 @@ struct Exec {
         }
         if (is_input(t)) continue;
         SEUNET_CHECK(written[o.dst], "net: internal: gradient of %s output missing", o.name);
-        mark((o.kind == OP_POOL ? "pool_bwd:" : "up_bwd:") + n);
+        mark(o.kind == OP_POOL ? "pool_bwd:" : "up_bwd:", o.name);
         if (o.kind == OP_POOL) {
           if (r.has_pool_idx) {
             // nothing to launch: the aggregation block that produced tensor t adds this gradient on the fly in both of its
-            // backward passes (launch_cat_bwd_x, pool_* arguments) -- no read-modify-write of the full-resolution gradient.
+            // backward passes (their PoolGrad argument) -- no read-modify-write of the full-resolution gradient.
             // (dc5, dc3 and dc1 have already differentiated E1, E3 and E5, the tensors these pools read)
             SEUNET_CHECK(written[t], "net: internal: gradient of %s input missing before its deferred pool gradient", o.name);
-            pool_am[t] = reinterpret_cast<const unsigned*>(at(r.pool_idx));
-            pool_g[t] = at(p.grad[o.dst]);
+            pool_grad[t] = PoolGrad{reinterpret_cast<const unsigned*>(at(r.pool_idx)), at(p.grad[o.dst])};
             continue;
           }
           if (int e = launch_maxpool_bwd(p.d.dtype, at(p.feat[t]), at(p.grad[o.dst]), p.C[t], at(p.grad[t]), written[t] ? 1 : 0,
@@ -718,94 +727,69 @@ struct Exec {
       const Dims& dm = p.dims[lv];
       const int P_slots = epi_partials(dm);
       if (o.kind == OP_GATED) {
-        SseBwdIn g{};
-        g.g_e = written[o.dst] ? at(p.grad[o.dst]) : nullptr;
-        g.g_side = nullptr;
-        g.g_level = lv == 0 ? (o.head == 0 ? g_pred0 : g_pred1) : fat(p.glvl[o.head][lv]);
-        SseHead hd = sse_head(o, drop1, drop2, false);
-        float* g_head = grads[find_param(reg, o.head == 0 ? "dc0_0.weight" : "dc0_1.weight")];
+        const GateBlock blk = gate_block(i);
+        SseBwdIn g{written[o.dst] ? at(p.grad[o.dst]) : nullptr, nullptr,
+                   lv == 0 ? (o.head == 0 ? g_pred0 : g_pred1) : fat(p.glvl[o.head][lv])};
+        SseHead hd = sse_head(o, false);
+        const HeadSlice hs = head_slice(o, grads);
+        float* g_head = hs.gw;
         if (p.d.n_classes > 1) {
           // general head path: the K level-map gradients of this level folded into the gradient of the block's side map (and the
           // head-weight gradient summed on the way); the block's passes then take g_side
           const int K = p.d.n_classes;
-          const float* dr = o.head == 0 ? drop1 : drop2;
           const long long V = dm.vox();
-          const float* glev = g.g_level;
           const long long cstride = lv == 0 ? V : (long long)dm.N * V, nstride = lv == 0 ? (long long)K * V : V;
-          mark("epi_bwd:" + n);
-          if (int e = launch_level_to_side_grad(glev, cstride, nstride, fat(r.side), (o.head == 0 ? P("dc0_0.weight") : P("dc0_1.weight")) + 2 * o.m,
-                                                o.head == 0 ? 24 : 12, dr ? dr + 2 * o.m : nullptr, o.head == 0 ? 24 : 12, K, fat(p.gside),
-                                                dat(p.cls_part), g_head ? g_head + 2 * o.m : nullptr, dm, s)) return e;
+          mark("epi_bwd:", o.name);
+          if (int e = launch_level_to_side_grad(g.g_level, cstride, nstride, fat(r.side), hs.w, hs.stride, hs.drop, hs.stride, K,
+                                                fat(p.gside), dat(p.cls_part), hs.gw, dm, s)) return e;
           g.g_level = nullptr;
           g.g_side = fat(p.gside);
           hd.side_out = nullptr;
           g_head = nullptr;          // (written above; the finalize kernel must not overwrite it)
         }
-        mark("epi_bwd:" + n);   // pass A: f64 sums + parameter-gradient records
-        if (int e = launch_sse_bwd(p.d.dtype, at(r.raw), fat(r.mean), fat(r.rstd), r.cout, sse_params(o), g, hd, nullptr, nullptr,
-                                   nullptr, dat(p.stats), fat(p.pgrad), dm, s)) return e;
+        mark("epi_bwd:", o.name);   // pass A: f64 sums + parameter-gradient records
+        if (int e = launch_sse_bwd_sums(p.d.dtype, blk, g, hd, SseSums{dat(p.stats), fat(p.pgrad)}, dm, s)) return e;
         mark("stats");
-        const int i_se2 = o.gates == 2 ? find_param(reg, n + ".conv_se2.weight") : -1;
         if (int e = launch_gate_bwd_finalize(dat(p.stats), P_slots, r.cout, dm.N, dm.vox(), fat(p.m1), fat(p.m2), fat(p.pgrad),
-                                             dm.N * P_slots, grads[find_param(reg, n + ".conv_se.weight")],
-                                             i_se2 >= 0 ? grads[i_se2] : nullptr, grads[find_param(reg, n + ".conv2.weight")],
-                                             grads[find_param(reg, n + ".conv2.bias")], g_head ? g_head + 2 * o.m : nullptr, s)) return e;
-        mark("in_bwd:" + n);    // pass B: recompute dxhat, apply the InstanceNorm backward, store draw over g_e
-        if (int e = launch_sse_bwd(p.d.dtype, at(r.raw), fat(r.mean), fat(r.rstd), r.cout, sse_params(o), g, hd, fat(p.m1), fat(p.m2),
-                                   at(p.grad[o.dst]), nullptr, nullptr, dm, s)) return e;
+                                             dm.N * P_slots, grads[bp.se], bp.se2 >= 0 ? grads[bp.se2] : nullptr, grads[bp.conv2_w],
+                                             grads[bp.conv2_b], g_head, s)) return e;
+        mark("in_bwd:", o.name);    // pass B: recompute dxhat, apply the InstanceNorm backward, store draw over g_e
+        if (int e = launch_sse_bwd_apply(p.d.dtype, blk, g, hd, SseApply{fat(p.m1), fat(p.m2), at(p.grad[o.dst])}, dm, s)) return e;
         written[o.dst] = true;
         // conv1.bias feeds an affine-less InstanceNorm: its gradient is identically zero; zeroed in one
         // launch after the loop
-        if (float* gb = grads[find_param(reg, n + ".conv1.bias")]) { zero_ptrs.push_back(gb); zero_counts.push_back(r.cout); }
+        if (float* gb = grads[bp.conv1_b]) { zero_ptrs.push_back(gb); zero_counts.push_back(r.cout); }
         if (int e = conv_backward(i, srcs(o), grads, written)) return e;
       } else {  // OP_CAT
         SEUNET_CHECK(written[o.dst], "net: internal: gradient of %s output missing", o.name);
-        mark("cat_bwd:" + n);   // pass A
-        const float* mu2 = o.xname ? fat(r.mean2) : nullptr;
-        const float* rs2 = o.xname ? fat(r.rstd2) : nullptr;
-        const int xi = o.xname ? find_param(reg, std::string(o.xname) + ".conv1.weight") : -1;
-        if (o.xname && p.fuse_x) {
-          // x-branch recomputed from the input in both passes; pass A also sums what its weight gradient is formed from
-          const float* w2 = P(std::string(o.xname) + ".conv1.weight");
-          const void* xin = at(p.feat[o.xsrc]);
-          if (int e = launch_cat_bwd_x(p.d.dtype, at(p.grad[o.dst]), at(r.raw), fat(r.mean), fat(r.rstd), xin, w2, p.d.in_channel, mu2, rs2,
-                                       r.cout, p.d.negative_slope, nullptr, nullptr, nullptr, nullptr, nullptr, dat(p.stats), dat(p.stats2),
-                                       grads[xi] ? dat(p.xwp) : nullptr, dm, s, pool_am[o.dst], pool_g[o.dst])) return e;
-          mark("stats");
-          if (grads[xi])
-            if (int e = launch_cat_xgrad_finalize(dat(p.xwp), dat(p.stats2), P_slots, dat(r.xtot), w2, r.cout, p.d.in_channel, dm.N,
-                                                  p.d.eps, grads[xi], s)) return e;
-          if (int e = launch_stats_finalize(dat(p.stats), P_slots, r.cout, dm.N, dm.vox(), 0.f, 1, fat(p.m1), fat(p.m2), s)) return e;
+        const CatBlock blk = cat_block(i);
+        const bool two = blk.b.kind != Branch2::None, recomputed = blk.b.kind == Branch2::Recomputed;
+        float* gxw = two ? grads[bp.xw] : nullptr;   // the x-branch weight's gradient, if asked for
+        const void* g_out = at(p.grad[o.dst]);
+        const PoolGrad pool = pool_grad[o.dst];
+        mark("cat_bwd:", o.name);   // pass A; a recomputed x-branch also sums what its weight gradient is formed from
+        const CatSums sums{dat(p.stats), dat(p.stats2), recomputed && gxw ? dat(p.xwp) : nullptr};
+        if (int e = launch_cat_bwd_sums(p.d.dtype, blk, g_out, pool, sums, dm, s)) return e;
+        mark("stats");
+        if (recomputed && gxw)
+          if (int e = launch_cat_xgrad_finalize(dat(p.xwp), dat(p.stats2), P_slots, dat(r.xtot), blk.b.w2, r.cout, p.d.in_channel, dm.N,
+                                                p.d.eps, gxw, s)) return e;
+        if (int e = launch_stats_finalize(dat(p.stats), P_slots, r.cout, dm.N, dm.vox(), 0.f, 1, fat(p.m1), fat(p.m2), s)) return e;
+        if (two)
           if (int e = launch_stats_finalize(dat(p.stats2), P_slots, r.cout, dm.N, dm.vox(), 0.f, 1, fat(p.m1b), fat(p.m2b), s)) return e;
-          mark("in_bwd:" + n);    // pass B
-          if (int e = launch_cat_bwd_x(p.d.dtype, at(p.grad[o.dst]), at(r.raw), fat(r.mean), fat(r.rstd), xin, w2, p.d.in_channel, mu2, rs2,
-                                       r.cout, p.d.negative_slope, fat(p.m1), fat(p.m2), fat(p.m1b), fat(p.m2b), at(p.grad[o.dst]), nullptr,
-                                       nullptr, nullptr, dm, s, pool_am[o.dst], pool_g[o.dst], grad_x ? gxl(lv) : nullptr,
-                                       lv == 1 ? 1 : 0)) return e;
-        } else {
-          const void* r2 = o.xname ? at(r.raw2) : nullptr;
-          if (int e = launch_cat_bwd(p.d.dtype, at(p.grad[o.dst]), at(r.raw), fat(r.mean), fat(r.rstd), r2, mu2, rs2, r.cout,
-                                     p.d.negative_slope, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, dat(p.stats),
-                                     dat(p.stats2), dm, s)) return e;
-          mark("stats");
-          if (int e = launch_stats_finalize(dat(p.stats), P_slots, r.cout, dm.N, dm.vox(), 0.f, 1, fat(p.m1), fat(p.m2), s)) return e;
-          if (o.xname)
-            if (int e = launch_stats_finalize(dat(p.stats2), P_slots, r.cout, dm.N, dm.vox(), 0.f, 1, fat(p.m1b), fat(p.m2b), s)) return e;
-          mark("in_bwd:" + n);    // pass B
-          if (int e = launch_cat_bwd(p.d.dtype, at(p.grad[o.dst]), at(r.raw), fat(r.mean), fat(r.rstd), r2, mu2, rs2, r.cout,
-                                     p.d.negative_slope, fat(p.m1), fat(p.m2), o.xname ? fat(p.m1b) : nullptr,
-                                     o.xname ? fat(p.m2b) : nullptr, at(p.grad[o.dst]), o.xname ? at(p.gx) : nullptr, nullptr, nullptr,
-                                     dm, s)) return e;
-          if (o.xname && grad_x) {   // gx_l (+)= W_x^T d2 from the stored d2 (level 1: on top of unpool_1(gx_2))
-            mark(std::string("input_grad:") + o.xname);
-            if (int e = launch_xgrad_contract(p.d.dtype, at(p.gx), r.cout, P(std::string(o.xname) + ".conv1.weight"), p.d.in_channel,
-                                              gxl(lv), lv == 1 ? 1 : 0, dm, s)) return e;
+        // pass B: draw over g_out; a stored x-branch's draw goes to gx, a recomputed one adds its input-gradient term on the fly
+        mark("in_bwd:", o.name);
+        CatApply ap{fat(p.m1), fat(p.m2), fat(p.m1b), fat(p.m2b), at(p.grad[o.dst]), two && !recomputed ? at(p.gx) : nullptr, nullptr, 0};
+        if (recomputed && grad_x) { ap.gx_out = gxl(lv); ap.gx_acc = lv == 1 ? 1 : 0; }
+        if (int e = launch_cat_bwd_apply(p.d.dtype, blk, g_out, pool, ap, dm, s)) return e;
+        if (two && !recomputed) {
+          if (grad_x) {   // gx_l (+)= W_x^T d2 from the stored d2 (level 1: on top of unpool_1(gx_2))
+            mark("input_grad:", o.xname);
+            if (int e = launch_xgrad_contract(p.d.dtype, at(p.gx), r.cout, par(bp.xw), p.d.in_channel, gxl(lv), lv == 1 ? 1 : 0, dm, s)) return e;
           }
-          if (o.xname && grads[xi]) {
-            mark(std::string("wgrad:") + o.xname);
-            SrcList xs{};
-            xs.n = 1; xs.ptr[0] = at(p.feat[o.xsrc]); xs.C[0] = 8;
-            if (int e = run_wgrad(r.x_wgrad, p.d.dtype, 1, 1, xs, p.d.in_channel, at(p.gx), r.cout, grads[xi], at(p.wgrad_ws),
+          if (gxw) {
+            mark("wgrad:", o.xname);
+            if (int e = run_wgrad(r.x_wgrad, p.d.dtype, 1, 1, xbranch_src(o), p.d.in_channel, at(p.gx), r.cout, gxw, at(p.wgrad_ws),
                                   p.wgrad_ws_bytes, dm, s)) return e;
           }
         }
@@ -819,7 +803,7 @@ struct Exec {
     if (grad_x) {
       // grad_x = convT_ec1(draw_ec1) + gx_0 + unpool_0(gx_1); ec1's pass B left draw_ec1 in grad[T_E0]
       mark("input_grad:ec1");
-      if (int e = launch_input_grad(p.d.dtype, at(p.grad[T_E0]), p.C[T_E0], P("ec1.conv1.weight"), at(p.feat[T_X0]), p.d.in_channel,
+      if (int e = launch_input_grad(p.d.dtype, at(p.grad[T_E0]), p.C[T_E0], par(opp[0].conv1_w), at(p.feat[T_X0]), p.d.in_channel,
                                     gxl(0), gxl(1), grad_x, p.dims[0], s)) return e;
     }
     mark("outside");
@@ -941,9 +925,10 @@ int seunet_net_read_tensor(const seunet_net_desc* desc, const float* const* para
         // in_channel <= 2: the branch is recomputed inside the aggregation epilogue and leaves no tensor: recompute it here by the
         // same device function, from the packed input in the workspace and the caller's weights
         SEUNET_CHECK(params != nullptr, "net_read_tensor: the recomputed x-branch %s needs the parameter list", name);
-        const std::vector<ParamInfo> reg = build_registry(p.d);
-        const int wi = find_param(reg, std::string(name) + ".conv1.weight");
-        SEUNET_CHECK(wi >= 0 && params[wi], "net_read_tensor: no weight for %s", name);
+        BlockParams blocks[kNumBlocks];
+        build_registry(p.d, blocks);
+        const int wi = blocks[find_block(o.xname)].conv1_w;
+        SEUNET_CHECK(params[wi], "net_read_tensor: no weight for %s", name);
         return launch_xbranch_values(p.d.dtype, ws + p.feat[o.xsrc], params[wi], r.cout, p.d.in_channel, out, p.dims[lv], (hipStream_t)s);
       }
       if (which == 0) return launch_unpack_cl(p.d.dtype, ws + r.raw2, r.cout, out, p.dims[lv], (hipStream_t)s);
