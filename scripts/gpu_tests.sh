@@ -5,13 +5,16 @@ rc=$?
 rc2=0
 rc3=0
 rc4=0
+rc5=0
+rc6=0
 echo "ops rc=$rc"; tail -3 gpurun_out/ops.log
 if [ $rc -le 1 ]; then
   timeout -k 10 900 python -m pytest tests/test_net_gpu.py -m gpu -q -s -p no:cacheprovider > gpurun_out/net.log 2>&1
   rc2=$?
   echo "net rc=$rc2"; grep -E "HIP-vs-f64|gradient rel-L2|bf16 logits|passed|failed|FAILED" gpurun_out/net.log | tail -20
   if [ $rc2 -le 1 ]; then
-    # every conv pass of the plan at its own shape, bitwise (measured: 50-55 s on an MI355X box, most of it the CPU reference)
+    # every conv pass of the plan at its own shape, bitwise, with the batch-1 plan and the batch-16 source distances (measured:
+    # 59-62 s on an MI355X box, most of it the CPU reference)
     # (its log is a temporary file: what a failure reports -- counts, first positions, planes -- is printed here)
     layers_log=$(mktemp)
     timeout -k 10 120 python -m pytest tests/test_conv_layers_gpu.py -m gpu -q -s -p no:cacheprovider > "$layers_log" 2>&1
@@ -28,6 +31,29 @@ if [ $rc -le 1 ]; then
       echo "epilogue layers rc=$rc4"; grep -E -A8 "beyond the bound|not bitwise equal" "$epi_log" | cut -c1-200 | head -60
       grep -E "passed|failed|FAILED|Error" "$epi_log" | tail -20
       rm -f "$epi_log"
+      if [ $rc4 -le 1 ]; then
+        # the same conv passes at the second shipped configuration, 2 x 2 x 160^3 at width 2 (BASELINE.json configs[4]), bitwise
+        # (batch 2; measured: 92-95 s on an MI355X box, most of it the CPU reference)
+        c4_log=$(mktemp)
+        timeout -k 10 190 python -m pytest tests/test_conv_layers_config4_gpu.py -m gpu -q -s -p no:cacheprovider > "$c4_log" 2>&1
+        rc5=$?
+        echo "config-4 layers rc=$rc5"; grep -E -A12 "not bitwise equal" "$c4_log" | cut -c1-200 | head -60
+        grep -E "passed|failed|FAILED|Error" "$c4_log" | tail -20
+        rm -f "$c4_log"
+        if [ $rc5 -le 1 ]; then
+          # and its epilogue / pooling / up-sampling / head passes and block-by-block forward (measured: 31-35 s on an MI355X box)
+          c4e_log=$(mktemp)
+          timeout -k 10 75 python -m pytest tests/test_epilogue_layers_config4_gpu.py -m gpu -q -s -p no:cacheprovider > "$c4e_log" 2>&1
+          rc6=$?
+          echo "config-4 epilogue layers rc=$rc6"; grep -E -A8 "beyond the bound|not bitwise equal" "$c4e_log" | cut -c1-200 | head -60
+          grep -E "passed|failed|FAILED|Error" "$c4e_log" | tail -20
+          rm -f "$c4e_log"
+        else
+          echo "config-4 layer run crashed or timed out (rc=$rc5): config-4 epilogue layer tests skipped"
+        fi
+      else
+        echo "epilogue layer run crashed or timed out (rc=$rc4): config-4 layer tests skipped"
+      fi
     else
       echo "layer run crashed or timed out (rc=$rc3): epilogue layer tests skipped"
     fi
@@ -37,8 +63,10 @@ if [ $rc -le 1 ]; then
 else
   echo "ops run crashed or timed out (rc=$rc): net and layer tests skipped"
 fi
-# exit status = the worst of the four runs (a crash / timeout / GPU fault is a failure, not a skip)
+# exit status = the worst of the six runs (a crash / timeout / GPU fault is a failure, not a skip)
 [ $rc2 -gt $rc ] && rc=$rc2
 [ $rc3 -gt $rc ] && rc=$rc3
 [ $rc4 -gt $rc ] && rc=$rc4
+[ $rc5 -gt $rc ] && rc=$rc5
+[ $rc6 -gt $rc ] && rc=$rc6
 exit $rc

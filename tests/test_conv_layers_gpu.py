@@ -1,332 +1,74 @@
-"""Every convolution pass of the network's plan, at the layer's own shape and on the kernel the plan routes it to, BITWISE.
+"""Every convolution pass of the network's plan, at the layer's own shape and on the kernel the plan routes it to, BITWISE
+(method, exactness argument and helpers: tests/conv_layer_cases.py).
 
 The cases are generated from ``SE_UNet.conv_plan`` for the benchmarked configuration (4 x 2 x 128^3, width 1) in bf16 and fp16
-storage, so a layer that is added or re-routed later is covered without editing this file.
-
-Why equality and not a tolerance: the operands are small integers.  With x, w, bias in {-3..3} every product and every partial
-sum of a 3x3x3 convolution with up to 256 input channels is an integer below 27 * 256 * 9 + 3 < 2^24, exact in f32 in ANY
-summation order -- on the matrix cores and in ``F.conv3d`` on the CPU alike -- and the 16-bit stored value is that integer
-rounded once to nearest-even (many outputs exceed 256 and many are exact ties, so the rounding is exercised).  For the weight
-gradient x, dy are in {-1, 0, 1}: every partial sum is bounded by N * voxels = 2^23.  A plain float32 convolution on the CPU is
-therefore an exact reference, and a kernel that drops or doubles one plane at a segment seam, or one patch of a work-item loop,
-differs by whole integers.  Only the InstanceNorm statistics carry a tolerance: the fp32 row of tests/test_ops_gpu.py
-(mean atol 2e-5, rstd rtol 2e-4), against float64 statistics of the exact integer result.
-
-The reference of a layer is computed once and shared by the two storage types (cases are ordered layer-major; one layer's
-tensors are kept at a time)."""
+storage, so a layer that is added or re-routed later is covered without editing this file.  Two smaller plans ride along:
+1 x 2 x 128^3 (bf16, all three passes: the segment seams of the marching kernels and the statistic partial count move with the
+batch) and the forward of the two-source layers at the source distances of the 16 x 2 x 128^3 inference plan (2^31 bytes and
+more: the range a signed 32-bit offset does not reach).  The 160^3 width-2 configuration has its own module,
+tests/test_conv_layers_config4_gpu.py."""
 import os
+import sys
 
 import pytest
 import torch
 import torch.nn.functional as F
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import conv_layer_cases as L  # noqa: E402
+from conv_layer_cases import DTYPES, assert_same, check_wgrad, ints, rounded, shared, sources, storage, wgrad_data  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
-DTYPES = ("bf16", "fp16")
 BATCH, EXTENT = 4, 128
-
-
-def _plan(dtype, batch=BATCH, width=1):
-    import seunet_amd  # noqa: F401
-    from seunet_amd import _lib
-    from seunet_amd.SE_UNet import conv_plan, make_desc
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    return conv_plan(make_desc(batch, 2, 1, EXTENT, EXTENT, EXTENT, width, _lib.dtype_code(dtype), 0, 0.01))
-
-
-PLANS = {dt: {c["name"]: c for c in _plan(dt)} for dt in DTYPES}
-LAYERS = [c["name"] for c in _plan("bf16")]
+CFG = L.Config(BATCH, EXTENT, 1)
+PLANS, LAYERS, CASES, DGRAD_CASES, _ROUTED, _ids = CFG.PLANS, CFG.LAYERS, CFG.CASES, CFG.DGRAD_CASES, CFG.ROUTED, L.ids
 # a plan that silently routed everything to one kernel would make the cases below pass vacuously
-_ROUTED = {(c[p], p) for dt in DTYPES for c in PLANS[dt].values() for p in ("fwd", "dgrad", "wgrad") if c[p]}
 assert len(LAYERS) == 24 and all(list(PLANS[dt]) == LAYERS for dt in DTYPES), LAYERS
 assert {k for k, _ in _ROUTED} >= {"Stream", "March", "Tiled", "Wgrad1x1"}, sorted(_ROUTED)
 assert {("Stream", p) for p in ("fwd", "dgrad", "wgrad")} | {("March", p) for p in ("fwd", "dgrad", "wgrad")} <= _ROUTED, sorted(_ROUTED)
 
-# (layer, storage type, layout of a two-source layer: "plan" = one allocation, the sources at the byte distance the plan
-# reports, as the network's workspace presents them to the 32-bit buffer descriptor; dc5 also with two separate allocations)
-CASES = [(n, dt, lay) for n in LAYERS for lay in (("plan", "separate") if n == "dc5" else ("plan",)) for dt in DTYPES]
-DGRAD_CASES = [c for c in CASES if PLANS[c[1]][c[0]]["need_dgrad"]]
-_ids = lambda c: "-".join(c) if isinstance(c, tuple) else None
+# 1 x 2 x 128^3: march_zsteps / ws_zsteps cut a sample's planes differently than at batch 4, seunet_epilogue_slots is 256
+# instead of 192 at every level but the last, and ec63's weight gradient leaves the whole-GEMM kernel for the tiled one
+ONE = L.Config(1, EXTENT, 1, dtypes=("bf16",))
+assert ONE.LAYERS == LAYERS and ONE.passes("ec63")[2] == "Tiled" and PLANS["bf16"]["ec63"]["wgrad"] == "Wgrad1x1"
+assert {("Stream", p) for p in ("fwd", "dgrad", "wgrad")} | {("March", p) for p in ("fwd", "dgrad", "wgrad")} <= ONE.ROUTED, sorted(ONE.ROUTED)
+
+# 16 x 2 x 128^3 (auto_batch's cap): dc5's sources are exactly 2^31 bytes apart and dc3's 2 365 587 456, inside [2^31, 2^32)
+# where a signed 32-bit byte offset breaks and test_two_sources_more_than_4gb_apart (>= 2^32) does not look
+BIG = L.Config(16, EXTENT, 1)
+PAIRED = [n for n in LAYERS if len(BIG.PLANS["bf16"][n]["src_c"]) == 2]
+assert PAIRED == ["dc1", "dc22", "dc3", "dc42", "dc5"], PAIRED
+assert abs(BIG.PLANS["bf16"]["dc5"]["src_dist"]) == 1 << 31 and abs(BIG.PLANS["bf16"]["dc3"]["src_dist"]) == 2365587456
+assert abs(PLANS["bf16"]["dc5"]["src_dist"]) < 1 << 31
 
 
 @pytest.fixture(scope="module")
 def S():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import seunet_amd  # noqa: F401
-    from seunet_amd import _lib, ops
-    _lib.load()
-    return ops
-
-
-def storage(dtype):
-    return torch.bfloat16 if dtype == "bf16" else torch.float16
-
-
-def ints(shape, lo, hi, seed):
-    """Seeded integers in [lo, hi] as int8 on the GPU (the CPU reference reads a copy of the same values)."""
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    return torch.randint(lo, hi + 1, shape, generator=g, device="cuda", dtype=torch.int8)
-
-
-_cache = {}
-
-
-def shared(key, make):
-    """One entry: the tensors of the layer under test, shared by its bf16 and fp16 cases; dropped when the next layer starts."""
-    if key not in _cache:
-        _cache.clear()
-        torch.cuda.empty_cache()
-        _cache[key] = make()
-    return _cache[key]
-
-
-def place_pair(a, b, dist):
-    """Copies of the channels-last tensors a, b inside ONE allocation with b.data_ptr() - a.data_ptr() == dist."""
-    na, nb = a.numel() * a.element_size(), b.numel() * b.element_size()
-    assert dist % 256 == 0 and (dist >= na or -dist >= nb), (dist, na, nb)
-    off_a, off_b = (0, dist) if dist > 0 else (-dist, 0)
-    buf = torch.empty(max(off_a + na, off_b + nb), dtype=torch.uint8, device=a.device)
-    assert buf.data_ptr() % 256 == 0
-    va = buf[off_a:off_a + na].view(a.dtype).view(a.shape)
-    vb = buf[off_b:off_b + nb].view(b.dtype).view(b.shape)
-    va.copy_(a)
-    vb.copy_(b)
-    assert vb.data_ptr() - va.data_ptr() == dist
-    return va, vb
-
-
-def sources(S, x_i8, c, dtype, layout):
-    """The layer's source tensors (channels-last, storage type) cut from the NCDHW int8 tensor of all its input channels."""
-    srcs, o = [], 0
-    for ch in c["src_c"]:
-        srcs.append(S.to_cl(x_i8[:, o:o + ch].float(), dtype))
-        o += ch
-    if len(srcs) == 2 and layout == "plan":
-        srcs = list(place_pair(srcs[0], srcs[1], c["src_dist"]))
-    return srcs
-
-
-def explain(got, want, axes):
-    """What differs: count, the first few positions with got / want, and the distinct indices along z and the 4-row y patches
-    (a seam bug reads as "planes 64 and 65 of every sample"); for a weight gradient the (co, ci, tap) positions."""
-    ne = got != want
-    lines = [f"{int(ne.sum())} of {ne.numel()} elements differ"]
-    if got.dim() == 5 and axes[0] == "n":
-        n0 = int(ne.flatten(1).any(1).nonzero()[0])
-        z0 = int(ne[n0].any(dim=0).flatten(1).any(1).nonzero()[0])
-        for c, y, x in ne[n0, :, z0].nonzero()[:6].tolist():
-            lines.append(f"  (n, c, z, y, x) = ({n0}, {c}, {z0}, {y}, {x}): got {float(got[n0, c, z0, y, x])} want {float(want[n0, c, z0, y, x])}")
-        zs = ne.permute(2, 0, 1, 3, 4).flatten(1).any(1).nonzero().flatten().tolist()
-        ys = ne.permute(3, 0, 1, 2, 4).flatten(1).any(1).nonzero().flatten().tolist()
-        xs = ne.permute(4, 0, 1, 2, 3).flatten(1).any(1).nonzero().flatten().tolist()
-        ns = ne.flatten(1).any(1).nonzero().flatten().tolist()
-        cs = ne.permute(1, 0, 2, 3, 4).flatten(1).any(1).nonzero().flatten().tolist()
-        lines += [f"  samples {ns}", f"  channels {cs}", f"  z planes {zs}", f"  y rows {ys} (4-row patches {sorted({y // 4 for y in ys})})",
-                  f"  x columns in 32-wide blocks {sorted({x // 32 for x in xs})}"]
-    else:
-        g, w = got.flatten(2), want.flatten(2)
-        for co, ci, t in (g != w).nonzero()[:8].tolist():
-            lines.append(f"  (co, ci, tap) = ({co}, {ci}, {t}): got {float(g[co, ci, t])} want {float(w[co, ci, t])}")
-        lines.append(f"  taps {sorted(set((g != w).nonzero()[:, 2].tolist()))}")
-    return "\n".join(lines)
-
-
-def assert_same(got, want, what, axes=("n", "c", "z", "y", "x")):
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    if not torch.equal(got, want):
-        pytest.fail(f"{what}: not bitwise equal\n{explain(got, want, axes)}", pytrace=False)
-
-
-def rounded(ref_cpu, dtype):
-    """The exact f32 integers rounded once to the storage type (on the CPU), back as f32 on the GPU."""
-    return ref_cpu.to(storage(dtype)).cuda().float()
-
-
-def conv_ref(x, w, b, taps, dil):
-    return F.conv3d(x, w, b, padding=dil, dilation=dil) if taps == 27 else F.conv3d(x, w, b)
-
-
-# ---------------------------------------------------------------------------------------------------
-# forward (+ InstanceNorm statistics)
-# ---------------------------------------------------------------------------------------------------
-def forward_data(c, seed):
-    n, d, h, w = c["dims"]
-    k = 3 if c["taps"] == 27 else 1
-    x = ints((n, sum(c["src_c"]), d, h, w), -3, 3, seed)
-    x[:, c["cin"]:] = 0                                  # ec1: the logical 2 of the 8 packed channels
-    wt = ints((c["cout"], c["cin"], k, k, k), -3, 3, seed + 1).float().cpu()
-    b = ints((c["cout"],), -3, 3, seed + 2).float().cpu() if c["taps"] == 27 else None     # (the aggregation convs have no bias)
-    ref = conv_ref(x[:, :c["cin"]].cpu().float(), wt, b, c["taps"], c["dilation"])
-    mean = torch.stack([r.double().mean(dim=(1, 2, 3)) for r in ref])
-    var = torch.stack([r.double().var(dim=(1, 2, 3), unbiased=False) for r in ref])
-    return x, wt, b, ref, mean, (var + 1e-5).rsqrt()
-
-
-def run_forward(S, kernel, srcs, wt, b, c):
-    if kernel == "Stream":
-        raw, part, slots = S.conv3d_stream(srcs[0], wt, b, c["dilation"], want_stats=True)
-    elif kernel == "March":
-        (raw,), part, slots = S.conv3d_march(srcs, wt, b, c["dilation"], want_stats=True)
-    else:
-        assert kernel == "Tiled", kernel
-        (raw,), part, slots = S.conv3d(srcs, wt, b, c["dilation"], S._lib.CONV_MFMA, cin=c["cin"], want_stats=True)
-    return raw, part, slots
-
-
-def check_stats(S, part, slots, c, mean64, rstd64, what):
-    n, d, h, w = c["dims"]
-    mean, rstd = S.stats_finalize(part, slots, d * h * w)
-    mean, rstd = mean.cpu().double()[:, :c["cout"]], rstd.cpu().double()[:, :c["cout"]]
-    em = float((mean - mean64).abs().max())
-    er = float(((rstd - rstd64).abs() / rstd64).max())
-    print(f"{what}: max |mean - float64| = {em:.3e} (|mean| <= {float(mean64.abs().max()):.3e}), max rel rstd error = {er:.3e}")
-    assert em <= 2e-5, f"{what}: mean off by {em:.3e} (atol 2e-5)"
-    assert er <= 2e-4, f"{what}: rstd off by {er:.3e} relative (rtol 2e-4)"
+    return L.ops_or_skip()
 
 
 @pytest.mark.parametrize("case", CASES, ids=_ids)
 def test_forward_and_statistics(S, case):
-    name, dtype, layout = case
-    c = PLANS[dtype][name]
-    x, wt, b, ref, mean64, rstd64 = shared(("fwd", name), lambda: forward_data(c, 1000 + 10 * LAYERS.index(name)))
-    srcs = sources(S, x, c, dtype, layout)
-    raw, part, slots = run_forward(S, c["fwd"], srcs, wt.cuda(), None if b is None else b.cuda(), c)
-    what = f"{name} forward on {c['fwd']} ({dtype}, {c['src_c']} -> {c['cout']} channels, dilation {c['dilation']}, {c['dims']})"
-    assert_same(S.from_cl(raw, c["cout"]), rounded(ref, dtype), what)
-    check_stats(S, part, slots, c, mean64, rstd64, what)
-
-
-# ---------------------------------------------------------------------------------------------------
-# data gradient
-# ---------------------------------------------------------------------------------------------------
-def dgrad_data(c, seed):
-    n, d, h, w = c["dims"]
-    k = 3 if c["taps"] == 27 else 1
-    cin = sum(c["src_c"])
-    dy = ints((n, c["cout"], d, h, w), -3, 3, seed)
-    wt = ints((c["cout"], cin, k, k, k), -3, 3, seed + 1).float().cpu()
-    # the transposed convolution as a convolution with the transposed, mirrored weight (exact in f32 like the forward)
-    ref = conv_ref(dy.cpu().float(), wt.transpose(0, 1).flip(2, 3, 4).contiguous(), None, c["taps"], c["dilation"])
-    prev = ints((n, cin, d, h, w), -3, 3, seed + 2)
-    return dy, wt, ref, prev
-
-
-def run_dgrad(S, kernel, dy_cl, wt, c, dsts, acc):
-    if kernel == "Stream":
-        S.conv3d_stream(dy_cl, wt, None, c["dilation"], transpose_flip=True, dst=dsts[0], accumulate=bool(acc[0]))
-    elif kernel == "March":
-        S.conv3d_march([dy_cl], wt, None, c["dilation"], transpose_flip=True, dsts=dsts, dst_channels=c["src_c"], accumulate=acc)
-    else:
-        assert kernel == "Tiled", kernel
-        S.conv3d([dy_cl], wt, None, c["dilation"], S._lib.CONV_MFMA, transpose_flip=True, dsts=dsts, dst_channels=c["src_c"], accumulate=acc)
-
-
-def tiled_rounds_before_it_adds(c):
-    """conv_igemm.hip, `+=` in 16-bit storage: a launch with a destination wider than 32 bytes per written voxel pitch goes
-    through the LDS stage, which holds the new values already rounded, and stores round(round(new) + old) (stated in the
-    kernel's comment on its store paths; found by this file: ec7 / ec10 / ec11 / ec12 / dc1 / dc2 in bf16 were one ulp off
-    round(new + old) on 3 % of the elements).  Launches whose destinations all have <= 16 channels add in f32 and round once."""
-    st = c["dilation"] if c["taps"] == 27 else 1
-    return c["dgrad"] == "Tiled" and any(ch * st > 16 for ch in c["src_c"])
+    L.forward_case(S, CFG, case)
 
 
 @pytest.mark.parametrize("case", DGRAD_CASES, ids=_ids)
 def test_data_gradient(S, case):
-    """Three destination states: overwrite (over a poisoned buffer), += onto an integer-valued previous gradient (expected:
-    the exact integer sum plus the old value, rounded ONCE -- on the marching and streaming kernels; the tiled kernel's staged
-    store path rounds the new value first, see ``tiled_rounds_before_it_adds``, and the expectation mirrors that), and -- for
-    the layers with several sources -- a null first destination (those channels are dropped) next to one that accumulates.
-    (In this plan only ec1 meets the network input, and it runs no data gradient at all; the x-branch's gradient does not go
-    through a convolution kernel.)"""
-    name, dtype, layout = case
-    c = PLANS[dtype][name]
-    dy, wt, ref, prev = shared(("dgrad", name), lambda: dgrad_data(c, 2000 + 10 * LAYERS.index(name)))
-    dy_cl = S.to_cl(dy.float(), dtype)
-    wt_g = wt.cuda()
-    split = c["src_c"]
-    offs = [sum(split[:i]) for i in range(len(split))]
-    what = f"{name} data gradient on {c['dgrad']} ({dtype}, {c['cout']} -> {split} channels, dilation {c['dilation']}, {c['dims']})"
-    states = [("overwrite", [0] * len(split), [False] * len(split)), ("+=", [1] * len(split), [False] * len(split))]
-    if len(split) > 1:
-        states.append(("null first destination, += second", [0, 1, 0][:len(split)], [True] + [False] * (len(split) - 1)))
-    for label, acc, null in states:
-        dsts = []
-        for o, ch, a, dropped in zip(offs, split, acc, null):
-            if dropped:
-                dsts.append(None)
-            elif a:
-                dsts.append(S.to_cl(prev[:, o:o + ch].float(), dtype))
-            else:
-                dsts.append(torch.full(tuple(dy_cl.shape[:4]) + (ch,), 7.0, dtype=dy_cl.dtype, device="cuda"))
-        if len(dsts) == 2 and layout == "plan" and not any(null):
-            dsts = list(place_pair(dsts[0], dsts[1], c["src_dist"]))
-        run_dgrad(S, c["dgrad"], dy_cl, wt_g, c, dsts, acc)
-        for i, (o, ch, a) in enumerate(zip(offs, split, acc)):
-            if dsts[i] is None:
-                continue
-            want = ref[:, o:o + ch]
-            if a:
-                new = want.to(storage(dtype)).float() if tiled_rounds_before_it_adds(c) else want
-                want = new + prev[:, o:o + ch].cpu().float()
-            assert_same(S.from_cl(dsts[i]), rounded(want, dtype), f"{what}, {label}, destination {i}")
-        del dsts
-
-
-# ---------------------------------------------------------------------------------------------------
-# weight gradient
-# ---------------------------------------------------------------------------------------------------
-def wgrad_data(c, seed):
-    n, d, h, w = c["dims"]
-    k = 3 if c["taps"] == 27 else 1
-    x = ints((n, sum(c["src_c"]), d, h, w), -1, 1, seed)
-    x[:, c["cin"]:] = 0
-    dy = ints((n, c["cout"], d, h, w), -1, 1, seed + 1)
-    pad = c["dilation"] if k == 3 else 0
-    ref = torch.nn.grad.conv3d_weight(x[:, :c["cin"]].cpu().float(), (c["cout"], c["cin"], k, k, k), dy.cpu().float(),
-                                      padding=pad, dilation=c["dilation"] if k == 3 else 1)
-    return x, dy, ref
-
-
-def run_wgrad(S, kernel, srcs, dy_cl, c):
-    """(the routed call, the call that forces the kernel the plan names)"""
-    L = S._lib
-    if kernel == "Stream":                       # routed by Plan::route itself, ahead of wgrad_kernel
-        f = lambda: S.conv3d_wgrad_stream(srcs[0], dy_cl, c["cin"], c["cout"], c["dilation"])
-        return f, f
-    forced = {"March": L.CONV_MARCH, "Wgrad1x1": L.CONV_MARCH, "Tiled": L.CONV_TILED}[kernel]
-    call = lambda impl: S.conv3d_wgrad(srcs, dy_cl, c["cin"], c["cout"], c["taps"], c["dilation"], impl)
-    return (lambda: call(L.CONV_MFMA)), (lambda: call(forced))
-
-
-def check_wgrad(S, c, srcs, dy_cl, ref, what):
-    routed, forced = run_wgrad(S, c["wgrad"], srcs, dy_cl, c)
-    dw = routed()
-    assert_same(dw.cpu(), ref, what, axes=("co", "ci", "tap"))
-    assert_same(forced(), dw, what + ": the kernel the plan names, forced, against the routed call", axes=("co", "ci", "tap"))
-    assert_same(routed(), dw, what + ": second run against the first", axes=("co", "ci", "tap"))
-    if c["wgrad"] == "Stream":                   # what seunet_conv3d_wgrad picks for the same operands must be exact as well
-        other = S.conv3d_wgrad(srcs, dy_cl, c["cin"], c["cout"], c["taps"], c["dilation"], S._lib.CONV_MFMA)
-        assert_same(other.cpu(), ref, what + ": seunet_conv3d_wgrad's own choice", axes=("co", "ci", "tap"))
+    """Overwrite, ``+=`` and a null first destination: see ``conv_layer_cases.dgrad_case``."""
+    L.dgrad_case(S, CFG, case)
 
 
 @pytest.mark.parametrize("case", CASES, ids=_ids)
 def test_weight_gradient(S, case):
-    name, dtype, layout = case
-    c = PLANS[dtype][name]
-    x, dy, ref = shared(("wgrad", name), lambda: wgrad_data(c, 3000 + 10 * LAYERS.index(name)))
-    srcs = sources(S, x, c, dtype, layout)
-    what = f"{name} weight gradient on {c['wgrad']} ({dtype}, {c['src_c']} x {c['cout']} channels, dilation {c['dilation']}, {c['dims']})"
-    check_wgrad(S, c, srcs, S.to_cl(dy.float(), dtype), ref, what)
+    L.wgrad_case(S, CFG, case)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_weight_gradient_of_a_256_channel_input_on_a_coarse_level(S, dtype):
     """wgrad_kernel's third clause (cin >= 256 takes the marching kernel below 48^3) is met by dc1 at width 2 only: 2 x 128
     channels on 4 x 32^3, its sources at the distance that plan gives them."""
-    c = {e["name"]: e for e in _plan(dtype, width=2)}["dc1"]
+    c = {e["name"]: e for e in L.plan_of(dtype, BATCH, EXTENT, 2)}["dc1"]
     assert c["cin"] == 256 and c["dims"] == (BATCH, 32, 32, 32) and c["wgrad"] == "March", c
     x, dy, ref = shared(("wgrad", "dc1 at width 2"), lambda: wgrad_data(c, 3500))
     srcs = sources(S, x, c, dtype, "plan")
@@ -341,7 +83,7 @@ def test_two_sources_more_than_4gb_apart(S, dtype):
     """launch_conv_march leaves the one-descriptor addressing when its two forward sources span 2^32 bytes or more, and
     wgrad_march_cfg refuses such a pair, so that the weight gradient falls back to the tiled kernel (the plan relies on both for
     dc1 / dc3 at large batches).  A dc5-shaped layer whose 32-channel sources sit at the two ends of one 4 GB + 64 MB allocation."""
-    L = S._lib
+    lib = S._lib
     shape, c_src, cout = (1, 16, 40, 64), 32, 32
     total = (1 << 32) + (64 << 20)
     try:
@@ -376,9 +118,34 @@ def test_two_sources_more_than_4gb_apart(S, dtype):
     fill(x)
     dy_cl = S.to_cl(dy.float(), dtype)
     ref = torch.nn.grad.conv3d_weight(x.cpu().float(), (cout, 2 * c_src, 3, 3, 3), dy.cpu().float(), padding=1)
-    dw = S.conv3d_wgrad(far, dy_cl, 2 * c_src, cout, 27, 1, L.CONV_MFMA)
+    dw = S.conv3d_wgrad(far, dy_cl, 2 * c_src, cout, 27, 1, lib.CONV_MFMA)
     assert_same(dw.cpu(), ref, f"weight gradient, sources 4 GB apart ({dtype})", axes=("co", "ci", "tap"))
-    assert_same(S.conv3d_wgrad(far, dy_cl, 2 * c_src, cout, 27, 1, L.CONV_TILED), dw, "routed call against the tiled kernel",
+    assert_same(S.conv3d_wgrad(far, dy_cl, 2 * c_src, cout, 27, 1, lib.CONV_TILED), dw, "routed call against the tiled kernel",
                 axes=("co", "ci", "tap"))
     with pytest.raises(RuntimeError, match="wgrad_march"):
-        S.conv3d_wgrad(far, dy_cl, 2 * c_src, cout, 27, 1, L.CONV_MARCH)
+        S.conv3d_wgrad(far, dy_cl, 2 * c_src, cout, 27, 1, lib.CONV_MARCH)
+
+
+# ---------------------------------------------------------------------------------------------------
+# the plan of one sample, and the source distances of the plan of sixteen
+# ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", ONE.CASES, ids=_ids)
+def test_batch_1_forward_and_statistics(S, case):
+    L.forward_case(S, ONE, case)
+
+
+@pytest.mark.parametrize("case", ONE.DGRAD_CASES, ids=_ids)
+def test_batch_1_data_gradient(S, case):
+    L.dgrad_case(S, ONE, case)
+
+
+@pytest.mark.parametrize("case", ONE.CASES, ids=_ids)
+def test_batch_1_weight_gradient(S, case):
+    L.wgrad_case(S, ONE, case)
+
+
+@pytest.mark.parametrize("case", [(n, dt) for n in PAIRED for dt in DTYPES], ids=_ids)
+def test_batch_16_forward_of_the_two_source_layers(S, case):
+    """Samples 0, 8 and 15 of the 16 x 128^3 forward: the first, one in the middle and the last (every sample of dc5's second
+    source lies 2^31 bytes or more past the first source's base; its last ends at 2^32)."""
+    L.forward_samples_case(S, BIG, case[0], case[1], (0, 8, 15))

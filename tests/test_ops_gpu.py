@@ -272,7 +272,7 @@ def _block_ref(raw, w_se, w_se2, w_side, b_side, slope=0.01):
 
 
 @pytest.mark.parametrize("dtype", DT)
-@pytest.mark.parametrize("c,gates", [(8, 1), (16, 1), (32, 2), (64, 2)])
+@pytest.mark.parametrize("c,gates", [(8, 1), (16, 1), (32, 2), (64, 2), (128, 2)])     # (128, 2): the width-2 network's
 def test_gate_epilogue_forward_backward(S, dtype, c, gates):
     n, d, h, w = 2, 6, 10, 12
     raw = rnd(dtype, gen(n, c, d, h, w, seed=12) * 2 + 0.3).requires_grad_(True)

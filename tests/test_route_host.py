@@ -23,7 +23,7 @@ def plan(L, batch, inch, d, width, dtype, impl=0):
 
 
 DESCS = [(4, 2, 128, 1, dt) for dt in ("bf16", "fp16", "fp32")] + [(1, 2, 64, 1, dt) for dt in ("bf16", "fp16", "fp32")] + [
-    (2, 2, 32, 1, "bf16"), (1, 2, 160, 2, "bf16"), (1, 3, 64, 1, "bf16"), (4, 3, 128, 1, "fp16")]
+    (2, 2, 32, 1, "bf16"), (1, 2, 160, 2, "bf16"), (2, 2, 160, 2, "bf16"), (2, 2, 160, 2, "fp16"), (1, 3, 64, 1, "bf16"), (4, 3, 128, 1, "fp16")]
 GATED = ["ec1", "ec2", "ec3", "ec4", "ec5", "ec6", "ec7", "ec8", "ec9", "ec10", "ec11", "ec12", "dc1", "dc2", "dc3", "dc4", "dc5", "dc6"]
 CAT = ["ec33", "ec63", "ec93", "ec123", "dc22", "dc42"]
 
@@ -152,3 +152,36 @@ def test_documented_routing_that_depends_on_width_and_batch(L):
     big = {c["name"]: c for c in plan(L, 16, 2, 128, 2, "bf16")[0]}
     assert abs(big["dc3"]["src_dist"]) >= 1 << 32 and big["dc3"]["wgrad"] == "Tiled"
     assert {c["name"]: c for c in plan(L, 4, 2, 128, 2, "bf16")[0]}["dc3"]["wgrad"] == "March"    # (the same layer within reach)
+
+
+@pytest.mark.parametrize("dtype", ["bf16", "fp16"])
+def test_documented_routing_of_config4(L, dtype):
+    """2 x 2 x 160^3, width 2, 16-bit storage (BASELINE.json configs[4]): the routing table of DESIGN.md's "... at the second
+    configuration" subsection, which tests/test_conv_layers_config4_gpu.py runs pass by pass."""
+    p, _ = plan(L, 2, 2, 160, 2, dtype)
+    by = {c["name"]: c for c in p}
+    passes = lambda n: (by[n]["fwd"], by[n]["dgrad"], by[n]["wgrad"])
+    shape = lambda n: (by[n]["dims"][1], by[n]["src_c"], by[n]["cout"], by[n]["dilation"])
+    assert all(c["dims"] == (2,) + (160 >> c["level"],) * 3 for c in p)
+    # the 16- and 32-channel layers at full resolution stream, as ec1 / ec2 do at width 1
+    assert passes("ec1") == ("Stream", None, "Stream") and passes("ec2") == ("Stream", "Stream", "Stream")
+    # 160^3: 32 -> 64 (dilation 2) and 64 -> 32 march in all three directions; dc5's 128 input channels keep its forward tiled
+    assert shape("ec3") == (160, [32], 64, 2) and passes("ec3") == ("March", "March", "March")
+    assert shape("dc6") == (160, [64], 32, 1) and passes("dc6") == ("March", "March", "March")
+    assert shape("dc5") == (160, [64, 64], 64, 1) and passes("dc5") == ("Tiled", "March", "March")
+    # 80^3
+    for n in ("ec4", "ec5"):
+        assert shape(n)[:3] == (80, [64], 64) and passes(n) == ("March", "March", "March"), (n, passes(n))
+    assert shape("ec6") == (80, [64], 128, 2) and passes("ec6") == ("March", "Tiled", "March")
+    assert shape("dc4") == (80, [128], 64, 1) and passes("dc4") == ("Tiled", "March", "March")
+    assert shape("dc3") == (80, [128, 128], 128, 1) and passes("dc3") == ("Tiled", "Tiled", "March")
+    # 40^3: 128 -> 128 with dilation 2, and dc1's 256 input channels: tiled but for the marching weight gradient
+    for n in ("ec8", "ec9"):
+        assert shape(n) == (40, [128], 128, 2) and passes(n) == ("Tiled", "Tiled", "March"), (n, passes(n))
+    assert shape("dc1") == (40, [128, 128], 128, 1) and passes("dc1") == ("Tiled", "Tiled", "March")
+    # ec63, 1x1x1 256 -> 128 at 80^3: a form wgrad_1x1.hip does not instantiate
+    assert (by["ec63"]["cin"], by["ec63"]["cout"], by["ec63"]["taps"]) == (256, 128, 1) and passes("ec63") == ("Tiled", "Tiled", "Tiled")
+    # the epilogue kernels' partial records per sample: the cap of 256 on levels 0 - 2, the floor branch (8000 // 128) on level 3
+    lib = L.load()
+    assert [lib.seunet_epilogue_slots(L.Dims(2, 160 >> l, 160 >> l, 160 >> l)) for l in range(4)] == [256, 256, 256, 62]
+    assert {c["cout"] for c in p} == {16, 32, 64, 128}
