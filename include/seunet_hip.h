@@ -350,6 +350,20 @@ int seunet_break_weight(const unsigned char* label, const unsigned char* pred, c
                         void* w_br, unsigned char* br_skel, int* status_dev, void* workspace, size_t workspace_bytes,
                         seunet_stream_t s);
 
+/* ---- 3-D skeletonisation ------------------------------------------------------------------------
+ * seunet_skeletonize: volume (n0, n1, n2) bytes, C-contiguous on the device, non-zero = foreground; out: n0*n1*n2 bytes, 1 on
+ * the skeleton and 0 elsewhere (out may not alias volume; the input is not modified).  The reference takes this volume from
+ * skimage.morphology.skeletonize_3d on the CPU (ske_and_parse.py:83, weight_br.py:128, prediction.py:127).  Here: Lee, Kashyap
+ * and Chu (1994) with the border order and raster-order re-check of the common implementations; equality with skimage has not
+ * been checked.  The definition is DESIGN.md 3d and tests/skeleton_oracle.py, which the result equals bit for bit; it is
+ * deterministic.  Any extents >= 1 with at most 2^31-1 voxels and fewer than 2^32 64-voxel words after padding (anything else:
+ * error).  passes_dev (device int, optional): the number of passes run, the last one, which deletes nothing, included.
+ * The call synchronises the stream once per pass.  workspace: seunet_skeleton_workspace_bytes(n0, n1, n2), caller-owned
+ * (0 and a message in seunet_last_error for extents outside the range above). */
+size_t seunet_skeleton_workspace_bytes(int n0, int n1, int n2);
+int seunet_skeletonize(const unsigned char* volume, int n0, int n1, int n2, unsigned char* out, int* passes_dev, void* workspace,
+                       size_t workspace_bytes, seunet_stream_t s);
+
 /* ---- CT preprocessing: preprocessing.py:26-130 with util.py:95-152 -----------------------------
  * CT volumes are int16, C-contiguous (h, w, z) on the device (the reference's orientation after its transposes), fewer than 2^31
  * voxels; masks are bytes, non-zero = 1.

@@ -361,6 +361,16 @@ int seunet_break_weight(const unsigned char* label, const unsigned char* pred, c
   return launch_break_weight(label, pred, skeleton, n0, n1, n2, w_br, br_skel, status_dev, workspace, workspace_bytes, S(s));
 }
 
+size_t seunet_skeleton_workspace_bytes(int n0, int n1, int n2) {
+  const size_t bytes = skeleton_workspace_bytes(n0, n1, n2);
+  if (bytes == 0) fail("skeleton_workspace_bytes: bad dimensions (%d, %d, %d): extents >= 1, at most 2^31-1 voxels", n0, n1, n2);
+  return bytes;
+}
+int seunet_skeletonize(const unsigned char* volume, int n0, int n1, int n2, unsigned char* out, int* passes_dev, void* workspace,
+                       size_t workspace_bytes, seunet_stream_t s) {
+  return launch_skeletonize(volume, n0, n1, n2, out, passes_dev, workspace, workspace_bytes, S(s));
+}
+
 int seunet_value_counts(const short* ct, long long n, int shift, unsigned int* counts, seunet_stream_t s) {
   return launch_value_counts(ct, n, shift, counts, S(s));
 }

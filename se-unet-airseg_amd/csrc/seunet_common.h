@@ -475,6 +475,10 @@ int launch_lib_weight(const unsigned char* label, int n0, int n1, int n2, const 
 size_t break_weight_workspace_bytes(int n0, int n1, int n2);
 int launch_break_weight(const unsigned char* label, const unsigned char* pred, const unsigned char* skel, int n0, int n1, int n2,
                         void* w_br, unsigned char* br_skel, int* status_dev, void* workspace, size_t ws_bytes, hipStream_t s);
+// 3-D thinning (skeleton.hip); workspace bytes are 0 for extents the bit layout cannot address
+size_t skeleton_workspace_bytes(int n0, int n1, int n2);
+int launch_skeletonize(const unsigned char* vol, int n0, int n1, int n2, unsigned char* out, int* passes_dev, void* workspace,
+                       size_t ws_bytes, hipStream_t s);
 // CT preprocessing (lung.hip): value counts, shift + clamp, per-slice lung field, mask combination, bounding box, crop
 int launch_value_counts(const short* ct, long long n, int shift, unsigned int* counts, hipStream_t s);
 int launch_shift_clamp(const short* ct, long long n, int shift, int clamp, int clamp_le, int clamp_to, short* out, hipStream_t s);

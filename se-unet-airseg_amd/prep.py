@@ -14,6 +14,7 @@ import torch
 from . import _lib
 
 _BLOCK_WORDS = 8          # 512 voxels per prefix-sum block
+SKELETON_ROUND_LAUNCHES = 32   # kRoundLaunches of csrc/skeleton.hip (scripts/bench_skeleton.py counts launches with it)
 
 
 def _vol(t, name):
@@ -62,6 +63,43 @@ def distance_transform_edt(volume: torch.Tensor, return_distances: bool = True, 
         _status(status, "distance_transform_edt: the volume has no zero voxel (the distance is undefined)")
     out = tuple(t for t in (sq, dist, ind) if t is not None)
     return out[0] if len(out) == 1 else out
+
+
+def skeletonize_3d(volume, return_passes: bool = False):
+    """The centreline volume the reference takes from ``skimage.morphology.skeletonize_3d(label)`` (ske_and_parse.py:83,
+    weight_br.py:128, prediction.py:127), thinned on the GPU (csrc/skeleton.hip): Lee, Kashyap and Chu (1994) with the border
+    order and raster-order re-check of the common implementations; equality with skimage has not been checked.  The
+    definition is DESIGN.md section 3d; the result equals tests/skeleton_oracle.py bit for bit and is deterministic.
+
+    CUDA uint8 / bool tensor in -> uint8 CUDA tensor (0/1) on the same device; numpy array in (any dtype, non-zero =
+    foreground) -> uint8 numpy out, like ``postprocess.largest_component``.  The input is not modified; an empty volume gives
+    zeros.  The result is the ``skeleton`` argument of ``break_weight``, ``hard_mining_candidates``, the ``from_case``
+    constructors and ``evaluation_case``.  ``return_passes``: also return the number of thinning passes run (the last one,
+    which deletes nothing, included)."""
+    as_numpy = isinstance(volume, np.ndarray)
+    if as_numpy:
+        if volume.ndim != 3:
+            raise ValueError(f"seunet prep: `volume` must be (n0, n1, n2), got {tuple(volume.shape)}")
+        if not torch.cuda.is_available():
+            raise RuntimeError("seunet prep: `volume` needs a GPU (there is no CPU path)")
+        vol = torch.from_numpy(np.ascontiguousarray(volume != 0).view(np.uint8)).cuda()
+    else:
+        vol = _vol(volume, "volume")
+    n0, n1, n2 = (int(v) for v in vol.shape)
+    dev = vol.device
+    out = torch.zeros((n0, n1, n2), dtype=torch.uint8, device=dev)
+    passes = torch.zeros(1, dtype=torch.int32, device=dev)
+    if vol.numel():
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            ws_bytes = int(lib.seunet_skeleton_workspace_bytes(n0, n1, n2))
+            if ws_bytes == 0:
+                raise ValueError(f"seunet prep: skeletonize_3d: {_lib.last_error()}")
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            _lib.check(lib.seunet_skeletonize(vol.data_ptr(), n0, n1, n2, out.data_ptr(), passes.data_ptr(), ws.data_ptr(), ws_bytes,
+                                              _lib.stream_ptr()), "skeletonize")
+    skel = out.cpu().numpy() if as_numpy else out
+    return (skel, int(passes.item())) if return_passes else skel
 
 
 class _Axis:

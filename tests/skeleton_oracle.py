@@ -1,0 +1,209 @@
+"""Plain numpy/Python statement of the project's 3-D thinning and the volumes it is tested on.
+
+Lee, Kashyap and Chu (1994) with the border order and raster-order re-check of the common implementations; equality with
+skimage has not been checked.  Everything here is written the slow, obvious way and shares nothing with the bit tricks of
+csrc/skeleton.hip: the Euler test counts the cells of the centre cube, the connectivity test is a graph search.
+
+Definition.  The volume is padded with one layer of background.  One pass is six sub-iterations over the border directions
+4, 3, 2, 1, 5, 6 (direction d = the neighbour DIRECTIONS[d] is background); passes repeat until one deletes nothing.  In a
+sub-iteration every voxel is first judged on the image as it stands: it is a candidate when it is foreground (a), its
+d-neighbour is background (b), it does not have exactly one foreground 26-neighbour (c), removing it keeps the Euler
+characteristic (d) and its foreground 26-neighbours form exactly one 26-connected component (e).  Then the candidates are
+visited in raster order, and one is deleted iff (e) still holds on the image with the deletions made so far."""
+import hashlib
+import itertools
+
+import numpy as np
+
+DIRECTIONS = {1: (0, 0, -1), 2: (0, 0, 1), 3: (0, 1, 0), 4: (0, -1, 0), 5: (1, 0, 0), 6: (-1, 0, 0)}
+ORDER = (4, 3, 2, 1, 5, 6)
+
+_CELLS = [c for c in itertools.product(range(3), repeat=3) if c != (1, 1, 1)]
+_ADJ = {c: [o for o in _CELLS if o != c and max(abs(c[0] - o[0]), abs(c[1] - o[1]), abs(c[2] - o[2])) <= 1] for c in _CELLS}
+
+
+def euler_delta(nb) -> int:
+    """dV - dE + dF - 1 for the centre of the 3x3x3 block `nb`: the cells of the closed centre cube that no other set cube
+    touches.  The centre cube spans [1, 2]^3; cube index x along an axis covers [x, x + 1]."""
+    dv = 0
+    for a, b, c in itertools.product((0, 1), repeat=3):                  # vertex (1+a, 1+b, 1+c): cubes a..a+1, b..b+1, c..c+1
+        others = [(a + i, b + j, c + k) for i, j, k in itertools.product((0, 1), repeat=3)]
+        dv += all(not nb[o] for o in others if o != (1, 1, 1))
+    de = 0
+    for axis in range(3):                                                # edge along `axis` at (1+b, 1+c) of the other two axes
+        for b, c in itertools.product((0, 1), repeat=2):
+            others = []
+            for j, k in itertools.product((0, 1), repeat=2):
+                o = [b + j, c + k]
+                o.insert(axis, 1)
+                others.append(tuple(o))
+            de += all(not nb[o] for o in others if o != (1, 1, 1))
+    df = 0
+    for axis in range(3):
+        for side in (0, 2):
+            o = [1, 1, 1]
+            o[axis] = side
+            df += not nb[tuple(o)]
+    return dv - de + df - 1
+
+
+def neighbour_components(nb) -> int:
+    """26-connected components of the foreground among the 26 neighbours (centre excluded)."""
+    todo = {c for c in _CELLS if nb[c]}
+    n = 0
+    while todo:
+        n += 1
+        stack = [todo.pop()]
+        while stack:
+            c = stack.pop()
+            for o in _ADJ[c]:
+                if o in todo:
+                    todo.remove(o)
+                    stack.append(o)
+    return n
+
+
+def skeletonize(volume, recheck: str = "raster"):
+    """-> (skeleton uint8 0/1, number of passes run, the last one, which deletes nothing, included).
+    `recheck`: "raster" is the definition; "none" and "reverse" are wrong on purpose (what the tests must tell apart)."""
+    vol = np.asarray(volume)
+    if vol.ndim != 3:
+        raise ValueError("skeletonize expects a 3-D volume")
+    img = np.zeros(tuple(s + 2 for s in vol.shape), dtype=bool)
+    img[1:-1, 1:-1, 1:-1] = vol != 0
+    passes = 0
+    while True:
+        passes += 1
+        deleted = 0
+        for d in ORDER:
+            di, dj, dk = DIRECTIONS[d]
+            shifted = np.zeros_like(img)
+            shifted[1:-1, 1:-1, 1:-1] = img[1 + di:img.shape[0] - 1 + di, 1 + dj:img.shape[1] - 1 + dj, 1 + dk:img.shape[2] - 1 + dk]
+            candidates = []
+            for i, j, k in np.argwhere(img & ~shifted):                  # (a), (b); argwhere is raster order
+                nb = img[i - 1:i + 2, j - 1:j + 2, k - 1:k + 2]
+                if int(nb.sum()) - 1 == 1:                               # (c)
+                    continue
+                if euler_delta(nb) != 0:                                 # (d)
+                    continue
+                if neighbour_components(nb) != 1:                        # (e)
+                    continue
+                candidates.append((i, j, k))
+            if recheck == "reverse":
+                candidates.reverse()
+            for i, j, k in candidates:
+                if recheck == "none" or neighbour_components(img[i - 1:i + 2, j - 1:j + 2, k - 1:k + 2]) == 1:
+                    img[i, j, k] = False
+                    deleted += 1
+        if deleted == 0:
+            break
+    return img[1:-1, 1:-1, 1:-1].astype(np.uint8), passes
+
+
+def digest(skel) -> str:
+    return hashlib.sha256(np.packbits(np.asarray(skel).astype(np.uint8).ravel()).tobytes()).hexdigest()[:16]
+
+
+def topology(volume):
+    """(26-connected foreground components, 6-connected background components, Euler characteristic of the union of closed
+    unit cubes) of the zero-padded volume."""
+    from scipy import ndimage
+    v = np.pad(np.asarray(volume) != 0, 1)
+    fg = ndimage.label(v, structure=np.ones((3, 3, 3)))[1]
+    bg = ndimage.label(~v)[1]
+    c = np.pad(v, 1)                                                     # cells between cubes: any incident cube set
+    s = c.shape
+    def any_of(offsets):
+        out = np.zeros((s[0] - 1, s[1] - 1, s[2] - 1), dtype=bool)
+        for a, b, e in offsets:
+            out |= c[a:s[0] - 1 + a, b:s[1] - 1 + b, e:s[2] - 1 + e]
+        return out
+    verts = any_of(itertools.product((0, 1), repeat=3)).sum()
+    edges = sum(any_of([tuple(np.insert(np.array(o), ax, 1)) for o in itertools.product((0, 1), repeat=2)]).sum() for ax in range(3))
+    faces = 0
+    for ax in range(3):
+        offs = []
+        for side in (0, 1):
+            o = [1, 1, 1]
+            o[ax] = side
+            offs.append(tuple(o))
+        faces += any_of(offs).sum()
+    return int(fg), int(bg), int(verts) - int(edges) + int(faces) - int(v.sum())
+
+
+def stamp(v, a, b, r2):
+    """Integer line of balls: n = max|b - a|; for t = 0..n, p = a + ((b - a) * t) // n; set every voxel within r2 of p."""
+    n = max(abs(b[i] - a[i]) for i in range(3))
+    r = int(np.sqrt(r2)) + 1
+    for t in range(n + 1):
+        p = [a[i] + ((b[i] - a[i]) * t) // n for i in range(3)]
+        for off in itertools.product(range(-r, r + 1), repeat=3):
+            if off[0] ** 2 + off[1] ** 2 + off[2] ** 2 > r2:
+                continue
+            q = [p[i] + off[i] for i in range(3)]
+            if all(0 <= q[i] < v.shape[i] for i in range(3)):
+                v[q[0], q[1], q[2]] = 1
+
+
+TREE_STAMPS = (((10, 12, 4), (10, 12, 60), 18), ((10, 12, 60), (5, 6, 96), 7), ((10, 12, 60), (15, 19, 100), 7),
+               ((5, 6, 96), (3, 3, 130), 3), ((5, 6, 96), (8, 10, 129), 3), ((15, 19, 100), (17, 21, 131), 3))
+
+
+def make_case(name):
+    if name == "tree":
+        v = np.zeros((20, 24, 134), dtype=np.uint8)
+        for a, b, r2 in TREE_STAMPS:
+            stamp(v, a, b, r2)
+        return v
+    if name == "ring":
+        v = np.zeros((10, 26, 26), dtype=np.uint8)
+        v[2:8, 3:23, 3:23] = 1
+        v[2:8, 9:17, 9:17] = 0
+        return v
+    if name == "shell":
+        i, j, k = np.indices((17, 17, 17))
+        r2 = (i - 8) ** 2 + (j - 8) ** 2 + (k - 8) ** 2
+        return ((r2 >= 20) & (r2 <= 56)).astype(np.uint8)
+    if name == "noise":
+        return (np.random.default_rng(20261017).random((12, 13, 14)) < 0.55).astype(np.uint8)
+    if name == "box":
+        return np.ones((6, 7, 9), dtype=np.uint8)
+    if name == "two":
+        v = np.zeros((10, 10, 20), dtype=np.uint8)
+        v[1:5, 1:5, 1:9] = 1
+        v[6:9, 5:9, 11:19] = 1
+        return v
+    if name == "empty":
+        return np.zeros((3, 4, 5), dtype=np.uint8)
+    if name == "line":
+        v = np.zeros((1, 1, 70), dtype=np.uint8)
+        v[0, 0, 3:69] = 1
+        return v
+    raise KeyError(name)
+
+
+# case -> (input voxels, skeleton voxels, digest, topology triple of input and output)
+EXPECTED = {
+    "tree": (6327, 209, "5642a0d0d418461c", (1, 1, 1)),
+    "ring": (2016, 51, "a3967366f7524407", (1, 1, 0)),
+    "shell": (1426, 372, "4cbdcfd499af76e3", (1, 2, 2)),
+    "noise": (1214, 405, "1c33d14433f8f5ec", (1, 30, -68)),
+    "box": (378, 3, "c25d657d69118383", (1, 1, 1)),
+    "two": (224, 7, "1c3ac8ef4bcd7f4e", (2, 1, 2)),
+    "empty": (0, 0, "af5570f5a1810b7a", (0, 1, 0)),
+    "line": (66, 66, "a7020a8122bea3c4", (1, 1, 1)),
+}
+CASES = tuple(EXPECTED)
+
+_cache = {}
+
+
+def solved(name):
+    """(input, skeleton, passes) of a case, computed once per process; callers must not modify the arrays."""
+    if name not in _cache:
+        v = make_case(name)
+        sk, passes = skeletonize(v)
+        v.setflags(write=False)
+        sk.setflags(write=False)
+        _cache[name] = (v, sk, passes)
+    return _cache[name]
