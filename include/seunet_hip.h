@@ -364,6 +364,41 @@ size_t seunet_skeleton_workspace_bytes(int n0, int n1, int n2);
 int seunet_skeletonize(const unsigned char* volume, int n0, int n1, int n2, unsigned char* out, int* passes_dev, void* workspace,
                        size_t workspace_bytes, seunet_stream_t s);
 
+/* ---- airway tree parsing: the ATM'22 branch labelling --------------------------------------------
+ * atm22_skel_parse.py:83-135 as driven by tree_parsing.py:114-159.  Volumes are C-contiguous (n0, n1, n2) on the device, axis 2
+ * contiguous; masks are bytes with non-zero = 1; label volumes are int32.  Fewer than 2^31 voxels; seunet_parse_assign also has
+ * the EDT's limit of 32767 per axis (anything else: error).  Integer work throughout: every output is bitwise the reference's
+ * and does not depend on the order in which the device executes anything.  workspaces: the *_workspace_bytes of the same
+ * extents, caller-owned; nothing is allocated and no call synchronises the stream (num_dev / status_dev are device ints the
+ * caller reads when it needs them on the host).
+ *
+ * seunet_skeleton_branches: skeleton_parsing (:83-101).  A skeleton voxel whose 3x3x3 sum with mode 'reflect' (index -1 -> 0,
+ *   n -> n - 1: a voxel on a face counts itself and its in-face neighbours again) exceeds 3 is a branch point and is removed;
+ *   the rest is labelled with 26-connectivity; components with fewer than min_voxels voxels (the reference: 5) are removed; the
+ *   survivors are numbered 1..num in raster order of their first voxel, as the reference's second ndimage.label numbers them.
+ *   cd: int32 numbers (0 elsewhere); skeleton_parse (optional): bytes, cd != 0; num_dev (device int, optional): num.
+ * seunet_parse_assign: tree_parsing_func (:103-108): parsing[v] = label[v] != 0 ? cd[f(v)] : 0 with f(v) the feature transform
+ *   of seunet_edt (bitwise scipy's, ties included) for the sites skeleton_parse != 0.  The (3, n0, n1, n2) index volume is
+ *   never stored: the last EDT pass gathers cd.  An empty skeleton_parse is an error: status_dev (device int, optional) is 1
+ *   then, 0 otherwise, and parsing is all zeros.
+ * seunet_label_stats: the statistics loc_trachea and adjacent_map (:110-135) take from a label volume with values 0..num:
+ *   counts = device u32[num + 1] voxels per value; adjacency_bits = (num + 1) rows of ceil((num + 1) / 64) u64 words, bit b of
+ *   word w of row a set iff values a != 64 w + b, both > 0, meet across a face (symmetric).  Both are zeroed here.  status_dev
+ *   (device int): 1 if a value outside 0..num was met (it is ignored), 0 otherwise.  num <= seunet_label_stats_max_num() = 4095
+ *   (the default nbins of the metric sums - 1): a larger num is an error.
+ * seunet_relabel: out[i] = lut[parsing[i]] over n elements, lut = device int32[nlut]; a value outside 0..nlut-1 gives 0.  out may
+ *   alias parsing. */
+size_t seunet_skeleton_branches_workspace_bytes(int n0, int n1, int n2);
+int seunet_skeleton_branches(const unsigned char* skeleton, int n0, int n1, int n2, int min_voxels, int* cd, unsigned char* skeleton_parse,
+                             int* num_dev, void* workspace, size_t workspace_bytes, seunet_stream_t s);
+size_t seunet_parse_assign_workspace_bytes(int n0, int n1, int n2);
+int seunet_parse_assign(const unsigned char* skeleton_parse, const int* cd, const unsigned char* label, int n0, int n1, int n2,
+                        int* parsing, int* status_dev, void* workspace, size_t workspace_bytes, seunet_stream_t s);
+int seunet_label_stats_max_num(void);
+int seunet_label_stats(const int* parsing, int n0, int n1, int n2, int num, unsigned int* counts, unsigned long long* adjacency_bits,
+                       int* status_dev, seunet_stream_t s);
+int seunet_relabel(const int* parsing, long long n, const int* lut, int nlut, int* out, seunet_stream_t s);
+
 /* ---- CT preprocessing: preprocessing.py:26-130 with util.py:95-152 -----------------------------
  * CT volumes are int16, C-contiguous (h, w, z) on the device (the reference's orientation after its transposes), fewer than 2^31
  * voxels; masks are bytes, non-zero = 1.

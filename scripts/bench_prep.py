@@ -1,5 +1,6 @@
 """Device-event times of the stage-2/3 preparation (se-unet-airseg_amd/prep.py) on a synthetic tube-tree case, next to scipy
-on the host when it is installed (--scipy).  Usage: python scripts/bench_prep.py [--shapes 300x512x512,600x512x512] [--reps 3]"""
+on the host when it is installed (--scipy).  The parse leg times the ATM'22 tree parsing (whole and per entry point) on the same
+case; its yardstick is edt_dist_indices_ms of the same run.  Usage: python scripts/bench_prep.py [--shapes 300x512x512,600x512x512] [--reps 3]"""
 import argparse
 import json
 import os
@@ -59,6 +60,19 @@ def main():
         r["candidates_ms"] = timed(lambda: A.hard_mining_candidates(lab, skel, pred), args.reps)
         r["lib_weight_ms"] = timed(lambda: A.lib_weight(lab), args.reps)
         r["break_weight_ms"] = timed(lambda: A.break_weight(lab, pred, skel), args.reps)
+        # parse leg: the ATM'22 tree parsing, whole and per entry point; the yardstick is edt_dist_indices_ms above
+        parse, cd, num0 = A.skeleton_parsing(skel)
+        plain = A.tree_parsing_func(parse, lab, cd)
+        counts, adj = A.prep._label_stats(plain, num0)
+        lut, num, rounds = A.prep.refine_labels(counts, adj, num0)
+        r["parse_branches"], r["parse_num"], r["parse_rounds"] = num0, num, rounds
+        r["parse_tree_parsing_ms"] = timed(lambda: A.tree_parsing(lab, skel), args.reps)
+        r["parse_skeleton_parsing_ms"] = timed(lambda: A.skeleton_parsing(skel), args.reps)
+        r["parse_tree_parsing_func_ms"] = timed(lambda: A.tree_parsing_func(parse, lab, cd), args.reps)
+        r["parse_label_adjacency_ms"] = timed(lambda: A.label_adjacency(plain, num0), args.reps)
+        r["parse_relabel_ms"] = timed(lambda: A.relabel(plain, lut), args.reps)
+        t = time.perf_counter(); A.prep.refine_labels(counts, adj, num0); r["parse_refine_host_ms"] = (time.perf_counter() - t) * 1e3
+        r["parse_over_edt_indices"] = r["parse_tree_parsing_ms"] / r["edt_dist_indices_ms"]
         if args.scipy:
             try:
                 import numpy as np
@@ -72,6 +86,9 @@ def main():
                 r["scipy_edt_indices_s"] = time.perf_counter() - t
                 t = time.perf_counter(); ndimage.convolve(lh.astype(np.float32), np.ones((7, 7, 7), np.float32), mode="mirror")
                 r["scipy_box7_s"] = time.perf_counter() - t
+                sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+                import parse_oracle
+                t = time.perf_counter(); parse_oracle.tree_parsing(lh, skel.cpu().numpy()); r["parse_oracle_s"] = time.perf_counter() - t
         print(json.dumps(r), flush=True)
         del lab, skel, pred, inv
         torch.cuda.empty_cache()

@@ -10,7 +10,8 @@ from .SE_UNet import CapturedForward, CATConv, DropLayer, SE_UNet, SSEConv, SSEC
 from .optim import AdamW
 from .pipeline import (AirwayHMData3GPU, AirwayHMDataGPU, CropSegDataGPU, aug_code, crop_batch, draw_stage1_plan, draw_stage2_plan,
                        draw_stage3_plan, two_channel_volume)
-from .prep import CandidateSet, break_weight, distance_transform_edt, hard_mining_candidates, lib_weight, skeletonize_3d
+from .prep import (CandidateSet, break_weight, distance_transform_edt, hard_mining_candidates, label_adjacency, lib_weight, relabel,
+                   skeleton_parsing, skeletonize_3d, tree_parsing, tree_parsing_func)
 from .preprocess import cut_mask, get_l, large_connected_domain26, preprocess_ct, th_2t
 from .postprocess import (MetricSums, double_threshold_iteration, evaluation_case, largest_component, maximum_3d,
                           postprocess_prediction, zero_borders)
@@ -21,4 +22,4 @@ __all__ = ["SE_UNet", "SSEConv", "SSEConv2", "CATConv", "DropLayer", "get_model"
            "general_union_loss_lib", "atr_loss", "fused_logit_loss", "fused_stage_loss",
            "sliding_window_predict", "sliding_window_validate", "two_channel", "window_starts", "window_table", "AdamW", "CropSegDataGPU", "AirwayHMDataGPU", "AirwayHMData3GPU", "aug_code", "crop_batch", "draw_stage1_plan", "draw_stage2_plan", "draw_stage3_plan", "two_channel_volume", "double_threshold_iteration", "postprocess_prediction", "zero_borders", "maximum_3d", "largest_component",
            "evaluation_case", "MetricSums", "CandidateSet", "distance_transform_edt", "hard_mining_candidates", "lib_weight",
-           "break_weight", "skeletonize_3d", "preprocess_ct", "th_2t", "get_l", "large_connected_domain26", "cut_mask"]
+           "break_weight", "skeletonize_3d", "skeleton_parsing", "tree_parsing_func", "label_adjacency", "tree_parsing", "relabel", "preprocess_ct", "th_2t", "get_l", "large_connected_domain26", "cut_mask"]

@@ -129,6 +129,13 @@ PROTOTYPES = {
     "seunet_break_weight": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "seunet_skeleton_workspace_bytes": (_sz, [_i, _i, _i]),
     "seunet_skeletonize": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "seunet_skeleton_branches_workspace_bytes": (_sz, [_i, _i, _i]),
+    "seunet_skeleton_branches": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "seunet_parse_assign_workspace_bytes": (_sz, [_i, _i, _i]),
+    "seunet_parse_assign": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "seunet_label_stats_max_num": (_i, []),
+    "seunet_label_stats": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "seunet_relabel": (_i, [_vp, _ll, _vp, _i, _vp, _vp]),
     "seunet_adamw_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _i, _i, _vp]),
     "seunet_net_param_count": (_i, [C.POINTER(NetDesc)]),
     "seunet_net_param_info": (_i, [C.POINTER(NetDesc), _i, C.c_char_p, _i, _ip, _ip]),

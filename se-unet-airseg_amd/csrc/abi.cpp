@@ -371,6 +371,31 @@ int seunet_skeletonize(const unsigned char* volume, int n0, int n1, int n2, unsi
   return launch_skeletonize(volume, n0, n1, n2, out, passes_dev, workspace, workspace_bytes, S(s));
 }
 
+size_t seunet_skeleton_branches_workspace_bytes(int n0, int n1, int n2) {
+  if (n0 < 1 || n1 < 1 || n2 < 1 || (long long)n0 * n1 * n2 >= (1ll << 31)) { fail("skeleton_branches_workspace_bytes: bad dimensions"); return 0; }
+  return skeleton_branches_workspace_bytes(n0, n1, n2);
+}
+int seunet_skeleton_branches(const unsigned char* skeleton, int n0, int n1, int n2, int min_voxels, int* cd, unsigned char* skeleton_parse,
+                             int* num_dev, void* workspace, size_t workspace_bytes, seunet_stream_t s) {
+  return launch_skeleton_branches(skeleton, n0, n1, n2, min_voxels, cd, skeleton_parse, num_dev, workspace, workspace_bytes, S(s));
+}
+size_t seunet_parse_assign_workspace_bytes(int n0, int n1, int n2) {
+  if (n0 < 1 || n1 < 1 || n2 < 1) { fail("parse_assign_workspace_bytes: bad dimensions"); return 0; }
+  return parse_assign_workspace_bytes(n0, n1, n2);
+}
+int seunet_parse_assign(const unsigned char* skeleton_parse, const int* cd, const unsigned char* label, int n0, int n1, int n2,
+                        int* parsing, int* status_dev, void* workspace, size_t workspace_bytes, seunet_stream_t s) {
+  return launch_parse_assign(skeleton_parse, cd, label, n0, n1, n2, parsing, status_dev, workspace, workspace_bytes, S(s));
+}
+int seunet_label_stats_max_num(void) { return label_stats_max_num(); }
+int seunet_label_stats(const int* parsing, int n0, int n1, int n2, int num, unsigned int* counts, unsigned long long* adjacency_bits,
+                       int* status_dev, seunet_stream_t s) {
+  return launch_label_stats(parsing, n0, n1, n2, num, counts, adjacency_bits, status_dev, S(s));
+}
+int seunet_relabel(const int* parsing, long long n, const int* lut, int nlut, int* out, seunet_stream_t s) {
+  return launch_relabel(parsing, n, lut, nlut, out, S(s));
+}
+
 int seunet_value_counts(const short* ct, long long n, int shift, unsigned int* counts, seunet_stream_t s) {
   return launch_value_counts(ct, n, shift, counts, S(s));
 }

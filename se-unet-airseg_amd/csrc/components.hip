@@ -109,6 +109,10 @@ cc_count_kernel(const int* __restrict__ L, long long n, unsigned int* __restrict
   atomicAdd(&cnt[r], (unsigned int)len);
 }
 
+void launch_cc_count(const int* L, long long n, unsigned int* cnt, hipStream_t s) {
+  cc_count_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(L, n, cnt);
+}
+
 // pass 0: best = max key over roots; pass 1: second = max key over roots other than best
 __global__ void __launch_bounds__(256)
 cc_select_kernel(const int* __restrict__ L, const unsigned int* __restrict__ cnt, long long n, int pass, CcSel* sel) {

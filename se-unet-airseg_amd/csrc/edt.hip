@@ -56,12 +56,7 @@ edt_pass0_kernel(const unsigned char* __restrict__ vol, int n0, long long plane,
   }
 }
 
-struct EdtOut {            // what the last pass writes (each optional)
-  int* sqdist;
-  double* dist;
-  int* indices;            // (3, n0, n1, n2)
-  int* lin;                // linear index of the feature (internal users)
-};
+// EdtOut (what the last pass writes, each part optional): seunet_common.h
 
 // pass D (1 or 2) along axis D.  in0 / in1: features along axes 0 / 1 of the previous passes (in1 for D == 2 only).
 // D == 1 writes out0 / out1 (features along axes 0 / 1); D == 2 writes the final outputs.
@@ -131,6 +126,7 @@ edt_pass_kernel(const short* __restrict__ in0, const short* __restrict__ in1, in
         if (o.dist) o.dist[v] = -1.0;
         if (o.indices) { o.indices[v] = -1; o.indices[v + (long long)n0 * n1 * n2] = -1; o.indices[v + 2ll * n0 * n1 * n2] = -1; }
         if (o.lin) o.lin[v] = -1;
+        if (o.gather_out) o.gather_out[v] = 0;
       }
       continue;
     }
@@ -153,6 +149,7 @@ edt_pass_kernel(const short* __restrict__ in0, const short* __restrict__ in1, in
       if (o.dist) o.dist[v] = sqrt((double)d1);
       if (o.indices) { o.indices[v] = j0; o.indices[v + n] = j1; o.indices[v + 2 * n] = (int)gc; }
       if (o.lin) o.lin[v] = (int)(((long long)j0 * n1 + j1) * n2 + gc);
+      if (o.gather_out) o.gather_out[v] = o.gather_mask[v] != 0 ? o.gather_src[((long long)j0 * n1 + j1) * n2 + gc] : 0;
     }
   }
 }
@@ -169,8 +166,8 @@ size_t edt_workspace_bytes(int n0, int n1, int n2) {
   return align_up(n * 2, 256) * 4 + align_up(n * 4, 256);     // f0, pass-1 features (2), stack positions; stack offsets
 }
 
-static int run_edt(const unsigned char* vol, bool invert, int n0, int n1, int n2, EdtOut o, int* status_dev, void* workspace,
-                   size_t ws_bytes, hipStream_t s) {
+int run_edt(const unsigned char* vol, bool invert, int n0, int n1, int n2, EdtOut o, int* status_dev, void* workspace, size_t ws_bytes,
+            hipStream_t s) {
   SEUNET_CHECK(vol && workspace, "edt: null argument");
   if (edt_check(n0, n1, n2, "edt")) return 1;
   SEUNET_CHECK(ws_bytes >= edt_workspace_bytes(n0, n1, n2), "edt: workspace too small");
@@ -194,7 +191,7 @@ static int run_edt(const unsigned char* vol, bool invert, int n0, int n1, int n2
 
 int launch_edt(const unsigned char* vol, int n0, int n1, int n2, int* sqdist, double* dist, int* indices, int* status_dev,
                void* workspace, size_t ws_bytes, hipStream_t s) {
-  return run_edt(vol, false, n0, n1, n2, EdtOut{sqdist, dist, indices, nullptr}, status_dev, workspace, ws_bytes, s);
+  return run_edt(vol, false, n0, n1, n2, EdtOut{sqdist, dist, indices, nullptr, nullptr, nullptr, nullptr}, status_dev, workspace, ws_bytes, s);
 }
 
 // ---- bit-packed candidate masks ---------------------------------------------------------------------------------------
@@ -519,7 +516,7 @@ int launch_break_weight(const unsigned char* label, const unsigned char* pred, c
   SEUNET_HIP(hipMemsetAsync(flag, 0, (size_t)n, s));
   SEUNET_HIP(hipMemsetAsync(maxf, 0, sizeof(u64), s));
   fnskel_kernel<<<blocks, 256, 0, s>>>(label, pred, skel, n, fn);
-  if (run_edt(skel, true, n0, n1, n2, EdtOut{nullptr, nullptr, nullptr, lin}, status_dev, ws, e_b, s)) return 1;
+  if (run_edt(skel, true, n0, n1, n2, EdtOut{nullptr, nullptr, nullptr, lin, nullptr, nullptr, nullptr}, status_dev, ws, e_b, s)) return 1;
   br_maxf_kernel<<<blocks, 256, 0, s>>>(lin, fn, label, skel, n0, n1, n2, maxf);
   cc_label26(fn, n0, n1, n2, L, s);
   br_endpoint_kernel<<<blocks, 256, 0, s>>>(L, skel, n0, n1, n2, flag);

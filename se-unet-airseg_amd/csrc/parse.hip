@@ -1,0 +1,261 @@
+// Airway tree parsing on the device: the ATM'22 branch labelling behind the BD metric.
+//
+// Reference (CPU, numpy / scipy.ndimage):
+//   atm22_skel_parse.py:83-101   skeleton_parsing: 3x3x3 sum of the skeleton (ndimage.convolve, mode 'reflect') * skeleton; voxels
+//                                with a sum above 3 (self + more than two neighbours) are branch points and removed; ndimage.label
+//                                with the full 3x3x3 structure; components under 5 voxels removed; labelled AGAIN
+//   atm22_skel_parse.py:103-108  tree_parsing_func: feature transform of EDT(1 - skeleton_parse); cd[inds] * label
+//   atm22_skel_parse.py:110-135  loc_trachea (voxel counts per label), adjacent_map (6-adjacency between labels)
+//   tree_parsing.py:148-159      the refinement loop: every step replaces one label value by another, so it runs on the host on
+//                                the counts and the adjacency of the first volume, and one look-up pass applies it (prep.py)
+// scipy numbers components in raster order of their first voxel, and the union-find of components.hip labels a component with
+// its minimum linear index, so scipy's number = rank of the root among the roots.  Removing whole components leaves the others as
+// they are: the second labelling is the rank among the roots that survive.  Ranks come from a prefix sum over the volume (block
+// counts, one scan, in-block ballots): no atomic decides an order, the result is deterministic.
+// Integer / index work: results are bit-identical to the reference (tests/test_parse_gpu.py against tests/golden/parse_known.npz).
+#include "seunet_common.h"
+#include <algorithm>
+
+namespace seunet {
+
+typedef unsigned long long u64;
+
+// ---- skeleton_parsing ---------------------------------------------------------------------------------------------------
+
+// keep[i] = skeleton voxel whose 3x3x3 sum (centre included) is at most 3.  'reflect' at radius 1 repeats the edge voxel
+// (index -1 -> 0, n -> n - 1): a voxel on a face counts itself and its in-face neighbours twice.
+__global__ void __launch_bounds__(256)
+branch_point_kernel(const unsigned char* __restrict__ skel, int n0, int n1, int n2, unsigned char* __restrict__ keep) {
+  const long long n = (long long)n0 * n1 * n2;
+  const long long i = blockIdx.x * 256ll + threadIdx.x;
+  if (i >= n) return;
+  if (skel[i] == 0) { keep[i] = 0; return; }
+  const int i2 = (int)(i % n2);
+  const long long r = i / n2;
+  const int i1 = (int)(r % n1), i0 = (int)(r / n1);
+  int cnt = 0;
+  for (int a = -1; a <= 1; ++a)
+    for (int b = -1; b <= 1; ++b) {
+      const int x0 = std::min(std::max(i0 + a, 0), n0 - 1), x1 = std::min(std::max(i1 + b, 0), n1 - 1);
+      const unsigned char* row = skel + ((long long)x0 * n1 + x1) * n2;
+      for (int c = -1; c <= 1; ++c) cnt += row[std::min(std::max(i2 + c, 0), n2 - 1)] != 0;
+    }
+  keep[i] = cnt <= 3 ? 1 : 0;
+}
+
+__device__ __forceinline__ bool surviving_root(const int* L, const unsigned int* cnt, long long i, long long n, int min_voxels) {
+  return i < n && L[i] == (int)i && cnt[i] >= (unsigned int)min_voxels;
+}
+
+// surviving roots per block of 256 voxels
+__global__ void __launch_bounds__(256)
+root_count_kernel(const int* __restrict__ L, const unsigned int* __restrict__ cnt, long long n, int min_voxels,
+                  unsigned int* __restrict__ block_roots) {
+  __shared__ unsigned int w[4];
+  const long long i = blockIdx.x * 256ll + threadIdx.x;
+  const u64 m = __ballot(surviving_root(L, cnt, i, n, min_voxels));
+  if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = (unsigned int)__builtin_popcountll(m);
+  __syncthreads();
+  if (threadIdx.x == 0) block_roots[blockIdx.x] = w[0] + w[1] + w[2] + w[3];
+}
+
+// exclusive prefix sum of block_roots in place, one workgroup; total -> *num
+__global__ void __launch_bounds__(1024)
+root_scan_kernel(unsigned int* __restrict__ block_roots, long long nb, int* __restrict__ num) {
+  __shared__ unsigned int part[1024];
+  const long long chunk = (nb + 1023) / 1024;
+  const long long lo = std::min<long long>(threadIdx.x * chunk, nb), hi = std::min<long long>(lo + chunk, nb);
+  unsigned int sum = 0;
+  for (long long k = lo; k < hi; ++k) sum += block_roots[k];
+  part[threadIdx.x] = sum;
+  __syncthreads();
+  for (int off = 1; off < 1024; off <<= 1) {         // inclusive scan of the 1024 chunk sums
+    const unsigned int add = threadIdx.x >= (unsigned)off ? part[threadIdx.x - off] : 0u;
+    __syncthreads();
+    part[threadIdx.x] += add;
+    __syncthreads();
+  }
+  unsigned int run = part[threadIdx.x] - sum;
+  for (long long k = lo; k < hi; ++k) {
+    const unsigned int c = block_roots[k];
+    block_roots[k] = run;
+    run += c;
+  }
+  if (threadIdx.x == 1023 && num) *num = (int)part[1023];
+}
+
+// cnt[root] := the component's number (1-based rank among the surviving roots), 0 for a removed one.  Every lane touches only
+// its own entry.
+__global__ void __launch_bounds__(256)
+root_number_kernel(const int* __restrict__ L, unsigned int* __restrict__ cnt, long long n, int min_voxels,
+                   const unsigned int* __restrict__ block_prefix) {
+  __shared__ unsigned int w[4];
+  const long long i = blockIdx.x * 256ll + threadIdx.x;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const bool root = i < n && L[i] == (int)i;
+  const bool keep = root && cnt[i] >= (unsigned int)min_voxels;
+  const u64 m = __ballot(keep);
+  if (lane == 0) w[wave] = (unsigned int)__builtin_popcountll(m);
+  __syncthreads();
+  if (!root) return;
+  unsigned int before = block_prefix[blockIdx.x];
+  for (int k = 0; k < wave; ++k) before += w[k];
+  before += (unsigned int)__builtin_popcountll(m & ((1ull << lane) - 1ull));
+  cnt[i] = keep ? before + 1u : 0u;
+}
+
+__global__ void __launch_bounds__(256)
+branch_number_kernel(const int* __restrict__ L, const unsigned int* __restrict__ number, long long n, int* __restrict__ cd,
+                     unsigned char* __restrict__ parse) {
+  const long long i = blockIdx.x * 256ll + threadIdx.x;
+  if (i >= n) return;
+  const int r = L[i];
+  const int v = r >= 0 ? (int)number[r] : 0;
+  cd[i] = v;
+  if (parse) parse[i] = v ? 1 : 0;
+}
+
+static int parse_check(int n0, int n1, int n2, const char* what) {
+  SEUNET_CHECK(n0 >= 1 && n1 >= 1 && n2 >= 1, "%s: bad extents (%d, %d, %d)", what, n0, n1, n2);
+  SEUNET_CHECK((long long)n0 * n1 * n2 < (1ll << 31), "%s: %lld voxels: fewer than 2^31 supported", what, (long long)n0 * n1 * n2);
+  return 0;
+}
+
+size_t skeleton_branches_workspace_bytes(int n0, int n1, int n2) {
+  const size_t n = (size_t)n0 * n1 * n2;
+  return align_up(n * 4, 256) * 2 + align_up(n, 256) + align_up(((n + 255) / 256) * 4, 256);   // labels, counts, kept voxels, block sums
+}
+
+int launch_skeleton_branches(const unsigned char* skel, int n0, int n1, int n2, int min_voxels, int* cd, unsigned char* skeleton_parse,
+                             int* num_dev, void* workspace, size_t ws_bytes, hipStream_t s) {
+  SEUNET_CHECK(skel && cd && workspace, "skeleton_branches: null argument");
+  if (parse_check(n0, n1, n2, "skeleton_branches")) return 1;
+  SEUNET_CHECK(min_voxels >= 0, "skeleton_branches: min_voxels %d", min_voxels);
+  SEUNET_CHECK(ws_bytes >= skeleton_branches_workspace_bytes(n0, n1, n2), "skeleton_branches: workspace too small");
+  const long long n = (long long)n0 * n1 * n2;
+  unsigned char* ws = reinterpret_cast<unsigned char*>(workspace);
+  const size_t i_b = align_up((size_t)n * 4, 256);
+  int* L = reinterpret_cast<int*>(ws);
+  unsigned int* cnt = reinterpret_cast<unsigned int*>(ws + i_b);
+  unsigned char* keep = ws + 2 * i_b;
+  unsigned int* block_roots = reinterpret_cast<unsigned int*>(ws + 2 * i_b + align_up((size_t)n, 256));
+  const unsigned blocks = (unsigned)((n + 255) / 256);
+  SEUNET_HIP(hipMemsetAsync(cnt, 0, (size_t)n * 4, s));
+  branch_point_kernel<<<blocks, 256, 0, s>>>(skel, n0, n1, n2, keep);
+  cc_label26(keep, n0, n1, n2, L, s);
+  launch_cc_count(L, n, cnt, s);
+  root_count_kernel<<<blocks, 256, 0, s>>>(L, cnt, n, min_voxels, block_roots);
+  root_scan_kernel<<<1, 1024, 0, s>>>(block_roots, (long long)blocks, num_dev);
+  root_number_kernel<<<blocks, 256, 0, s>>>(L, cnt, n, min_voxels, block_roots);
+  branch_number_kernel<<<blocks, 256, 0, s>>>(L, cnt, n, cd, skeleton_parse);
+  SEUNET_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- tree_parsing_func ----------------------------------------------------------------------------------------------------
+// The feature transform of edt.hip with the sites = the voxels of skeleton_parse; its last pass gathers cd at the nearest site
+// instead of storing the (3, n0, n1, n2) index volume.
+
+size_t parse_assign_workspace_bytes(int n0, int n1, int n2) { return edt_workspace_bytes(n0, n1, n2); }
+
+int launch_parse_assign(const unsigned char* skeleton_parse, const int* cd, const unsigned char* label, int n0, int n1, int n2,
+                        int* parsing, int* status_dev, void* workspace, size_t ws_bytes, hipStream_t s) {
+  SEUNET_CHECK(skeleton_parse && cd && label && parsing && workspace, "parse_assign: null argument");
+  EdtOut o{};
+  o.gather_src = cd;
+  o.gather_mask = label;
+  o.gather_out = parsing;
+  return run_edt(skeleton_parse, true, n0, n1, n2, o, status_dev, workspace, ws_bytes, s);
+}
+
+// ---- label statistics -------------------------------------------------------------------------------------------------------
+
+constexpr int kStatsBins = 4096;          // labels 0 .. 4095: one LDS histogram per workgroup (16 KB)
+
+__device__ __forceinline__ void adjacency_set(u64* __restrict__ bits, int words, int a, int b) {
+  u64* w = bits + (size_t)a * words + (b >> 6);
+  const u64 bit = 1ull << (b & 63);
+  if ((*w & bit) == 0) atomicOr(w, bit);          // a stale read only costs one more atomic
+}
+
+__global__ void __launch_bounds__(256)
+label_stats_kernel(const int* __restrict__ parsing, int n0, int n1, int n2, int num, unsigned int* __restrict__ counts,
+                   u64* __restrict__ bits, int words, int* __restrict__ status) {
+  __shared__ unsigned int hist[kStatsBins];
+  for (int k = threadIdx.x; k <= num; k += 256) hist[k] = 0u;
+  __syncthreads();
+  const long long plane = (long long)n1 * n2, n = (long long)n0 * plane;
+  const int lane = threadIdx.x & 63;
+  for (long long base = blockIdx.x * 256ll; base < n; base += (long long)gridDim.x * 256) {
+    const long long i = base + threadIdx.x;
+    int a = -1;
+    if (i < n) {
+      a = parsing[i];
+      if (a < 0 || a > num) { *status = 1; a = -1; }
+    }
+    // one LDS atomic per run of equal labels inside a wave (components.hip, cc_count_kernel)
+    const int prev = dpp_settle(__shfl_up(a, 1, 64));
+    const bool lead = a >= 0 && (lane == 0 || prev != a);
+    const u64 leaders = __ballot(lead), in = __ballot(a >= 0);
+    if (lead) {
+      const u64 after = (lane == 63) ? 0ull : ((leaders | ~in) >> (lane + 1));
+      const int len = after ? __builtin_ctzll(after) + 1 : 64 - lane;
+      atomicAdd(&hist[a], (unsigned int)len);
+    }
+    if (a > 0) {
+      const int i2 = (int)(i % n2);
+      const long long r = i / n2;
+      const int i1 = (int)(r % n1), i0 = (int)(r / n1);
+      int nb[3] = {0, 0, 0};
+      if (i2 + 1 < n2) nb[0] = parsing[i + 1];
+      if (i1 + 1 < n1) nb[1] = parsing[i + n2];
+      if (i0 + 1 < n0) nb[2] = parsing[i + plane];
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        const int b = nb[q];
+        if (b > 0 && b <= num && b != a) { adjacency_set(bits, words, a, b); adjacency_set(bits, words, b, a); }
+      }
+    }
+  }
+  __syncthreads();
+  for (int k = threadIdx.x; k <= num; k += 256)
+    if (hist[k]) atomicAdd(&counts[k], hist[k]);
+}
+
+int label_stats_max_num() { return kStatsBins - 1; }
+
+int launch_label_stats(const int* parsing, int n0, int n1, int n2, int num, unsigned int* counts, u64* adjacency_bits, int* status_dev,
+                       hipStream_t s) {
+  SEUNET_CHECK(parsing && counts && adjacency_bits && status_dev, "label_stats: null argument");
+  if (parse_check(n0, n1, n2, "label_stats")) return 1;
+  SEUNET_CHECK(num >= 0 && num <= label_stats_max_num(), "label_stats: num %d: labels 0 .. %d are supported", num, label_stats_max_num());
+  const long long n = (long long)n0 * n1 * n2;
+  const int words = (num + 1 + 63) / 64;
+  SEUNET_HIP(hipMemsetAsync(counts, 0, (size_t)(num + 1) * 4, s));
+  SEUNET_HIP(hipMemsetAsync(adjacency_bits, 0, (size_t)(num + 1) * words * 8, s));
+  SEUNET_HIP(hipMemsetAsync(status_dev, 0, sizeof(int), s));
+  const unsigned blocks = (unsigned)std::min<long long>((n + 255) / 256, 2048);
+  label_stats_kernel<<<blocks, 256, 0, s>>>(parsing, n0, n1, n2, num, counts, adjacency_bits, words, status_dev);
+  SEUNET_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- relabel ------------------------------------------------------------------------------------------------------------------
+
+__global__ void __launch_bounds__(256)
+relabel_kernel(const int* parsing, long long n, const int* __restrict__ lut, int nlut, int* out) {
+  const long long i = blockIdx.x * 256ll + threadIdx.x;
+  if (i >= n) return;
+  const int v = parsing[i];
+  out[i] = (v >= 0 && v < nlut) ? lut[v] : 0;
+}
+
+int launch_relabel(const int* parsing, long long n, const int* lut, int nlut, int* out, hipStream_t s) {
+  SEUNET_CHECK(parsing && lut && out && n >= 1 && nlut >= 1, "relabel: bad argument");
+  SEUNET_CHECK(n < (1ll << 31) * 256, "relabel: %lld elements", n);
+  relabel_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(parsing, n, lut, nlut, out);
+  SEUNET_LAUNCH_CHECK();
+  return 0;
+}
+
+}  // namespace seunet

@@ -459,6 +459,7 @@ size_t cc_workspace_bytes(int H, int W, int Z);
 void cc_label26(const unsigned char* vol, int H, int W, int Z, int* L, hipStream_t s);   // component labels (minimum index), -1 off
 int launch_largest_component(const unsigned char* vol, int H, int W, int Z, int rule, unsigned char* out, int* status_dev,
                              void* workspace, size_t ws_bytes, hipStream_t s);
+void launch_cc_count(const int* L, long long n, unsigned int* cnt, hipStream_t s);   // cnt[root] += voxels (cnt zeroed by the caller)
 size_t metric_out_bytes(int nbins);
 int launch_metric_sums(const unsigned char* pred, const unsigned char* label, const unsigned char* skel, const int* parsing, long long n,
                        int nbins, void* out, size_t out_bytes, hipStream_t s);
@@ -466,6 +467,18 @@ int launch_metric_sums(const unsigned char* pred, const unsigned char* label, co
 size_t edt_workspace_bytes(int n0, int n1, int n2);
 int launch_edt(const unsigned char* vol, int n0, int n1, int n2, int* sqdist, double* dist, int* indices, int* status_dev,
                void* workspace, size_t ws_bytes, hipStream_t s);
+struct EdtOut {            // what the last pass of the feature transform writes (each part optional)
+  int* sqdist;
+  double* dist;
+  int* indices;            // (3, n0, n1, n2)
+  int* lin;                // linear index of the feature (internal users)
+  const int* gather_src;   // gather_out[v] = gather_mask[v] != 0 ? gather_src[feature of v] : 0 (all three or none)
+  const unsigned char* gather_mask;
+  int* gather_out;
+};
+// invert = false: sites are the zero voxels (distance_transform_edt(vol)); true: the non-zero ones (EDT of 1 - vol)
+int run_edt(const unsigned char* vol, bool invert, int n0, int n1, int n2, EdtOut o, int* status_dev, void* workspace, size_t ws_bytes,
+            hipStream_t s);
 int launch_mask_bits(const unsigned char* mask, long long n, unsigned long long* bits, hipStream_t s);
 int launch_hm_candidates(const unsigned char* label, const unsigned char* skel, const unsigned char* pred, int n0, int n1, int n2,
                          unsigned long long* skel_bits, unsigned long long* small_bits, hipStream_t s);
@@ -479,6 +492,17 @@ int launch_break_weight(const unsigned char* label, const unsigned char* pred, c
 size_t skeleton_workspace_bytes(int n0, int n1, int n2);
 int launch_skeletonize(const unsigned char* vol, int n0, int n1, int n2, unsigned char* out, int* passes_dev, void* workspace,
                        size_t ws_bytes, hipStream_t s);
+// airway tree parsing (parse.hip): skeleton branches, nearest-branch assignment, label statistics, relabelling
+size_t skeleton_branches_workspace_bytes(int n0, int n1, int n2);
+int launch_skeleton_branches(const unsigned char* skel, int n0, int n1, int n2, int min_voxels, int* cd, unsigned char* skeleton_parse,
+                             int* num_dev, void* workspace, size_t ws_bytes, hipStream_t s);
+size_t parse_assign_workspace_bytes(int n0, int n1, int n2);
+int launch_parse_assign(const unsigned char* skeleton_parse, const int* cd, const unsigned char* label, int n0, int n1, int n2,
+                        int* parsing, int* status_dev, void* workspace, size_t ws_bytes, hipStream_t s);
+int label_stats_max_num();
+int launch_label_stats(const int* parsing, int n0, int n1, int n2, int num, unsigned int* counts, unsigned long long* adjacency_bits,
+                       int* status_dev, hipStream_t s);
+int launch_relabel(const int* parsing, long long n, const int* lut, int nlut, int* out, hipStream_t s);
 // CT preprocessing (lung.hip): value counts, shift + clamp, per-slice lung field, mask combination, bounding box, crop
 int launch_value_counts(const short* ct, long long n, int shift, unsigned int* counts, hipStream_t s);
 int launch_shift_clamp(const short* ct, long long n, int shift, int clamp, int clamp_le, int clamp_to, short* out, hipStream_t s);

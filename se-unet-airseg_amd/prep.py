@@ -254,3 +254,252 @@ def break_weight(label: torch.Tensor, pred: torch.Tensor, skeleton: torch.Tensor
                    "break_weight")
         _status(status, "break_weight: the skeleton is empty")
     return w, brs
+
+
+# ---- airway tree parsing: the ATM'22 branch labelling (csrc/parse.hip) -------------------------------
+
+def _mask_in(a, name):
+    """A 0/1 volume argument -> (uint8 CUDA tensor, came-as-numpy)."""
+    if isinstance(a, np.ndarray):
+        if a.ndim != 3:
+            raise ValueError(f"seunet prep: `{name}` must be (n0, n1, n2), got {tuple(a.shape)}")
+        if not torch.cuda.is_available():
+            raise RuntimeError(f"seunet prep: `{name}` needs a GPU (there is no CPU path)")
+        return torch.from_numpy(np.ascontiguousarray(a != 0).view(np.uint8)).cuda(), True
+    return _vol(a, name), False
+
+
+def _labels_in(a, name):
+    """An integer label volume argument -> (int32 CUDA tensor, came-as-numpy)."""
+    if isinstance(a, np.ndarray):
+        if a.ndim != 3:
+            raise ValueError(f"seunet prep: `{name}` must be (n0, n1, n2), got {tuple(a.shape)}")
+        if not torch.cuda.is_available():
+            raise RuntimeError(f"seunet prep: `{name}` needs a GPU (there is no CPU path)")
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).cuda(), True
+    if not isinstance(a, torch.Tensor) or not a.is_cuda:
+        raise RuntimeError(f"seunet prep: `{name}` must be a CUDA tensor resident on the GPU (there is no CPU path)")
+    if a.dim() != 3:
+        raise ValueError(f"seunet prep: `{name}` must be (n0, n1, n2), got {tuple(a.shape)}")
+    if a.dtype not in (torch.int32, torch.int64, torch.int16, torch.uint8):
+        raise TypeError(f"seunet prep: `{name}` has dtype {a.dtype}; expected an integer label volume")
+    return a.to(torch.int32).contiguous(), False
+
+
+def _out(t, as_numpy):
+    return t.cpu().numpy() if as_numpy else t
+
+
+def _skeleton_parsing(skel, min_voxels):
+    n0, n1, n2 = (int(v) for v in skel.shape)
+    dev = skel.device
+    parse = torch.zeros((n0, n1, n2), dtype=torch.uint8, device=dev)
+    cd = torch.zeros((n0, n1, n2), dtype=torch.int32, device=dev)
+    if skel.numel() == 0:
+        return parse, cd, 0
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        ws_bytes = int(lib.seunet_skeleton_branches_workspace_bytes(n0, n1, n2))
+        if ws_bytes == 0:
+            raise ValueError(f"seunet prep: skeleton_parsing: {_lib.last_error()}")
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        num = torch.zeros(1, dtype=torch.int32, device=dev)
+        _lib.check(lib.seunet_skeleton_branches(skel.data_ptr(), n0, n1, n2, int(min_voxels), cd.data_ptr(), parse.data_ptr(),
+                                                num.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream_ptr()), "skeleton_branches")
+        return parse, cd, int(num.item())
+
+
+def skeleton_parsing(skeleton, min_voxels: int = 5):
+    """``skeleton_parsing`` of the ATM'22 parser (atm22_skel_parse.py:83-101) -> ``(skeleton_parse uint8, cd int32, num)``,
+    bitwise the reference's: skeleton voxels whose 3x3x3 sum (``ndimage.convolve``, mode 'reflect') exceeds 3 are removed, the
+    rest is labelled with 26-connectivity, components under ``min_voxels`` voxels are removed, and the survivors are numbered
+    as the reference's second ``ndimage.label`` numbers them.  CUDA tensor in -> CUDA tensors out, numpy in -> numpy out; the
+    input is not modified.  Reading ``num`` synchronises once."""
+    skel, as_numpy = _mask_in(skeleton, "skeleton")
+    parse, cd, num = _skeleton_parsing(skel, min_voxels)
+    return _out(parse, as_numpy), _out(cd, as_numpy), num
+
+
+def _assign(parse, label, cd):
+    n0, n1, n2 = (int(v) for v in label.shape)
+    dev = label.device
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        ws = torch.empty(max(int(lib.seunet_parse_assign_workspace_bytes(n0, n1, n2)), 1), dtype=torch.uint8, device=dev)
+        out = torch.empty((n0, n1, n2), dtype=torch.int32, device=dev)
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+        _lib.check(lib.seunet_parse_assign(parse.data_ptr(), cd.data_ptr(), label.data_ptr(), n0, n1, n2, out.data_ptr(),
+                                           status.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "parse_assign")
+        _status(status, "tree_parsing_func: skeleton_parse is empty (the nearest branch is undefined)")
+    return out
+
+
+def tree_parsing_func(skeleton_parse, label, cd):
+    """``tree_parsing_func`` (atm22_skel_parse.py:103-108; also the last line of ``ske_and_parse.airway_parse``): every voxel of
+    ``label`` gets the number ``cd`` holds at the nearest voxel of ``skeleton_parse``, nearest as scipy's
+    ``distance_transform_edt(1 - skeleton_parse, return_indices=True)`` decides it, ties included; 0 outside the label.  int32,
+    bitwise the reference's.  An empty ``skeleton_parse`` raises ValueError."""
+    parse, np0 = _mask_in(skeleton_parse, "skeleton_parse")
+    lab, np1 = _mask_in(label, "label")
+    c, np2 = _labels_in(cd, "cd")
+    _same(parse, lab, "skeleton_parse", "label")
+    _same(parse, c, "skeleton_parse", "cd")
+    if parse.numel() == 0:
+        raise ValueError("seunet prep: tree_parsing_func: skeleton_parse is empty (the nearest branch is undefined)")
+    return _out(_assign(parse, lab, c), np0 and np1 and np2)
+
+
+def _label_stats(parsing, num):
+    """(counts int64[num + 1], adjacency bool[num + 1, num + 1]) of an int32 device volume with values 0..num."""
+    lib = _lib.load()
+    num = int(num)
+    cap = int(lib.seunet_label_stats_max_num())
+    if not 0 <= num <= cap:
+        raise ValueError(f"seunet prep: label statistics support labels up to {cap}, got num = {num}")
+    n0, n1, n2 = (int(v) for v in parsing.shape)
+    words = (num + 1 + 63) // 64
+    dev = parsing.device
+    with torch.cuda.device(dev):
+        counts = torch.empty(num + 1, dtype=torch.int32, device=dev)
+        bits = torch.empty((num + 1, words), dtype=torch.int64, device=dev)
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+        if parsing.numel():
+            _lib.check(lib.seunet_label_stats(parsing.data_ptr(), n0, n1, n2, num, counts.data_ptr(), bits.data_ptr(), status.data_ptr(),
+                                              _lib.stream_ptr()), "label_stats")
+        else:
+            counts.zero_(); bits.zero_(); status.zero_()
+        _status(status, f"label statistics: the volume holds a label outside 0..{num}")
+        c = counts.cpu().numpy().view(np.uint32).astype(np.int64)
+        b = bits.cpu().numpy().view(np.uint8)
+    adj = np.unpackbits(b, axis=1, bitorder="little")[:, :num + 1].astype(bool)
+    return c, adj
+
+
+def label_adjacency(parsing, num: int):
+    """The two statistics the refinement of the ATM'22 parser takes from a label volume, in one pass on the device:
+    ``counts`` (int64[num], voxels of label k + 1: ``loc_trachea``, atm22_skel_parse.py:110-118) and ``ad`` (uint8[num, num],
+    ``ad[i, j] = 1`` iff labels i + 1 and j + 1 meet across a face: ``adjacent_map``, :120-135).  numpy arrays.  A label outside
+    0..num raises ValueError, as does a ``num`` above the kernel's cap (4095)."""
+    vol, _ = _labels_in(parsing, "parsing")
+    c, adj = _label_stats(vol, num)
+    return c[1:], adj[1:, 1:].astype(np.uint8)
+
+
+def _parent_children(ad: np.ndarray, trachea: int, num: int):
+    """Breadth-first parent / children relation from the trachea (0-based), atm22_skel_parse.py:137-165: a level is taken from
+    its end, children in ascending order, a visited node takes a further parent when it lies exactly one generation below, and
+    the generation counter is uint8 (it wraps)."""
+    parent = np.zeros((num, num), dtype=np.uint8)
+    children = np.zeros((num, num), dtype=np.uint8)
+    generation = np.zeros(num, dtype=np.uint8)
+    parent[trachea, trachea] = 1
+    level = [trachea]
+    while level:
+        todo, level = level, []
+        while todo:
+            cur = todo.pop()
+            for child in np.flatnonzero(ad[cur] > 0):
+                if not parent[child].any():
+                    parent[child, cur] = 1
+                    children[cur, child] = 1
+                    generation[child] = generation[cur] + 1
+                    level.append(int(child))
+                elif generation[cur] + 1 == generation[child]:
+                    parent[child, cur] = 1
+                    children[cur, child] = 1
+    return parent, children
+
+
+def _merge_steps(parent: np.ndarray, children: np.ndarray):
+    """The (from, to) label replacements (1-based values) of one merge sweep and the 0-based labels it deletes, in the
+    reference's order (atm22_skel_parse.py:219-243 = :167-196): all parents of a multi-parent node fuse into the first, then an
+    only child fuses into its parent."""
+    steps, deleted = [], []
+    for node in np.flatnonzero(parent.sum(axis=1) > 1):
+        ps = np.flatnonzero(parent[node] > 0)
+        for p in ps[1:]:
+            steps.append((int(p) + 1, int(ps[0]) + 1))
+            if p not in deleted:
+                deleted.append(int(p))
+    for node in np.flatnonzero(children.sum(axis=1) == 1):
+        if node in deleted:
+            continue
+        child = int(np.flatnonzero(children[node] == 1)[0])
+        if child not in deleted:
+            steps.append((child + 1, int(node) + 1))
+            deleted.append(child)
+    return steps, deleted
+
+
+def refine_labels(counts: np.ndarray, adjacency: np.ndarray, num: int):
+    """The refinement loop of tree_parsing.py:148-159 on the statistics of the unrefined volume instead of the volume:
+    ``counts`` (int[num + 1]) and ``adjacency`` (bool[num + 1, num + 1]) indexed by label value.  Every step of the loop replaces
+    one label value by another everywhere, so a table over the values follows it exactly: the counts of fused values add and
+    their adjacency rows unite.  -> ``(lut int32[num + 1], final num, rounds)`` with ``final = lut[unrefined]``."""
+    size = int(num) + 1
+    counts = np.asarray(counts, dtype=np.int64).copy()
+    adj = np.asarray(adjacency, dtype=bool).copy()
+    lut = np.arange(size, dtype=np.int64)
+    rounds = 0
+    while num > 0:
+        trachea = int(np.argsort(counts[1:num + 1].astype(np.float64))[-1])
+        parent, children = _parent_children(adj[1:num + 1, 1:num + 1].astype(np.uint8), trachea, num)
+        steps, deleted = _merge_steps(parent, children)
+        if not deleted:
+            break
+        rounds += 1
+        m = np.arange(size, dtype=np.int64)                  # value at the start of the round -> value now
+        for _ in range(2):                                   # whether_refinement merges in place, tree_refinement merges again
+            for a, b in steps:
+                m[m == a] = b
+        gone = np.asarray(deleted)
+        for i in range(num):                                 # compaction, in place and in ascending order
+            if i not in deleted:
+                m[m == i + 1] = i + 1 - int((gone < i).sum())
+        num -= len(deleted)
+        counts = np.bincount(m, weights=counts, minlength=size).astype(np.int64)
+        a, b = np.nonzero(adj)
+        adj = np.zeros_like(adj)
+        adj[m[a], m[b]] = True
+        adj[np.arange(size), np.arange(size)] = False
+        lut = m[lut]
+    return lut.astype(np.int32), int(num), rounds
+
+
+def tree_parsing(label, skeleton=None, refine: bool = True, return_num: bool = False):
+    """The ATM'22 parser from the skeleton on (tree_parsing.py:114-159 without meshes and pictures): the int32 ``parsing`` volume
+    ``evaluation_case`` and ``branch_detected_calculation`` take, bitwise the reference's.  ``skeleton=None`` thins the label
+    with ``skeletonize_3d``.  Steps: ``skeleton_parsing``, ``tree_parsing_func``, then the refinement loop, which runs on the host
+    on one pass of label statistics (``refine_labels``) and is applied by one look-up pass.  ``refine=False`` stops before the
+    loop.  ``return_num``: also return the number of branches.  CUDA tensor in -> CUDA tensor out, numpy in -> numpy out."""
+    lab, as_numpy = _mask_in(label, "label")
+    if skeleton is None:
+        skel = skeletonize_3d(lab)
+    else:
+        skel, _ = _mask_in(skeleton, "skeleton")
+        _same(lab, skel, "label", "skeleton")
+    parse, cd, num = _skeleton_parsing(skel, 5)
+    if num == 0:
+        raise ValueError("seunet prep: tree_parsing: no skeleton branch of 5 voxels or more (the nearest branch is undefined)")
+    parsing = _assign(parse, lab, cd)
+    if refine:
+        counts, adj = _label_stats(parsing, num)
+        lut, num, _ = refine_labels(counts, adj, num)
+        table = torch.from_numpy(lut).to(lab.device)
+        with torch.cuda.device(lab.device):
+            _lib.check(_lib.load().seunet_relabel(parsing.data_ptr(), parsing.numel(), table.data_ptr(), table.numel(),
+                                                  parsing.data_ptr(), _lib.stream_ptr()), "relabel")
+    out = _out(parsing, as_numpy)
+    return (out, num) if return_num else out
+
+
+def relabel(parsing, lut):
+    """``lut[parsing]`` on the device (``seunet_relabel``): int32 out; a value outside the table gives 0."""
+    vol, as_numpy = _labels_in(parsing, "parsing")
+    table = torch.as_tensor(np.ascontiguousarray(np.asarray(lut.cpu() if isinstance(lut, torch.Tensor) else lut), dtype=np.int32)).to(vol.device)
+    out = torch.empty_like(vol)
+    if vol.numel():
+        with torch.cuda.device(vol.device):
+            _lib.check(_lib.load().seunet_relabel(vol.data_ptr(), vol.numel(), table.data_ptr(), table.numel(), out.data_ptr(),
+                                                  _lib.stream_ptr()), "relabel")
+    return _out(out, as_numpy)
