@@ -31,23 +31,9 @@
 //   grid          blockIdx.x is remapped so that each XCD (private L2) owns a contiguous run of tiles
 #include "seunet_common.h"
 #include "lds_dma.h"
-#include <utility>
-#include <type_traits>
+#include "mfma.h"
 
 namespace seunet {
-
-typedef bf16_t bf16x8 __attribute__((ext_vector_type(8)));
-typedef f16_t f16x8 __attribute__((ext_vector_type(8)));
-// LDS fragments are read as 8 x 16-bit patterns (bf16x8); the matrix instruction is chosen by the storage type
-template <typename T> __device__ __forceinline__ float __attribute__((ext_vector_type(16)))
-mfma32_16bit(bf16x8 a, bf16x8 b, float __attribute__((ext_vector_type(16))) c) {
-  if constexpr (std::is_same<T, f16_t>::value)
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 static constexpr int CV_TZ = 4, CV_TY = 4, CV_TX = 32;
 
@@ -233,9 +219,7 @@ conv_igemm_kernel(ConvKArgs a) {
     for (int r = 0; r < 16; ++r) acc[ms][r] = 0.f;
 
   fetch_setup(0);
-  [&]<int... I>(std::integer_sequence<int, I...>) __attribute__((always_inline)) {
-    (fetch_item(std::integral_constant<int, I>{}), ...);
-  }(std::make_integer_sequence<int, F_ITEMS>{});
+  static_for<F_ITEMS>([&](auto i_c) __attribute__((always_inline)) { fetch_item(i_c); });
   STAMP(0);   // prologue: index plan + first prefetch issue
   for (int chunk = 0; chunk < a.nchunks; ++chunk) {
     __syncthreads();   // every wave is done reading the previous chunk's tiles
@@ -252,9 +236,7 @@ conv_igemm_kernel(ConvKArgs a) {
     // other workgroup's MFMAs cover the issue time.
     if (chunk + 1 < a.nchunks) {
       fetch_setup(chunk + 1);
-      [&]<int... I>(std::integer_sequence<int, I...>) __attribute__((always_inline)) {
-        (fetch_item(std::integral_constant<int, I>{}), ...);
-      }(std::make_integer_sequence<int, F_ITEMS>{});
+      static_for<F_ITEMS>([&](auto i_c) __attribute__((always_inline)) { fetch_item(i_c); });
     }
     STAMP(4);   // prefetch issue
 
@@ -288,21 +270,19 @@ conv_igemm_kernel(ConvKArgs a) {
         }
       };
       load_step(std::integral_constant<int, 0>{});
-      [&]<int... ST>(std::integer_sequence<int, ST...>) __attribute__((always_inline)) {
-        ([&]() __attribute__((always_inline)) {
-          constexpr int b = ST & 1;
-          load_step(std::integral_constant<int, ST + 1>{});
-          __builtin_amdgcn_sched_barrier(0);   // (the reads stay ahead of this step's MFMAs)
+      static_for<NST>([&](auto st_c) __attribute__((always_inline)) {
+        constexpr int ST = decltype(st_c)::value, b = ST & 1;
+        load_step(std::integral_constant<int, ST + 1>{});
+        __builtin_amdgcn_sched_barrier(0);   // (the reads stay ahead of this step's MFMAs)
 #pragma unroll
-          for (int ms = 0; ms < 4; ++ms) {
-            if constexpr (sizeof(T) == 2)
-              acc[ms] = mfma32_16bit<T>(wf[b], af[b][ms], acc[ms]);
-            else
-              acc[ms] = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[b], af[b][ms], acc[ms], 0, 0, 0);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-        }(), ...);
-      }(std::make_integer_sequence<int, NST>{});
+        for (int ms = 0; ms < 4; ++ms) {
+          if constexpr (sizeof(T) == 2)
+            acc[ms] = mfma_32x32x16<T>(wf[b], af[b][ms], acc[ms]);
+          else
+            acc[ms] = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[b], af[b][ms], acc[ms], 0, 0, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      });
     }
     STAMP(5);   // MFMA block of this chunk
   }
@@ -462,7 +442,6 @@ conv_igemm_kernel(ConvKArgs a) {
 #pragma unroll
           for (int i = 0; i < 4; ++i) v[i] = acc[ms][4 * q + i];
           if constexpr (sizeof(T) == 2) {
-            typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
             if (dacc) {
               const u32x2 o = __builtin_amdgcn_raw_buffer_load_b64(rd, off, 0, 0);
               v[0] += unpack_lo<T>(o.x); v[1] += unpack_hi<T>(o.x);
@@ -498,7 +477,6 @@ conv_igemm_kernel(ConvKArgs a) {
       for (int q = 0; q < 4; ++q) {
         unsigned char* sp = stage + (ms * 32 + col) * ROWB + (8 * q + 4 * h) * (int)sizeof(T);
         if constexpr (sizeof(T) == 2) {
-          typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
           u32x2 u;
           u.x = pack2<T>(acc[ms][4 * q], acc[ms][4 * q + 1]);
           u.y = pack2<T>(acc[ms][4 * q + 2], acc[ms][4 * q + 3]);

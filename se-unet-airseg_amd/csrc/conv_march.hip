@@ -29,22 +29,9 @@
 // One workgroup per CU: a 4 x 128^3 batch at 64 -> 32 channels is exactly 256 marches of 128 planes.
 #include "seunet_common.h"
 #include "lds_dma.h"
-#include <utility>
-#include <type_traits>
+#include "mfma.h"
 
 namespace seunet {
-
-typedef bf16_t mbf16x8 __attribute__((ext_vector_type(8)));
-typedef f16_t mf16x8 __attribute__((ext_vector_type(8)));
-typedef float mf32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int mu32x2 __attribute__((ext_vector_type(2)));
-
-template <typename T> __device__ __forceinline__ mf32x4 mm16b(mbf16x8 a, mbf16x8 b, mf32x4 c) {
-  if constexpr (std::is_same<T, f16_t>::value)
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(mf16x8, a), __builtin_bit_cast(mf16x8, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
 
 struct MarchArgs {
   const void* src0; const void* src1;   // one or two source tensors of srcC channels each (virtual concatenation)
@@ -90,12 +77,6 @@ template <int NP> __device__ __forceinline__ int march_swz(int hx) {
   else return (hx >> 1) & 7;
 }
 
-template <int N, typename F> __device__ __forceinline__ void static_for(F&& f) {
-  [&]<int... I>(std::integer_sequence<int, I...>) __attribute__((always_inline)) {
-    (f(std::integral_constant<int, I>{}), ...);
-  }(std::make_integer_sequence<int, N>{});
-}
-
 // MODE 0: forward (bias + InstanceNorm partial sums); 1: data gradient; 2: data gradient with accumulation (+=)
 // BUF: the source(s) of a sample fit one 32-bit buffer descriptor: the plane DMA goes through it (dma16_buf; in the main loop of the
 // dc5 data gradient 1.25 -> 1.06 other instructions per MFMA and 65 -> 12 scalar-register spill reads against dma16)
@@ -133,11 +114,11 @@ conv_march_kernel(MarchArgs a) {
 
   // ---- weights: registers for the whole march.  wpack: [16-channel group][tap][K-step][lane][8 elements] ----
   const int g16 = nb * NGW + ng;
-  mbf16x8 wreg[NTAP * KS];
+  bf16x8 wreg[NTAP * KS];
   {
     const uint4* wp = reinterpret_cast<const uint4*>(a.wpack) + (size_t)g16 * (NTAP * KS * 64) + lane;
 #pragma unroll
-    for (int k = 0; k < NTAP * KS; ++k) wreg[k] = __builtin_bit_cast(mbf16x8, wp[k * 64]);
+    for (int k = 0; k < NTAP * KS; ++k) wreg[k] = __builtin_bit_cast(bf16x8, wp[k * 64]);
     // 64-channel inputs: 216 weight registers + fragments + addresses do not fit the 256 architectural VGPRs, and left alone the
     // allocator parks weights in the accumulator half and copies them back before every use (170 v_accvgpr_read per step of the
     // dc5 forward: the forward's 2.68 of 4 busy SIMDs against the data gradient's 2.98).  The matrix instruction takes its A
@@ -265,9 +246,9 @@ conv_march_kernel(MarchArgs a) {
         foff[ks][dx][b] = (unsigned)((rg * RYW * MA_HXP + hx) * VB + (((4 * ks + g) ^ march_swz<NP>(hx)) * 16));
       }
 
-  mf32x4 acc[3][RYW][2];
+  f32x4 acc[3][RYW][2];
   // (no initialisation: the first MFMA of every (set, row, block) takes `cinit` as its C operand)
-  mf32x4 cinit;
+  f32x4 cinit;
 #pragma unroll
   for (int e = 0; e < 4; ++e) cinit[e] = (MODE == 0 && a.bias != nullptr) ? a.bias[co0 + 4 * g + e] : 0.f;
 
@@ -302,13 +283,13 @@ conv_march_kernel(MarchArgs a) {
     const bool rowok = jok && y < a.H;                                  // wave-uniform
     const __amdgpu_buffer_rsrc_t rdr = __builtin_amdgcn_make_buffer_rsrc(dbase, 0, rowok ? dst_records : 0, RSRC_WORD3);
     const int soff = __builtin_amdgcn_readfirstlane(rowok ? (z * a.H + y) * row_pitch : 0);
-    mf32x4 v = acc[AI][r][b];
+    f32x4 v = acc[AI][r][b];
     // the accumulator leaves the accumulator half HERE (one copy, at the epilogue's place in the unit): with several vector
     // uses the compiler otherwise copies every accumulator out right after its last MFMA and keeps a whole set in VGPRs
     asm volatile("" : "+v"(v));
     if constexpr (MODE == 2) {
-      const mu32x2 o = *reinterpret_cast<const mu32x2*>(smem + Geo::OLD + (((s & 1) * MA_NW + wave) * RYW + r) * 1024 +
-                                                        (16 * b + n16) * 32 + g * 8);
+      const u32x2 o = *reinterpret_cast<const u32x2*>(smem + Geo::OLD + (((s & 1) * MA_NW + wave) * RYW + r) * 1024 +
+                                                      (16 * b + n16) * 32 + g * 8);
       v[0] += unpack_lo<T>(o.x); v[1] += unpack_hi<T>(o.x);
       v[2] += unpack_lo<T>(o.y); v[3] += unpack_hi<T>(o.y);
     }
@@ -320,7 +301,7 @@ conv_march_kernel(MarchArgs a) {
       // keeps all the epilogue values in registers until then)
       asm volatile("" : "+v"(s1[0]), "+v"(s1[1]), "+v"(s1[2]), "+v"(s1[3]), "+v"(s2[0]), "+v"(s2[1]), "+v"(s2[2]), "+v"(s2[3]));
     }
-    mu32x2 u;
+    u32x2 u;
     u.x = pack2<T>(v[0], v[1]);
     u.y = pack2<T>(v[2], v[3]);
     __builtin_amdgcn_raw_buffer_store_b64(u, rdr, b == 0 ? lx0 : lx1, soff, 0);
@@ -351,14 +332,14 @@ conv_march_kernel(MarchArgs a) {
     // fragments are requested PFD units ahead of their MFMAs (2 was measured: no change on any layer, the waves do not wait
     // for fragments -- SQ_WAIT_INST_LDS is 1 % of the wave cycles)
     constexpr int PFD = MA_PFD;
-    mbf16x8 fr[PFD + 1][2];
+    bf16x8 fr[PFD + 1][2];
     auto load_unit = [&](auto u_c) __attribute__((always_inline)) {
       constexpr int u = decltype(u_c)::value;
       if constexpr (u < NU) {
         constexpr int hi = u / (3 * KS), ks = (u / 3) % KS, dx = u % 3;
 #pragma unroll
         for (int b = 0; b < 2; ++b)
-          fr[u % (PFD + 1)][b] = *reinterpret_cast<const mbf16x8*>(pl + foff[ks][dx][b] + hi * ROWB);
+          fr[u % (PFD + 1)][b] = *reinterpret_cast<const bf16x8*>(pl + foff[ks][dx][b] + hi * ROWB);
       }
     };
     static_for<PFD>([&](auto k_c) __attribute__((always_inline)) { load_unit(k_c); });
@@ -388,8 +369,8 @@ conv_march_kernel(MarchArgs a) {
           for (int dz = 0; dz < 3; ++dz) {                // output plane s - dz
             const int ai = (PH - dz + 3) % 3;
             const int tap = (dz * 3 + dy) * 3 + dx;
-            if (dz == 0 && dy == 0 && dx == 0 && ks == 0) acc[ai][r][b] = mm16b<T>(wreg[tap * KS + ks], fr[u % (PFD + 1)][b], cinit);
-            else acc[ai][r][b] = mm16b<T>(wreg[tap * KS + ks], fr[u % (PFD + 1)][b], acc[ai][r][b]);
+            if (dz == 0 && dy == 0 && dx == 0 && ks == 0) acc[ai][r][b] = mfma_16x16x32<T>(wreg[tap * KS + ks], fr[u % (PFD + 1)][b], cinit);
+            else acc[ai][r][b] = mfma_16x16x32<T>(wreg[tap * KS + ks], fr[u % (PFD + 1)][b], acc[ai][r][b]);
           }
         }
       // one scheduling region per unit: the next unit's two fragment reads first, then the unit's MFMAs with the vector work of
@@ -489,16 +470,15 @@ conv_march_kernel(MarchArgs a) {
 // ------------------------------------------------------------------------------------------------------------------
 struct MarchPackArgs { const float* w; void* out; int cin_w, cout_w, tflip, cin_e, cout_e, ks; };
 
+// blk = (group * 27 + tap) * KS + ks; one wave writes the 64 fragments
 template <typename T>
-__global__ void __launch_bounds__(64)
-conv_march_pack_kernel(MarchPackArgs p) {
-  // blockIdx.x = (group * 27 + tap) * KS + ks; one wave writes the 64 fragments
+__device__ __forceinline__ void conv_march_pack_body(const MarchPackArgs& p, unsigned blk) {
   const int lane = threadIdx.x;
-  const int ks = blockIdx.x % p.ks, gt = blockIdx.x / p.ks;
+  const int ks = blk % p.ks, gt = blk / p.ks;
   const int tap = gt % 27, grp = gt / 27;
   const int co = grp * 16 + (lane & 15);
   const int kg = lane >> 4;
-  T* out = reinterpret_cast<T*>(p.out) + ((size_t)blockIdx.x * 64 + lane) * 8;
+  T* out = reinterpret_cast<T*>(p.out) + ((size_t)blk * 64 + lane) * 8;
   for (int j = 0; j < 8; ++j) {
     const int ci = 32 * ks + 8 * kg + j;
     float v = 0.f;
@@ -507,27 +487,16 @@ conv_march_pack_kernel(MarchPackArgs p) {
     out[j] = from_f32<T>(v);
   }
 }
+template <typename T>
+__global__ void __launch_bounds__(64)
+conv_march_pack_kernel(MarchPackArgs p) { conv_march_pack_body<T>(p, blockIdx.x); }
 
 // all the weight tensors of a pass in one launch: blockIdx.y = list entry
 struct MarchPackList { MarchPackArgs e[12]; int blocks[12]; };
 template <typename T>
 __global__ void __launch_bounds__(64)
 conv_march_pack_multi_kernel(MarchPackList l) {
-  const MarchPackArgs& p = l.e[blockIdx.y];
-  if ((int)blockIdx.x >= l.blocks[blockIdx.y]) return;
-  const int lane = threadIdx.x;
-  const int ks = blockIdx.x % p.ks, gt = blockIdx.x / p.ks;
-  const int tap = gt % 27, grp = gt / 27;
-  const int co = grp * 16 + (lane & 15);
-  const int kg = lane >> 4;
-  T* out = reinterpret_cast<T*>(p.out) + ((size_t)blockIdx.x * 64 + lane) * 8;
-  for (int j = 0; j < 8; ++j) {
-    const int ci = 32 * ks + 8 * kg + j;
-    float v = 0.f;
-    if (co < p.cout_e && ci < p.cin_e)
-      v = p.tflip ? p.w[((long long)ci * p.cin_w + co) * 27 + (26 - tap)] : p.w[((long long)co * p.cin_w + ci) * 27 + tap];
-    out[j] = from_f32<T>(v);
-  }
+  if ((int)blockIdx.x < l.blocks[blockIdx.y]) conv_march_pack_body<T>(l.e[blockIdx.y], blockIdx.x);
 }
 
 // ---- configuration by channel counts -------------------------------------------------------------------------------
@@ -552,7 +521,6 @@ bool conv_march_supported(int dtype, int taps, int dil, const SrcList& src, cons
 }
 size_t conv_march_wpack_bytes(int cin_e, int cout_e) { return (size_t)(cout_e / 16) * 27 * (cin_e / 32) * 64 * 16; }
 
-static int march_patch_rows(const MarchCfg& c) { return c.ryw * (MA_NW / c.ngw); }
 // output planes per march: the fewest steps on the critical path -- rounds of workgroups over the chip's 256 CUs (one
 // workgroup per CU) x steps of the longest march, a march of Z planes running Z + 2 steps rounded up to a multiple of 3
 static int march_zsteps(int planes, long long wg_per_seg) {
@@ -566,24 +534,46 @@ static int march_zsteps(int planes, long long wg_per_seg) {
   }
   return best;
 }
+// The launch cut: patches, N blocks (of 16 * NGW output channels), z segments per parity class, output planes per segment.
+// conv_march_slots() and launch_conv_march() both take it from march_cut(); the grid and the statistics records follow from it
+// alone.  Unlike the streaming kernel's, this cut depends on the batch (march_zsteps counts the workgroups of the whole launch).
+struct MarchCut {
+  int nyb, nxb, nblk, planes, zsteps, nseg, dil;
+  int slots() const { return nyb * nxb * nseg * dil; }                      // statistics records per sample and channel
+  dim3 grid(int n) const { return dim3(nyb * nxb, nseg * dil * nblk, n); }
+};
+static MarchCut march_cut(const MarchCfg& c, Dims d, int dil, int cout_e) {
+  MarchCut m;
+  m.dil = dil;
+  const int ry = c.ryw * (MA_NW / c.ngw);                                   // rows of a patch
+  m.nyb = cdiv(d.H, ry); m.nxb = cdiv(d.W, MA_TX);
+  m.nblk = cout_e / (16 * c.ngw);
+  m.planes = cdiv(d.D, dil);
+  m.zsteps = march_zsteps(m.planes, (long long)m.nyb * m.nxb * d.N * m.nblk * dil);
+  m.nseg = cdiv(m.planes, m.zsteps);
+  return m;
+}
 int conv_march_slots(Dims d, int dil, int cin_e, int cout_e) {
   MarchCfg c;
   if (!march_cfg(SEUNET_BF16, 27, dil, cin_e, cout_e, 0, c)) return 0;
-  const int ry = march_patch_rows(c);
-  const int npatch = cdiv(d.H, ry) * cdiv(d.W, MA_TX);
-  const int planes = cdiv(d.D, dil);
-  const int nblk = cout_e / (16 * c.ngw);
-  const int zs = march_zsteps(planes, (long long)npatch * d.N * nblk * dil);
-  return npatch * cdiv(planes, zs) * dil;
+  return march_cut(c, d, dil, cout_e).slots();
 }
 
-int launch_conv_march_pack(int dtype, const float* w, int cin_w, int cout_w, int tflip, int cin_e, int cout_e, void* wpack, hipStream_t s) {
+// one packing job, validated: the kernel's arguments and its workgroup count
+static int march_pack_args(int dtype, const float* w, int cin_w, int cout_w, int tflip, int cin_e, int cout_e, void* wpack,
+                           MarchPackArgs& p, int& blocks) {
   MarchCfg c;
   SEUNET_CHECK(march_cfg(dtype, 27, 1, cin_e, cout_e, 0, c) && w && wpack, "conv_march_pack: unsupported shape (%d -> %d channels)", cin_e, cout_e);
   const int we_in = tflip ? cout_w : cin_w, we_out = tflip ? cin_w : cout_w;
   SEUNET_CHECK(we_in <= cin_e && we_out <= cout_e, "conv_march_pack: weight (%d -> %d) exceeds the tensors (%d -> %d)", we_in, we_out, cin_e, cout_e);
-  MarchPackArgs p{w, wpack, cin_w, cout_w, tflip, we_in, we_out, c.ks};
-  const int blocks = (cout_e / 16) * 27 * c.ks;
+  p = MarchPackArgs{w, wpack, cin_w, cout_w, tflip, we_in, we_out, c.ks};
+  blocks = (cout_e / 16) * 27 * c.ks;
+  return 0;
+}
+int launch_conv_march_pack(int dtype, const float* w, int cin_w, int cout_w, int tflip, int cin_e, int cout_e, void* wpack, hipStream_t s) {
+  MarchPackArgs p{};
+  int blocks = 0;
+  if (int e = march_pack_args(dtype, w, cin_w, cout_w, tflip, cin_e, cout_e, wpack, p, blocks)) return e;
   if (dtype == SEUNET_F16) conv_march_pack_kernel<f16_t><<<blocks, 64, 0, s>>>(p);
   else conv_march_pack_kernel<bf16_t><<<blocks, 64, 0, s>>>(p);
   SEUNET_LAUNCH_CHECK();
@@ -597,12 +587,7 @@ int launch_conv_march_pack_multi(int dtype, const MarchPackJob* jobs, int n, hip
     int maxb = 0;
     for (int i = 0; i < m; ++i) {
       const MarchPackJob& j = jobs[base + i];
-      MarchCfg c;
-      SEUNET_CHECK(march_cfg(dtype, 27, 1, j.cin_e, j.cout_e, 0, c) && j.w && j.wpack, "conv_march_pack: unsupported shape (%d -> %d channels)", j.cin_e, j.cout_e);
-      const int we_in = j.tflip ? j.cout_w : j.cin_w, we_out = j.tflip ? j.cin_w : j.cout_w;
-      SEUNET_CHECK(we_in <= j.cin_e && we_out <= j.cout_e, "conv_march_pack: weight (%d -> %d) exceeds the tensors (%d -> %d)", we_in, we_out, j.cin_e, j.cout_e);
-      l.e[i] = MarchPackArgs{j.w, j.wpack, j.cin_w, j.cout_w, j.tflip, we_in, we_out, c.ks};
-      l.blocks[i] = (j.cout_e / 16) * 27 * c.ks;
+      if (int e = march_pack_args(dtype, j.w, j.cin_w, j.cout_w, j.tflip, j.cin_e, j.cout_e, j.wpack, l.e[i], l.blocks[i])) return e;
       maxb = l.blocks[i] > maxb ? l.blocks[i] : maxb;
     }
     if (dtype == SEUNET_F16) conv_march_pack_multi_kernel<f16_t><<<dim3(maxb, m), 64, 0, s>>>(l);
@@ -689,14 +674,10 @@ int launch_conv_march(int dtype, int dil, const SrcList& src, const void* wpack,
   const int mode = fwd ? 0 : (any_acc ? 2 : 1);
   MarchCfg c;
   march_cfg(dtype, 27, dil, src.total(), dst.total(), mode, c);
-  const int ry = march_patch_rows(c);
-  a.nyb = cdiv(d.H, ry); a.nxb = cdiv(d.W, MA_TX);
-  a.nblk = a.cout / (16 * c.ngw);
-  const int planes = cdiv(d.D, dil);
-  a.zsteps = march_zsteps(planes, (long long)a.nyb * a.nxb * d.N * a.nblk * dil);
-  a.nseg = cdiv(planes, a.zsteps);
-  SEUNET_CHECK(d.N <= 65535 && (long long)a.nseg * dil * a.nblk <= 65535, "conv_march: grid too large");
-  dim3 grid(a.nyb * a.nxb, a.nseg * dil * a.nblk, d.N);
+  const MarchCut cut = march_cut(c, d, dil, a.cout);
+  a.nyb = cut.nyb; a.nxb = cut.nxb; a.nblk = cut.nblk; a.zsteps = cut.zsteps; a.nseg = cut.nseg;
+  SEUNET_CHECK(d.N <= 65535 && (long long)cut.nseg * dil * cut.nblk <= 65535, "conv_march: grid too large");
+  const dim3 grid = cut.grid(d.N);
   if (dtype == SEUNET_F16) return dil == 1 ? march_launch_cfg<f16_t, 1>(c, mode, a, grid, s) : march_launch_cfg<f16_t, 2>(c, mode, a, grid, s);
   return dil == 1 ? march_launch_cfg<bf16_t, 1>(c, mode, a, grid, s) : march_launch_cfg<bf16_t, 2>(c, mode, a, grid, s);
 }

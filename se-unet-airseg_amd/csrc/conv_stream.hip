@@ -29,27 +29,11 @@
 // of consecutive voxels (conflict-free), DMA instructions write 1 KB contiguous.
 #include "seunet_common.h"
 #include "lds_dma.h"
-#include <utility>
-#include <type_traits>
+#include "mfma.h"
 
 namespace seunet {
 
 extern unsigned long long* g_conv_debug;   // conv_igemm.hip (diagnostic builds)
-
-typedef bf16_t bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x2s __attribute__((ext_vector_type(2)));
-typedef f16_t f16x8s __attribute__((ext_vector_type(8)));
-// fragments are 8 x 16-bit patterns; the matrix instruction follows the storage type (bf16 | f16)
-template <typename T> __device__ __forceinline__ f32x16 st_mfma32(bf16x8 a, bf16x8 b, f32x16 c) {
-  if constexpr (std::is_same<T, f16_t>::value) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8s, a), __builtin_bit_cast(f16x8s, b), c, 0, 0, 0);
-  else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-template <typename T> __device__ __forceinline__ f32x4 st_mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
-  if constexpr (std::is_same<T, f16_t>::value) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8s, a), __builtin_bit_cast(f16x8s, b), c, 0, 0, 0);
-  else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
 
 struct StreamArgs {
   const void* src; const void* wpack; const float* bias;
@@ -175,9 +159,7 @@ conv_stream_kernel(StreamArgs a) {
   };
   auto dma_plane = [&](int s, int slot) __attribute__((always_inline)) {
     const PlaneRef r = plane_of(s, slot);
-    [&]<int... I>(std::integer_sequence<int, I...>) __attribute__((always_inline)) {
-      (dma_item(r, std::integral_constant<int, I>{}), ...);
-    }(std::make_integer_sequence<int, ITEMS>{});
+    static_for<ITEMS>([&](auto i_c) __attribute__((always_inline)) { dma_item(r, i_c); });
   };
 
   // gradient accumulation (DACC): the destination row this wave will finish at step s arrives by one more DMA instruction,
@@ -336,33 +318,29 @@ conv_stream_kernel(StreamArgs a) {
 #pragma unroll
       for (int e = 0; e < ACCR; ++e) cinit[e] = (FWD && COUTP == 16) ? bias_r[BR == 1 ? 0 : e] : 0.f;
     }
-    [&]<int... RI>(std::integer_sequence<int, RI...>) __attribute__((always_inline)) {
-      ([&]() __attribute__((always_inline)) {
-        constexpr int ri = RI;                             // input row y = ra + DIL * (ri - 1): tap dy = ri - 1
-        load_row(std::integral_constant<int, ri + 1>{});
-        [&]<int... I>(std::integer_sequence<int, I...>) __attribute__((always_inline)) {
-          (((I % 3) == ri ? dma_item(pref, std::integral_constant<int, I>{}) : (void)0), ...);
-        }(std::make_integer_sequence<int, ITEMS>{});
-        if (ri == 2) dma_old(s + Geo::PF, slot_pf);
-        __builtin_amdgcn_sched_barrier(0);                 // (the next row's reads stay ahead of this row's MFMAs)
+    static_for<3>([&](auto ri_c) __attribute__((always_inline)) {
+      constexpr int ri = decltype(ri_c)::value;          // input row y = ra + DIL * (ri - 1): tap dy = ri - 1
+      load_row(std::integral_constant<int, ri + 1>{});
+      static_for<ITEMS>([&](auto i_c) __attribute__((always_inline)) { if constexpr (decltype(i_c)::value % 3 == ri) dma_item(pref, i_c); });
+      if (ri == 2) dma_old(s + Geo::PF, slot_pf);
+      __builtin_amdgcn_sched_barrier(0);                 // (the next row's reads stay ahead of this row's MFMAs)
 #pragma unroll
-        for (int dxi = 0; dxi < NDX; ++dxi)
+      for (int dxi = 0; dxi < NDX; ++dxi)
 #pragma unroll
-          for (int dz = -1; dz <= 1; ++dz) {               // output plane s - dz
-            const int ai = (PH - dz + 3) % 3;
-            const int tap = ((dz + 1) * 3 + ri) * NDX + dxi;
-            // the set that the previous step finished starts over here (tap dz = -1 of the first row): its first MFMA takes
-            // the bias vector (forward) / zero as C, so nothing is ever zeroed and the epilogue adds no bias
-            const bool first = dz == -1 && ri == 0 && dxi == 0;
+        for (int dz = -1; dz <= 1; ++dz) {               // output plane s - dz
+          const int ai = (PH - dz + 3) % 3;
+          const int tap = ((dz + 1) * 3 + ri) * NDX + dxi;
+          // the set that the previous step finished starts over here (tap dz = -1 of the first row): its first MFMA takes
+          // the bias vector (forward) / zero as C, so nothing is ever zeroed and the epilogue adds no bias
+          const bool first = dz == -1 && ri == 0 && dxi == 0;
 #pragma unroll
-            for (int b = 0; b < NBX; ++b) {
-              if constexpr (COUTP == 32) acc[ai][b] = st_mfma32<T>(wreg[tap], fr[ri & 1][dxi][b], first ? cinit : acc[ai][b]);
-              else acc[ai][b] = st_mfma16<T>(wreg[tap], fr[ri & 1][dxi][b], first ? cinit : acc[ai][b]);
-            }
+          for (int b = 0; b < NBX; ++b) {
+            if constexpr (COUTP == 32) acc[ai][b] = mfma_32x32x16<T>(wreg[tap], fr[ri & 1][dxi][b], first ? cinit : acc[ai][b]);
+            else acc[ai][b] = mfma_16x16x32<T>(wreg[tap], fr[ri & 1][dxi][b], first ? cinit : acc[ai][b]);
           }
-        __builtin_amdgcn_sched_barrier(0);
-      }(), ...);
-    }(std::make_integer_sequence<int, 3>{});
+        }
+      __builtin_amdgcn_sched_barrier(0);
+    });
   };
 
   // ---- epilogue of the finished output plane q = (q0 - 1 + s) - 1 held in acc[(PH + 2) % 3] ----
@@ -392,14 +370,14 @@ conv_stream_kernel(StreamArgs a) {
       SSTAMP(6);   // statistics
 #endif
       // runs of 4 consecutive channels -> 8-byte pieces
-      u32x2s u[ACCR / 4];
+      u32x2 u[ACCR / 4];
 #pragma unroll
       for (int pc = 0; pc < ACCR / 4; ++pc) {
         float w4[4] = {v[4 * pc], v[4 * pc + 1], v[4 * pc + 2], v[4 * pc + 3]};
         if constexpr (DACC) {
           const int c0 = chan(4 * pc);
-          const u32x2s o = *reinterpret_cast<const u32x2s*>(smem + Geo::OLD + (slot * ST_NW + wave) * Geo::OLDI * 1024 +
-                                                             ((b * NB + fn) * a.dstC + c0) * (int)sizeof(T));
+          const u32x2 o = *reinterpret_cast<const u32x2*>(smem + Geo::OLD + (slot * ST_NW + wave) * Geo::OLDI * 1024 +
+                                                           ((b * NB + fn) * a.dstC + c0) * (int)sizeof(T));
           w4[0] += unpack_lo<T>(o.x); w4[1] += unpack_hi<T>(o.x);
           w4[2] += unpack_lo<T>(o.y); w4[3] += unpack_hi<T>(o.y);
         }
@@ -412,7 +390,7 @@ conv_stream_kernel(StreamArgs a) {
       } else {
 #pragma unroll
         for (int pc = 0; pc < ACCR / 4; ++pc)
-          *reinterpret_cast<u32x2s*>(smem + stg_w[b][pc]) = u[pc];
+          *reinterpret_cast<u32x2*>(smem + stg_w[b][pc]) = u[pc];
       }
       SSTAMP(7);     // packing + store issue
     }
@@ -422,7 +400,7 @@ conv_stream_kernel(StreamArgs a) {
       asm volatile("" ::: "memory");
 #pragma unroll
       for (int k = 0; k < NSTG; ++k) {
-        const u32x2s qv = *reinterpret_cast<const u32x2s*>(smem + stg_r[k]);
+        const u32x2 qv = *reinterpret_cast<const u32x2*>(smem + stg_r[k]);
         __builtin_amdgcn_raw_buffer_store_b64(qv, rd, stg_o[k], soff, 0);
       }
       asm volatile("" ::: "memory");
@@ -452,6 +430,7 @@ conv_stream_kernel(StreamArgs a) {
   SSTAMP(0);   // prologue: plans, weights, first planes
   int slot = 0, slot_pf = Geo::PF;         // s % Geo::RING, (s + Geo::PF) % Geo::RING
   for (int s0 = 0; s0 < nsteps; s0 += 3) {
+    // (spelled out, not static_for: with the step as a lambda ARGUMENT the compiler lays the three steps out differently)
     [&]<int... PH>(std::integer_sequence<int, PH...>) __attribute__((always_inline)) {
       ([&]() __attribute__((always_inline)) {
         const int s = s0 + PH;
@@ -571,7 +550,14 @@ bool conv_stream_supported(int dtype, int taps, int dil, int src_c, int dst_c) {
 
 size_t conv_stream_wpack_bytes(int src_c) { return (size_t)27 * 64 * 16; (void)src_c; }
 
-static int stream_zsteps(Dims d, int dil) {
+// The launch cut of one sample: patches, z segments per parity class, output planes per segment.  conv_stream_slots() and
+// launch_conv_stream() both take it from stream_cut(); the grid and the statistics records follow from it alone.
+struct StreamCut {
+  int planes, zsteps, nzseg, nyb, nxb, dil;
+  int slots() const { return nyb * nxb * nzseg * dil; }                    // statistics records per sample: one per workgroup
+  dim3 grid(int n) const { return dim3(nyb * nxb, nzseg * dil, n); }
+};
+static StreamCut stream_cut(Dims d, int dil) {
   // Output planes per workgroup.  Every workgroup pays a prologue (plan, weights, first planes: 8 % of a wave's time at 34 steps,
   // round-4 stamps) and two halo steps, and the kernels with more than 128 registers per lane (every variant but the 8-channel
   // one) have ONE workgroup resident per CU, so nothing hides them: the march is as long as the volume allows while a batch of
@@ -582,19 +568,20 @@ static int stream_zsteps(Dims d, int dil) {
   // the statistics records, hence the bits of a sample's result, must not depend on the batch it sits in (the data-parallel
   // equivalence tests and the window loop rely on that), so a batch of one 128^3 sample fills a quarter of the chip here.
   constexpr int target = 256;
-  const int planes = cdiv(d.D, dil);
-  const long long base = (long long)cdiv(d.H, ST_TY) * cdiv(d.W, ST_TX) * dil * 4;
+  StreamCut c;
+  c.dil = dil;
+  c.planes = cdiv(d.D, dil);
+  c.nyb = cdiv(d.H, ST_TY); c.nxb = cdiv(d.W, ST_TX);
+  const long long base = (long long)c.nyb * c.nxb * dil * 4;
   long long segs = (target + base - 1) / base;
-  const int cap = cdiv(planes, 8);
+  const int cap = cdiv(c.planes, 8);
   if (segs > cap) segs = cap;
   if (segs < 1) segs = 1;
-  return cdiv(planes, (int)segs);
+  c.zsteps = cdiv(c.planes, (int)segs);
+  c.nzseg = cdiv(c.planes, c.zsteps);
+  return c;
 }
-int conv_stream_slots(Dims d, int dil) {
-  const int planes = cdiv(d.D, dil);
-  const int zs = stream_zsteps(d, dil);
-  return cdiv(d.H, ST_TY) * cdiv(d.W, ST_TX) * cdiv(planes, zs) * dil;
-}
+int conv_stream_slots(Dims d, int dil) { return stream_cut(d, dil).slots(); }
 
 static int stream_pack_args(int dtype, const float* w, int cin_w, int cout_w, int tflip, int src_c, int dst_c, void* wpack, StreamPackArgs& p) {
   const int cin_e = tflip ? cout_w : cin_w, cout_e = tflip ? cin_w : cout_w;
@@ -671,12 +658,10 @@ int launch_conv_stream(int dtype, int dil, const void* src, int src_c, const voi
   a.debug = g_conv_debug;
   SEUNET_CHECK(a.zero != nullptr, "conv_stream: no zero page on this device");
   a.N = d.N; a.D = d.D; a.H = d.H; a.W = d.W;
-  const int planes = cdiv(d.D, dil);
-  a.zsteps = stream_zsteps(d, dil);
-  a.nzseg = cdiv(planes, a.zsteps);
-  a.nyb = cdiv(d.H, ST_TY); a.nxb = cdiv(d.W, ST_TX);
-  SEUNET_CHECK(d.N <= 65535 && a.nzseg * dil <= 65535, "conv_stream: grid too large");
-  dim3 grid(a.nyb * a.nxb, a.nzseg * dil, d.N);
+  const StreamCut cut = stream_cut(d, dil);
+  a.zsteps = cut.zsteps; a.nzseg = cut.nzseg; a.nyb = cut.nyb; a.nxb = cut.nxb;
+  const dim3 grid = cut.grid(d.N);
+  SEUNET_CHECK(grid.z <= 65535 && grid.y <= 65535, "conv_stream: grid too large");
   return dtype == SEUNET_F16 ? stream_dispatch<f16_t>(var, dil, a, grid, s) : stream_dispatch<bf16_t>(var, dil, a, grid, s);
 }
 

@@ -19,17 +19,13 @@
 //               second kernel sums the slabs 16-way parallel in a fixed order (deterministic, no atomics, f64) straight
 //               into the PyTorch (Cout,Cin,3,3,3) layout
 #include "seunet_common.h"
-#include <utility>
+#include "mfma.h"
+#include <climits>
 #include <cstdlib>
-#include <type_traits>
 
 namespace seunet {
 
 extern unsigned long long* g_conv_debug;   // conv_igemm.hip
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef bf16_t bf16x4 __attribute__((ext_vector_type(4)));
-typedef bf16_t bf16x8 __attribute__((ext_vector_type(8)));
 
 struct WgArgs {
   const void* src0; const void* src1; const void* src2;
@@ -148,7 +144,6 @@ wgrad_kernel(WgArgs a) {
   // across the MFMA phase, and the spills that follow reload through scratch behind s_waitcnt vmcnt(0) -- i.e. behind
   // every DMA already in flight
   static_assert(XG <= 16 && HZ <= 4 && HY <= 8 && HX <= 64, "packed halo coordinates");
-  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
   u32x4* cslot = reinterpret_cast<u32x4*>(smem + PPV * (XPL + YPL) + tid * 32);
   {
     unsigned w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -255,8 +250,6 @@ wgrad_kernel(WgArgs a) {
       // behind a full LDS latency: the phase ran at half speed) plus a separate address register per step.  Here the A
       // fragments of step s + 2 and the B fragments of the next (row, kk) are requested before the MFMA of step s
       // issues (rotating buffers, compile-time indices), and a step's address is "per-tap base register + immediate".
-      typedef __attribute__((address_space(3))) bf16x4 lds_b4;
-      typedef float f32x4 __attribute__((ext_vector_type(4)));
       constexpr int ROWS = (TAPS == 27) ? TZ * TY : TZ * TY / NW;    // 1x1x1: the rows are split over the waves
       constexpr int NSTEP = ROWS * NT;                               // one step = (row, tap): 2 x 2 MFMAs of 16x16x32
       auto a_off = [](int ri) constexpr {   // byte offset of a row inside the X image, relative to the tap base
@@ -274,8 +267,8 @@ wgrad_kernel(WgArgs a) {
           constexpr int ti = st % NT, ri = st / NT;
 #pragma unroll
           for (int blk = 0; blk < 2; ++blk) {
-            abuf[st % 3][blk][0] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b4*)(abase[ti] + a_off(ri) + blk * 2 * XPL));
-            abuf[st % 3][blk][1] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b4*)(abase[ti] + a_off(ri) + blk * 2 * XPL + 64));
+            abuf[st % 3][blk][0] = read_tr16((const lds_bf16x4*)(abase[ti] + a_off(ri) + blk * 2 * XPL));
+            abuf[st % 3][blk][1] = read_tr16((const lds_bf16x4*)(abase[ti] + a_off(ri) + blk * 2 * XPL + 64));
           }
         }
       };
@@ -284,40 +277,33 @@ wgrad_kernel(WgArgs a) {
         if constexpr (ri < ROWS) {
 #pragma unroll
           for (int blk = 0; blk < 2; ++blk) {
-            bbuf[ri % 2][blk][0] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b4*)(bbase + b_off(ri) + blk * 2 * YPL));
-            bbuf[ri % 2][blk][1] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b4*)(bbase + b_off(ri) + blk * 2 * YPL + 64));
+            bbuf[ri % 2][blk][0] = read_tr16((const lds_bf16x4*)(bbase + b_off(ri) + blk * 2 * YPL));
+            bbuf[ri % 2][blk][1] = read_tr16((const lds_bf16x4*)(bbase + b_off(ri) + blk * 2 * YPL + 64));
           }
         }
       };
       load_b(std::integral_constant<int, 0>{});
       load_a(std::integral_constant<int, 0>{});
       load_a(std::integral_constant<int, 1>{});
-      [&]<int... ST>(std::integer_sequence<int, ST...>) __attribute__((always_inline)) {
-        ([&]() __attribute__((always_inline)) {
-          constexpr int ti = ST % NT, ri = ST / NT;
-          load_a(std::integral_constant<int, ST + 2>{});
-          if constexpr (ti == 0) load_b(std::integral_constant<int, ri + 1>{});
-          __builtin_amdgcn_sched_barrier(0);   // (the reads stay ahead of this step's MFMAs)
+      static_for<NSTEP>([&](auto st_c) __attribute__((always_inline)) {
+        constexpr int ST = decltype(st_c)::value, ti = ST % NT, ri = ST / NT;
+        load_a(std::integral_constant<int, ST + 2>{});
+        if constexpr (ti == 0) load_b(std::integral_constant<int, ri + 1>{});
+        __builtin_amdgcn_sched_barrier(0);   // (the reads stay ahead of this step's MFMAs)
 #pragma unroll
-          for (int ab = 0; ab < 2; ++ab) {
-            const bf16x8 afr = __builtin_shufflevector(abuf[ST % 3][ab][0], abuf[ST % 3][ab][1], 0, 1, 2, 3, 4, 5, 6, 7);
+        for (int ab = 0; ab < 2; ++ab) {
+          const bf16x8 afr = frag_join(abuf[ST % 3][ab][0], abuf[ST % 3][ab][1]);
 #pragma unroll
-            for (int bb = 0; bb < 2; ++bb) {
-              const bf16x8 bfr = __builtin_shufflevector(bbuf[ri % 2][bb][0], bbuf[ri % 2][bb][1], 0, 1, 2, 3, 4, 5, 6, 7);
-              const int q = 4 * (2 * ab + bb);           // block (ab, bb) lives in elements q .. q + 3 of acc[ti]
-              f32x4 c = {acc[ti][q], acc[ti][q + 1], acc[ti][q + 2], acc[ti][q + 3]};
-              if constexpr (std::is_same<T, f16_t>::value) {   // (the transposing LDS read is type-agnostic: 16-bit patterns)
-                typedef f16_t f16x8 __attribute__((ext_vector_type(8)));
-                c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, afr), __builtin_bit_cast(f16x8, bfr), c, 0, 0, 0);
-              } else {
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afr, bfr, c, 0, 0, 0);
-              }
-              acc[ti][q] = c[0]; acc[ti][q + 1] = c[1]; acc[ti][q + 2] = c[2]; acc[ti][q + 3] = c[3];
-            }
+          for (int bb = 0; bb < 2; ++bb) {
+            const bf16x8 bfr = frag_join(bbuf[ri % 2][bb][0], bbuf[ri % 2][bb][1]);
+            const int q = 4 * (2 * ab + bb);           // block (ab, bb) lives in elements q .. q + 3 of acc[ti]
+            f32x4 c = {acc[ti][q], acc[ti][q + 1], acc[ti][q + 2], acc[ti][q + 3]};
+            c = mfma_16x16x32<T>(afr, bfr, c);
+            acc[ti][q] = c[0]; acc[ti][q + 1] = c[1]; acc[ti][q + 2] = c[2]; acc[ti][q + 3] = c[3];
           }
-          __builtin_amdgcn_sched_barrier(0);   // keep the issue order written here
-        }(), ...);
-      }(std::make_integer_sequence<int, NSTEP>{});
+        }
+        __builtin_amdgcn_sched_barrier(0);   // keep the issue order written here
+      });
     } else {
       for (int row = 0; row < TZ * TY; ++row) {
         if (TAPS == 1 && (row % NW) != wave) continue;   // 1x1x1: rows are split over the waves
@@ -419,23 +405,24 @@ wgrad_reduce_kernel(const float* __restrict__ slab, int nslab, int taps, int cin
 
 // persistent workgroups per (ci, co) combo == slabs the reduce kernel has to sum; ~2 resident workgroups per CU in total
 static inline int wgrad_groups(int combos, int total_tiles) {
-  int g = 512 / combos;   // two resident workgroups per CU
+  int g = WG_TILED_SLABS / combos;   // two resident workgroups per CU
   if (g < 16) g = 16;
-  if (g > 512) g = 512;
+  if (g > WG_TILED_SLABS) g = WG_TILED_SLABS;
   if (g > total_tiles) g = total_tiles;
   if (g < 1) g = 1;
   return g;
 }
+static size_t wgrad_tiled_bytes(int taps, int combos, int groups) {
+  return 256 + (size_t)combos * groups * taps * 1024 * sizeof(float);   // 256 zero bytes + slabs
+}
 
+// one workspace serves whichever weight-gradient kernel the layer is routed to: the most any of them asks for these channels,
+// whatever the volume (each term is defined next to the launcher that checks it)
 size_t wgrad_workspace_bytes(int taps, int cin, int cout) {
   const int combos = cdiv(cin, 32) * cdiv(cout, 32);
-  const int g = 512 / combos < 16 ? 16 : (512 / combos > 512 ? 512 : 512 / combos);
-  size_t bytes = 256 + (size_t)combos * g * taps * 1024 * sizeof(float);   // 256 zero bytes + slabs
-  if (taps == 1) {   // the whole-GEMM 1x1x1 kernel (wgrad_1x1.hip): 256 workgroups x all 16 x 16 pairs
-    const size_t b1 = 256 + (size_t)256 * (size_t)(cdiv(cin, 64) * 4) * (size_t)cdiv(cout, 16) * 256 * sizeof(float);
-    if (b1 > bytes) bytes = b1;
-  }
-  return bytes;
+  const size_t tiled = wgrad_tiled_bytes(taps, combos, wgrad_groups(combos, INT_MAX));
+  const size_t other = taps == 1 ? wgrad_1x1_workspace_bytes(cin, cout) : wgrad_march_workspace_bytes(taps, cin, cout);
+  return tiled > other ? tiled : other;
 }
 
 template <typename T, int TAPS, int DIL, int NW>
@@ -452,6 +439,15 @@ static int wgrad_launch_one(const WgArgs& a, dim3 grid, hipStream_t s) {
   return 0;
 }
 
+static void wg_sources(WgArgs& a, const SrcList& x, int cin_logical) {   // the virtual concatenation and its channel bounds
+  a.src0 = x.ptr[0]; a.srcC0 = x.C[0];
+  a.src1 = x.n > 1 ? x.ptr[1] : nullptr; a.srcC1 = x.n > 1 ? x.C[1] : 0;
+  a.src2 = x.n > 2 ? x.ptr[2] : nullptr; a.srcC2 = x.n > 2 ? x.C[2] : 0;
+  a.cin = cin_logical;
+  a.cum1 = x.n > 1 ? x.C[0] : x.total();
+  a.cum2 = x.n > 2 ? x.C[0] + x.C[1] : x.total();
+}
+
 // x: input activation (may be a concatenation), cin_logical leading channels carry weights;
 // dy: gradient w.r.t. the raw conv output, [N][V][cout]; dw: (cout, cin_logical, taps) f32, overwritten.
 int launch_wgrad(int dtype, int taps, int dil, const SrcList& x, int cin_logical, const void* dy, int cout,
@@ -462,12 +458,7 @@ int launch_wgrad(int dtype, int taps, int dil, const SrcList& x, int cin_logical
   SEUNET_CHECK(cout % 8 == 0 && cin_logical >= 1 && cin_logical <= x.total(), "wgrad: bad channel counts");
   SEUNET_CHECK(ws_bytes >= wgrad_workspace_bytes(taps, cin_logical, cout), "wgrad: workspace too small");
   WgArgs a{};
-  a.src0 = x.ptr[0]; a.srcC0 = x.C[0];
-  a.src1 = x.n > 1 ? x.ptr[1] : nullptr; a.srcC1 = x.n > 1 ? x.C[1] : 0;
-  a.src2 = x.n > 2 ? x.ptr[2] : nullptr; a.srcC2 = x.n > 2 ? x.C[2] : 0;
-  a.cin = cin_logical;
-  a.cum1 = x.n > 1 ? x.C[0] : x.total();
-  a.cum2 = x.n > 2 ? x.C[0] + x.C[1] : x.total();
+  wg_sources(a, x, cin_logical);
   a.dy = dy; a.cout = cout;
   a.zero = device_zero_page();
   SEUNET_CHECK(a.zero != nullptr, "wgrad: cannot allocate the device zero page");
@@ -535,12 +526,7 @@ __global__ void wgrad_naive_kernel(WgArgs a, int taps, int dil, float* __restric
 int launch_wgrad_naive(int dtype, int taps, int dil, const SrcList& x, int cin_logical, const void* dy, int cout,
                        float* dw, Dims d, hipStream_t s) {
   WgArgs a{};
-  a.src0 = x.ptr[0]; a.srcC0 = x.C[0];
-  a.src1 = x.n > 1 ? x.ptr[1] : nullptr; a.srcC1 = x.n > 1 ? x.C[1] : 0;
-  a.src2 = x.n > 2 ? x.ptr[2] : nullptr; a.srcC2 = x.n > 2 ? x.C[2] : 0;
-  a.cin = cin_logical;
-  a.cum1 = x.n > 1 ? x.C[0] : x.total();
-  a.cum2 = x.n > 2 ? x.C[0] + x.C[1] : x.total();
+  wg_sources(a, x, cin_logical);
   a.dy = dy; a.cout = cout;
   a.N = d.N; a.D = d.D; a.H = d.H; a.W = d.W;
   const long long total = (long long)cout * cin_logical * taps;

@@ -14,16 +14,10 @@
 //   * one slab per workgroup, fixed-order f64 slab sum (deterministic, no atomics).
 #include "seunet_common.h"
 #include "lds_dma.h"
-#include <utility>
-#include <type_traits>
+#include "mfma.h"
 #include <cstdlib>
 
 namespace seunet {
-
-typedef bf16_t w1b16x4 __attribute__((ext_vector_type(4)));
-typedef bf16_t w1b16x8 __attribute__((ext_vector_type(8)));
-typedef f16_t w1f16x8 __attribute__((ext_vector_type(8)));
-typedef float w1f32x4 __attribute__((ext_vector_type(4)));
 
 struct W1Args {
   const void* src[3]; int srcC[3]; int nsrc;      // X: up to three tensors of 32 or 64 channels each
@@ -35,27 +29,6 @@ struct W1Args {
 };
 
 static constexpr int W1_NW = 4;
-
-// piece permutation of voxel v in a record of np 16-byte pieces (np = 4, 8, 16): a transposing read takes, per 16 lanes, 4
-// consecutive voxels x two adjacent pieces; 32 lanes = voxels v..v+3 and v+8..v+11 (see wgrad_march.hip).  XOR on the pair index.
-__device__ __forceinline__ int w1_swz(int np, int v) {
-  if (np == 4) return ((v >> 3) & 1) << 1;
-  if (np == 8) return (((v >> 1) & 1) | (((v >> 3) & 1) << 1)) << 1;
-  return ((v & 3) | (((v >> 3) & 1) << 2)) << 1;
-}
-
-template <typename T> __device__ __forceinline__ w1f32x4 w1_mfma(w1b16x8 a, w1b16x8 b, w1f32x4 c) {
-  if constexpr (std::is_same<T, f16_t>::value)
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(w1f16x8, a), __builtin_bit_cast(w1f16x8, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ w1b16x8 w1_frag(unsigned addr0, unsigned addr1) {
-  typedef __attribute__((address_space(3))) w1b16x4 lds_b4;
-  const w1b16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b4*)(size_t)addr0);
-  const w1b16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b4*)(size_t)addr1);
-  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
 
 // CIBW: 16-channel input blocks per wave; NCOB: 16-channel output blocks (all of them, every wave); CH: voxels per chunk
 template <typename T, int CIBW, int NCOB, int CH>
@@ -88,7 +61,7 @@ wgrad_1x1_kernel(W1Args a) {
 #pragma unroll
       for (int r = 0; r < 2; ++r) {
         const int v = 32 * ks + 8 * grp + 4 * r + q;
-        xoff[c][ks][r] = (unsigned)(roff[s] + v * C * 2 + (((cl / 8 + (p >> 1)) ^ w1_swz(np, v)) * 16) + (p & 1) * 8);
+        xoff[c][ks][r] = (unsigned)(roff[s] + v * C * 2 + (((cl / 8 + (p >> 1)) ^ tr16_swz(np, v)) * 16) + (p & 1) * 8);
       }
   }
   {
@@ -100,7 +73,7 @@ wgrad_1x1_kernel(W1Args a) {
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
           const int v = 32 * ks + 8 * grp + 4 * r + q;
-          yoff[k][ks][r] = (unsigned)(yoff0 + v * a.cout * 2 + (((k * 2 + (p >> 1)) ^ w1_swz(npy, v)) * 16) + (p & 1) * 8);
+          yoff[k][ks][r] = (unsigned)(yoff0 + v * a.cout * 2 + (((k * 2 + (p >> 1)) ^ tr16_swz(npy, v)) * 16) + (p & 1) * 8);
         }
   }
 
@@ -125,7 +98,7 @@ wgrad_1x1_kernel(W1Args a) {
     else { sel = 0; C = a.srcC[0]; rel = byte; }
     const int sh = 31 - __clz(C * 2);                        // records are 64, 128 or 256 bytes
     const int v = rel >> sh, slot = (rel & (C * 2 - 1)) >> 4;
-    const int piece = slot ^ w1_swz(C / 8, v);
+    const int piece = slot ^ tr16_swz(C / 8, v);
     plan[it] = (it < items && id < ni) ? ((unsigned)sel | ((unsigned)((v << sh) + piece * 16) << 4) | ((unsigned)v << 20)) : 0xFFFFFFFFu;
   }
   const unsigned char* zero_page = reinterpret_cast<const unsigned char*>(a.zero) + lane * 16;
@@ -152,11 +125,11 @@ wgrad_1x1_kernel(W1Args a) {
     }
   };
 
-  w1f32x4 acc[CIBW][NCOB];
+  f32x4 acc[CIBW][NCOB];
 #pragma unroll
   for (int c = 0; c < CIBW; ++c)
 #pragma unroll
-    for (int k = 0; k < NCOB; ++k) acc[c][k] = w1f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int k = 0; k < NCOB; ++k) acc[c][k] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   // chunks blockIdx.x, blockIdx.x + gridDim.x, ...; PF = nst - 1 chunks are in flight ahead of the one being multiplied (the
   // launch is bound by HBM latency x bytes in flight: two stages of 24 KB per CU were 3.6 TB/s)
@@ -180,15 +153,15 @@ wgrad_1x1_kernel(W1Args a) {
     const unsigned sb = lds_base + (unsigned)(st * stage);
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-      w1b16x8 xf[CIBW], yf[NCOB];
+      bf16x8 xf[CIBW], yf[NCOB];
 #pragma unroll
-      for (int c = 0; c < CIBW; ++c) xf[c] = w1_frag(sb + xoff[c][ks][0], sb + xoff[c][ks][1]);
+      for (int c = 0; c < CIBW; ++c) xf[c] = frag_tr16(sb + xoff[c][ks][0], sb + xoff[c][ks][1]);
 #pragma unroll
-      for (int k = 0; k < NCOB; ++k) yf[k] = w1_frag(sb + yoff[k][ks][0], sb + yoff[k][ks][1]);
+      for (int k = 0; k < NCOB; ++k) yf[k] = frag_tr16(sb + yoff[k][ks][0], sb + yoff[k][ks][1]);
 #pragma unroll
       for (int c = 0; c < CIBW; ++c)
 #pragma unroll
-        for (int k = 0; k < NCOB; ++k) acc[c][k] = w1_mfma<T>(yf[k], xf[c], acc[c][k]);
+        for (int k = 0; k < NCOB; ++k) acc[c][k] = mfma_16x16x32<T>(yf[k], xf[c], acc[c][k]);
     }
     __builtin_amdgcn_s_barrier();                            // every wave is done reading this stage before it is refilled
     st = st + 1 == nst ? 0 : st + 1;
@@ -200,7 +173,7 @@ wgrad_1x1_kernel(W1Args a) {
 #pragma unroll
   for (int c = 0; c < CIBW; ++c)
 #pragma unroll
-    for (int k = 0; k < NCOB; ++k) *reinterpret_cast<w1f32x4*>(out + (c * NCOB + k) * 256) = acc[c][k];
+    for (int k = 0; k < NCOB; ++k) *reinterpret_cast<f32x4*>(out + (c * NCOB + k) * 256) = acc[c][k];
 }
 
 // sum of the slabs, 16-way parallel in a fixed order, f64 -> dw (cout, cin)
@@ -261,6 +234,22 @@ bool wgrad_1x1_supported(int dtype, const SrcList& x, int cin_logical, int cout)
   return wgrad_1x1_cfg(dtype, x, cin_logical, cout, c);
 }
 
+// The launch cut: chunks of the flat voxel index, the persistent workgroups that share them, one slab per workgroup.  A slab is
+// [wave][input block of the wave][output block][lane][4]; every admitted configuration has cibw = cin / 64 and ncob = cout / 16,
+// and the workspace bound rounds other channel counts up.
+static constexpr int W1_MAX_WG = 256;                     // one workgroup per CU
+static size_t w1_slab_floats(int cin, int cout) { return (size_t)W1_NW * cdiv(cin, 64) * cdiv(cout, 16) * 256; }
+static size_t w1_bytes(int groups, int cin, int cout) { return 256 + (size_t)groups * w1_slab_floats(cin, cout) * sizeof(float); }   // 256 B reserved + slabs
+struct W1Cut { long long nvox; int nchunk, groups; };
+static W1Cut w1_cut(const W1Cfg& c, Dims d) {
+  W1Cut m;
+  m.nvox = (long long)d.N * d.vox();
+  m.nchunk = (int)((m.nvox + c.ch - 1) / c.ch);
+  m.groups = m.nchunk < W1_MAX_WG ? m.nchunk : W1_MAX_WG;
+  return m;
+}
+size_t wgrad_1x1_workspace_bytes(int cin, int cout) { return w1_bytes(W1_MAX_WG, cin, cout); }
+
 template <typename T, int CIBW, int NCOB, int CH>
 static int wgrad_1x1_launch(const W1Args& a, int grid, int lds, hipStream_t s) {
   static unsigned long long configured = 0;
@@ -275,7 +264,8 @@ int launch_wgrad_1x1(int dtype, const SrcList& x, int cin_logical, const void* d
   W1Cfg c;
   SEUNET_CHECK(wgrad_1x1_cfg(dtype, x, cin_logical, cout, c),
                "wgrad_1x1: 16-bit tensors, 1..3 sources of 32 or 64 channels (64, 128 or 192 together), 32 / 64 / 128 output channels only");
-  SEUNET_CHECK(ws_bytes >= 256, "wgrad_1x1: workspace too small");
+  const W1Cut cut = w1_cut(c, d);
+  SEUNET_CHECK(ws_bytes >= w1_bytes(cut.groups, cin_logical, cout), "wgrad_1x1: workspace too small");
   W1Args a{};
   for (int i = 0; i < 3; ++i) { a.src[i] = i < x.n ? x.ptr[i] : nullptr; a.srcC[i] = i < x.n ? x.C[i] : 0; }
   a.nsrc = x.n;
@@ -283,11 +273,9 @@ int launch_wgrad_1x1(int dtype, const SrcList& x, int cin_logical, const void* d
   a.zero = device_zero_page();
   SEUNET_CHECK(a.zero != nullptr, "wgrad_1x1: cannot allocate the device zero page");
   a.slab = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(workspace) + 256);
-  a.nvox = (long long)d.N * d.vox();
-  a.nchunk = (int)((a.nvox + c.ch - 1) / c.ch);
-  const int grid = a.nchunk < 256 ? a.nchunk : 256;
-  const size_t per = (size_t)W1_NW * c.cibw * c.ncob * 256;
-  SEUNET_CHECK(ws_bytes >= 256 + (size_t)grid * per * sizeof(float), "wgrad_1x1: workspace too small");
+  a.nvox = cut.nvox;
+  a.nchunk = cut.nchunk;
+  const int grid = cut.groups;
   const int lds = (cin_logical + cout) * 2 * c.ch * c.nst + 1024;
   a.nst = c.nst;
   int e = -1;
@@ -300,7 +288,7 @@ int launch_wgrad_1x1(int dtype, const SrcList& x, int cin_logical, const void* d
     else e = wgrad_1x1_launch<T, 3, 8, 64>(a, grid, lds, s);
   });
   if (e) return e;
-  wgrad_1x1_reduce_kernel<<<(unsigned)(per / 16), 256, 0, s>>>(a.slab, grid, c.cibw, c.ncob, cin_logical, dw);
+  wgrad_1x1_reduce_kernel<<<(unsigned)(w1_slab_floats(cin_logical, cout) / 16), 256, 0, s>>>(a.slab, grid, c.cibw, c.ncob, cin_logical, dw);
   SEUNET_LAUNCH_CHECK();
   return 0;
 }

@@ -20,16 +20,10 @@
 //     by a second kernel in a fixed order in f64 (deterministic, no atomics) into the PyTorch (Cout, Cin, 3, 3, 3) layout.
 #include "seunet_common.h"
 #include "lds_dma.h"
-#include <utility>
-#include <type_traits>
+#include "mfma.h"
 #include <cstdlib>
 
 namespace seunet {
-
-typedef bf16_t wmb16x4 __attribute__((ext_vector_type(4)));
-typedef bf16_t wmb16x8 __attribute__((ext_vector_type(8)));
-typedef f16_t wmf16x8 __attribute__((ext_vector_type(8)));
-typedef float wmf32x4 __attribute__((ext_vector_type(4)));
 
 struct WmArgs {
   const void* src0; const void* src1;   // X: one or two tensors of srcC channels each (virtual concatenation)
@@ -60,39 +54,6 @@ template <int NCB, int NOB, int DIL> struct WmGeo {
   static_assert(LDS <= 160 * 1024, "LDS budget");
   static_assert((HY - 1) * ROWBX + WM_HXP * VBX < 65536 && (WM_RY - 1) * ROWBY + WM_TX * VBY < 65536, "immediates");
 };
-
-// piece permutation of the voxel at column v.  A transposing read takes, per 16 lanes, 4 consecutive voxels x 32 bytes (two
-// adjacent pieces); 32 lanes = the voxels v..v+3 and v+8..v+11.  64-byte records: the four voxels already sit in different
-// banks, bit 3 of v separates the two groups.  128-byte records: voxels v and v+2 share their banks -> bit 1 of v moves the
-// piece pair, bit 3 separates the groups.  (XOR acts on the pair index: bit 0 of the piece stays.)
-template <int NP> __device__ __forceinline__ int wm_swz(int v) {
-  if constexpr (NP == 4) return ((v >> 3) & 1) << 1;
-  else return ((((v >> 1) & 1) | (((v >> 3) & 1) << 1))) << 1;
-}
-
-template <int N, typename F> __device__ __forceinline__ void wm_for(F&& f) {
-  [&]<int... I>(std::integer_sequence<int, I...>) __attribute__((always_inline)) {
-    (f(std::integral_constant<int, I>{}), ...);
-  }(std::make_integer_sequence<int, N>{});
-}
-
-// The matrix instruction as inline asm with the accumulator pinned to the accumulator half of the register file ("+a": D = C
-// in place).  Through the builtin the register allocator spread the 216 accumulator registers over both halves and then
-// spilled fragments; the asm leaves the vector half to the fragments and addresses.  Its operands are ordinary data
-// dependencies (the compiler still waits for the LDS reads that produce them); an accumulator is only read back after the
-// last march (behind explicit wait states).
-template <typename T> __device__ __forceinline__ void wm_mfma(wmf32x4& c, wmb16x8 a, wmb16x8 b) {
-  if constexpr (std::is_same<T, f16_t>::value) asm("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
-  else asm("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
-}
-
-// 8 voxels of one channel: two transposing reads of 4 voxels x 16 channels each (lane i of a 16-lane group receives channel i)
-__device__ __forceinline__ wmb16x8 wm_frag(unsigned addr0, unsigned addr1) {
-  typedef __attribute__((address_space(3))) wmb16x4 lds_b4;
-  const wmb16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b4*)(size_t)addr0);
-  const wmb16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b4*)(size_t)addr1);
-  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
 
 // processing order of the X rows: dilation 2 pairs X row hy with the dY rows hy, hy-2, hy-4 -> even rows first, then odd
 template <int DIL, int HY> __host__ __device__ constexpr int wm_row(int i) {
@@ -144,21 +105,21 @@ wgrad_march_kernel(WmArgs a) {
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
       const int hx = DIL * dx + 8 * grp + 4 * r + q;
-      xoff[dx][r] = (unsigned)(hx * VBX + (((cib * 2 + (p >> 1)) ^ wm_swz<NPX>(hx)) * 16) + (p & 1) * 8);
+      xoff[dx][r] = (unsigned)(hx * VBX + (((cib * 2 + (p >> 1)) ^ tr16_swz(NPX, hx)) * 16) + (p & 1) * 8);
     }
 #pragma unroll
   for (int k = 0; k < PW; ++k)
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
       const int v = 8 * grp + 4 * r + q;
-      yoff[k][r] = (unsigned)(v * VBY + ((((cog * PW + k) * 2 + (p >> 1)) ^ wm_swz<NPY>(v)) * 16) + (p & 1) * 8);
+      yoff[k][r] = (unsigned)(v * VBY + ((((cog * PW + k) * 2 + (p >> 1)) ^ tr16_swz(NPY, v)) * 16) + (p & 1) * 8);
     }
 
-  wmf32x4 acc[PW][27];
+  f32x4 acc[PW][27];
 #pragma unroll
   for (int k = 0; k < PW; ++k)
 #pragma unroll
-    for (int t = 0; t < 27; ++t) acc[k][t] = wmf32x4{0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < 27; ++t) acc[k][t] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   const long long xplane = (long long)a.H * a.W * a.srcC * (long long)sizeof(T);
   const long long yplane = (long long)a.H * a.W * a.cout * (long long)sizeof(T);
@@ -199,7 +160,7 @@ wgrad_march_kernel(WmArgs a) {
       const int L = id * 64 + lane;
       const int v = L / NPX, sl = L % NPX;
       const int hy = v / WM_HXP, hx = v % WM_HXP;
-      const int ch = ci0 + ((sl ^ wm_swz<NPX>(hx)) * 8);
+      const int ch = ci0 + ((sl ^ tr16_swz(NPX, hx)) * 8);
       const int y = y0 - DIL + hy, x = x0 - DIL + hx;
       const bool s1 = ch >= a.srcC;
       const int cl = s1 ? ch - a.srcC : ch;
@@ -211,7 +172,7 @@ wgrad_march_kernel(WmArgs a) {
       const int L = (wave + WM_NW * it) * 64 + lane;
       const int v = L / NPY, sl = L % NPY;
       const int r = v / WM_TX, xx = v % WM_TX;
-      const int ch = co0 + ((sl ^ wm_swz<NPY>(xx)) * 8);
+      const int ch = co0 + ((sl ^ tr16_swz(NPY, xx)) * 8);
       const int y = y0 + r, x = x0 + xx;
       doy[it] = (y < a.H && x < a.W) ? (unsigned)(((y * a.W + x) * a.cout + ch) * (int)sizeof(T)) : 0xFFFFFFFFu;
     }
@@ -269,16 +230,16 @@ wgrad_march_kernel(WmArgs a) {
           for (int r = 0; r < 2; ++r) ya[tz][k][r] = pb + yoff[k][r];
       }
     };
-    wmb16x8 xf[2][3];
-    wmb16x8 yw[RY][3][PW];
+    bf16x8 xf[2][3];
+    bf16x8 yw[RY][3][PW];
     // fragment f of row i (processing order) of the current addresses: f < 3: X, x-tap f; else dY row hy of plane tz, pair k
     auto load_frag = [&](auto i_c, auto f_c) __attribute__((always_inline)) {
       constexpr int i = decltype(i_c)::value, f = decltype(f_c)::value;
       constexpr int hy = wm_row<DIL, HY>(i);
-      if constexpr (f < 3) xf[i & 1][f] = wm_frag(xa[f][0] + hy * ROWBX, xa[f][1] + hy * ROWBX);
+      if constexpr (f < 3) xf[i & 1][f] = frag_tr16(xa[f][0] + hy * ROWBX, xa[f][1] + hy * ROWBX);
       else {
         constexpr int tz = (f - 3) / PW, k = (f - 3) % PW;
-        yw[hy][tz][k] = wm_frag(ya[tz][k][0] + hy * ROWBY, ya[tz][k][1] + hy * ROWBY);
+        yw[hy][tz][k] = frag_tr16(ya[tz][k][0] + hy * ROWBY, ya[tz][k][1] + hy * ROWBY);
       }
     };
     // MFMA m of row i: (the m / 9PW-th valid y-tap, oldest dY row first; dz; x-tap; pair)
@@ -289,7 +250,7 @@ wgrad_march_kernel(WmArgs a) {
       constexpr int rem = m % (9 * PW), tz = rem / (3 * PW), dx = (rem / PW) % 3, k = rem % PW;
       constexpr int r = hy - DIL * ty;
       static_assert(r >= 0 && r < RY, "row pairing");
-      wm_mfma<T>(acc[k][(tz * 3 + ty) * 3 + dx], yw[r][tz][k], xf[i & 1][dx]);
+      mfma_16x16x32_pinned<T>(acc[k][(tz * 3 + ty) * 3 + dx], yw[r][tz][k], xf[i & 1][dx]);
     };
     // one row: the fragments of row `nx` are requested one by one between equal shares of row i's MFMAs (hand-placed:
     // sched_barrier fences keep the order), so that every read has most of a row of MFMAs to land
@@ -297,10 +258,10 @@ wgrad_march_kernel(WmArgs a) {
       constexpr int i = decltype(i_c)::value, nx = decltype(nx_c)::value;
       constexpr int NF = wm_row_frags<DIL, HY, PW>(nx), NM = wm_row_mfmas<DIL, HY, PW>(i);
       extra();
-      wm_for<NF>([&](auto g_c) __attribute__((always_inline)) {
+      static_for<NF>([&](auto g_c) __attribute__((always_inline)) {
         constexpr int g = decltype(g_c)::value;
         load_frag(nx_c, g_c);
-        wm_for<(g + 1) * NM / NF - g * NM / NF>([&](auto j_c) __attribute__((always_inline)) {
+        static_for<(g + 1) * NM / NF - g * NM / NF>([&](auto j_c) __attribute__((always_inline)) {
           mfma_one(i_c, std::integral_constant<int, g * NM / NF + decltype(j_c)::value>{});
         });
         __builtin_amdgcn_sched_barrier(0);
@@ -318,22 +279,22 @@ wgrad_march_kernel(WmArgs a) {
     if (nsteps == 0) continue;           // (block-uniform)
     {
       const PlaneRef p0 = plane_of(0, 0, 0), p1 = plane_of(1, 1, 1);
-      wm_for<LOADS_PER_STEP>([&](auto it_c) __attribute__((always_inline)) { issue_item(p0, it_c); });
-      wm_for<LOADS_PER_STEP>([&](auto it_c) __attribute__((always_inline)) { issue_item(p1, it_c); });
+      static_for<LOADS_PER_STEP>([&](auto it_c) __attribute__((always_inline)) { issue_item(p0, it_c); });
+      static_for<LOADS_PER_STEP>([&](auto it_c) __attribute__((always_inline)) { issue_item(p1, it_c); });
     }
     wait_loads<LOADS_PER_STEP>();
     __builtin_amdgcn_s_barrier();
     int xs = 0, ys = 0;                  // ring slots of step s: s % 3, s % 5
     set_addr(0, 0, 0);
-    wm_for<wm_row_frags<DIL, HY, PW>(0)>([&](auto f_c) __attribute__((always_inline)) { load_frag(std::integral_constant<int, 0>{}, f_c); });
+    static_for<wm_row_frags<DIL, HY, PW>(0)>([&](auto f_c) __attribute__((always_inline)) { load_frag(std::integral_constant<int, 0>{}, f_c); });
     for (int s = 0; s < nsteps; ++s) {
       const int xs2 = xs + 2 >= WM_XRING ? xs + 2 - WM_XRING : xs + 2;
       const int ys2 = ys + 2 >= WM_YRING ? ys + 2 - WM_YRING : ys + 2;
       const PlaneRef pr = plane_of(s + 2, xs2, ys2);
-      wm_for<HY - 1>([&](auto i_c) __attribute__((always_inline)) {
+      static_for<HY - 1>([&](auto i_c) __attribute__((always_inline)) {
         constexpr int i = decltype(i_c)::value;
         row(i_c, std::integral_constant<int, i + 1>{}, [&]() __attribute__((always_inline)) {
-          wm_for<LOADS_PER_STEP>([&](auto it_c) __attribute__((always_inline)) {
+          static_for<LOADS_PER_STEP>([&](auto it_c) __attribute__((always_inline)) {
             constexpr int it = decltype(it_c)::value;
             if constexpr ((it * (HY - 1)) / LOADS_PER_STEP == i) issue_item(pr, it_c);
           });
@@ -357,7 +318,7 @@ wgrad_march_kernel(WmArgs a) {
 #pragma unroll
   for (int k = 0; k < PW; ++k)
 #pragma unroll
-    for (int t = 0; t < 27; ++t) *reinterpret_cast<wmf32x4*>(out + (k * 27 + t) * 256) = acc[k][t];
+    for (int t = 0; t < 27; ++t) *reinterpret_cast<f32x4*>(out + (k * 27 + t) * 256) = acc[k][t];
 }
 
 // sum of the slabs, 16-way parallel in a fixed order, f64 -> dw (cout, cin, 27)
@@ -393,6 +354,53 @@ wgrad_march_reduce_kernel(const float* __restrict__ slab, int nslab, int ncb, in
 }
 
 struct WmCfg { int ncb, nob; };
+static WmCfg wm_blocks(int cin, int cout) {   // 16-channel blocks (input, output) of a workgroup
+  if (cin % 64 == 0) return {4, 2};
+  if (cout % 64 == 0) return {2, 4};
+  return {2, 2};
+}
+
+// The launch cut.  Channel part (wm_channels): the (ci, co) combos and the most workgroups a combo gets -- one per CU over all
+// combos.  Spatial part (wm_cut): patches, z segments per parity class, dY planes per segment, hence the work items and the
+// persistent workgroups that share them, one slab each.  The launcher reads grid, slab count and need from it, the bound gmax.
+static constexpr int WM_MAX_WG = 256;
+struct WmCut {
+  int xc, yc, pw, nco, combos, gmax;
+  int nyb, nxb, nseg, zsteps, items, groups;
+  size_t slab_floats() const { return (size_t)WM_NW * pw * 27 * 256; }
+  size_t bytes(int g) const { return 256 + (size_t)combos * g * slab_floats() * sizeof(float); }   // 256 B reserved + slabs
+};
+static WmCut wm_channels(const WmCfg& c, int cin, int cout) {
+  WmCut m{};
+  m.xc = 16 * c.ncb; m.yc = 16 * c.nob; m.pw = c.ncb * c.nob / WM_NW;
+  m.nco = cout / m.yc;
+  m.combos = (cin / m.xc) * m.nco;
+  m.gmax = WM_MAX_WG / m.combos < 1 ? 1 : WM_MAX_WG / m.combos;
+  return m;
+}
+static WmCut wm_cut(const WmCfg& c, int cin, int cout, Dims d, int dil) {
+  WmCut m = wm_channels(c, cin, cout);
+  m.nyb = cdiv(d.H, WM_RY); m.nxb = cdiv(d.W, WM_TX);
+  const int nplanes = cdiv(d.D, dil);
+  const int per_seg = d.N * dil * m.nyb * m.nxb;
+  m.nseg = 1;
+  while (per_seg * m.nseg < m.gmax && nplanes / (m.nseg * 2) >= 8) m.nseg *= 2;
+  m.zsteps = cdiv(nplanes, m.nseg);
+  m.items = per_seg * m.nseg;
+  m.groups = m.items < m.gmax ? m.items : m.gmax;
+  return m;
+}
+// The most this kernel asks of the workspace that wgrad_workspace_bytes() sizes.  It never exceeds the tiled kernel's need for
+// the same channels, so it does not move that size.  In slabs of the tiled kernel (27 x 32 x 32 floats, one per workgroup and
+// 32 x 32 combo): a marching slab is pw of them and covers pw of those combos, so a marching launch of m combos fills at most
+// pw * m * (WM_MAX_WG / m) of them, or pw * m when m > WM_MAX_WG; the tiled kernel on the same pw * m combos keeps
+// pw * m * max(16, WG_TILED_SLABS / (pw * m)), and pw <= 2 (WmGeo).
+static_assert(WM_NW * 256 == 32 * 32 && 2 * WM_MAX_WG <= WG_TILED_SLABS, "a marching launch fits the tiled kernel's slabs");
+size_t wgrad_march_workspace_bytes(int taps, int cin, int cout) {
+  if (taps != 27 || cin < 32 || cout < 32 || cin % 32 || cout % 32) return 0;      // (never routed here: wgrad_march_cfg)
+  const WmCut m = wm_channels(wm_blocks(cin, cout), cin, cout);
+  return m.bytes(m.gmax);
+}
 static bool wgrad_march_cfg(int dtype, int taps, int dil, const SrcList& x, int cin_logical, int cout, Dims d, long long src_dist, WmCfg& c) {
   if (dtype_size(dtype) != 2 || taps != 27 || (dil != 1 && dil != 2)) return false;
   if (x.n < 1 || x.n > 2 || (x.n == 2 && x.C[0] != x.C[1])) return false;
@@ -405,9 +413,7 @@ static bool wgrad_march_cfg(int dtype, int taps, int dil, const SrcList& x, int 
     const long long dist = x.n == 2 ? (src_dist < 0 ? -src_dist : src_dist) : 0;
     if (dist + xs >= 0xFFFFFFFFll || ys >= 0xFFFFFFFFll) return false;
   }
-  if (cin_logical % 64 == 0) c = {4, 2};
-  else if (cout % 64 == 0) c = {2, 4};
-  else c = {2, 2};
+  c = wm_blocks(cin_logical, cout);
   return true;
 }
 
@@ -431,27 +437,16 @@ int launch_wgrad_march(int dtype, int taps, int dil, const SrcList& x, int cin_l
   WmCfg c;
   SEUNET_CHECK(wgrad_march_cfg(dtype, taps, dil, x, cin_logical, cout, d, x.gap(), c),
                "wgrad_march: 16-bit 3x3x3 layers with 32k input and 32k output channels (one tensor or two equal halves) only");
-  SEUNET_CHECK(ws_bytes >= 256, "wgrad_march: workspace too small");
-  const int xc = 16 * c.ncb, yc = 16 * c.nob, pw = c.ncb * c.nob / WM_NW;
+  const WmCut cut = wm_cut(c, cin_logical, cout, d, dil);
+  SEUNET_CHECK(ws_bytes >= cut.bytes(cut.groups), "wgrad_march: workspace too small");
   WmArgs a{};
   a.src0 = x.ptr[0]; a.src1 = x.n > 1 ? x.ptr[1] : nullptr; a.srcC = x.C[0]; a.nsrc = x.n;
   a.dy = dy; a.cout = cout;
   a.slab = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(workspace) + 256);
   a.N = d.N; a.D = d.D; a.H = d.H; a.W = d.W;
-  a.nyb = cdiv(d.H, WM_RY); a.nxb = cdiv(d.W, WM_TX);
-  a.nco = cout / yc;
-  const int combos = (cin_logical / xc) * a.nco;
-  const int gmax = 256 / combos < 1 ? 1 : 256 / combos;             // one workgroup per CU in total
-  const int nplanes = cdiv(d.D, dil);
-  const int per_seg = d.N * dil * a.nyb * a.nxb;
-  int nseg = 1;
-  while (per_seg * nseg < gmax && nplanes / (nseg * 2) >= 8) nseg *= 2;
-  a.nseg = nseg; a.zsteps = cdiv(nplanes, nseg);
-  a.items = per_seg * nseg;
-  const int G = a.items < gmax ? a.items : gmax;
-  const size_t per = (size_t)WM_NW * pw * 27 * 256;
-  SEUNET_CHECK(ws_bytes >= 256 + (size_t)combos * G * per * sizeof(float), "wgrad_march: workspace too small");
-  dim3 grid(G, combos);
+  a.nyb = cut.nyb; a.nxb = cut.nxb; a.nseg = cut.nseg; a.zsteps = cut.zsteps;
+  a.nco = cut.nco; a.items = cut.items;
+  const dim3 grid(cut.groups, cut.combos);
   int e = -1;
   SEUNET_DTYPE_SWITCH(dtype, if constexpr (sizeof(T) == 2) {
     if (c.ncb == 4 && dil == 1) e = wgrad_march_launch<T, 4, 2, 1>(a, grid, s);
@@ -462,7 +457,8 @@ int launch_wgrad_march(int dtype, int taps, int dil, const SrcList& x, int cin_l
     else e = wgrad_march_launch<T, 2, 2, 2>(a, grid, s);
   });
   if (e) return e;
-  wgrad_march_reduce_kernel<<<dim3((unsigned)(per / 16), combos), 256, 0, s>>>(a.slab, G, c.ncb, pw, xc, yc, a.nco, cin_logical, dw);
+  const dim3 rgrid((unsigned)(cut.slab_floats() / 16), cut.combos);
+  wgrad_march_reduce_kernel<<<rgrid, 256, 0, s>>>(a.slab, cut.groups, c.ncb, cut.pw, cut.xc, cut.yc, cut.nco, cin_logical, dw);
   SEUNET_LAUNCH_CHECK();
   return 0;
 }

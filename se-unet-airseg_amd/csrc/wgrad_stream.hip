@@ -15,14 +15,9 @@
 //     workgroup writes ONE compact slab [27][ci][co]; a second kernel sums the slabs (f64, fixed order: deterministic).
 #include "seunet_common.h"
 #include "lds_dma.h"
-#include <utility>
-#include <type_traits>
+#include "mfma.h"
 
 namespace seunet {
-
-typedef bf16_t bf16x4w __attribute__((ext_vector_type(4)));
-typedef bf16_t bf16x8w __attribute__((ext_vector_type(8)));
-typedef float f32x4w __attribute__((ext_vector_type(4)));
 
 struct WsArgs {
   const void* x; const void* dy; float* slab;
@@ -60,7 +55,6 @@ wgrad_stream_kernel(WsArgs a) {
   constexpr int NDY = Geo::NDY, RX = Geo::RX, RY = Geo::RY, XITEMS = Geo::XITEMS, YITEMS = Geo::YITEMS;
   constexpr int CB = Geo::CB, OB = Geo::OB, AU = Geo::AU, AUG = Geo::AUG;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  typedef __attribute__((address_space(3))) bf16x4w lds_b4;
   const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem;
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -137,12 +131,8 @@ wgrad_stream_kernel(WsArgs a) {
   };
   auto dma_group = [&](int s, int xslot, int jd, int yslot, int part) __attribute__((always_inline)) {
     // part 0 / 1: first / second half of the instructions (spread over the two rows of a step); part 2: everything
-    [&]<int... I>(std::integer_sequence<int, I...>) __attribute__((always_inline)) {
-      (((part == 2 || (I & 1) == part) ? dma_x(s, xslot, std::integral_constant<int, I>{}) : (void)0), ...);
-    }(std::make_integer_sequence<int, XITEMS>{});
-    [&]<int... I>(std::integer_sequence<int, I...>) __attribute__((always_inline)) {
-      (((part == 2 || (I & 1) == part) ? dma_y(jd, yslot, std::integral_constant<int, I>{}) : (void)0), ...);
-    }(std::make_integer_sequence<int, YITEMS>{});
+    static_for<XITEMS>([&](auto i_c) __attribute__((always_inline)) { if (part == 2 || (decltype(i_c)::value & 1) == part) dma_x(s, xslot, i_c); });
+    static_for<YITEMS>([&](auto i_c) __attribute__((always_inline)) { if (part == 2 || (decltype(i_c)::value & 1) == part) dma_y(jd, yslot, i_c); });
   };
 
   // ---- fragment addressing (ds_read_b64_tr_b16): 16-lane group g = k-group (voxels 8g..8g+7), lane li = 4q + p supplies the
@@ -154,7 +144,7 @@ wgrad_stream_kernel(WsArgs a) {
   // dY: columns = co; offset of (row 0, block 0)
   const int yfrag0 = ((8 * g + fq) * COUT + 4 * fp) * 2;
 
-  f32x4w acc[AUG][3][OB];
+  f32x4 acc[AUG][3][OB];
 #pragma unroll
   for (int u = 0; u < AUG; ++u)
 #pragma unroll
@@ -164,15 +154,11 @@ wgrad_stream_kernel(WsArgs a) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) acc[u][dz][ob][e] = 0.f;
 
-  auto read_x = [&](const unsigned char* p) __attribute__((always_inline)) -> bf16x8w {   // second read: + 4 voxels = + 64 B
-    const bf16x4w lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b4*)p);
-    const bf16x4w hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b4*)(p + 64));
-    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+  auto read_x = [&](const unsigned char* p) __attribute__((always_inline)) -> bf16x8 {   // second read: + 4 voxels = + 64 B
+    return frag_tr16((const lds_bf16x4*)p, (const lds_bf16x4*)(p + 64));
   };
-  auto read_y = [&](const unsigned char* p) __attribute__((always_inline)) -> bf16x8w {   // + 4 voxels = + 4 * COUT * 2 B
-    const bf16x4w lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b4*)p);
-    const bf16x4w hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b4*)(p + 8 * COUT));
-    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+  auto read_y = [&](const unsigned char* p) __attribute__((always_inline)) -> bf16x8 {   // + 4 voxels = + 4 * COUT * 2 B
+    return frag_tr16((const lds_bf16x4*)p, (const lds_bf16x4*)(p + 8 * COUT));
   };
 
   // ---- one step: X plane s (slot xs) against the dY planes jd = s (dz = +1), s + 1 (dz = 0), s + 2 (dz = -1) ----
@@ -181,7 +167,7 @@ wgrad_stream_kernel(WsArgs a) {
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
       const int w = 2 * rp + r;                                       // output row
-      bf16x8w bf[3][OB];
+      bf16x8 bf[3][OB];
 #pragma unroll
       for (int dzi = 0; dzi < 3; ++dzi) {                              // dz = dzi - 1  <->  dY jd = s + 2 - dzi ... (dz = +1: jd = s)
         int ysl = ys0 + (2 - dzi);
@@ -199,17 +185,12 @@ wgrad_stream_kernel(WsArgs a) {
         int dyi, dxo, cb;
         if constexpr (XF) { dyi = au >> 1; dxo = 2 * (au & 1); cb = 0; }
         else { dyi = au / (3 * CB); dxo = (au / CB) % 3; cb = au % CB; }
-        const bf16x8w af = read_x(xp + ((w + DIL * dyi) * HX + DIL * dxo) * 16 + (XF ? 0 : cb * 2 * PS));
+        const bf16x8 af = read_x(xp + ((w + DIL * dyi) * HX + DIL * dxo) * 16 + (XF ? 0 : cb * 2 * PS));
 #pragma unroll
         for (int dzi = 0; dzi < 3; ++dzi)
 #pragma unroll
           for (int ob = 0; ob < OB; ++ob)
-            if constexpr (std::is_same<T, f16_t>::value) {   // (the transposing reads are type-agnostic 16-bit patterns)
-              typedef f16_t f16x8w __attribute__((ext_vector_type(8)));
-              acc[u][dzi][ob] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8w, af), __builtin_bit_cast(f16x8w, bf[dzi][ob]), acc[u][dzi][ob], 0, 0, 0);
-            } else {
-              acc[u][dzi][ob] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf[dzi][ob], acc[u][dzi][ob], 0, 0, 0);
-            }
+            acc[u][dzi][ob] = mfma_16x16x32<T>(af, bf[dzi][ob], acc[u][dzi][ob]);
       }
     }
   };
@@ -217,9 +198,7 @@ wgrad_stream_kernel(WsArgs a) {
   // ---- the march: as in conv_stream.hip, at the top of step s the only loads younger than X plane s (and its dY plane) are
   //      those of the WS_PF - 1 steps issued after it; no stores in flight here ----
   int ysl = 0;
-  [&]<int... I>(std::integer_sequence<int, I...>) __attribute__((always_inline)) {   // the two dY planes ahead of group 0
-    ((dma_y(0, 0, std::integral_constant<int, I>{}), dma_y(1, 1, std::integral_constant<int, I>{})), ...);
-  }(std::make_integer_sequence<int, YITEMS>{});
+  static_for<YITEMS>([&](auto i_c) __attribute__((always_inline)) { dma_y(0, 0, i_c); dma_y(1, 1, i_c); });   // the two dY planes ahead of group 0
 #pragma unroll
   for (int k = 0; k < WS_PF; ++k) dma_group(k, k, k + 2, k + 2, 2);
   wait_loads<(WS_PF - 1) * Geo::LOADS_PER_STEP>();
@@ -241,7 +220,7 @@ wgrad_stream_kernel(WsArgs a) {
 
   // ---- sum the four row-pair partials of each group (fixed order) and write the workgroup's slab [27][CIN][COUT] ----
   float* slab = a.slab + (((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * (size_t)Geo::SLAB;
-  f32x4w* stage = reinterpret_cast<f32x4w*>(smem);                    // [wave][tile in round][lane]
+  f32x4* stage = reinterpret_cast<f32x4*>(smem);                      // [wave][tile in round][lane]
   constexpr int TILES = AUG * 3 * OB, ROUND = 8;
 #pragma unroll
   for (int t0 = 0; t0 < TILES; t0 += ROUND) {
@@ -259,7 +238,7 @@ wgrad_stream_kernel(WsArgs a) {
       const int tl = t0 + k, u = tl / (3 * OB), dzi = (tl / OB) % 3, ob = tl % OB;
       const int au = gg * AUG + u;
       if (tl < TILES && au < AU) {
-        f32x4w sum = stage[((gg + 0) * ROUND + k) * 64 + ln];
+        f32x4 sum = stage[((gg + 0) * ROUND + k) * 64 + ln];
 #pragma unroll
         for (int p = 1; p < 4; ++p) sum += stage[((gg + 2 * p) * ROUND + k) * 64 + ln];
         const int co = ob * 16 + (ln & 15);
@@ -309,22 +288,30 @@ static bool ws_shape_ok(int cin, int cout, int dil) {
 bool wgrad_stream_supported(int dtype, int taps, int dil, int x_c, int dy_c) {
   return (dtype == SEUNET_BF16 || dtype == SEUNET_F16) && taps == 27 && (dil == 1 || dil == 2) && ws_shape_ok(x_c, dy_c, dil);
 }
-static int ws_zsteps(Dims d, int dil) {
+// The launch cut: patches, z segments per parity class, dY planes per segment.  wgrad_stream_workspace_bytes() and
+// launch_wgrad_stream() both take it from ws_cut(); the grid and the slab count (one slab per workgroup) follow from it alone.
+struct WsCut {
+  int planes, zsteps, nzseg, nyb, nxb, dil, n;
+  int slabs() const { return nyb * nxb * nzseg * dil * n; }
+  dim3 grid() const { return dim3(nyb * nxb, nzseg * dil, n); }
+};
+static WsCut ws_cut(Dims d, int dil) {
   // long marches: few slabs, the pipeline fill amortised; aim at >= 256 workgroups (one per CU)
-  const int planes = cdiv(d.D, dil);
-  const int base = cdiv(d.H, WS_TY) * cdiv(d.W, WS_TX) * d.N * dil;
+  WsCut c;
+  c.dil = dil; c.n = d.N;
+  c.planes = cdiv(d.D, dil);
+  c.nyb = cdiv(d.H, WS_TY); c.nxb = cdiv(d.W, WS_TX);
+  const int base = c.nyb * c.nxb * d.N * dil;
   int segs = (256 + base - 1) / base;
   if (segs < 1) segs = 1;
-  if (segs > cdiv(planes, 8)) segs = cdiv(planes, 8);
+  if (segs > cdiv(c.planes, 8)) segs = cdiv(c.planes, 8);
   if (segs < 1) segs = 1;
-  return cdiv(planes, segs);
-}
-static int ws_slabs(Dims d, int dil) {
-  const int planes = cdiv(d.D, dil);
-  return cdiv(d.H, WS_TY) * cdiv(d.W, WS_TX) * cdiv(planes, ws_zsteps(d, dil)) * dil * d.N;
+  c.zsteps = cdiv(c.planes, segs);
+  c.nzseg = cdiv(c.planes, c.zsteps);
+  return c;
 }
 size_t wgrad_stream_workspace_bytes(int x_c, int dy_c, int dil, Dims d) {
-  return (size_t)ws_slabs(d, dil) * 27 * x_c * dy_c * sizeof(float);
+  return (size_t)ws_cut(d, dil).slabs() * (27 * x_c * dy_c) * sizeof(float);
 }
 
 template <typename T, int CIN, int COUT, int DIL>
@@ -348,18 +335,17 @@ int launch_wgrad_stream(int dtype, int dil, const void* x, int x_c, int cin_w, c
                         void* workspace, size_t ws_bytes, Dims d, hipStream_t s) {
   SEUNET_CHECK(wgrad_stream_supported(dtype, 27, dil, x_c, dy_c), "wgrad_stream: unsupported shape (%d x %d channels, dilation %d)", x_c, dy_c, dil);
   SEUNET_CHECK(x && dy && dw && workspace && cin_w >= 1 && cin_w <= x_c && cout_w >= 1 && cout_w <= dy_c, "wgrad_stream: bad argument");
-  SEUNET_CHECK(ws_bytes >= wgrad_stream_workspace_bytes(x_c, dy_c, dil, d), "wgrad_stream: workspace too small");
+  const WsCut cut = ws_cut(d, dil);
+  const int per = 27 * x_c * dy_c;                       // floats per slab
+  SEUNET_CHECK(ws_bytes >= (size_t)cut.slabs() * per * sizeof(float), "wgrad_stream: workspace too small");
   SEUNET_CHECK((long long)d.D * d.H * d.W * (x_c > dy_c ? x_c : dy_c) * 2 < 0xFFFFFFFFll,
                "wgrad_stream: one sample exceeds the 32-bit buffer offsets of this kernel");
   WsArgs a{};
   a.x = x; a.dy = dy; a.slab = reinterpret_cast<float*>(workspace);
   a.N = d.N; a.D = d.D; a.H = d.H; a.W = d.W;
-  const int planes = cdiv(d.D, dil);
-  a.zsteps = ws_zsteps(d, dil);
-  a.nzseg = cdiv(planes, a.zsteps);
-  a.nyb = cdiv(d.H, WS_TY); a.nxb = cdiv(d.W, WS_TX);
+  a.zsteps = cut.zsteps; a.nzseg = cut.nzseg; a.nyb = cut.nyb; a.nxb = cut.nxb;
   SEUNET_CHECK(d.N <= 65535, "wgrad_stream: batch too large");
-  dim3 grid(a.nyb * a.nxb, a.nzseg * dil, d.N);
+  const dim3 grid = cut.grid();
   int e = 1;
   if (x_c == 8 && dy_c == 8) e = dil == 1 ? ws_launch<8, 8, 1>(dtype, a, grid, s) : ws_launch<8, 8, 2>(dtype, a, grid, s);
   else if (x_c == 8 && dy_c == 16) e = dil == 1 ? ws_launch<8, 16, 1>(dtype, a, grid, s) : ws_launch<8, 16, 2>(dtype, a, grid, s);
@@ -367,8 +353,7 @@ int launch_wgrad_stream(int dtype, int dil, const void* x, int x_c, int cin_w, c
   else if (x_c == 16 && dy_c == 32) e = dil == 1 ? ws_launch<16, 32, 1>(dtype, a, grid, s) : ws_launch<16, 32, 2>(dtype, a, grid, s);
   else if (x_c == 32 && dy_c == 16) e = ws_launch<32, 16, 1>(dtype, a, grid, s);
   if (e) return e;
-  const int per = 27 * x_c * dy_c;
-  wgrad_stream_reduce_kernel<<<cdiv(per, 16), 256, 0, s>>>(a.slab, grid.x * grid.y * grid.z, per, x_c, dy_c, cin_w, cout_w, dw);
+  wgrad_stream_reduce_kernel<<<cdiv(per, 16), 256, 0, s>>>(a.slab, cut.slabs(), per, x_c, dy_c, cin_w, cout_w, dw);
   SEUNET_LAUNCH_CHECK();
   return 0;
 }
