@@ -22,6 +22,9 @@ extern "C" {
 
 // diagnostic hook (not part of the public header): device buffer of 8 u64 that -DSEUNET_STAMP builds add cycle sums to
 int seunet_debug_set_buffer(void* p) { seunet::g_conv_debug = reinterpret_cast<unsigned long long*>(p); return 0; }
+// diagnostic hook (not part of the public header, host only): the kernel form an x2 up-sampling pass takes for these
+// arguments -- 0 gather, 1 tiled, 2 march
+int seunet_debug_upsample2_form(int dtype, int c, seunet_dims dims, int backward) { return upsample2_form(dtype, c, D(dims), backward != 0); }
 
 int seunet_version(void) { return 201; }
 const char* seunet_last_error(void) { return get_error(); }

@@ -7,7 +7,7 @@
 // The per-level x-branch terms gx_l = W_xl^T d2_xl ([N][V_l][in_channel] f32) come from pass B of the aggregation block
 // (epilogue.hip cat_bwd_kernel XG when the branch is recomputed from the input; xgrad_contract_kernel below from the stored
 // d2 otherwise).  unpool_l routes to the FIRST strict maximum of each 2x2x2 window of the stored input copy (feat[T_X0] /
-// feat[T_X1]), the forward's own rule (resample.hip maxpool_bwd_kernel).  In bf16 / fp16 storage the network computes on its
+// feat[T_X1]), the forward's own rule (layout.hip maxpool_bwd_kernel).  In bf16 / fp16 storage the network computes on its
 // rounded copy of x: this is the gradient with respect to that copy, the rounding passed straight through.
 // Everything here is f32, written once per element (no atomics): the result is deterministic.
 #include "seunet_common.h"

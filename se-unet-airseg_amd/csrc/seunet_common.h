@@ -54,6 +54,13 @@ static inline bool dtype_ok(int dtype) { return dtype == SEUNET_F32 || dtype == 
   } while (0)
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// workgroups of a flat grid-stride pass over `total` items: at most 16 per CU
+static inline int grid_for(long long total, int block = 256) {
+  long long g = (total + block - 1) / block;
+  if (g > 256 * 16) g = 256 * 16;
+  if (g < 1) g = 1;
+  return (int)g;
+}
 
 // ---- small POD descriptors shared by launchers and the net executor ---------------
 struct Dims {
@@ -261,7 +268,7 @@ __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + __ex
 #endif  // __HIPCC__
 
 // ---- launcher prototypes (one per kernel family; defined in the .hip files) ----------
-// layout
+// layout (layout.hip)
 int launch_pack_input(int dtype, const float* x_ncdhw, int in_channel, void* out_cl8, Dims d, hipStream_t s);
 int launch_unpack_cl(int dtype, const void* in_cl, int C, float* out_ncdhw, Dims d, hipStream_t s);
 int launch_pack_cl(int dtype, const float* in_ncdhw, int C, void* out_cl, int Cpad, Dims d, hipStream_t s);
@@ -423,14 +430,15 @@ int launch_xgrad_contract(int dtype, const void* d2, int C, const float* w2, int
 int launch_xgrad_unpool(int dtype, const void* x_fine, int in_channel, const float* gx_coarse, float* gx_fine, Dims fine, hipStream_t s);
 int launch_input_grad(int dtype, const void* draw, int ce, const float* w_ec1, const void* x0, int in_channel, const float* gx0,
                       const float* gx1, float* grad_x, Dims d, hipStream_t s);
-// pooling / interpolation / heads (resample.hip)
+// pooling (layout.hip) / x2 interpolation of feature maps (resample.hip)
 int launch_maxpool_fwd(int dtype, const void* in, int C, void* out, Dims din, hipStream_t s);
 int launch_maxpool_bwd(int dtype, const void* in, const void* g_out, int C, void* g_in,
                        int accumulate, Dims din, hipStream_t s);
 int launch_upsample2_fwd(int dtype, const void* in, int C, void* out, Dims din, hipStream_t s);
 int launch_upsample2_bwd(int dtype, const void* g_out, int C, void* g_in, int accumulate,
                          Dims din, hipStream_t s);
-int launch_multi_zero(float* const* ptrs, const int* counts, int n, hipStream_t s);
+int upsample2_form(int dtype, int C, Dims din, bool backward);   // the form of the pass's cut: 0 gather, 1 tiled, 2 march
+int launch_multi_zero(float* const* ptrs, const int* counts, int n, hipStream_t s);   // (layout.hip)
 // n_classes > 1: the general head path (classes.hip)
 int class_max();
 int class_grad_records(Dims d);
@@ -537,6 +545,7 @@ int launch_adamw(float* const* params, const float* const* grads, float* const* 
 // raises a kernel's dynamic-LDS limit once per (instantiation, device): under a lock, the device's bit is set on success only
 int configure_kernel_lds(unsigned long long& mask, const void* fn, int bytes);
 const void* device_zero_page();   // >= 256 zero bytes on the current device (allocated once per device, never freed)
+// side maps / deep-supervision heads (heads.hip)
 int launch_side_upsample(const float* side, int C, int scale, float* out_ncdhw, int c_total,
                          int c_off, Dims dlow, hipStream_t s);
 int launch_head_fwd(const float* const* level_maps, int nlevels, const float* bias, float* pred,

@@ -9,7 +9,11 @@ of that layer must leave all of them where they are.
 The shapes reach every branch of the cut functions: a sample with fewer than 8 planes, the ``planes / 8`` cap on the segments
 ((1, 80, 8, 64)), dilation 2 with an odd depth, H and W that are no multiples of the patch, 128^3 at batch 1 and 4; for
 conv_march both channel configurations and the 64 -> 32 / 32 -> 64 mixes, because its cut depends on the batch and on the
-number of N blocks."""
+number of N blocks.
+
+The x2 up-sampling passes have a cut as well: it names the kernel form (gather, tiled or z-marching) a (storage type, channels,
+extents) combination runs on.  ``UP2_FORMS`` pins that form for every shape of ``test_ops_gpu.test_upsample2_forward_backward_shapes``
+-- which takes its shapes from here -- and ``HEAD_BWD_TMP_FLOATS`` pins the workspace of the heads' backward."""
 import ctypes as C
 import hashlib
 import json
@@ -87,6 +91,31 @@ NETS = [[11276056832, 76546048, [-54525952, -33554432, -591396864, -268435456, -
  [12478484992, 114819072, [-54525952, -33554432, -591396864, -268435456, -536870912],
   '12f56e7a96362311917c8f8b429ac2f3df6640d51e5e348c842200c1c7fc6713']]
 
+# seunet_head_bwd_tmp_floats per shape, recorded from the library before the size query and the launcher shared one layout
+HEAD_BWD_TMP_FLOATS = [3268, 3314, 9420, 61672, 79476, 275708, 393664, 197056, 3146944, 12587200, 12291392]
+# The form of the x2 up-sampling, written down from the conditions of the launchers as they stood before the cuts existed.
+# (n, c, d, h, w) of the coarse tensor -> (forward 16-bit, forward f32, backward 16-bit, backward f32).
+#   forward:  march for C = 32 / 64 / 128 with every extent >= 2 and 2 * 3 * 68 * C * sizeof(T) <= 112 KB of LDS (128 channels
+#             in f32 would need 208 896 B); else tiled while 4 * 68 * C * 4 B <= 144 KB (C <= 128: 136 channels need 147 968 B);
+#             else gather
+#   backward: march in 16-bit storage for C = 32 / 64 / 128 with every extent >= 4; else tiled for C <= 128 and W >= 2; else gather
+UP2_FORMS = {
+    (1, 32, 5, 7, 70): ("march", "march", "march", "tiled"),
+    (2, 64, 3, 4, 33): ("march", "march", "tiled", "tiled"),
+    (1, 8, 1, 1, 2): ("tiled", "tiled", "tiled", "tiled"),
+    (1, 16, 2, 9, 64): ("tiled", "tiled", "tiled", "tiled"),
+    (1, 128, 2, 3, 5): ("march", "tiled", "tiled", "tiled"),
+    (2, 64, 9, 4, 33): ("march", "march", "march", "tiled"),
+    (1, 128, 4, 6, 20): ("march", "tiled", "march", "tiled"),
+    (1, 32, 40, 9, 17): ("march", "march", "march", "tiled"),
+    (1, 32, 33, 16, 16): ("march", "march", "march", "tiled"),
+    (1, 64, 4, 4, 4): ("march", "march", "march", "tiled"),
+    # the smallest shapes that reach the gather kernels: more than 128 channels (both directions), coarse W = 1 (backward)
+    (1, 136, 2, 3, 3): ("gather", "gather", "gather", "gather"),
+    (1, 8, 2, 3, 1): ("tiled", "tiled", "gather", "gather"),
+}
+UP2_FORM_NAMES = ["gather", "tiled", "march"]
+
 
 @pytest.fixture(scope="module")
 def L():
@@ -159,3 +188,39 @@ def test_network_arena_and_conv_records(L, i):
     got, plan = net(L, DESCS[i])
     assert got[:3] == NETS[i][:3], plan
     assert got[3] == NETS[i][3], json.dumps(plan, sort_keys=True, indent=1)
+
+
+def upsample2_form(L, dtype, c, dims, backward):
+    lib = L.load()
+    f = lib.seunet_debug_upsample2_form                      # diagnostic export, not in the public header
+    f.restype, f.argtypes = C.c_int, [C.c_int, C.c_int, L.Dims, C.c_int]
+    return UP2_FORM_NAMES[f(L.dtype_code(dtype), c, L.Dims(*dims), int(backward))]
+
+
+def test_upsample2_forms_of_the_tested_shapes(L):
+    forms = {f for row in UP2_FORMS.values() for f in row}
+    assert forms == set(UP2_FORM_NAMES)                      # every form of both directions is reached
+    assert {row[0] for row in UP2_FORMS.values()} == forms and {row[2] for row in UP2_FORMS.values()} == forms
+    for (n, c, d, h, w), want in UP2_FORMS.items():
+        got = tuple(upsample2_form(L, dt, c, (n, d, h, w), bwd) for bwd in (False, True) for dt in ("bf16", "fp32"))
+        assert got == want, (n, c, d, h, w)
+        for bwd in (False, True):                            # both 16-bit storage types take the same route
+            assert upsample2_form(L, "fp16", c, (n, d, h, w), bwd) == want[2 * bwd], (n, c, d, h, w, bwd)
+
+
+@pytest.mark.parametrize("desc", DESCS, ids=lambda d: "-".join(str(v) for v in d))
+def test_upsample2_forms_of_the_network(L, desc):
+    """up0 / up1 / up2 up-sample levels 3 / 2 / 1 with 64 / 64 / 32 channels per unit of width: the forward marches in every
+    storage type (at most 128 channels in 16 bits, 64 in f32), the backward marches in 16-bit storage (every coarse extent of these
+    descriptors is >= 4) and is tiled in f32."""
+    batch, _, d, width, dtype = desc
+    for level, c in ((3, 64 * width), (2, 64 * width), (1, 32 * width)):
+        dims = (batch, d >> level, d >> level, d >> level)
+        assert d >> level >= 4 and c * (4 if dtype == "fp32" else 2) <= 256
+        assert upsample2_form(L, dtype, c, dims, False) == "march", (level, c, dims)
+        assert upsample2_form(L, dtype, c, dims, True) == ("tiled" if dtype == "fp32" else "march"), (level, c, dims)
+
+
+def test_head_bwd_tmp_floats(L):
+    lib = L.load()
+    assert [lib.seunet_head_bwd_tmp_floats(L.Dims(*s)) for s in SHAPES] == HEAD_BWD_TMP_FLOATS

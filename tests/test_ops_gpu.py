@@ -11,6 +11,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from test_launch_cut_host import UP2_FORMS
+
 pytestmark = pytest.mark.gpu
 
 
@@ -725,13 +727,13 @@ def test_conv_march_dropped_destination_and_long_march(S):
 
 
 @pytest.mark.parametrize("dtype", DT)
-@pytest.mark.parametrize("shape", [(1, 32, 5, 7, 70), (2, 64, 3, 4, 33), (1, 8, 1, 1, 2), (1, 16, 2, 9, 64), (1, 128, 2, 3, 5),
-                                   (2, 64, 9, 4, 33), (1, 128, 4, 6, 20), (1, 32, 40, 9, 17), (1, 32, 33, 16, 16), (1, 64, 4, 4, 4)])
+@pytest.mark.parametrize("shape", list(UP2_FORMS))
 def test_upsample2_forward_backward_shapes(S, dtype, shape):
-    """x2 trilinear (align_corners=True) on the tiled kernels: more than one 128-voxel x-chunk, odd extents, single rows,
-    the 128-channel case (width x2); the backward takes the z-marching kernel when C is 32 / 64 / 128 and every coarse
-    extent is >= 4 (ragged y / x tiles, several z segments, a ragged last segment), the per-plane tiled kernel or the gather
-    kernel otherwise."""
+    """x2 trilinear (align_corners=True): more than one 128-voxel x-chunk, odd extents, single rows and columns, the
+    128-channel case (width x2), ragged y / x tiles, several z segments, a ragged last segment.  Which kernel form (gather,
+    tiled, z-marching) each shape takes in each direction and storage type is pinned on the host by
+    test_launch_cut_host.test_upsample2_forms_of_the_tested_shapes, from whose table the shapes are taken; the last two are
+    the smallest that reach the gather kernels (more than 128 channels; a backward with a coarse W of 1)."""
     n, c, d, h, w = shape
     y = rnd(dtype, gen(n, c, d, h, w, seed=41)).requires_grad_(True)
     u_ref = F.interpolate(y, scale_factor=2, mode="trilinear", align_corners=True)
