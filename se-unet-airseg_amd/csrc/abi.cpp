@@ -1,6 +1,7 @@
 // extern "C" entry points of libseunet_hip.so (per-op part; the whole-network calls live in net.cpp).
 // Thin argument marshalling only: every function validates, forwards to a launcher and returns a status.
 #include "seunet_common.h"
+#include "volume.h"
 #include "../../include/seunet_hip.h"
 
 using namespace seunet;
@@ -25,6 +26,35 @@ int seunet_debug_set_buffer(void* p) { seunet::g_conv_debug = reinterpret_cast<u
 // diagnostic hook (not part of the public header, host only): the kernel form an x2 up-sampling pass takes for these
 // arguments -- 0 gather, 1 tiled, 2 march
 int seunet_debug_upsample2_form(int dtype, int c, seunet_dims dims, int backward) { return upsample2_form(dtype, c, D(dims), backward != 0); }
+
+// diagnostic hook (not part of the public header, host only): the workspace layout of a volume operation as its launcher
+// carves it.  op: 0 cc, 1 get_l, 2 edt, 3 lib_weight, 4 break_weight, 5 skeleton_branches, 6 dti, 7 skeleton, 8 parse_assign.
+// Returns the number of sub-buffers (0: extents the op rejects, -1: no such op) and writes (offset, bytes up to the next
+// sub-buffer or the end) of the first `cap`.
+int seunet_debug_volume_layout(int op, int n0, int n1, int n2, size_t* offsets, int cap) {
+  if (n0 < 1 || n1 < 1 || n2 < 1) return 0;
+  size_t at[16];                       // no operation has more than 9 sub-buffers
+  WsCarver c(nullptr);
+  c.log = at;
+  c.log_cap = 16;
+  switch (op) {
+    case 0: cc_ws(c, n0, n1, n2); break;
+    case 1: get_l_ws(c, n0, n1, n2); break;
+    case 2: case 8: edt_ws(c, n0, n1, n2); break;
+    case 3: lib_weight_ws(c, n0, n1, n2); break;
+    case 4: break_weight_ws(c, n0, n1, n2); break;
+    case 5: branches_ws(c, n0, n1, n2); break;
+    case 6: dti_ws(c, n0, n1, n2); break;
+    case 7: if (!skeleton_ws(c, n0, n1, n2)) return 0; break;
+    default: return -1;
+  }
+  if (c.taken > c.log_cap) return -1;
+  for (int i = 0; i < c.taken && i < cap && offsets; ++i) {
+    offsets[2 * i] = at[i];
+    offsets[2 * i + 1] = (i + 1 < c.taken ? at[i + 1] : c.bytes()) - at[i];
+  }
+  return c.taken;
+}
 
 int seunet_version(void) { return 201; }
 const char* seunet_last_error(void) { return get_error(); }

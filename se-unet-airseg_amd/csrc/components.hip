@@ -20,22 +20,12 @@
 // in its own launch.  Rows are pre-linked per wavefront with ballots (a run of foreground voxels along z inside one
 // 64-voxel wave span starts compressed), which removes the long serial chains along the contiguous axis.
 // Integer / index work: results are bit-identical to the CPU reference (tests/test_components_gpu.py).
-#include "seunet_common.h"
+#include "volume.h"
 #include <algorithm>
 
 namespace seunet {
 
-typedef unsigned long long u64;
-
-struct CcSel {            // device-side scalars of one call
-  u64 best, second;       // (voxel count << 32) | root index ; 0 = none
-  int touches;            // largest component has a voxel in one of the three test slices
-  int chosen;             // root index of the selected component, -1 = none
-  int status;             // 0 ok, 1 no component at all, 2 second component needed but absent
-  int pad;
-};
-
-// cc_find / cc_union: seunet_common.h (shared with the per-slice labelling of lung.hip)
+// cc_find / cc_union, CcSel and the workspace layout CcWs: volume.h
 
 // L[i] = start of the z-run of voxel i inside its wave span (foreground), -1 (background).  INVERT labels the complement.
 template <bool INVERT>
@@ -63,7 +53,7 @@ cc_merge_kernel(int* L, long long n, int H, int W, int Z) {
   const long long i = blockIdx.x * 256ll + threadIdx.x;
   if (i >= n) return;
   if (L[i] < 0) return;
-  const int z = (int)(i % Z);
+  const int z = (int)(i % Z);             // (vox3 spelled out: with the helper the 26-neighbour instantiation compiles differently)
   const long long r = i / Z;
   const int y = (int)(r % W), x = (int)(r / W);
   // (0, 0, -1): already linked inside a wave span by cc_init_kernel, except across the span boundary
@@ -109,8 +99,10 @@ cc_count_kernel(const int* __restrict__ L, long long n, unsigned int* __restrict
   atomicAdd(&cnt[r], (unsigned int)len);
 }
 
+void launch_cc_compress(int* L, long long n, hipStream_t s) { cc_compress_kernel<<<blocks_256(n), 256, 0, s>>>(L, n); }
+
 void launch_cc_count(const int* L, long long n, unsigned int* cnt, hipStream_t s) {
-  cc_count_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(L, n, cnt);
+  cc_count_kernel<<<blocks_256(n), 256, 0, s>>>(L, n, cnt);
 }
 
 // pass 0: best = max key over roots; pass 1: second = max key over roots other than best
@@ -122,12 +114,7 @@ cc_select_kernel(const int* __restrict__ L, const unsigned int* __restrict__ cnt
     key = ((u64)cnt[i] << 32) | (u64)(unsigned int)i;
     if (pass == 1 && key == sel->best) key = 0;
   }
-  // wave maximum first: one atomic per wave
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const u64 o = shfl_xor_settled(key, off);
-    key = o > key ? o : key;
-  }
+  key = wave_max(key);   // one atomic per wave
   if ((threadIdx.x & 63) == 0 && key) atomicMax(pass == 0 ? &sel->best : &sel->second, key);
 }
 
@@ -166,9 +153,8 @@ cc_border_kernel(const int* __restrict__ L, int H, int W, int Z, unsigned int* _
   const long long n = (long long)H * W * Z;
   const long long i = blockIdx.x * 256ll + threadIdx.x;
   if (i >= n) return;
-  const int z = (int)(i % Z);
-  const long long r = i / Z;
-  const int y = (int)(r % W), x = (int)(r / W);
+  const Vox3 p = vox3(i, W, Z);
+  const int x = p.i0, y = p.i1, z = p.i2;
   if (!(x == 0 || x == H - 1 || y == 0 || y == W - 1 || z == 0 || z == Z - 1)) return;
   if (L[i] >= 0) flag[L[i]] = 1u;
 }
@@ -184,30 +170,28 @@ cc_fill_kernel(const int* __restrict__ L, const unsigned int* __restrict__ flag,
 // weight, edt.hip).  Stream-ordered launches only.
 void cc_label26(const unsigned char* vol, int H, int W, int Z, int* L, hipStream_t s) {
   const long long n = (long long)H * W * Z;
-  const unsigned blocks = (unsigned)((n + 255) / 256);
+  const unsigned blocks = blocks_256(n);
   cc_init_kernel<false><<<blocks, 256, 0, s>>>(vol, n, Z, L);
   cc_merge_kernel<true><<<blocks, 256, 0, s>>>(L, n, H, W, Z);
-  cc_compress_kernel<<<blocks, 256, 0, s>>>(L, n);
+  launch_cc_compress(L, n, s);
 }
 
-size_t cc_workspace_bytes(int H, int W, int Z) {
-  const size_t n = (size_t)H * W * Z;
-  return align_up(n * 4, 256) * 2 + 256;               // labels, counts / border flags, CcSel
-}
+size_t cc_workspace_bytes(int H, int W, int Z) { return measured(cc_ws, H, W, Z); }
 
 int launch_largest_component(const unsigned char* vol, int H, int W, int Z, int rule, unsigned char* out, int* status_dev,
                              void* workspace, size_t ws_bytes, hipStream_t s) {
   SEUNET_CHECK(vol && out && workspace && H >= 1 && W >= 1 && Z >= 1, "largest_component: bad argument");
   SEUNET_CHECK(rule >= 0 && rule <= 2, "largest_component: rule %d (0 = evaluation_case, train.py:749-757; 1 = maximum_3d, util.py:58-75; "
                "2 = large_connected_domain26, util.py:156-165)", rule);
+  if (volume_check("largest_component", H, W, Z, 0, true)) return 1;
+  WsCarver carve(workspace);
+  const CcWs w = cc_ws(carve, H, W, Z);
+  SEUNET_CHECK(ws_bytes >= carve.bytes(), "largest_component: workspace too small");
   const long long n = (long long)H * W * Z;
-  SEUNET_CHECK(n < (1ll << 31), "largest_component: %lld voxels exceed the 32-bit label range", n);
-  SEUNET_CHECK(ws_bytes >= cc_workspace_bytes(H, W, Z), "largest_component: workspace too small");
-  unsigned char* ws = reinterpret_cast<unsigned char*>(workspace);
-  int* L = reinterpret_cast<int*>(ws);
-  unsigned int* cnt = reinterpret_cast<unsigned int*>(ws + align_up((size_t)n * 4, 256));
-  CcSel* sel = reinterpret_cast<CcSel*>(ws + 2 * align_up((size_t)n * 4, 256));
-  const unsigned blocks = (unsigned)((n + 255) / 256);
+  int* L = w.labels;
+  unsigned int* cnt = w.counts;
+  CcSel* sel = w.sel;
+  const unsigned blocks = blocks_256(n);
   SEUNET_HIP(hipMemsetAsync(cnt, 0, (size_t)n * 4, s));
   SEUNET_HIP(hipMemsetAsync(sel, 0, sizeof(CcSel), s));
   cc_label26(vol, H, W, Z, L, s);
@@ -216,7 +200,7 @@ int launch_largest_component(const unsigned char* vol, int H, int W, int Z, int 
   if (rule == 1) {
     cc_select_kernel<<<blocks, 256, 0, s>>>(L, cnt, n, 1, sel);
     const long long rows = (long long)H * W;
-    cc_slices_kernel<<<(unsigned)((rows * 3 + 255) / 256), 256, 0, s>>>(L, rows, Z, sel);
+    cc_slices_kernel<<<blocks_256(rows * 3), 256, 0, s>>>(L, rows, Z, sel);
   }
   cc_choose_kernel<<<1, 64, 0, s>>>(sel, rule);
   cc_mask_kernel<<<blocks, 256, 0, s>>>(L, n, sel, out);
@@ -224,7 +208,7 @@ int launch_largest_component(const unsigned char* vol, int H, int W, int Z, int 
     SEUNET_HIP(hipMemsetAsync(cnt, 0, (size_t)n * 4, s));
     cc_init_kernel<true><<<blocks, 256, 0, s>>>(out, n, Z, L);
     cc_merge_kernel<false><<<blocks, 256, 0, s>>>(L, n, H, W, Z);
-    cc_compress_kernel<<<blocks, 256, 0, s>>>(L, n);
+    launch_cc_compress(L, n, s);
     cc_border_kernel<<<blocks, 256, 0, s>>>(L, H, W, Z, cnt);
     cc_fill_kernel<<<blocks, 256, 0, s>>>(L, cnt, n, out);
   }
@@ -264,8 +248,7 @@ metric_sums_kernel(const unsigned char* __restrict__ pred, const unsigned char* 
     for (int off = 32; off >= 1; off >>= 1) v += shfl_xor_settled(v, off);
     if ((threadIdx.x & 63) == 0 && v) atomicAdd(&sums[q], v);
   }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) { const int o = shfl_xor_settled(mx, off); mx = o > mx ? o : mx; }
+  mx = wave_max(mx);
   if ((threadIdx.x & 63) == 0 && mx) atomicMax(max_id, mx);
 }
 

@@ -17,11 +17,9 @@
 //     2i + j = t are independent and ordered after t-1, so one workgroup walks the skewed wavefront t = 0 .. 2(h-1)+(w-1)
 //     with one thread per row and a barrier per step.  512^3: 1534 steps of <= 256 rows.
 // Integer / bit work: the result is bit-identical to the reference loop (tests/test_postprocess_gpu.py).
-#include "seunet_common.h"
+#include "volume.h"
 
 namespace seunet {
-
-typedef unsigned long long u64;
 
 // strong / weak masks, bit-packed along k.  One thread per (row, word).
 __global__ void __launch_bounds__(256)
@@ -103,25 +101,23 @@ dti_unpack_kernel(const u64* __restrict__ g, long long rows, int z, int nw, unsi
   out[idx] = (unsigned char)((g[row * nw + (k >> 6)] >> (k & 63)) & 1ull);
 }
 
-size_t dti_workspace_bytes(int h, int w, int z) {
-  const long long nw = (z + 63) / 64;
-  return (size_t)(2 * (long long)h * w * nw * 8);
-}
+size_t dti_workspace_bytes(int h, int w, int z) { return measured(dti_ws, h, w, z); }
 
 int launch_dti(const double* pred, int h, int w, int z, double h_thresh, double l_thresh, int pred_dtype, unsigned char* out,
                void* workspace, size_t ws_bytes, hipStream_t s) {
   SEUNET_CHECK(pred && out && workspace && h >= 1 && w >= 1 && z >= 1, "dti: bad argument");
   SEUNET_CHECK(pred_dtype == 0 || pred_dtype == 1, "dti: pred_dtype %d (0 = float64 copy of prediction.py, 1 = float32 copy of train.py / test.py)", pred_dtype);
-  SEUNET_CHECK(ws_bytes >= dti_workspace_bytes(h, w, z), "dti: workspace too small");
+  WsCarver carve(workspace);
+  const DtiWs ws = dti_ws(carve, h, w, z);
+  SEUNET_CHECK(ws_bytes >= carve.bytes(), "dti: workspace too small");
   const int nw = (z + 63) / 64;
   const long long rows = (long long)h * w;
-  u64* g = reinterpret_cast<u64*>(workspace);
-  u64* weak = g + rows * nw;
+  u64 *g = ws.g, *weak = ws.weak;
   double hs = h_thresh * 255.0, ls = l_thresh * 255.0;         // (h_thresh*255, l_thresh*255 in float64, prediction.py:20,28)
   if (pred_dtype == 1) { hs = (double)(float)hs; ls = (double)(float)ls; }   // weak python scalars adopt the array's float32
-  dti_pack_kernel<<<(unsigned)((rows * nw + 255) / 256), 256, 0, s>>>(pred, rows, z, nw, hs, ls, pred_dtype, g, weak);
+  dti_pack_kernel<<<blocks_256(rows * nw), 256, 0, s>>>(pred, rows, z, nw, hs, ls, pred_dtype, g, weak);
   dti_sweep_kernel<<<1, 1024, 0, s>>>(g, weak, h, w, nw);
-  dti_unpack_kernel<<<(unsigned)((rows * z + 255) / 256), 256, 0, s>>>(g, rows, z, nw, out);
+  dti_unpack_kernel<<<blocks_256(rows * z), 256, 0, s>>>(g, rows, z, nw, out);
   SEUNET_LAUNCH_CHECK();
   return 0;
 }

@@ -23,15 +23,13 @@
 //
 // Integer / index work and IEEE-rounded float chains in the reference's order: results are bit-identical to the reference
 // (tests/test_prep_gpu.py against tests/golden/prep_known.npz).
-#include "seunet_common.h"
+#include "volume.h"
 #include <algorithm>
 
 // numpy does not contract a * b + c into a fused multiply-add; hipcc does by default
 #pragma clang fp contract(off)
 
 namespace seunet {
-
-typedef unsigned long long u64;
 
 // ---- exact EDT / feature transform ----------------------------------------------------------------------------------
 
@@ -56,7 +54,7 @@ edt_pass0_kernel(const unsigned char* __restrict__ vol, int n0, long long plane,
   }
 }
 
-// EdtOut (what the last pass writes, each part optional): seunet_common.h
+// EdtOut (what the last pass writes, each part optional) and the workspace layout EdtWs: volume.h
 
 // pass D (1 or 2) along axis D.  in0 / in1: features along axes 0 / 1 of the previous passes (in1 for D == 2 only).
 // D == 1 writes out0 / out1 (features along axes 0 / 1); D == 2 writes the final outputs.
@@ -154,37 +152,22 @@ edt_pass_kernel(const short* __restrict__ in0, const short* __restrict__ in1, in
   }
 }
 
-static int edt_check(int n0, int n1, int n2, const char* what) {
-  SEUNET_CHECK(n0 >= 1 && n1 >= 1 && n2 >= 1, "%s: bad extents (%d, %d, %d)", what, n0, n1, n2);
-  SEUNET_CHECK(n0 <= 32767 && n1 <= 32767 && n2 <= 32767, "%s: extents (%d, %d, %d): at most 32767 per axis", what, n0, n1, n2);
-  SEUNET_CHECK((long long)n0 * n1 * n2 < (1ll << 31), "%s: %lld voxels: fewer than 2^31 supported", what, (long long)n0 * n1 * n2);
-  return 0;
-}
-
-size_t edt_workspace_bytes(int n0, int n1, int n2) {
-  const size_t n = (size_t)n0 * n1 * n2;
-  return align_up(n * 2, 256) * 4 + align_up(n * 4, 256);     // f0, pass-1 features (2), stack positions; stack offsets
-}
+size_t edt_workspace_bytes(int n0, int n1, int n2) { return measured(edt_ws, n0, n1, n2); }
 
 int run_edt(const unsigned char* vol, bool invert, int n0, int n1, int n2, EdtOut o, int* status_dev, void* workspace, size_t ws_bytes,
             hipStream_t s) {
   SEUNET_CHECK(vol && workspace, "edt: null argument");
-  if (edt_check(n0, n1, n2, "edt")) return 1;
-  SEUNET_CHECK(ws_bytes >= edt_workspace_bytes(n0, n1, n2), "edt: workspace too small");
-  const size_t n = (size_t)n0 * n1 * n2;
-  unsigned char* ws = reinterpret_cast<unsigned char*>(workspace);
-  short* f0 = reinterpret_cast<short*>(ws);
-  short* fa = reinterpret_cast<short*>(ws + align_up(n * 2, 256));
-  short* fb = reinterpret_cast<short*>(ws + 2 * align_up(n * 2, 256));
-  short* spos = reinterpret_cast<short*>(ws + 3 * align_up(n * 2, 256));
-  int* sr = reinterpret_cast<int*>(ws + 4 * align_up(n * 2, 256));
+  if (volume_check("edt", n0, n1, n2, kEdtMaxExtent)) return 1;
+  WsCarver carve(workspace);
+  const EdtWs w = edt_ws(carve, n0, n1, n2);
+  SEUNET_CHECK(ws_bytes >= carve.bytes(), "edt: workspace too small");
   if (status_dev) SEUNET_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(status_dev), 1, 1, s));
   const long long plane = (long long)n1 * n2;
-  if (invert) edt_pass0_kernel<true><<<(unsigned)((plane + 255) / 256), 256, 0, s>>>(vol, n0, plane, f0, status_dev);
-  else edt_pass0_kernel<false><<<(unsigned)((plane + 255) / 256), 256, 0, s>>>(vol, n0, plane, f0, status_dev);
+  if (invert) edt_pass0_kernel<true><<<blocks_256(plane), 256, 0, s>>>(vol, n0, plane, w.f0, status_dev);
+  else edt_pass0_kernel<false><<<blocks_256(plane), 256, 0, s>>>(vol, n0, plane, w.f0, status_dev);
   const long long l1 = (long long)n0 * n2, l2 = (long long)n0 * n1;
-  edt_pass_kernel<1><<<(unsigned)((l1 + 255) / 256), 256, 0, s>>>(f0, nullptr, n0, n1, n2, spos, sr, fa, fb, o);
-  edt_pass_kernel<2><<<(unsigned)((l2 + 255) / 256), 256, 0, s>>>(fa, fb, n0, n1, n2, spos, sr, nullptr, nullptr, o);
+  edt_pass_kernel<1><<<blocks_256(l1), 256, 0, s>>>(w.f0, nullptr, n0, n1, n2, w.spos, w.sr, w.fa, w.fb, o);
+  edt_pass_kernel<2><<<blocks_256(l2), 256, 0, s>>>(w.fa, w.fb, n0, n1, n2, w.spos, w.sr, nullptr, nullptr, o);
   SEUNET_LAUNCH_CHECK();
   return 0;
 }
@@ -219,9 +202,8 @@ hm_candidates_kernel(const unsigned char* __restrict__ label, const unsigned cha
     sk = on && pred[i] != 1;
     sm = !on || label[i] == 0;
     if (!sm) {
-      const int i2 = (int)(i % n2);
-      const long long r = i / n2;
-      const int i1 = (int)(r % n1), i0 = (int)(r / n1);
+      const Vox3 p = vox3(i, n1, n2);
+      const int i0 = p.i0, i1 = p.i1, i2 = p.i2;
       for (int a = std::max(i0 - 1, 0); a <= std::min(i0 + 1, n0 - 1) && !sm; ++a)
         for (int b = std::max(i1 - 1, 0); b <= std::min(i1 + 1, n1 - 1) && !sm; ++b) {
           const unsigned char* row = label + ((long long)a * n1 + b) * n2;
@@ -235,7 +217,7 @@ hm_candidates_kernel(const unsigned char* __restrict__ label, const unsigned cha
 
 int launch_mask_bits(const unsigned char* mask, long long n, u64* bits, hipStream_t s) {
   SEUNET_CHECK(mask && bits && n >= 1, "mask_bits: bad argument");
-  mask_bits_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(mask, n, bits);
+  mask_bits_kernel<<<blocks_256(n), 256, 0, s>>>(mask, n, bits);
   SEUNET_LAUNCH_CHECK();
   return 0;
 }
@@ -243,9 +225,9 @@ int launch_mask_bits(const unsigned char* mask, long long n, u64* bits, hipStrea
 int launch_hm_candidates(const unsigned char* label, const unsigned char* skel, const unsigned char* pred, int n0, int n1, int n2,
                          u64* skel_bits, u64* small_bits, hipStream_t s) {
   SEUNET_CHECK(label && skel && pred && skel_bits && small_bits, "hard_mining_candidates: null argument");
-  if (edt_check(n0, n1, n2, "hard_mining_candidates")) return 1;
+  if (volume_check("hard_mining_candidates", n0, n1, n2, kEdtMaxExtent)) return 1;
   const long long n = (long long)n0 * n1 * n2;
-  hm_candidates_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(label, skel, pred, n0, n1, n2, skel_bits, small_bits);
+  hm_candidates_kernel<<<blocks_256(n), 256, 0, s>>>(label, skel, pred, n0, n1, n2, skel_bits, small_bits);
   SEUNET_LAUNCH_CHECK();
   return 0;
 }
@@ -279,7 +261,7 @@ box7_kernel(const unsigned char* __restrict__ in, int n0, int n1, int n2, unsign
   const long long n = (long long)n0 * n1 * n2;
   const long long i = blockIdx.x * 256ll + threadIdx.x;
   if (i >= n) return;
-  const int i2 = (int)(i % n2);
+  const int i2 = (int)(i % n2);     // (not vox3: the row index r itself is used)
   const long long r = i / n2;
   const int i1 = (int)(r % n1);
   int acc = 0;
@@ -306,22 +288,21 @@ lib_weight_kernel(const unsigned char* __restrict__ cnt12, const unsigned char* 
   out[i] = (f16_t)f32_opaque(table.v[c] * (label[i] != 0 ? 1.0f : 0.0f));
 }
 
-size_t lib_weight_workspace_bytes(int n0, int n1, int n2) { return align_up((size_t)n0 * n1 * n2, 256) * 2; }
+size_t lib_weight_workspace_bytes(int n0, int n1, int n2) { return measured(lib_weight_ws, n0, n1, n2); }
 
 int launch_lib_weight(const unsigned char* label, int n0, int n1, int n2, const float* table, void* out, void* workspace,
                       size_t ws_bytes, hipStream_t s) {
   SEUNET_CHECK(label && table && out && workspace, "lib_weight: null argument");
-  if (edt_check(n0, n1, n2, "lib_weight")) return 1;
-  SEUNET_CHECK(ws_bytes >= lib_weight_workspace_bytes(n0, n1, n2), "lib_weight: workspace too small");
-  const long long n = (long long)n0 * n1 * n2;
+  if (volume_check("lib_weight", n0, n1, n2, kEdtMaxExtent)) return 1;
+  WsCarver carve(workspace);
+  const LibWeightWs w = lib_weight_ws(carve, n0, n1, n2);
+  SEUNET_CHECK(ws_bytes >= carve.bytes(), "lib_weight: workspace too small");
   LibTable t;
   for (int k = 0; k < 344; ++k) t.v[k] = table[k];
-  unsigned char* c2 = reinterpret_cast<unsigned char*>(workspace);
-  unsigned char* c12 = c2 + align_up((size_t)n, 256);
-  const unsigned blocks = (unsigned)((n + 255) / 256);
-  box7_kernel<2><<<blocks, 256, 0, s>>>(label, n0, n1, n2, c2);
-  box7_kernel<1><<<blocks, 256, 0, s>>>(c2, n0, n1, n2, c12);
-  lib_weight_kernel<<<blocks, 256, 0, s>>>(c12, label, n0, n1, n2, t, reinterpret_cast<f16_t*>(out));
+  const unsigned blocks = blocks_256((long long)n0 * n1 * n2);
+  box7_kernel<2><<<blocks, 256, 0, s>>>(label, n0, n1, n2, w.c2);
+  box7_kernel<1><<<blocks, 256, 0, s>>>(w.c2, n0, n1, n2, w.c12);
+  lib_weight_kernel<<<blocks, 256, 0, s>>>(w.c12, label, n0, n1, n2, t, reinterpret_cast<f16_t*>(out));
   SEUNET_LAUNCH_CHECK();
   return 0;
 }
@@ -387,12 +368,7 @@ br_maxf_kernel(const int* __restrict__ lin, const unsigned char* __restrict__ fn
     const int ft = lin[i];
     if (ft >= 0 && fn[ft] && label[i]) f = sqrt((double)sq_to(i, ft, n1, n2)) * (1.0 - (skel[i] != 0 ? 1.0 : 0.0));
   }
-  u64 key = __builtin_bit_cast(u64, f);                        // non-negative doubles order like their bit patterns
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const u64 o = shfl_xor_settled(key, off);
-    key = o > key ? o : key;
-  }
+  const u64 key = wave_max(__builtin_bit_cast(u64, f));        // non-negative doubles order like their bit patterns
   if ((threadIdx.x & 63) == 0 && key) atomicMax(maxf, key);
 }
 
@@ -403,17 +379,7 @@ br_endpoint_kernel(const int* __restrict__ L, const unsigned char* __restrict__ 
   const long long n = (long long)n0 * n1 * n2;
   const long long i = blockIdx.x * 256ll + threadIdx.x;
   if (i >= n || L[i] < 0) return;
-  const int i2 = (int)(i % n2);
-  const long long r = i / n2;
-  const int i1 = (int)(r % n1), i0 = (int)(r / n1);
-  int cnt = 0;
-  for (int a = -1; a <= 1; ++a)                               // 'reflect' at radius 1 repeats the edge voxel
-    for (int b = -1; b <= 1; ++b) {
-      const int x0 = std::min(std::max(i0 + a, 0), n0 - 1), x1 = std::min(std::max(i1 + b, 0), n1 - 1);
-      const unsigned char* row = skel + ((long long)x0 * n1 + x1) * n2;
-      for (int c = -1; c <= 1; ++c) cnt += row[std::min(std::max(i2 + c, 0), n2 - 1)] != 0;
-    }
-  if (cnt == 2) flag[L[i]] = 1;
+  if (count27_clamped(skel, vox3(i, n1, n2), n0, n1, n2) == 2) flag[L[i]] = 1;   // 'reflect' at radius 1 repeats the edge voxel
 }
 
 __global__ void __launch_bounds__(256)
@@ -437,9 +403,8 @@ br_shell_kernel(const unsigned char* __restrict__ brl, int n0, int n1, int n2, u
   const long long n = (long long)n0 * n1 * n2;
   const long long i = blockIdx.x * 256ll + threadIdx.x;
   if (i >= n) return;
-  const int i2 = (int)(i % n2);
-  const long long r = i / n2;
-  const int i1 = (int)(r % n1), i0 = (int)(r / n1);
+  const Vox3 v = vox3(i, n1, n2);
+  const int i0 = v.i0, i1 = v.i1, i2 = v.i2;
   const long long p = (long long)n1 * n2;
   const bool on = !brl[i] && ((i2 > 0 && brl[i - 1]) || (i2 + 1 < n2 && brl[i + 1]) || (i1 > 0 && brl[i - n2]) ||
                               (i1 + 1 < n1 && brl[i + n2]) || (i0 > 0 && brl[i - p]) || (i0 + 1 < n0 && brl[i + p]));
@@ -468,9 +433,8 @@ br_final_kernel(const int* __restrict__ lin, const unsigned char* __restrict__ f
   // w_br
   float w_br = 0.0f;
   if (brl[i]) {
-    const int i2 = (int)(i % n2);
-    const long long r = i / n2;
-    const int i1 = (int)(r % n1), i0 = (int)(r / n1);
+    const Vox3 v = vox3(i, n1, n2);
+    const int i0 = v.i0, i1 = v.i1, i2 = v.i2;
     int best = 4;
     for (int a = -1; a <= 1; ++a)
       for (int b = -1; b <= 1; ++b)
@@ -491,39 +455,29 @@ br_final_kernel(const int* __restrict__ lin, const unsigned char* __restrict__ f
   w_out[i] = __builtin_bit_cast(unsigned short, (f16_t)t);
 }
 
-size_t break_weight_workspace_bytes(int n0, int n1, int n2) {
-  const size_t n = (size_t)n0 * n1 * n2;
-  return edt_workspace_bytes(n0, n1, n2) + align_up(n * 4, 256) * 2 + align_up(n, 256) * 5 + 256;
-}
+size_t break_weight_workspace_bytes(int n0, int n1, int n2) { return measured(break_weight_ws, n0, n1, n2); }
 
 int launch_break_weight(const unsigned char* label, const unsigned char* pred, const unsigned char* skel, int n0, int n1, int n2,
                         void* w_br, unsigned char* br_skel, int* status_dev, void* workspace, size_t ws_bytes, hipStream_t s) {
   SEUNET_CHECK(label && pred && skel && w_br && br_skel && workspace, "break_weight: null argument");
-  if (edt_check(n0, n1, n2, "break_weight")) return 1;
-  SEUNET_CHECK(ws_bytes >= break_weight_workspace_bytes(n0, n1, n2), "break_weight: workspace too small");
+  if (volume_check("break_weight", n0, n1, n2, kEdtMaxExtent)) return 1;
+  WsCarver carve(workspace);
+  const BreakWeightWs w = break_weight_ws(carve, n0, n1, n2);
+  SEUNET_CHECK(ws_bytes >= carve.bytes(), "break_weight: workspace too small");
   const long long n = (long long)n0 * n1 * n2;
-  unsigned char* ws = reinterpret_cast<unsigned char*>(workspace);
-  const size_t e_b = edt_workspace_bytes(n0, n1, n2), i_b = align_up((size_t)n * 4, 256), b_b = align_up((size_t)n, 256);
-  int* lin = reinterpret_cast<int*>(ws + e_b);
-  int* L = reinterpret_cast<int*>(ws + e_b + i_b);
-  unsigned char* fn = ws + e_b + 2 * i_b;
-  unsigned char* flag = fn + b_b;
-  unsigned char* brs = flag + b_b;
-  unsigned char* brl = brs + b_b;
-  unsigned char* shell = brl + b_b;
-  u64* maxf = reinterpret_cast<u64*>(shell + b_b);
-  const unsigned blocks = (unsigned)((n + 255) / 256);
-  SEUNET_HIP(hipMemsetAsync(flag, 0, (size_t)n, s));
-  SEUNET_HIP(hipMemsetAsync(maxf, 0, sizeof(u64), s));
-  fnskel_kernel<<<blocks, 256, 0, s>>>(label, pred, skel, n, fn);
-  if (run_edt(skel, true, n0, n1, n2, EdtOut{nullptr, nullptr, nullptr, lin, nullptr, nullptr, nullptr}, status_dev, ws, e_b, s)) return 1;
-  br_maxf_kernel<<<blocks, 256, 0, s>>>(lin, fn, label, skel, n0, n1, n2, maxf);
-  cc_label26(fn, n0, n1, n2, L, s);
-  br_endpoint_kernel<<<blocks, 256, 0, s>>>(L, skel, n0, n1, n2, flag);
-  br_skel_kernel<<<blocks, 256, 0, s>>>(L, flag, n, brs);
-  br_label_kernel<<<blocks, 256, 0, s>>>(lin, brs, label, n, brl);
-  br_shell_kernel<<<blocks, 256, 0, s>>>(brl, n0, n1, n2, shell);
-  br_final_kernel<<<blocks, 256, 0, s>>>(lin, fn, label, skel, brs, brl, shell, maxf, n0, n1, n2,
+  const unsigned blocks = blocks_256(n);
+  SEUNET_HIP(hipMemsetAsync(w.flag, 0, (size_t)n, s));
+  SEUNET_HIP(hipMemsetAsync(w.maxf, 0, sizeof(u64), s));
+  fnskel_kernel<<<blocks, 256, 0, s>>>(label, pred, skel, n, w.fn);
+  if (run_edt(skel, true, n0, n1, n2, EdtOut{nullptr, nullptr, nullptr, w.lin, nullptr, nullptr, nullptr}, status_dev, w.edt.f0, w.edt_bytes, s))
+    return 1;
+  br_maxf_kernel<<<blocks, 256, 0, s>>>(w.lin, w.fn, label, skel, n0, n1, n2, w.maxf);
+  cc_label26(w.fn, n0, n1, n2, w.labels, s);
+  br_endpoint_kernel<<<blocks, 256, 0, s>>>(w.labels, skel, n0, n1, n2, w.flag);
+  br_skel_kernel<<<blocks, 256, 0, s>>>(w.labels, w.flag, n, w.brs);
+  br_label_kernel<<<blocks, 256, 0, s>>>(w.lin, w.brs, label, n, w.brl);
+  br_shell_kernel<<<blocks, 256, 0, s>>>(w.brl, n0, n1, n2, w.shell);
+  br_final_kernel<<<blocks, 256, 0, s>>>(w.lin, w.fn, label, skel, w.brs, w.brl, w.shell, w.maxf, n0, n1, n2,
                                          reinterpret_cast<unsigned short*>(w_br), br_skel);
   SEUNET_LAUNCH_CHECK();
   return 0;

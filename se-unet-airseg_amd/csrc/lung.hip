@@ -9,18 +9,16 @@
 //                  when they have more than min_area pixels
 //   box / crops    preprocessing.py:81-104 (the margin arithmetic is the caller's)
 //
-// The per-slice labelling is the union-find of components.hip (cc_find / cc_union, seunet_common.h) restricted to in-plane
+// The per-slice labelling is the union-find of components.hip (cc_find / cc_union, volume.h) restricted to in-plane
 // neighbours: lanes run along the contiguous axis 2, so a wave holds up to 64 different slices at one (i, j), every neighbour
 // read (strides Z and W*Z) is coalesced, and no link ever crosses from one slice to another.  For a fixed n the minimum
 // linear index of a component is the raster order of its first pixel (i, j), i.e. skimage's / scipy's label order, which is the
 // tie rule of np.argmax over the bincounts.  The per-slice argmax is one 64-bit atomicMax of (count << 32) | ~root into a
 // Z-entry array: the most pixels first, then the smallest root.  Integer work only: the result is deterministic.
-#include "seunet_common.h"
+#include "volume.h"
 #include <algorithm>
 
 namespace seunet {
-
-typedef unsigned long long u64;
 
 // ---- value counts -----------------------------------------------------------------------------------------------------------
 // One block counts LUNG_COUNT_CHUNK consecutive voxels into 65536 16-bit counters packed two to an LDS word (128 KiB); the chunk
@@ -84,7 +82,7 @@ lung_shift_clamp_kernel(const short* __restrict__ ct, long long n, int shift, in
 int launch_shift_clamp(const short* ct, long long n, int shift, int clamp, int clamp_le, int clamp_to, short* out, hipStream_t s) {
   SEUNET_CHECK(ct && out && n >= 1, "shift_clamp: bad argument");
   SEUNET_CHECK(clamp_to >= -32768 && clamp_to <= 32767, "shift_clamp: clamp value %d is not an int16", clamp_to);
-  lung_shift_clamp_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(ct, n, shift, clamp, clamp_le, (short)clamp_to, out);
+  lung_shift_clamp_kernel<<<blocks_256(n), 256, 0, s>>>(ct, n, shift, clamp, clamp_le, (short)clamp_to, out);
   SEUNET_LAUNCH_CHECK();
   return 0;
 }
@@ -118,8 +116,8 @@ lung_merge_kernel(int* L, long long n, int W, int Z) {
   const long long i = blockIdx.x * 256ll + threadIdx.x;
   if (i >= n) return;
   if (L[i] < 0) return;
-  const long long r = i / Z;
-  const int y = (int)(r % W), x = (int)(r / W);
+  const Vox3 p = vox3(i, W, Z);
+  const int x = p.i0, y = p.i1;
   const long long sx = (long long)W * Z;
   if (y > 0 && L[i - Z] >= 0) cc_union(L, (int)i, (int)(i - Z));
   if (x > 0) {
@@ -129,13 +127,6 @@ lung_merge_kernel(int* L, long long n, int W, int Z) {
       if (y < W - 1 && L[i - sx + Z] >= 0) cc_union(L, (int)i, (int)(i - sx + Z));
     }
   }
-}
-
-__global__ void __launch_bounds__(256)
-lung_compress_kernel(int* L, long long n) {
-  const long long i = blockIdx.x * 256ll + threadIdx.x;
-  if (i >= n) return;
-  if (L[i] >= 0) L[i] = cc_find(L, (int)i);
 }
 
 // pixel count per root (roots of neighbouring lanes lie in different slices: no wave aggregation)
@@ -180,8 +171,8 @@ __global__ void __launch_bounds__(256)
 lung_border_kernel(const int* __restrict__ L, long long n, int H, int W, int Z, unsigned int* __restrict__ flag) {
   const long long i = blockIdx.x * 256ll + threadIdx.x;
   if (i >= n) return;
-  const long long r = i / Z;
-  const int y = (int)(r % W), x = (int)(r / W);
+  const Vox3 p = vox3(i, W, Z);
+  const int x = p.i0, y = p.i1;
   if (!(x == 0 || x == H - 1 || y == 0 || y == W - 1)) return;
   if (L[i] >= 0) flag[L[i]] = 1u;
 }
@@ -208,44 +199,40 @@ lung_write_kernel(const int* __restrict__ L, long long n, int Z, const u64* __re
   out[i] = (r >= 0 && (in1 || in2)) ? 1 : 0;
 }
 
-size_t get_l_workspace_bytes(int H, int W, int Z) {
-  const size_t n = (size_t)H * W * Z;
-  return align_up(n * 4, 256) * 2 + align_up((size_t)Z * 8, 256) * 3;   // labels, counts / border flags, three per-slice keys
-}
+size_t get_l_workspace_bytes(int H, int W, int Z) { return measured(get_l_ws, H, W, Z); }
 
 int launch_get_l(const short* ct, int H, int W, int Z, double T, int min_area, unsigned char* out, void* workspace, size_t ws_bytes,
                  hipStream_t s) {
   SEUNET_CHECK(ct && out && workspace && H >= 1 && W >= 1 && Z >= 1 && min_area >= 0, "get_l: bad argument");
+  if (volume_check("get_l", H, W, Z, 0, true)) return 1;
+  WsCarver carve(workspace);
+  const GetLWs w = get_l_ws(carve, H, W, Z);
+  SEUNET_CHECK(ws_bytes >= carve.bytes(), "get_l: workspace too small");
   const long long n = (long long)H * W * Z;
-  SEUNET_CHECK(n < (1ll << 31), "get_l: %lld voxels exceed the 32-bit label range", n);
-  SEUNET_CHECK(ws_bytes >= get_l_workspace_bytes(H, W, Z), "get_l: workspace too small");
-  unsigned char* ws = reinterpret_cast<unsigned char*>(workspace);
-  int* L = reinterpret_cast<int*>(ws);
-  unsigned int* cnt = reinterpret_cast<unsigned int*>(ws + align_up((size_t)n * 4, 256));
-  u64* best = reinterpret_cast<u64*>(ws + 2 * align_up((size_t)n * 4, 256));
-  u64* top1 = best + align_up((size_t)Z * 8, 256) / 8;
-  u64* top2 = top1 + align_up((size_t)Z * 8, 256) / 8;
+  int* L = w.labels;
+  unsigned int* cnt = w.counts;
+  u64 *best = w.best, *top1 = w.top1, *top2 = w.top2;
   const SliceRange r = get_l_range(Z);
-  const unsigned blocks = (unsigned)((n + 255) / 256);
+  const unsigned blocks = blocks_256(n);
   SEUNET_HIP(hipMemsetAsync(cnt, 0, (size_t)n * 4, s));
-  SEUNET_HIP(hipMemsetAsync(best, 0, align_up((size_t)Z * 8, 256) * 3, s));
+  SEUNET_HIP(hipMemsetAsync(best, 0, w.key_bytes, s));          // best, top1 and top2
   // img1: the largest 8-connected component of ct >= T per slice (skimage's measure.label default connectivity in 2-D)
   lung_threshold_kernel<<<blocks, 256, 0, s>>>(ct, n, Z, T, r, L);
   lung_merge_kernel<true><<<blocks, 256, 0, s>>>(L, n, W, Z);
-  lung_compress_kernel<<<blocks, 256, 0, s>>>(L, n);
+  launch_cc_compress(L, n, s);
   lung_count_kernel<<<blocks, 256, 0, s>>>(L, n, cnt);
   lung_select_kernel<false><<<blocks, 256, 0, s>>>(L, cnt, n, Z, nullptr, best);
   // its holes: the 4-connected background components (binary_fill_holes' default cross) that do not reach the slice border
   lung_complement_kernel<<<blocks, 256, 0, s>>>(L, n, Z, r, best);
   SEUNET_HIP(hipMemsetAsync(cnt, 0, (size_t)n * 4, s));
   lung_merge_kernel<false><<<blocks, 256, 0, s>>>(L, n, W, Z);
-  lung_compress_kernel<<<blocks, 256, 0, s>>>(L, n);
+  launch_cc_compress(L, n, s);
   lung_border_kernel<<<blocks, 256, 0, s>>>(L, n, H, W, Z, cnt);
   lung_holes_kernel<<<blocks, 256, 0, s>>>(L, n, cnt);
   // the holes relabelled 8-connected (holes touching at a corner merge), the two largest per slice
   SEUNET_HIP(hipMemsetAsync(cnt, 0, (size_t)n * 4, s));
   lung_merge_kernel<true><<<blocks, 256, 0, s>>>(L, n, W, Z);
-  lung_compress_kernel<<<blocks, 256, 0, s>>>(L, n);
+  launch_cc_compress(L, n, s);
   lung_count_kernel<<<blocks, 256, 0, s>>>(L, n, cnt);
   lung_select_kernel<false><<<blocks, 256, 0, s>>>(L, cnt, n, Z, nullptr, top1);
   lung_select_kernel<true><<<blocks, 256, 0, s>>>(L, cnt, n, Z, top1, top2);
@@ -268,7 +255,7 @@ lung_combine_kernel(const unsigned char* __restrict__ a, const unsigned char* __
 int launch_mask_combine(const unsigned char* a, const unsigned char* b, long long n, int op, unsigned char* out, hipStream_t s) {
   SEUNET_CHECK(a && b && out && n >= 1, "mask_combine: bad argument");
   SEUNET_CHECK(op == 0 || op == 1, "mask_combine: op %d (0 = xor, 1 = or)", op);
-  lung_combine_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(a, b, n, op, out);
+  lung_combine_kernel<<<blocks_256(n), 256, 0, s>>>(a, b, n, op, out);
   SEUNET_LAUNCH_CHECK();
   return 0;
 }
@@ -283,9 +270,8 @@ lung_box_kernel(const unsigned char* __restrict__ mask, long long n, int W, int 
   int lo[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, hi[3] = {-1, -1, -1};
   for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
     if (!mask[i]) continue;
-    const int z = (int)(i % Z);
-    const long long r = i / Z;
-    const int c[3] = {(int)(r / W), (int)(r % W), z};
+    const Vox3 p = vox3(i, W, Z);
+    const int c[3] = {p.i0, p.i1, p.i2};
 #pragma unroll
     for (int a = 0; a < 3; ++a) { lo[a] = min(lo[a], c[a]); hi[a] = max(hi[a], c[a]); }
   }
@@ -319,10 +305,8 @@ __global__ void __launch_bounds__(256)
 lung_crop_kernel(const T* __restrict__ src, int W, int Z, int x0, int y0, int z0, int cw, int cz, long long m, T* __restrict__ dst) {
   const long long i = blockIdx.x * 256ll + threadIdx.x;
   if (i >= m) return;
-  const int z = (int)(i % cz);
-  const long long r = i / cz;
-  const int y = (int)(r % cw), x = (int)(r / cw);
-  dst[i] = src[((long long)(x0 + x) * W + (y0 + y)) * Z + (z0 + z)];
+  const Vox3 p = vox3(i, cw, cz);
+  dst[i] = src[((long long)(x0 + p.i0) * W + (y0 + p.i1)) * Z + (z0 + p.i2)];
 }
 
 int launch_crop3d(const void* src, int elem_bytes, int H, int W, int Z, const int* box, void* dst, hipStream_t s) {
@@ -334,7 +318,7 @@ int launch_crop3d(const void* src, int elem_bytes, int H, int W, int Z, const in
                  box[2 * a], box[2 * a + 1], a, ext[a]);
   const int cw = box[3] - box[2], cz = box[5] - box[4];
   const long long m = (long long)(box[1] - box[0]) * cw * cz;
-  const unsigned blocks = (unsigned)((m + 255) / 256);
+  const unsigned blocks = blocks_256(m);
   if (elem_bytes == 1)
     lung_crop_kernel<unsigned char><<<blocks, 256, 0, s>>>((const unsigned char*)src, W, Z, box[0], box[2], box[4], cw, cz, m,
                                                           (unsigned char*)dst);

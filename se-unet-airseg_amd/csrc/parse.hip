@@ -13,34 +13,21 @@
 // they are: the second labelling is the rank among the roots that survive.  Ranks come from a prefix sum over the volume (block
 // counts, one scan, in-block ballots): no atomic decides an order, the result is deterministic.
 // Integer / index work: results are bit-identical to the reference (tests/test_parse_gpu.py against tests/golden/parse_known.npz).
-#include "seunet_common.h"
+#include "volume.h"
 #include <algorithm>
 
 namespace seunet {
 
-typedef unsigned long long u64;
-
 // ---- skeleton_parsing ---------------------------------------------------------------------------------------------------
 
-// keep[i] = skeleton voxel whose 3x3x3 sum (centre included) is at most 3.  'reflect' at radius 1 repeats the edge voxel
-// (index -1 -> 0, n -> n - 1): a voxel on a face counts itself and its in-face neighbours twice.
+// keep[i] = skeleton voxel whose 3x3x3 sum (centre included, mode 'reflect': count27_clamped) is at most 3
 __global__ void __launch_bounds__(256)
 branch_point_kernel(const unsigned char* __restrict__ skel, int n0, int n1, int n2, unsigned char* __restrict__ keep) {
   const long long n = (long long)n0 * n1 * n2;
   const long long i = blockIdx.x * 256ll + threadIdx.x;
   if (i >= n) return;
   if (skel[i] == 0) { keep[i] = 0; return; }
-  const int i2 = (int)(i % n2);
-  const long long r = i / n2;
-  const int i1 = (int)(r % n1), i0 = (int)(r / n1);
-  int cnt = 0;
-  for (int a = -1; a <= 1; ++a)
-    for (int b = -1; b <= 1; ++b) {
-      const int x0 = std::min(std::max(i0 + a, 0), n0 - 1), x1 = std::min(std::max(i1 + b, 0), n1 - 1);
-      const unsigned char* row = skel + ((long long)x0 * n1 + x1) * n2;
-      for (int c = -1; c <= 1; ++c) cnt += row[std::min(std::max(i2 + c, 0), n2 - 1)] != 0;
-    }
-  keep[i] = cnt <= 3 ? 1 : 0;
+  keep[i] = count27_clamped(skel, vox3(i, n1, n2), n0, n1, n2) <= 3 ? 1 : 0;
 }
 
 __device__ __forceinline__ bool surviving_root(const int* L, const unsigned int* cnt, long long i, long long n, int min_voxels) {
@@ -115,39 +102,26 @@ branch_number_kernel(const int* __restrict__ L, const unsigned int* __restrict__
   if (parse) parse[i] = v ? 1 : 0;
 }
 
-static int parse_check(int n0, int n1, int n2, const char* what) {
-  SEUNET_CHECK(n0 >= 1 && n1 >= 1 && n2 >= 1, "%s: bad extents (%d, %d, %d)", what, n0, n1, n2);
-  SEUNET_CHECK((long long)n0 * n1 * n2 < (1ll << 31), "%s: %lld voxels: fewer than 2^31 supported", what, (long long)n0 * n1 * n2);
-  return 0;
-}
-
-size_t skeleton_branches_workspace_bytes(int n0, int n1, int n2) {
-  const size_t n = (size_t)n0 * n1 * n2;
-  return align_up(n * 4, 256) * 2 + align_up(n, 256) + align_up(((n + 255) / 256) * 4, 256);   // labels, counts, kept voxels, block sums
-}
+size_t skeleton_branches_workspace_bytes(int n0, int n1, int n2) { return measured(branches_ws, n0, n1, n2); }
 
 int launch_skeleton_branches(const unsigned char* skel, int n0, int n1, int n2, int min_voxels, int* cd, unsigned char* skeleton_parse,
                              int* num_dev, void* workspace, size_t ws_bytes, hipStream_t s) {
   SEUNET_CHECK(skel && cd && workspace, "skeleton_branches: null argument");
-  if (parse_check(n0, n1, n2, "skeleton_branches")) return 1;
+  if (volume_check("skeleton_branches", n0, n1, n2, 0)) return 1;
   SEUNET_CHECK(min_voxels >= 0, "skeleton_branches: min_voxels %d", min_voxels);
-  SEUNET_CHECK(ws_bytes >= skeleton_branches_workspace_bytes(n0, n1, n2), "skeleton_branches: workspace too small");
+  WsCarver carve(workspace);
+  const BranchesWs w = branches_ws(carve, n0, n1, n2);
+  SEUNET_CHECK(ws_bytes >= carve.bytes(), "skeleton_branches: workspace too small");
   const long long n = (long long)n0 * n1 * n2;
-  unsigned char* ws = reinterpret_cast<unsigned char*>(workspace);
-  const size_t i_b = align_up((size_t)n * 4, 256);
-  int* L = reinterpret_cast<int*>(ws);
-  unsigned int* cnt = reinterpret_cast<unsigned int*>(ws + i_b);
-  unsigned char* keep = ws + 2 * i_b;
-  unsigned int* block_roots = reinterpret_cast<unsigned int*>(ws + 2 * i_b + align_up((size_t)n, 256));
-  const unsigned blocks = (unsigned)((n + 255) / 256);
-  SEUNET_HIP(hipMemsetAsync(cnt, 0, (size_t)n * 4, s));
-  branch_point_kernel<<<blocks, 256, 0, s>>>(skel, n0, n1, n2, keep);
-  cc_label26(keep, n0, n1, n2, L, s);
-  launch_cc_count(L, n, cnt, s);
-  root_count_kernel<<<blocks, 256, 0, s>>>(L, cnt, n, min_voxels, block_roots);
-  root_scan_kernel<<<1, 1024, 0, s>>>(block_roots, (long long)blocks, num_dev);
-  root_number_kernel<<<blocks, 256, 0, s>>>(L, cnt, n, min_voxels, block_roots);
-  branch_number_kernel<<<blocks, 256, 0, s>>>(L, cnt, n, cd, skeleton_parse);
+  const unsigned blocks = blocks_256(n);
+  SEUNET_HIP(hipMemsetAsync(w.counts, 0, (size_t)n * 4, s));
+  branch_point_kernel<<<blocks, 256, 0, s>>>(skel, n0, n1, n2, w.keep);
+  cc_label26(w.keep, n0, n1, n2, w.labels, s);
+  launch_cc_count(w.labels, n, w.counts, s);
+  root_count_kernel<<<blocks, 256, 0, s>>>(w.labels, w.counts, n, min_voxels, w.block_roots);
+  root_scan_kernel<<<1, 1024, 0, s>>>(w.block_roots, (long long)blocks, num_dev);
+  root_number_kernel<<<blocks, 256, 0, s>>>(w.labels, w.counts, n, min_voxels, w.block_roots);
+  branch_number_kernel<<<blocks, 256, 0, s>>>(w.labels, w.counts, n, cd, skeleton_parse);
   SEUNET_LAUNCH_CHECK();
   return 0;
 }
@@ -203,9 +177,8 @@ label_stats_kernel(const int* __restrict__ parsing, int n0, int n1, int n2, int 
       atomicAdd(&hist[a], (unsigned int)len);
     }
     if (a > 0) {
-      const int i2 = (int)(i % n2);
-      const long long r = i / n2;
-      const int i1 = (int)(r % n1), i0 = (int)(r / n1);
+      const Vox3 p = vox3(i, n1, n2);
+      const int i0 = p.i0, i1 = p.i1, i2 = p.i2;
       int nb[3] = {0, 0, 0};
       if (i2 + 1 < n2) nb[0] = parsing[i + 1];
       if (i1 + 1 < n1) nb[1] = parsing[i + n2];
@@ -227,7 +200,7 @@ int label_stats_max_num() { return kStatsBins - 1; }
 int launch_label_stats(const int* parsing, int n0, int n1, int n2, int num, unsigned int* counts, u64* adjacency_bits, int* status_dev,
                        hipStream_t s) {
   SEUNET_CHECK(parsing && counts && adjacency_bits && status_dev, "label_stats: null argument");
-  if (parse_check(n0, n1, n2, "label_stats")) return 1;
+  if (volume_check("label_stats", n0, n1, n2, 0)) return 1;
   SEUNET_CHECK(num >= 0 && num <= label_stats_max_num(), "label_stats: num %d: labels 0 .. %d are supported", num, label_stats_max_num());
   const long long n = (long long)n0 * n1 * n2;
   const int words = (num + 1 + 63) / 64;
@@ -253,7 +226,7 @@ relabel_kernel(const int* parsing, long long n, const int* __restrict__ lut, int
 int launch_relabel(const int* parsing, long long n, const int* lut, int nlut, int* out, hipStream_t s) {
   SEUNET_CHECK(parsing && lut && out && n >= 1 && nlut >= 1, "relabel: bad argument");
   SEUNET_CHECK(n < (1ll << 31) * 256, "relabel: %lld elements", n);
-  relabel_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(parsing, n, lut, nlut, out);
+  relabel_kernel<<<blocks_256(n), 256, 0, s>>>(parsing, n, lut, nlut, out);
   SEUNET_LAUNCH_CHECK();
   return 0;
 }

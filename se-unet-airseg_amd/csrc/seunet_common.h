@@ -448,82 +448,7 @@ int launch_level_to_side_grad(const float* glev, long long cstride, long long ns
                               const float* drop, int drop_stride, int K, float* g_side, double* partial, float* dhead, Dims d,
                               hipStream_t s);
 int launch_class_bias_grad(const float* per_sample, int N, int K, float* out, hipStream_t s);
-// connected components / metrics (components.hip)
-// Union-find on labels = minimum linear index (every element points to a smaller index of its set, roots to themselves; a union
-// is an atomicMin on the larger root).  Parents only decrease, so a stale read is still an ancestor and cc_find terminates.
-__device__ __forceinline__ int cc_find(const int* L, int i) {
-  int p = L[i];
-  while (p != i) { i = p; p = L[i]; }      // strictly decreasing chain: terminates even on stale reads
-  return i;
-}
-
-__device__ __forceinline__ void cc_union(int* L, int a, int b) {
-  bool done;
-  do {
-    a = cc_find(L, a);
-    b = cc_find(L, b);
-    if (a < b) { const int old = atomicMin(&L[b], a); done = old == b; b = old; }
-    else if (b < a) { const int old = atomicMin(&L[a], b); done = old == a; a = old; }
-    else done = true;
-  } while (!done);
-}
-size_t cc_workspace_bytes(int H, int W, int Z);
-void cc_label26(const unsigned char* vol, int H, int W, int Z, int* L, hipStream_t s);   // component labels (minimum index), -1 off
-int launch_largest_component(const unsigned char* vol, int H, int W, int Z, int rule, unsigned char* out, int* status_dev,
-                             void* workspace, size_t ws_bytes, hipStream_t s);
-void launch_cc_count(const int* L, long long n, unsigned int* cnt, hipStream_t s);   // cnt[root] += voxels (cnt zeroed by the caller)
-size_t metric_out_bytes(int nbins);
-int launch_metric_sums(const unsigned char* pred, const unsigned char* label, const unsigned char* skel, const int* parsing, long long n,
-                       int nbins, void* out, size_t out_bytes, hipStream_t s);
-// stage-2/3 preparation (edt.hip): exact EDT / feature transform, candidate bit masks, LIB weight, break weight
-size_t edt_workspace_bytes(int n0, int n1, int n2);
-int launch_edt(const unsigned char* vol, int n0, int n1, int n2, int* sqdist, double* dist, int* indices, int* status_dev,
-               void* workspace, size_t ws_bytes, hipStream_t s);
-struct EdtOut {            // what the last pass of the feature transform writes (each part optional)
-  int* sqdist;
-  double* dist;
-  int* indices;            // (3, n0, n1, n2)
-  int* lin;                // linear index of the feature (internal users)
-  const int* gather_src;   // gather_out[v] = gather_mask[v] != 0 ? gather_src[feature of v] : 0 (all three or none)
-  const unsigned char* gather_mask;
-  int* gather_out;
-};
-// invert = false: sites are the zero voxels (distance_transform_edt(vol)); true: the non-zero ones (EDT of 1 - vol)
-int run_edt(const unsigned char* vol, bool invert, int n0, int n1, int n2, EdtOut o, int* status_dev, void* workspace, size_t ws_bytes,
-            hipStream_t s);
-int launch_mask_bits(const unsigned char* mask, long long n, unsigned long long* bits, hipStream_t s);
-int launch_hm_candidates(const unsigned char* label, const unsigned char* skel, const unsigned char* pred, int n0, int n1, int n2,
-                         unsigned long long* skel_bits, unsigned long long* small_bits, hipStream_t s);
-size_t lib_weight_workspace_bytes(int n0, int n1, int n2);
-int launch_lib_weight(const unsigned char* label, int n0, int n1, int n2, const float* table, void* out, void* workspace,
-                      size_t ws_bytes, hipStream_t s);
-size_t break_weight_workspace_bytes(int n0, int n1, int n2);
-int launch_break_weight(const unsigned char* label, const unsigned char* pred, const unsigned char* skel, int n0, int n1, int n2,
-                        void* w_br, unsigned char* br_skel, int* status_dev, void* workspace, size_t ws_bytes, hipStream_t s);
-// 3-D thinning (skeleton.hip); workspace bytes are 0 for extents the bit layout cannot address
-size_t skeleton_workspace_bytes(int n0, int n1, int n2);
-int launch_skeletonize(const unsigned char* vol, int n0, int n1, int n2, unsigned char* out, int* passes_dev, void* workspace,
-                       size_t ws_bytes, hipStream_t s);
-// airway tree parsing (parse.hip): skeleton branches, nearest-branch assignment, label statistics, relabelling
-size_t skeleton_branches_workspace_bytes(int n0, int n1, int n2);
-int launch_skeleton_branches(const unsigned char* skel, int n0, int n1, int n2, int min_voxels, int* cd, unsigned char* skeleton_parse,
-                             int* num_dev, void* workspace, size_t ws_bytes, hipStream_t s);
-size_t parse_assign_workspace_bytes(int n0, int n1, int n2);
-int launch_parse_assign(const unsigned char* skeleton_parse, const int* cd, const unsigned char* label, int n0, int n1, int n2,
-                        int* parsing, int* status_dev, void* workspace, size_t ws_bytes, hipStream_t s);
-int label_stats_max_num();
-int launch_label_stats(const int* parsing, int n0, int n1, int n2, int num, unsigned int* counts, unsigned long long* adjacency_bits,
-                       int* status_dev, hipStream_t s);
-int launch_relabel(const int* parsing, long long n, const int* lut, int nlut, int* out, hipStream_t s);
-// CT preprocessing (lung.hip): value counts, shift + clamp, per-slice lung field, mask combination, bounding box, crop
-int launch_value_counts(const short* ct, long long n, int shift, unsigned int* counts, hipStream_t s);
-int launch_shift_clamp(const short* ct, long long n, int shift, int clamp, int clamp_le, int clamp_to, short* out, hipStream_t s);
-size_t get_l_workspace_bytes(int H, int W, int Z);
-int launch_get_l(const short* ct, int H, int W, int Z, double T, int min_area, unsigned char* out, void* workspace, size_t ws_bytes,
-                 hipStream_t s);
-int launch_mask_combine(const unsigned char* a, const unsigned char* b, long long n, int op, unsigned char* out, hipStream_t s);
-int launch_mask_box(const unsigned char* mask, int H, int W, int Z, int* box, hipStream_t s);
-int launch_crop3d(const void* src, int elem_bytes, int H, int W, int Z, const int* box, void* dst, hipStream_t s);
+// the volume operations (components, lung field, EDT / weights, skeleton, tree parsing, double threshold): volume.h
 // input pipeline (pipeline.hip)
 int launch_crop_batch(const void* img, int img_dtype, const unsigned char* label, const void* weight, int w_dtype,
                       const unsigned char* skel, int D, int H, int W, int cube, int ncrop, const int* starts, const int* aug,
@@ -536,9 +461,6 @@ int launch_window_accumulate(const float* logits, int apply_sigmoid, int nwin, c
                              int Z, hipStream_t s);
 int launch_window_finalize(const double* acc, int X, int Y, int Z, int cube, int nx, const int* xs, int ny, const int* ys, int nz,
                            const int* zs, int dup0, double* out, hipStream_t s);
-size_t dti_workspace_bytes(int h, int w, int z);
-int launch_dti(const double* pred, int h, int w, int z, double h_thresh, double l_thresh, int pred_dtype, unsigned char* out,
-               void* workspace, size_t ws_bytes, hipStream_t s);
 int launch_adamw(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
                  const long long* counts, int n, double lr, double beta1, double beta2, double eps, double weight_decay,
                  int step, int maximize, hipStream_t s);

@@ -24,12 +24,10 @@
 // most candidates are still open); one workgroup then loops over what is left with a barrier per round, like dti_sweep_kernel
 // walks its wavefront.  No kernel waits for another workgroup.  Nothing depends on the order of the compacted list (filled with
 // an atomic counter), so the result is deterministic.
-#include "seunet_common.h"
+#include "volume.h"
 #include <algorithm>
 
 namespace seunet {
-
-typedef unsigned long long u64;
 
 namespace {
 
@@ -307,11 +305,15 @@ __global__ void skel_set_int_kernel(int* p, int v) {
 
 struct SkelLayout {
   SkelGeom g;
-  size_t padded_words, plane_bytes, list_bytes, total;
+  SkelCtl* ctl;
+  u64* bits;                  // the image, then the two undecided masks: planes_bytes from `bits` on hold the three padded volumes
+  u64* und[2];
+  size_t planes_bytes;
+  unsigned *list, *open_list; // words with candidates; words still open in the single-workgroup loop
 };
 
-// false: the extents are outside what the bit layout addresses
-bool skel_layout(int n0, int n1, int n2, SkelLayout* L) {
+// false: the extents are outside what the bit layout addresses (nothing is carved)
+bool skel_layout(WsCarver& c, int n0, int n1, int n2, SkelLayout* L) {
   if (n0 < 1 || n1 < 1 || n2 < 1) return false;
   const unsigned long long n = (unsigned long long)n0 * n1 * n2;
   if (n > 0x7fffffffull) return false;
@@ -322,18 +324,28 @@ bool skel_layout(int n0, int n1, int n2, SkelLayout* L) {
   g.words = (long long)n0 * n1 * g.W;
   const unsigned long long padded = (unsigned long long)(n0 + 2ll) * g.plane_stride * g.row_stride;
   if (padded > 0xffffffffull) return false;                  // the word lists hold 32-bit indices
-  L->padded_words = (size_t)padded;
-  L->plane_bytes = align_up((size_t)padded * 8, 256);
-  L->list_bytes = align_up((size_t)g.words * 4, 256);
-  L->total = 256 + 3 * L->plane_bytes + 2 * L->list_bytes;
+  static_assert(sizeof(SkelCtl) <= 256, "SkelCtl outgrew its slot");
+  L->ctl = c.take<SkelCtl>(1);
+  const size_t planes_at = c.bytes();
+  L->bits = c.take<u64>((size_t)padded);
+  L->und[0] = c.take<u64>((size_t)padded);
+  L->und[1] = c.take<u64>((size_t)padded);
+  L->planes_bytes = c.bytes() - planes_at;
+  L->list = c.take<unsigned>((size_t)g.words);
+  L->open_list = c.take<unsigned>((size_t)g.words);
   return true;
 }
 
 }  // namespace
 
-size_t skeleton_workspace_bytes(int n0, int n1, int n2) {
+bool skeleton_ws(WsCarver& c, int n0, int n1, int n2) {
   SkelLayout L;
-  return skel_layout(n0, n1, n2, &L) ? L.total : 0;
+  return skel_layout(c, n0, n1, n2, &L);
+}
+
+size_t skeleton_workspace_bytes(int n0, int n1, int n2) {
+  WsCarver c(nullptr);
+  return skeleton_ws(c, n0, n1, n2) ? c.bytes() : 0;
 }
 
 int launch_skeletonize(const unsigned char* vol, int n0, int n1, int n2, unsigned char* out, int* passes_dev, void* workspace,
@@ -341,21 +353,19 @@ int launch_skeletonize(const unsigned char* vol, int n0, int n1, int n2, unsigne
   SEUNET_CHECK(vol && out && workspace, "skeletonize: null argument");
   SEUNET_CHECK(n0 >= 1 && n1 >= 1 && n2 >= 1, "skeletonize: bad dimensions (%d, %d, %d)", n0, n1, n2);
   SkelLayout L;
-  SEUNET_CHECK(skel_layout(n0, n1, n2, &L), "skeletonize: (%d, %d, %d) exceeds 2^31-1 voxels or 2^32-1 padded 64-voxel words", n0, n1, n2);
-  SEUNET_CHECK(ws_bytes >= L.total, "skeletonize: workspace too small (%zu bytes, %zu needed)", ws_bytes, L.total);
-  static_assert(sizeof(SkelCtl) <= 256, "SkelCtl outgrew its slot");
-  unsigned char* ws = reinterpret_cast<unsigned char*>(workspace);
-  SkelCtl* ctl = reinterpret_cast<SkelCtl*>(ws);
-  u64* bits = reinterpret_cast<u64*>(ws + 256);
-  u64* und[2] = {reinterpret_cast<u64*>(ws + 256 + L.plane_bytes), reinterpret_cast<u64*>(ws + 256 + 2 * L.plane_bytes)};
-  unsigned* list = reinterpret_cast<unsigned*>(ws + 256 + 3 * L.plane_bytes);
-  unsigned* open_list = reinterpret_cast<unsigned*>(ws + 256 + 3 * L.plane_bytes + L.list_bytes);
+  WsCarver carve(workspace);
+  SEUNET_CHECK(skel_layout(carve, n0, n1, n2, &L), "skeletonize: (%d, %d, %d) exceeds 2^31-1 voxels or 2^32-1 padded 64-voxel words", n0, n1, n2);
+  SEUNET_CHECK(ws_bytes >= carve.bytes(), "skeletonize: workspace too small (%zu bytes, %zu needed)", ws_bytes, carve.bytes());
+  SkelCtl* ctl = L.ctl;
+  u64* bits = L.bits;
+  u64* const* und = L.und;
+  unsigned *list = L.list, *open_list = L.open_list;
   const SkelGeom g = L.g;
   const unsigned word_blocks = (unsigned)((g.words + 3) / 4);
   const unsigned round_blocks = std::min(word_blocks, 2048u);
   static const int order[6] = {4, 3, 2, 1, 5, 6};
 
-  SEUNET_HIP(hipMemsetAsync(bits, 0, 3 * L.plane_bytes, s));    // the zero borders of the image and of both undecided masks
+  SEUNET_HIP(hipMemsetAsync(bits, 0, L.planes_bytes, s));    // the zero borders of the image and of both undecided masks
   skel_pack_kernel<<<word_blocks, 256, 0, s>>>(vol, g, bits);
   int passes = 0;
   for (;;) {

@@ -1,0 +1,275 @@
+// Shared layer of the volume operations (components.hip, lung.hip, edt.hip, parse.hip, skeleton.hip, dti.hip): their launcher
+// prototypes, ONE workspace layout per operation, the extent check and the voxel / wave helpers their kernels share.
+//
+// Workspace contract: every operation has a layout struct filled by one function that walks a WsCarver.  Over a null base
+// the walk measures (`X_workspace_bytes`), over the caller's workspace it carves (the launcher); no launcher computes an
+// offset of its own, so a buffer cannot be added to one side only.  seunet_debug_volume_layout (abi.cpp) reports the same walk
+// to tests/test_volume_layout_host.py, which pins the byte counts.
+#pragma once
+#include "seunet_common.h"
+#include <algorithm>
+
+namespace seunet {
+
+typedef unsigned long long u64;
+
+// workgroups of a one-thread-per-item pass of 256-thread blocks (grid_for clamps to 4096 workgroups for grid-stride passes)
+static inline unsigned blocks_256(long long n) { return (unsigned)((n + 255) / 256); }
+
+// Bump carver over a device workspace, the sibling of Plan::take in net.cpp.  A null base measures: take() returns null and
+// only the offset advances.  `log` (the layout report only; null in queries and launchers) receives the offset of every take.
+struct WsCarver {
+  unsigned char* base;
+  size_t off = 0;
+  size_t* log = nullptr;
+  int log_cap = 0, taken = 0;
+  explicit WsCarver(void* workspace) : base(reinterpret_cast<unsigned char*>(workspace)) {}
+  template <typename T> T* take(size_t count, size_t align = 256) {
+    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    if (taken < log_cap) log[taken] = off;
+    ++taken;
+    off += align_up(count * sizeof(T), align);
+    return p;
+  }
+  size_t bytes() const { return off; }
+};
+// what a layout function carves in all: the body of every X_workspace_bytes
+template <typename Layout> size_t measured(Layout layout, int n0, int n1, int n2) {
+  WsCarver c(nullptr);
+  layout(c, n0, n1, n2);
+  return c.bytes();
+}
+
+// Extent checks of the launchers.  max_extent 0: no per-axis limit (32767 where features are int16, edt.hip).  label_range:
+// the wording of components.hip / lung.hip, whose labels are the 32-bit linear indices.
+static inline int volume_check(const char* what, int n0, int n1, int n2, int max_extent, bool label_range = false) {
+  SEUNET_CHECK(n0 >= 1 && n1 >= 1 && n2 >= 1, "%s: bad extents (%d, %d, %d)", what, n0, n1, n2);
+  SEUNET_CHECK(max_extent == 0 || (n0 <= max_extent && n1 <= max_extent && n2 <= max_extent),
+               "%s: extents (%d, %d, %d): at most %d per axis", what, n0, n1, n2, max_extent);
+  const long long n = (long long)n0 * n1 * n2;
+  SEUNET_CHECK(n < (1ll << 31),
+               label_range ? "%s: %lld voxels exceed the 32-bit label range" : "%s: %lld voxels: fewer than 2^31 supported", what, n);
+  return 0;
+}
+constexpr int kEdtMaxExtent = 32767;      // features are int16 between the EDT passes
+
+// ---- connected components / metrics (components.hip) --------------------------------------------------------------------
+// Union-find on labels = minimum linear index (every element points to a smaller index of its set, roots to themselves; a union
+// is an atomicMin on the larger root).  Parents only decrease, so a stale read is still an ancestor and cc_find terminates.
+// Shared with the per-slice labelling of lung.hip.
+__device__ __forceinline__ int cc_find(const int* L, int i) {
+  int p = L[i];
+  while (p != i) { i = p; p = L[i]; }      // strictly decreasing chain: terminates even on stale reads
+  return i;
+}
+
+__device__ __forceinline__ void cc_union(int* L, int a, int b) {
+  bool done;
+  do {
+    a = cc_find(L, a);
+    b = cc_find(L, b);
+    if (a < b) { const int old = atomicMin(&L[b], a); done = old == b; b = old; }
+    else if (b < a) { const int old = atomicMin(&L[a], b); done = old == a; a = old; }
+    else done = true;
+  } while (!done);
+}
+
+struct CcSel {            // device-side scalars of one call
+  u64 best, second;       // (voxel count << 32) | root index ; 0 = none
+  int touches;            // largest component has a voxel in one of the three test slices
+  int chosen;             // root index of the selected component, -1 = none
+  int status;             // 0 ok, 1 no component at all, 2 second component needed but absent
+  int pad;
+};
+
+struct CcWs {
+  int* labels;
+  unsigned int* counts;   // voxel counts per root, then the border flags of the hole filling
+  CcSel* sel;
+};
+static inline CcWs cc_ws(WsCarver& c, int H, int W, int Z) {
+  const size_t n = (size_t)H * W * Z;
+  return CcWs{c.take<int>(n), c.take<unsigned int>(n), c.take<CcSel>(1)};   // (a braced list is evaluated left to right)
+}
+
+size_t cc_workspace_bytes(int H, int W, int Z);
+void cc_label26(const unsigned char* vol, int H, int W, int Z, int* L, hipStream_t s);   // component labels (minimum index), -1 off
+int launch_largest_component(const unsigned char* vol, int H, int W, int Z, int rule, unsigned char* out, int* status_dev,
+                             void* workspace, size_t ws_bytes, hipStream_t s);
+void launch_cc_compress(int* L, long long n, hipStream_t s);                          // L[i] = root of i
+void launch_cc_count(const int* L, long long n, unsigned int* cnt, hipStream_t s);   // cnt[root] += voxels (cnt zeroed by the caller)
+size_t metric_out_bytes(int nbins);
+int launch_metric_sums(const unsigned char* pred, const unsigned char* label, const unsigned char* skel, const int* parsing, long long n,
+                       int nbins, void* out, size_t out_bytes, hipStream_t s);
+
+// ---- stage-2/3 preparation (edt.hip): exact EDT / feature transform, candidate bit masks, LIB weight, break weight ---------
+size_t edt_workspace_bytes(int n0, int n1, int n2);
+struct EdtWs {
+  short *f0, *fa, *fb;    // features along axis 0 after pass 0; along axes 0 / 1 after pass 1
+  short* spos;            // the stack of each line: positions
+  int* sr;                //                         off-line offsets
+};
+static inline EdtWs edt_ws(WsCarver& c, int n0, int n1, int n2) {
+  const size_t n = (size_t)n0 * n1 * n2;
+  return EdtWs{c.take<short>(n), c.take<short>(n), c.take<short>(n), c.take<short>(n), c.take<int>(n)};
+}
+
+struct LibWeightWs { unsigned char *c2, *c12; };   // 7-tap counts along axis 2, then along axes 1 and 2
+static inline LibWeightWs lib_weight_ws(WsCarver& c, int n0, int n1, int n2) {
+  const size_t n = (size_t)n0 * n1 * n2;
+  return LibWeightWs{c.take<unsigned char>(n), c.take<unsigned char>(n)};
+}
+
+struct BreakWeightWs {
+  EdtWs edt;              // one whole EDT workspace (run_edt lays it out again): edt_bytes from edt.f0 on
+  size_t edt_bytes;
+  int *lin, *labels;      // feature (linear index) of every voxel; component labels of fn_skel
+  unsigned char *fn, *flag, *brs, *brl, *shell;
+  u64* maxf;
+};
+static inline BreakWeightWs break_weight_ws(WsCarver& c, int n0, int n1, int n2) {
+  const size_t n = (size_t)n0 * n1 * n2;
+  BreakWeightWs w;
+  w.edt_bytes = edt_workspace_bytes(n0, n1, n2);
+  WsCarver edt(c.take<unsigned char>(w.edt_bytes));
+  w.edt = edt_ws(edt, n0, n1, n2);
+  w.lin = c.take<int>(n);
+  w.labels = c.take<int>(n);
+  w.fn = c.take<unsigned char>(n);
+  w.flag = c.take<unsigned char>(n);
+  w.brs = c.take<unsigned char>(n);
+  w.brl = c.take<unsigned char>(n);
+  w.shell = c.take<unsigned char>(n);
+  w.maxf = c.take<u64>(1);
+  return w;
+}
+
+int launch_edt(const unsigned char* vol, int n0, int n1, int n2, int* sqdist, double* dist, int* indices, int* status_dev,
+               void* workspace, size_t ws_bytes, hipStream_t s);
+struct EdtOut {            // what the last pass of the feature transform writes (each part optional)
+  int* sqdist;
+  double* dist;
+  int* indices;            // (3, n0, n1, n2)
+  int* lin;                // linear index of the feature (internal users)
+  const int* gather_src;   // gather_out[v] = gather_mask[v] != 0 ? gather_src[feature of v] : 0 (all three or none)
+  const unsigned char* gather_mask;
+  int* gather_out;
+};
+// invert = false: sites are the zero voxels (distance_transform_edt(vol)); true: the non-zero ones (EDT of 1 - vol)
+int run_edt(const unsigned char* vol, bool invert, int n0, int n1, int n2, EdtOut o, int* status_dev, void* workspace, size_t ws_bytes,
+            hipStream_t s);
+int launch_mask_bits(const unsigned char* mask, long long n, unsigned long long* bits, hipStream_t s);
+int launch_hm_candidates(const unsigned char* label, const unsigned char* skel, const unsigned char* pred, int n0, int n1, int n2,
+                         unsigned long long* skel_bits, unsigned long long* small_bits, hipStream_t s);
+size_t lib_weight_workspace_bytes(int n0, int n1, int n2);
+int launch_lib_weight(const unsigned char* label, int n0, int n1, int n2, const float* table, void* out, void* workspace,
+                      size_t ws_bytes, hipStream_t s);
+size_t break_weight_workspace_bytes(int n0, int n1, int n2);
+int launch_break_weight(const unsigned char* label, const unsigned char* pred, const unsigned char* skel, int n0, int n1, int n2,
+                        void* w_br, unsigned char* br_skel, int* status_dev, void* workspace, size_t ws_bytes, hipStream_t s);
+
+// ---- 3-D thinning (skeleton.hip); workspace bytes are 0 for extents the bit layout cannot address -------------------------
+size_t skeleton_workspace_bytes(int n0, int n1, int n2);
+bool skeleton_ws(WsCarver& c, int n0, int n1, int n2);     // the walk of SkelLayout alone (layout report); false: rejected extents
+int launch_skeletonize(const unsigned char* vol, int n0, int n1, int n2, unsigned char* out, int* passes_dev, void* workspace,
+                       size_t ws_bytes, hipStream_t s);
+
+// ---- airway tree parsing (parse.hip): skeleton branches, nearest-branch assignment, label statistics, relabelling ---------
+struct BranchesWs {
+  int* labels;
+  unsigned int* counts;          // voxels per root, then the root's number
+  unsigned char* keep;           // skeleton voxels that are no branch points
+  unsigned int* block_roots;     // surviving roots per block of 256 voxels, then their prefix sums
+};
+static inline BranchesWs branches_ws(WsCarver& c, int n0, int n1, int n2) {
+  const size_t n = (size_t)n0 * n1 * n2;
+  return BranchesWs{c.take<int>(n), c.take<unsigned int>(n), c.take<unsigned char>(n), c.take<unsigned int>((n + 255) / 256)};
+}
+
+size_t skeleton_branches_workspace_bytes(int n0, int n1, int n2);
+int launch_skeleton_branches(const unsigned char* skel, int n0, int n1, int n2, int min_voxels, int* cd, unsigned char* skeleton_parse,
+                             int* num_dev, void* workspace, size_t ws_bytes, hipStream_t s);
+size_t parse_assign_workspace_bytes(int n0, int n1, int n2);
+int launch_parse_assign(const unsigned char* skeleton_parse, const int* cd, const unsigned char* label, int n0, int n1, int n2,
+                        int* parsing, int* status_dev, void* workspace, size_t ws_bytes, hipStream_t s);
+int label_stats_max_num();
+int launch_label_stats(const int* parsing, int n0, int n1, int n2, int num, unsigned int* counts, unsigned long long* adjacency_bits,
+                       int* status_dev, hipStream_t s);
+int launch_relabel(const int* parsing, long long n, const int* lut, int nlut, int* out, hipStream_t s);
+
+// ---- CT preprocessing (lung.hip): value counts, shift + clamp, per-slice lung field, mask combination, bounding box, crop --
+struct GetLWs {
+  int* labels;
+  unsigned int* counts;          // pixels per root, then the border flags
+  u64 *best, *top1, *top2;       // per-slice keys, back to back: one memset of key_bytes from `best` clears the three
+  size_t key_bytes;
+};
+static inline GetLWs get_l_ws(WsCarver& c, int H, int W, int Z) {
+  const size_t n = (size_t)H * W * Z;
+  GetLWs w;
+  w.labels = c.take<int>(n);
+  w.counts = c.take<unsigned int>(n);
+  const size_t keys_at = c.bytes();
+  w.best = c.take<u64>((size_t)Z);
+  w.top1 = c.take<u64>((size_t)Z);
+  w.top2 = c.take<u64>((size_t)Z);
+  w.key_bytes = c.bytes() - keys_at;
+  return w;
+}
+
+int launch_value_counts(const short* ct, long long n, int shift, unsigned int* counts, hipStream_t s);
+int launch_shift_clamp(const short* ct, long long n, int shift, int clamp, int clamp_le, int clamp_to, short* out, hipStream_t s);
+size_t get_l_workspace_bytes(int H, int W, int Z);
+int launch_get_l(const short* ct, int H, int W, int Z, double T, int min_area, unsigned char* out, void* workspace, size_t ws_bytes,
+                 hipStream_t s);
+int launch_mask_combine(const unsigned char* a, const unsigned char* b, long long n, int op, unsigned char* out, hipStream_t s);
+int launch_mask_box(const unsigned char* mask, int H, int W, int Z, int* box, hipStream_t s);
+int launch_crop3d(const void* src, int elem_bytes, int H, int W, int Z, const int* box, void* dst, hipStream_t s);
+
+// ---- double threshold (dti.hip) -------------------------------------------------------------------------------------------
+struct DtiWs { u64 *g, *weak; };   // strong mask (swept in place into the result), weak mask; rows of ceil(z / 64) words
+static inline DtiWs dti_ws(WsCarver& c, int h, int w, int z) {
+  const size_t words = (size_t)h * w * ((z + 63) / 64);
+  return DtiWs{c.take<u64>(words, 8), c.take<u64>(words, 8)};   // the two halves have never been padded: word alignment only
+}
+size_t dti_workspace_bytes(int h, int w, int z);
+int launch_dti(const double* pred, int h, int w, int z, double h_thresh, double l_thresh, int pred_dtype, unsigned char* out,
+               void* workspace, size_t ws_bytes, hipStream_t s);
+
+// ---- device helpers -------------------------------------------------------------------------------------------------------
+// raster index -> coordinates of an (n0, n1, n2) volume (n0 is not needed)
+struct Vox3 { int i0, i1, i2; };
+__device__ __forceinline__ Vox3 vox3(long long i, int n1, int n2) {
+  const int i2 = (int)(i % n2);
+  const long long r = i / n2;
+  Vox3 p;
+  p.i1 = (int)(r % n1);
+  p.i0 = (int)(r / n1);
+  p.i2 = i2;
+  return p;
+}
+
+// non-zero voxels of the 3x3x3 block around p, centre included, with indices clamped to the volume: scipy's mode 'reflect' at
+// radius 1 repeats the edge voxel (index -1 -> 0, n -> n - 1), so a voxel on a face counts itself and its in-face neighbours twice
+__device__ __forceinline__ int count27_clamped(const unsigned char* __restrict__ vol, Vox3 p, int n0, int n1, int n2) {
+  int cnt = 0;
+  for (int a = -1; a <= 1; ++a)
+    for (int b = -1; b <= 1; ++b) {
+      const int x0 = std::min(std::max(p.i0 + a, 0), n0 - 1), x1 = std::min(std::max(p.i1 + b, 0), n1 - 1);
+      const unsigned char* row = vol + ((long long)x0 * n1 + x1) * n2;
+      for (int c = -1; c <= 1; ++c) cnt += row[std::min(std::max(p.i2 + c, 0), n2 - 1)] != 0;
+    }
+  return cnt;
+}
+
+// maximum over the 64 lanes, in every lane
+template <typename V> __device__ __forceinline__ V wave_max(V v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const V o = shfl_xor_settled(v, off);
+    v = o > v ? o : v;
+  }
+  return v;
+}
+
+}  // namespace seunet

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._volume import out as _out, read_status, upload_mask, workspace
 
 
 def double_threshold_iteration(pred: Union[np.ndarray, torch.Tensor], h_thresh: float, l_thresh: float,
@@ -40,11 +41,10 @@ def double_threshold_iteration(pred: Union[np.ndarray, torch.Tensor], h_thresh: 
     lib = _lib.load()
     h, w, z = (int(v) for v in t.shape)
     with torch.cuda.device(t.device):
-        nbytes = lib.seunet_dti_workspace_bytes(h, w, z)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=t.device)
+        ws = workspace(lib.seunet_dti_workspace_bytes, h, w, z, device=t.device)
         out = torch.empty((h, w, z), dtype=torch.uint8, device=t.device)
         _lib.check(lib.seunet_dti(t.data_ptr(), h, w, z, float(h_thresh), float(l_thresh), code, out.data_ptr(), ws.data_ptr(),
-                                  nbytes, _lib.stream_ptr()), "dti")
+                                  ws.numel(), _lib.stream_ptr()), "dti")
     return out.cpu().numpy().astype(np.float64) if as_numpy else out
 
 
@@ -69,10 +69,12 @@ def postprocess_prediction(pred, h_thresh: float = 0.5, l_thresh: float = 0.4):
 # largest 26-connected component (+ hole filling) and the ATM'22 metrics, on the device
 # ----------------------------------------------------------------------------------------------------------------------
 def _as_u8_cuda(a, name):
+    """(uint8 CUDA tensor, came-as-numpy).  Unlike prep's masks a tensor of ANY dtype is taken (non-zero = 1) and the rank is the
+    caller's to check, so the policy stays here; only the upload is shared."""
     if isinstance(a, np.ndarray):
         if not torch.cuda.is_available():
             raise RuntimeError(f"seunet {name}: needs a GPU (no CPU path)")
-        return torch.from_numpy(np.ascontiguousarray(a != 0).view(np.uint8)).cuda(), True
+        return upload_mask(a), True
     if not a.is_cuda:
         raise RuntimeError(f"seunet {name}: needs a CUDA tensor or a numpy array (no CPU path)")
     return (a != 0).to(torch.uint8).contiguous(), False
@@ -85,13 +87,12 @@ def _largest(vol, rule, name):
     lib = _lib.load()
     h, w, z = (int(v) for v in t.shape)
     with torch.cuda.device(t.device):
-        nbytes = lib.seunet_cc_workspace_bytes(h, w, z)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=t.device)
+        ws = workspace(lib.seunet_cc_workspace_bytes, h, w, z, device=t.device)
         out = torch.empty((h, w, z), dtype=torch.uint8, device=t.device)
         status = torch.zeros(1, dtype=torch.int32, device=t.device)
-        _lib.check(lib.seunet_largest_component(t.data_ptr(), h, w, z, rule, out.data_ptr(), status.data_ptr(), ws.data_ptr(), nbytes,
+        _lib.check(lib.seunet_largest_component(t.data_ptr(), h, w, z, rule, out.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(),
                                                 _lib.stream_ptr()), name)
-    return out, int(status.item()), as_numpy
+    return out, read_status(status), as_numpy
 
 
 def largest_component(pred):
@@ -99,7 +100,7 @@ def largest_component(pred):
     most voxels as a uint8 mask (``large_cd``); an empty prediction gives an empty mask (``pred.astype(np.uint8)``).
     numpy in -> uint8 numpy out; CUDA tensor in -> uint8 CUDA tensor out."""
     out, _, as_numpy = _largest(pred, _lib.CC_EVALUATION, "largest_component")
-    return out.cpu().numpy() if as_numpy else out
+    return _out(out, as_numpy)
 
 
 def maximum_3d(region01):

@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._volume import mask_in, out as _out, read_status, workspace
 
 _BLOCK_WORDS = 8          # 512 voxels per prefix-sum block
 SKELETON_ROUND_LAUNCHES = 32   # kRoundLaunches of csrc/skeleton.hip (scripts/bench_skeleton.py counts launches with it)
@@ -35,7 +36,7 @@ def _same(a, b, na, nb):
 
 
 def _status(status, what):
-    if int(status.item()) != 0:
+    if read_status(status) != 0:
         raise ValueError(f"seunet prep: {what}")
 
 
@@ -52,8 +53,7 @@ def distance_transform_edt(volume: torch.Tensor, return_distances: bool = True, 
     lib = _lib.load()
     dev = vol.device
     with torch.cuda.device(dev):
-        ws_bytes = lib.seunet_edt_workspace_bytes(n0, n1, n2)
-        ws = torch.empty(max(int(ws_bytes), 1), dtype=torch.uint8, device=dev)
+        ws = workspace(lib.seunet_edt_workspace_bytes, n0, n1, n2, device=dev, min_bytes=1)
         sq = torch.empty((n0, n1, n2), dtype=torch.int32, device=dev) if return_sqdist else None
         dist = torch.empty((n0, n1, n2), dtype=torch.float64, device=dev) if return_distances else None
         ind = torch.empty((3, n0, n1, n2), dtype=torch.int32, device=dev) if return_indices else None
@@ -76,15 +76,7 @@ def skeletonize_3d(volume, return_passes: bool = False):
     zeros.  The result is the ``skeleton`` argument of ``break_weight``, ``hard_mining_candidates``, the ``from_case``
     constructors and ``evaluation_case``.  ``return_passes``: also return the number of thinning passes run (the last one,
     which deletes nothing, included)."""
-    as_numpy = isinstance(volume, np.ndarray)
-    if as_numpy:
-        if volume.ndim != 3:
-            raise ValueError(f"seunet prep: `volume` must be (n0, n1, n2), got {tuple(volume.shape)}")
-        if not torch.cuda.is_available():
-            raise RuntimeError("seunet prep: `volume` needs a GPU (there is no CPU path)")
-        vol = torch.from_numpy(np.ascontiguousarray(volume != 0).view(np.uint8)).cuda()
-    else:
-        vol = _vol(volume, "volume")
+    vol, as_numpy = _mask_in(volume, "volume")
     n0, n1, n2 = (int(v) for v in vol.shape)
     dev = vol.device
     out = torch.zeros((n0, n1, n2), dtype=torch.uint8, device=dev)
@@ -92,13 +84,10 @@ def skeletonize_3d(volume, return_passes: bool = False):
     if vol.numel():
         lib = _lib.load()
         with torch.cuda.device(dev):
-            ws_bytes = int(lib.seunet_skeleton_workspace_bytes(n0, n1, n2))
-            if ws_bytes == 0:
-                raise ValueError(f"seunet prep: skeletonize_3d: {_lib.last_error()}")
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            _lib.check(lib.seunet_skeletonize(vol.data_ptr(), n0, n1, n2, out.data_ptr(), passes.data_ptr(), ws.data_ptr(), ws_bytes,
+            ws = workspace(lib.seunet_skeleton_workspace_bytes, n0, n1, n2, device=dev, what="seunet prep: skeletonize_3d")
+            _lib.check(lib.seunet_skeletonize(vol.data_ptr(), n0, n1, n2, out.data_ptr(), passes.data_ptr(), ws.data_ptr(), ws.numel(),
                                               _lib.stream_ptr()), "skeletonize")
-    skel = out.cpu().numpy() if as_numpy else out
+    skel = _out(out, as_numpy)
     return (skel, int(passes.item())) if return_passes else skel
 
 
@@ -226,7 +215,7 @@ def lib_weight(label: torch.Tensor) -> torch.Tensor:
     lib = _lib.load()
     table = np.ascontiguousarray(lib_table())
     with torch.cuda.device(label.device):
-        ws = torch.empty(int(lib.seunet_lib_weight_workspace_bytes(n0, n1, n2)), dtype=torch.uint8, device=label.device)
+        ws = workspace(lib.seunet_lib_weight_workspace_bytes, n0, n1, n2, device=label.device)
         out = torch.empty((n0, n1, n2), dtype=torch.float16, device=label.device)
         _lib.check(lib.seunet_lib_weight(label.data_ptr(), n0, n1, n2, table.ctypes.data, out.data_ptr(), ws.data_ptr(), ws.numel(),
                                          _lib.stream_ptr()), "lib_weight")
@@ -245,7 +234,7 @@ def break_weight(label: torch.Tensor, pred: torch.Tensor, skeleton: torch.Tensor
     lib = _lib.load()
     dev = label.device
     with torch.cuda.device(dev):
-        ws = torch.empty(int(lib.seunet_break_weight_workspace_bytes(n0, n1, n2)), dtype=torch.uint8, device=dev)
+        ws = workspace(lib.seunet_break_weight_workspace_bytes, n0, n1, n2, device=dev)
         w = torch.empty((n0, n1, n2), dtype=torch.float16, device=dev)
         brs = torch.empty((n0, n1, n2), dtype=torch.uint8, device=dev)
         status = torch.empty(1, dtype=torch.int32, device=dev)
@@ -259,14 +248,8 @@ def break_weight(label: torch.Tensor, pred: torch.Tensor, skeleton: torch.Tensor
 # ---- airway tree parsing: the ATM'22 branch labelling (csrc/parse.hip) -------------------------------
 
 def _mask_in(a, name):
-    """A 0/1 volume argument -> (uint8 CUDA tensor, came-as-numpy)."""
-    if isinstance(a, np.ndarray):
-        if a.ndim != 3:
-            raise ValueError(f"seunet prep: `{name}` must be (n0, n1, n2), got {tuple(a.shape)}")
-        if not torch.cuda.is_available():
-            raise RuntimeError(f"seunet prep: `{name}` needs a GPU (there is no CPU path)")
-        return torch.from_numpy(np.ascontiguousarray(a != 0).view(np.uint8)).cuda(), True
-    return _vol(a, name), False
+    """A 0/1 volume argument -> (uint8 CUDA tensor, came-as-numpy): numpy of any dtype, or a uint8 / bool CUDA tensor (``_vol``)."""
+    return mask_in(a, name, "seunet prep", _vol)
 
 
 def _labels_in(a, name):
@@ -286,10 +269,6 @@ def _labels_in(a, name):
     return a.to(torch.int32).contiguous(), False
 
 
-def _out(t, as_numpy):
-    return t.cpu().numpy() if as_numpy else t
-
-
 def _skeleton_parsing(skel, min_voxels):
     n0, n1, n2 = (int(v) for v in skel.shape)
     dev = skel.device
@@ -299,13 +278,10 @@ def _skeleton_parsing(skel, min_voxels):
         return parse, cd, 0
     lib = _lib.load()
     with torch.cuda.device(dev):
-        ws_bytes = int(lib.seunet_skeleton_branches_workspace_bytes(n0, n1, n2))
-        if ws_bytes == 0:
-            raise ValueError(f"seunet prep: skeleton_parsing: {_lib.last_error()}")
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws = workspace(lib.seunet_skeleton_branches_workspace_bytes, n0, n1, n2, device=dev, what="seunet prep: skeleton_parsing")
         num = torch.zeros(1, dtype=torch.int32, device=dev)
         _lib.check(lib.seunet_skeleton_branches(skel.data_ptr(), n0, n1, n2, int(min_voxels), cd.data_ptr(), parse.data_ptr(),
-                                                num.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream_ptr()), "skeleton_branches")
+                                                num.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "skeleton_branches")
         return parse, cd, int(num.item())
 
 
@@ -325,7 +301,7 @@ def _assign(parse, label, cd):
     dev = label.device
     lib = _lib.load()
     with torch.cuda.device(dev):
-        ws = torch.empty(max(int(lib.seunet_parse_assign_workspace_bytes(n0, n1, n2)), 1), dtype=torch.uint8, device=dev)
+        ws = workspace(lib.seunet_parse_assign_workspace_bytes, n0, n1, n2, device=dev, min_bytes=1)
         out = torch.empty((n0, n1, n2), dtype=torch.int32, device=dev)
         status = torch.empty(1, dtype=torch.int32, device=dev)
         _lib.check(lib.seunet_parse_assign(parse.data_ptr(), cd.data_ptr(), label.data_ptr(), n0, n1, n2, out.data_ptr(),

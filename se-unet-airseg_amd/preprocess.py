@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._volume import out as _out, workspace
 from .postprocess import _largest, maximum_3d
 
 HU_SHIFT = 1024          # preprocessing.py:47
@@ -45,10 +46,6 @@ def _ct_cuda(ct, name) -> Tuple[torch.Tensor, bool]:
     if t.dim() != 3:
         raise ValueError(f"seunet {name}: expected a 3-D volume, got shape {tuple(t.shape)}")
     return t, as_numpy
-
-
-def _out(t: torch.Tensor, as_numpy: bool):
-    return t.cpu().numpy() if as_numpy else t
 
 
 # ---- host arithmetic on the histograms -------------------------------------------------------------------------------------
@@ -147,10 +144,9 @@ def _get_l(t: torch.Tensor, T: float, min_area: int) -> torch.Tensor:
     lib = _lib.load()
     h, w, z = (int(v) for v in t.shape)
     with torch.cuda.device(t.device):
-        nbytes = lib.seunet_get_l_workspace_bytes(h, w, z)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=t.device)
+        ws = workspace(lib.seunet_get_l_workspace_bytes, h, w, z, device=t.device)
         out = torch.empty((h, w, z), dtype=torch.uint8, device=t.device)
-        _lib.check(lib.seunet_get_l(t.data_ptr(), h, w, z, float(T), int(min_area), out.data_ptr(), ws.data_ptr(), nbytes,
+        _lib.check(lib.seunet_get_l(t.data_ptr(), h, w, z, float(T), int(min_area), out.data_ptr(), ws.data_ptr(), ws.numel(),
                                     _lib.stream_ptr()), "get_l")
     return out
 
@@ -212,7 +208,7 @@ def large_connected_domain26(mask: Array):
     out, status, as_numpy = _largest(mask, _lib.CC_LARGEST_FILLED, "large_connected_domain26")
     if status != 0:
         raise IndexError("index -1 is out of bounds for axis 0 with size 0 (large_connected_domain26: the mask is empty, util.py:162)")
-    return out.cpu().numpy() if as_numpy else out
+    return _out(out, as_numpy)
 
 
 def cut_mask(mask: Array, box) -> Array:
