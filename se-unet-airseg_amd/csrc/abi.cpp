@@ -1,6 +1,7 @@
 // extern "C" entry points of libseunet_hip.so (per-op part; the whole-network calls live in net.cpp).
 // Thin argument marshalling only: every function validates, forwards to a launcher and returns a status.
 #include "seunet_common.h"
+#include "epilogue.h"
 #include "volume.h"
 #include "../../include/seunet_hip.h"
 

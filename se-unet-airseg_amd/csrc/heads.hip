@@ -3,7 +3,7 @@
 //   side maps     the per-block side-map up-sampling by 1/2/4/8 (reference SE_UNet.py:19,34,61,81)
 //   heads         reference SE_UNet.py:150-153,232-233: 1x1x1 conv over the DropLayer-scaled stack of
 //                 up-sampled side maps.  Both are linear, so the head weight and the DropLayer scale
-//                 are applied to each side map at its native resolution (epilogue.hip accumulates a
+//                 are applied to each side map at its native resolution (gate.hip accumulates a
 //                 single-channel "level map" per resolution) and only those maps are interpolated.
 #include "seunet_common.h"
 #include "trilinear.h"

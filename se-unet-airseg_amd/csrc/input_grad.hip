@@ -5,7 +5,7 @@
 //   dL/dx = convT_ec1(draw_ec1) + W_x33^T d2_x33 + unpool_0( W_x63^T d2_x63 + unpool_1( W_x93^T d2_x93 ) )
 //
 // The per-level x-branch terms gx_l = W_xl^T d2_xl ([N][V_l][in_channel] f32) come from pass B of the aggregation block
-// (epilogue.hip cat_bwd_kernel XG when the branch is recomputed from the input; xgrad_contract_kernel below from the stored
+// (cat.hip cat_bwd_kernel XG when the branch is recomputed from the input; xgrad_contract_kernel below from the stored
 // d2 otherwise).  unpool_l routes to the FIRST strict maximum of each 2x2x2 window of the stored input copy (feat[T_X0] /
 // feat[T_X1]), the forward's own rule (layout.hip maxpool_bwd_kernel).  In bf16 / fp16 storage the network computes on its
 // rounded copy of x: this is the gradient with respect to that copy, the rounding passed straight through.

@@ -4,6 +4,7 @@
 // offset of a caller-owned workspace whose layout is a pure function of seunet_net_desc (so the same
 // layout is recomputed by the backward call).
 #include "seunet_common.h"
+#include "epilogue.h"
 #include "../../include/seunet_hip.h"
 
 #include <algorithm>
@@ -215,7 +216,7 @@ struct Plan {
   size_t lvl[2][4], glvl[2][4];
   size_t stats, stats2, pgrad, m1, m2, m1b, m2b, wgrad_ws, head_tmp, gx, gx_bytes = 0, xwp = 0, xmom = 0;
   size_t gside = 0, cls_part = 0, cls_bias = 0;                // n_classes > 1: side-map gradient of one block, head-gradient records, per-(sample, class) bias sums
-  // x-branches (x33 / x63 / x93) recomputed from the <= 2-channel input instead of materialised (csrc/epilogue.hip, XR)
+  // x-branches (x33 / x63 / x93) recomputed from the <= 2-channel input instead of materialised (csrc/cat.hip, XR)
   bool fuse_x = false;
   size_t wgrad_ws_bytes;
   size_t total;

@@ -264,7 +264,6 @@ template <int LPV> __device__ __forceinline__ double stride_sum_d(double v) {
   for (int off = 32; off >= LPV; off >>= 1) v += shfl_xor_settled(v, off);
   return v;
 }
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + __expf(-x)); }
 #endif  // __HIPCC__
 
 // ---- launcher prototypes (one per kernel family; defined in the .hip files) ----------
@@ -340,89 +339,7 @@ ConvKernel wgrad_kernel(int dtype, int taps, int dil, const SrcList& x, int cin_
 int run_wgrad(ConvKernel k, int dtype, int taps, int dil, const SrcList& x, int cin_logical, const void* dy, int cout, float* dw,
               void* workspace, size_t ws_bytes, Dims d, hipStream_t s);
 
-// normalisation / gates / cat (epilogue.hip)
-int epi_partials(Dims d);         // partial slots per sample used by the epilogue kernels
-int launch_channel_stats(int dtype, const void* t, int C, double* partial, Dims d, hipStream_t s);
-int launch_stats_finalize(const double* partial, int slots, int C, int N, long long count,
-                          float eps, int mode, float* out_a, float* out_b, hipStream_t s);
-// A block's epilogue is described once and handed to its forward and to both backward passes.  The backward runs twice over
-// the block: the `_sums` launchers (pass A) write f64 partial sums -- of the InstanceNorm backward's two means per (n, c),
-// and of the parameter gradients -- and the `_apply` launchers (pass B) read the finalised means m1 / m2 and store draw.
-// Each pass has its own argument struct, so that it cannot be handed the other pass's buffers.
-struct NormIn { const void* raw; const float* mean; const float* rstd; };   // a conv output [N][V][C] (T), its InstanceNorm statistics [N][C]
-struct SseParams {
-  const float* w_se;      // [C]
-  const float* w_se2;     // [C] or null (one gate)
-  const float* w_side;    // [2][C]
-  const float* b_side;    // [2]
-  float slope;
-};
-struct GateBlock { NormIn a; int C; SseParams p; };
-struct SseHead {          // how the 2-channel side output is consumed
-  float* side_out;        // fp32 [N][V][2] or null
-  float* level_map;       // fp32 [N][V] head pre-activation map of this level, or null
-  int level_accumulate;   // 0: overwrite level_map, 1: +=
-  const float* head_w;    // [2] head weights of this block's two channels
-  const float* drop;      // [N][drop_stride] DropLayer scales (points at this block's channel 0) or null
-  int drop_stride;
-};
-struct SseBwdIn {
-  const void* g_e;        // gradient w.r.t. e (T) or null
-  const float* g_side;    // fp32 [N][V][2] gradient w.r.t. the side map, or null
-  const float* g_level;   // fp32 [N][V] gradient w.r.t. the level map, or null
-};
-// partial parameter-gradient record per (sample, slot):  4*C + 4 floats
-//   [0,C) dw_se  [C,2C) dw_se2  [2C,4C) dw_side[2][C]  [4C,4C+2) db_side  [4C+2,4C+4) dhead_w
-struct SseSums { double* stat_partial; float* pgrad_partial; };            // pass A outputs
-struct SseApply { const float* m1; const float* m2; void* draw_out; };     // pass B; draw_out may alias g_e
-int launch_sse_fwd(int dtype, const GateBlock& b, void* e_out, const SseHead& head, Dims d, hipStream_t s);
-int launch_sse_bwd_sums(int dtype, const GateBlock& b, const SseBwdIn& g, const SseHead& head, const SseSums& out, Dims d,
-                        hipStream_t s);
-int launch_sse_bwd_apply(int dtype, const GateBlock& b, const SseBwdIn& g, const SseHead& head, const SseApply& io, Dims d,
-                         hipStream_t s);
-int launch_gate_bwd_finalize(const double* stat_partial, int slots, int C, int N, long long count, float* m1, float* m2,
-                             const float* pgrad_partial, int records, float* dw_se, float* dw_se2, float* dw_side,
-                             float* db_side, float* dhead_w, hipStream_t s);
-int launch_pgrad_reduce(const float* pgrad_partial, int records, int C, float* dw_se,
-                        float* dw_se2, float* dw_side, float* db_side, float* dhead_w,
-                        hipStream_t s);
-struct Branch2 {          // the second branch of an aggregation block, added after its own InstanceNorm + LeakyReLU
-  enum Kind { None, Stored, Recomputed } kind;
-  const void* src;        // Stored: raw2 [N][V][C] (T); Recomputed: the packed network input [N][V][8] (T), raw2 = w2 x per voxel
-  const float* mean2;
-  const float* rstd2;
-  const float* w2;        // Recomputed: the 1x1x1 weight (C, in_channel) and in_channel (1 or 2)
-  int in_channel;
-};
-struct CatBlock { NormIn a; Branch2 b; int C; float slope; };
-// Recomputed only.  Forward: also write the 2x2x2 max-pool of the output (pooled null = not) and, if asked, each maximum's position.
-// Backward: the gradient of that max-pool, added to g_out on the fly in both passes (argmax null = none).
-struct PoolOut { void* pooled; unsigned* argmax; };
-struct PoolGrad { const unsigned* argmax; const void* g_pool; };
-struct CatSums {          // pass A outputs
-  double* stat_partial;
-  double* stat_partial2;  // second branch (Stored | Recomputed)
-  double* xw_partial;     // optional, Recomputed: one record per block of the x-branch weight-gradient sums (cat_bwd_kernel XW)
-};
-struct CatApply {         // pass B
-  const float *m1, *m2, *m1b, *m2b;   // (m1b, m2b: second branch)
-  void* dx;               // may alias g_out
-  void* dx2;              // Stored: draw of the second branch
-  float* gx_out;          // optional, Recomputed: + the x-branch's input-gradient term (XG), [N][V][in_channel] f32
-  int gx_acc;             // 0: overwrite gx_out, 1: +=
-};
-int launch_cat_fwd(int dtype, const CatBlock& b, void* out, const PoolOut& pool, Dims d, hipStream_t s);
-int launch_cat_bwd_sums(int dtype, const CatBlock& b, const void* g_out, const PoolGrad& pool, const CatSums& out, Dims d,
-                        hipStream_t s);
-int launch_cat_bwd_apply(int dtype, const CatBlock& b, const void* g_out, const PoolGrad& pool, const CatApply& io, Dims d,
-                         hipStream_t s);
-int xbranch_moment_slots(Dims d);
-int launch_xbranch_moments(int dtype, const void* x_in, double* partial, Dims d, hipStream_t s);
-int launch_xbranch_stats(const double* partial, int slots, const float* w2, int C, int in_channel, int N, long long count,
-                         float eps, float* mean2, float* rstd2, double* moments_out, hipStream_t s);
-int launch_cat_xgrad_finalize(const double* xw_partial, const double* stat_partial2, int slots, const double* moments, const float* w2,
-                              int C, int in_channel, int N, float eps, float* dw, hipStream_t s);
-int launch_xbranch_values(int dtype, const void* x_in, const float* w2, int C, int in_channel, float* out_ncdhw, Dims d, hipStream_t s);   // diagnostic
+// normalisation / gates / cat (epilogue.hip, gate.hip, cat.hip): epilogue.h
 
 // input gradient of the network (input_grad.hip; net.cpp seunet_net_backward_input)
 int launch_xgrad_contract(int dtype, const void* d2, int C, const float* w2, int in_channel, float* gx, int accumulate, Dims d,

@@ -9,7 +9,7 @@ Two evaluations of every backward expression are returned: its value, and the sa
 values (every sum a sum of magnitudes).  The second is the ``A`` / ``S`` of the bounds: a chain of K f32 roundings through an
 expression of sums and products is off by at most K u A (u = 2^-24, first order), whatever cancels in the value.
 
-Rounding counts (from csrc/epilogue.hip; lg = log2(C / 8), the depth of the cross-lane sum of a per-voxel dot product):
+Rounding counts (from csrc/gate.hip and csrc/cat.hip; lg = log2(C / 8), the depth of the cross-lane sum of a per-voxel dot product):
   * a = LeakyReLU((x - mean) rstd): 3.  A per-voxel dot product z = sum_c w_c a_c: 1 product + 7 + lg additions on top of its
     operands, so |dz| <= (11 + lg) u Z with Z = sum_c |w_c a_c|.
   * 16-bit gate g = rcp(1 + exp2(-log2e z)): constant and product 2 (as 2 u |z| on the exponent), v_exp_f32 1 ulp = 2 u,

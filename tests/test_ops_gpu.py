@@ -355,7 +355,7 @@ def test_cat_epilogue_forward_backward(S, dtype, two):
 
 
 @pytest.mark.parametrize("dtype", DT)
-@pytest.mark.parametrize("inch,c", [(2, 32), (1, 32), (2, 64), (2, 128)])
+@pytest.mark.parametrize("inch,c", [(2, 32), (1, 32), (2, 64), (2, 128), (2, 8), (1, 16)])
 def test_cat_epilogue_with_recomputed_x_branch(S, dtype, inch, c):
     """x-branch (x33 / x63 / x93): raw2 = conv1x1(x) is never stored -- statistics from the input moments, values
     recomputed in every pass; the weight gradient is formed in f64 from pass-A sums and the input's moments (it is what is left
