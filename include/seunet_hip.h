@@ -228,6 +228,44 @@ int seunet_loss_grad(const float* pred, int apply_sigmoid, const float* target, 
                      long long n, const double* sums, float c_dice, float c_gul, float c_atr, float g_scale,
                      const float* g_scale_dev, float* g_pred, seunet_stream_t s);
 
+/* Per-sample sums and values: the key of the online hard mining, train.py:442-446 and :249-253 (one
+ * general_union_loss_lib(pred_de[i], label[i], weight[i]).item() per sample there; here one pass and no synchronise).
+ * Sample b covers elements [b n, (b + 1) n) of every tensor; sums: [batch][7] f64 as above, values: [batch] f32, each
+ * f32(c_dice*dice + c_gul*gul + c_atr*atr) of that sample's sums formed in f64.  partial: seunet_loss_sample_partial_floats
+ * (batch) floats of scratch.  A sample's sums are the same bits whatever the batch it is part of and whatever `terms`
+ * asks for beside them.  batch <= 65535. */
+int seunet_loss_sample_partial_floats(int batch);
+int seunet_loss_sums_per_sample(const float* pred, int apply_sigmoid, const float* target, const float* weight, const float* skel,
+                                int batch, long long n_per_sample, float* partial, double* sums, int terms, seunet_stream_t s);
+int seunet_loss_sample_values(const double* sums, int batch, double c_dice, double c_gul, double c_atr, float* values,
+                              seunet_stream_t s);
+
+/* ---- online hard mining: the sample pool of save_data_online / save_data_online3 (train.py:78-138) and OnlineHMData /
+ * OnlineHMData3 (data.py:586-630) in HBM ----------------------------------------------------------------------------------
+ * The pool keeps the `capacity` samples with the largest key.  All of it is caller-owned device memory:
+ *   pool_data (K, 2, V) f32, pool_weight (K, 1, V) f32, pool_label / pool_skel (K, 1, V) u8 (pool_skel optional),
+ *   keys (K) f32, seq (K) i64, state (2) i64 = {count, next sequence number}; zeroing `state` empties the pool.
+ * V = voxels per sample, V % 16 == 0; every tensor 16-byte aligned; K = capacity <= 65535.
+ *   select:  one small launch; walks new_keys[0..batch) in order like the loop of save_data_online and writes slots_out
+ *            (DEVICE, [batch]): the slot a sample is stored in, or -1.  A non-finite key is never stored.  While the pool is
+ *            not full the next free slot is taken.  A full pool gives up its minimum (key, seq) entry -- of equal keys the
+ *            oldest -- unless the new key is strictly smaller (bisect.bisect, train.py:94-95: a key equal to the minimum is
+ *            accepted).  When a later sample of the call takes the slot an earlier one of the same call was given, the earlier
+ *            entry of slots_out becomes -1, so the slots of a call are distinct.  batch <= 1024.
+ *   scatter: one launch, the batch's data (batch, 2, V) / label / weight / skel (batch, 1, V) f32 into the slots of slots_dev
+ *            (DEVICE; negative or >= capacity: that sample is skipped).  label and skel must hold 0.0 and 1.0 only; they are
+ *            stored as (unsigned char)v.  data and weight are stored bit for bit.
+ *   gather:  slots_host is a HOST array (n <= 32, like `starts` of seunet_crop_batch); writes data_out (n, 2, V) and
+ *            label_out / weight_out / skel_out (n, 1, V) f32, the tensors train.py:479-481 builds. */
+int seunet_pool_select(const float* new_keys, int batch, float* keys, long long* seq, long long* state, int capacity, int* slots_out,
+                       seunet_stream_t s);
+int seunet_pool_scatter(const int* slots_dev, int batch, int capacity, long long voxels, const float* data, const float* label,
+                        const float* weight, const float* skel, float* pool_data, unsigned char* pool_label, float* pool_weight,
+                        unsigned char* pool_skel, seunet_stream_t s);
+int seunet_pool_gather(const int* slots_host, int n, int capacity, long long voxels, const float* pool_data,
+                       const unsigned char* pool_label, const float* pool_weight, const unsigned char* pool_skel, float* data_out,
+                       float* label_out, float* weight_out, float* skel_out, seunet_stream_t s);
+
 /* ---- optimizer step: torch.optim.AdamW(model.parameters(), lr=0.0001).step() -----------------
  * Replaces optimizer.step() at train.py:247,439,603 (constructed at train.py:188,386,569 with PyTorch's default
  * betas=(0.9,0.999), eps=1e-8, weight_decay=0.01, amsgrad=False).  All n tensors of a step are updated by

@@ -93,6 +93,12 @@ PROTOTYPES = {
     "seunet_loss_sums": (_i, [_vp, _i, _vp, _vp, _vp, _ll, _vp, _vp, _i, _vp]),
     "seunet_loss_value": (_i, [_vp, _d, _d, _d, _vp, _d, _d, _d, _vp, _vp]),
     "seunet_loss_grad": (_i, [_vp, _i, _vp, _vp, _vp, _ll, _vp, _f, _f, _f, _f, _vp, _vp, _vp]),
+    "seunet_loss_sample_partial_floats": (_i, [_i]),
+    "seunet_loss_sums_per_sample": (_i, [_vp, _i, _vp, _vp, _vp, _i, _ll, _vp, _vp, _i, _vp]),
+    "seunet_loss_sample_values": (_i, [_vp, _i, _d, _d, _d, _vp, _vp]),
+    "seunet_pool_select": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp]),
+    "seunet_pool_scatter": (_i, [_vp, _i, _i, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "seunet_pool_gather": (_i, [_ip, _i, _i, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "seunet_xbranch_moment_slots": (_i, [Dims]),
     "seunet_xbranch_moments": (_i, [_i, _vp, _vp, Dims, _vp]),
     "seunet_xbranch_stats": (_i, [_vp, _i, _vp, _i, _i, _i, _ll, _f, _vp, _vp, _vp, _vp]),

@@ -298,6 +298,39 @@ int seunet_loss_grad(const float* pred, int apply_sigmoid, const float* target, 
   return launch_loss_grad(pred, apply_sigmoid, target, weight, skel, n, sums, c_dice, c_gul, c_atr, g_scale, g_scale_dev, g_pred, S(s));
 }
 
+int seunet_loss_sample_partial_floats(int batch) {
+  if (batch < 1 || batch > 65535) { fail("loss_sample_partial_floats: batch %d (1..65535)", batch); return 0; }
+  return loss_sample_partials(batch) * SEUNET_LOSS_NSUMS;
+}
+int seunet_loss_sums_per_sample(const float* pred, int apply_sigmoid, const float* target, const float* weight, const float* skel,
+                                int batch, long long n_per_sample, float* partial, double* sums, int terms, seunet_stream_t s) {
+  SEUNET_CHECK(pred && target && partial && sums && n_per_sample >= 1, "loss_sums_per_sample: bad argument");
+  SEUNET_CHECK(batch >= 1 && batch <= 65535, "loss_sums_per_sample: batch %d (1..65535)", batch);
+  SEUNET_CHECK(terms >= 0 && terms <= 7, "loss_sums_per_sample: terms=%d is not a mask of SEUNET_LOSS_DICE | _GUL | _ATR", terms);
+  return launch_loss_sums_per_sample(pred, apply_sigmoid, target, weight, skel, batch, n_per_sample, partial, sums, terms, S(s));
+}
+int seunet_loss_sample_values(const double* sums, int batch, double c_dice, double c_gul, double c_atr, float* values, seunet_stream_t s) {
+  SEUNET_CHECK(sums && values && batch >= 1, "loss_sample_values: bad argument");
+  return launch_loss_sample_values(sums, batch, c_dice, c_gul, c_atr, values, S(s));
+}
+
+int seunet_pool_select(const float* new_keys, int batch, float* keys, long long* seq, long long* state, int capacity, int* slots_out,
+                       seunet_stream_t s) {
+  return launch_pool_select(new_keys, batch, keys, seq, state, capacity, slots_out, S(s));
+}
+int seunet_pool_scatter(const int* slots_dev, int batch, int capacity, long long voxels, const float* data, const float* label,
+                        const float* weight, const float* skel, float* pool_data, unsigned char* pool_label, float* pool_weight,
+                        unsigned char* pool_skel, seunet_stream_t s) {
+  return launch_pool_scatter(slots_dev, batch, capacity, voxels, data, label, weight, skel, pool_data, pool_label, pool_weight, pool_skel,
+                             S(s));
+}
+int seunet_pool_gather(const int* slots_host, int n, int capacity, long long voxels, const float* pool_data,
+                       const unsigned char* pool_label, const float* pool_weight, const unsigned char* pool_skel, float* data_out,
+                       float* label_out, float* weight_out, float* skel_out, seunet_stream_t s) {
+  return launch_pool_gather(slots_host, n, capacity, voxels, pool_data, pool_label, pool_weight, pool_skel, data_out, label_out,
+                            weight_out, skel_out, S(s));
+}
+
 int seunet_xbranch_moment_slots(seunet_dims dims) { return xbranch_moment_slots(D(dims)); }
 int seunet_xbranch_moments(int dtype, const void* x_in, double* partial, seunet_dims dims, seunet_stream_t s) {
   SEUNET_CHECK(x_in && partial, "xbranch_moments: null argument");

@@ -173,6 +173,108 @@ int launch_loss_value(const double* sums0, double c_dice0, double c_gul0, double
   return 0;
 }
 
+// ---- per-sample sums and values: the online-hard-mining key (train.py:442-446, :249-253) -------------------------------------
+// The reference re-evaluates general_union_loss_lib(pred_de[i], label[i], weight[i]) once per sample with a .item() each.  Here
+// one pass gives the seven sums of every sample: grid (SAMPLE_BLOCKS, batch), block (x, b) strides over sample b's elements
+// [b n, (b + 1) n) exactly as loss_sums_kernel strides over the whole array, and reduces with the same tree.  Nothing in a
+// block's work depends on gridDim.y or on another sample, so sample b's sums are the same bits alone or in any batch.
+// (The body restates loss_sums_kernel's instead of sharing a function with it: that kernel's code object stays as it is.)
+static constexpr int SAMPLE_BLOCKS = 256;                    // per sample: 1 per CU; 8 trips of the 16-byte path at 128^3
+static constexpr int SAMPLE_STRIDE = SAMPLE_BLOCKS * 256;    // threads that share one sample
+int loss_sample_partials(int batch) { return batch * SAMPLE_BLOCKS; }
+
+template <int TERMS>
+__global__ void __launch_bounds__(256)
+loss_sample_sums_kernel(const float* __restrict__ pred, int apply_sigmoid, const float* __restrict__ target,
+                        const float* __restrict__ weight, const float* __restrict__ skel, long long n,
+                        float* __restrict__ partial) {
+  const long long base = (long long)blockIdx.y * n;
+  pred += base;
+  target += base;
+  if (weight) weight += base;
+  if (skel) skel += base;
+  float s[SEUNET_LOSS_NSUMS];
+#pragma unroll
+  for (int k = 0; k < SEUNET_LOSS_NSUMS; ++k) s[k] = 0.f;
+  const bool vec = (n & 3) == 0 && ((reinterpret_cast<size_t>(pred) | reinterpret_cast<size_t>(target) |
+                                     reinterpret_cast<size_t>(weight) | reinterpret_cast<size_t>(skel)) & 15) == 0;
+  if (vec) {   // 16-byte loads
+    const long long n4 = n >> 2;
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += SAMPLE_STRIDE) {
+      const float4 p = reinterpret_cast<const float4*>(pred)[i], t = reinterpret_cast<const float4*>(target)[i];
+      const float4 w = weight ? reinterpret_cast<const float4*>(weight)[i] : make_float4(1.f, 1.f, 1.f, 1.f);
+      const float4 k = skel ? reinterpret_cast<const float4*>(skel)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+      loss_terms<TERMS>(p.x, apply_sigmoid, t.x, w.x, k.x, s);
+      loss_terms<TERMS>(p.y, apply_sigmoid, t.y, w.y, k.y, s);
+      loss_terms<TERMS>(p.z, apply_sigmoid, t.z, w.z, k.z, s);
+      loss_terms<TERMS>(p.w, apply_sigmoid, t.w, w.w, k.w, s);
+    }
+  } else {
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += SAMPLE_STRIDE)
+      loss_terms<TERMS>(pred[i], apply_sigmoid, target[i], weight ? weight[i] : 1.f, skel ? skel[i] : 0.f, s);
+  }
+  __shared__ float red[4][SEUNET_LOSS_NSUMS];
+#pragma unroll
+  for (int k = 0; k < SEUNET_LOSS_NSUMS; ++k) {
+    float v = s[k];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += shfl_xor_settled(v, off);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < SEUNET_LOSS_NSUMS) {
+    const int k = threadIdx.x;
+    partial[((long long)blockIdx.y * SAMPLE_BLOCKS + blockIdx.x) * SEUNET_LOSS_NSUMS + k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+  }
+}
+
+// block b: sample b; one wave per sum, lane l adds that sample's block partials l, l+64, ... in f64, then the fixed-order butterfly
+__global__ void __launch_bounds__(64 * SEUNET_LOSS_NSUMS)
+loss_sample_final_kernel(const float* __restrict__ partial, double* __restrict__ sums) {
+  const int k = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  partial += (long long)blockIdx.x * SAMPLE_BLOCKS * SEUNET_LOSS_NSUMS;
+  double s = 0.0;
+  for (int b = lane; b < SAMPLE_BLOCKS; b += 64) s += (double)partial[b * SEUNET_LOSS_NSUMS + k];
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) s += shfl_xor_settled(s, off);
+  if (lane == 0) sums[(long long)blockIdx.x * SEUNET_LOSS_NSUMS + k] = s;
+}
+
+int launch_loss_sums_per_sample(const float* pred, int apply_sigmoid, const float* target, const float* weight, const float* skel,
+                                int batch, long long n, float* partial, double* sums, int terms, hipStream_t s) {
+  terms &= 7;
+  if (terms == 0) terms = 7;
+  const dim3 grid(SAMPLE_BLOCKS, batch);
+  switch (terms) {
+    case 1: loss_sample_sums_kernel<1><<<grid, 256, 0, s>>>(pred, apply_sigmoid, target, weight, skel, n, partial); break;
+    case 2: loss_sample_sums_kernel<2><<<grid, 256, 0, s>>>(pred, apply_sigmoid, target, weight, skel, n, partial); break;
+    case 6: loss_sample_sums_kernel<6><<<grid, 256, 0, s>>>(pred, apply_sigmoid, target, weight, skel, n, partial); break;
+    default: loss_sample_sums_kernel<7><<<grid, 256, 0, s>>>(pred, apply_sigmoid, target, weight, skel, n, partial); break;
+  }
+  loss_sample_final_kernel<<<batch, 64 * SEUNET_LOSS_NSUMS, 0, s>>>(partial, sums);
+  SEUNET_LAUNCH_CHECK();
+  return 0;
+}
+
+// values[b]: the f64 ratio arithmetic of loss_value_kernel on sample b's sums, rounded once to f32
+__global__ void __launch_bounds__(64)
+loss_sample_values_kernel(const double* __restrict__ sums, int batch, double cd, double cg, double ca, float* __restrict__ values) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= batch) return;
+  const double* s = sums + (long long)b * SEUNET_LOSS_NSUMS;
+  double out = 0.0;
+  if (cd != 0.0) out = out + cd * (1.0 - (2.0 * s[0] + 1.0) / (s[1] + s[2] + 1.0));
+  if (cg != 0.0) out = out + cg * (1.0 - (s[3] + 1.0) / (s[4] + 1.0));
+  if (ca != 0.0) out = out + ca * (1.0 - (s[5] + 1.0) / (s[6] + 1.0));
+  values[b] = (float)out;
+}
+
+int launch_loss_sample_values(const double* sums, int batch, double c_dice, double c_gul, double c_atr, float* values, hipStream_t s) {
+  loss_sample_values_kernel<<<(batch + 63) / 64, 64, 0, s>>>(sums, batch, c_dice, c_gul, c_atr, values);
+  SEUNET_LAUNCH_CHECK();
+  return 0;
+}
+
 int launch_loss_grad(const float* pred, int apply_sigmoid, const float* target, const float* weight,
                      const float* skel, long long n, const double* sums, float c_dice, float c_gul,
                      float c_atr, float g_scale, const float* g_scale_dev, float* g_pred, hipStream_t s) {

@@ -405,4 +405,21 @@ int launch_loss_grad(const float* pred, int apply_sigmoid, const float* target,
                      const float* weight, const float* skel, long long n, const double* sums,
                      float c_dice, float c_gul, float c_atr, float g_scale,
                      const float* g_scale_dev, float* g_pred, hipStream_t s);
+// per-sample sums / values: the online-hard-mining key (loss.hip)
+int loss_sample_partials(int batch);
+int launch_loss_sums_per_sample(const float* pred, int apply_sigmoid, const float* target, const float* weight, const float* skel,
+                                int batch, long long n, float* partial, double* sums, int terms, hipStream_t s);
+int launch_loss_sample_values(const double* sums, int batch, double c_dice, double c_gul, double c_atr, float* values, hipStream_t s);
+// online-hard-mining sample pool (pool.hip)
+#define SEUNET_POOL_MAX_CAPACITY 65535
+#define SEUNET_POOL_MAX_BATCH 1024
+#define SEUNET_POOL_MAX_GATHER 32
+int launch_pool_select(const float* new_keys, int batch, float* keys, long long* seq, long long* state, int capacity, int* slots_out,
+                       hipStream_t s);
+int launch_pool_scatter(const int* slots_dev, int batch, int capacity, long long voxels, const float* data, const float* label,
+                        const float* weight, const float* skel, float* pool_data, unsigned char* pool_label, float* pool_weight,
+                        unsigned char* pool_skel, hipStream_t s);
+int launch_pool_gather(const int* slots_host, int n, int capacity, long long voxels, const float* pool_data,
+                       const unsigned char* pool_label, const float* pool_weight, const unsigned char* pool_skel, float* data_out,
+                       float* label_out, float* weight_out, float* skel_out, hipStream_t s);
 }  // namespace seunet

@@ -164,3 +164,31 @@ def fused_stage_loss(stage: int, pred_en, pred_de, label, weight=None, skel=None
     else:
         ca, cb = (0.0, 1.0, 0.5), (0.0, 0.5, 0.5)
     return _StageLoss.apply(pred_de, pred_en, label, weight, skel, ca, cb, group)
+
+
+def per_sample_loss(pred, target, weight=None, skel=None, c_dice=0.0, c_gul=1.0, c_atr=0.0, apply_sigmoid=False):
+    """(B,) f32 device tensor: c_dice*dice + c_gul*GUL + c_atr*ATR of every sample of the batch on its own.  The defaults give
+    the key of the reference's online hard mining, ``general_union_loss_lib(pred_de[i], label[i], weight[i])`` for each ``i``
+    (train.py:442-446, :249-253), without its B ``.item()`` synchronisations: one reduction pass over the batch, one value
+    launch, nothing waited for.  Outside autograd.  ``apply_sigmoid=True`` takes raw logits."""
+    if not pred.is_cuda:
+        raise RuntimeError("HIP losses need GPU tensors (no CPU fallback; the CPU oracle is oracle/seunet_oracle.py)")
+    if pred.dim() < 1 or pred.shape[0] < 1 or pred.numel() == 0:
+        raise ValueError(f"per_sample_loss: pred of shape {tuple(pred.shape)} has no batch axis to split")
+    p = pred.detach().contiguous().float()
+    t, w, s = _prep(target, p), _prep(weight, p), _prep(skel, p)
+    batch = p.shape[0]
+    lib = _lib.load()
+    with torch.cuda.device(p.device):
+        floats = lib.seunet_loss_sample_partial_floats(batch)
+        if floats <= 0:
+            raise RuntimeError(f"libseunet_hip loss_sample_partial_floats: {_lib.last_error()}")
+        partial = torch.empty(floats, dtype=torch.float32, device=p.device)
+        sums = torch.empty((batch, _lib.LOSS_NSUMS), dtype=torch.float64, device=p.device)
+        values = torch.empty(batch, dtype=torch.float32, device=p.device)
+        _lib.check(lib.seunet_loss_sums_per_sample(p.data_ptr(), int(apply_sigmoid), t.data_ptr(), _lib.ptr(w), _lib.ptr(s), batch,
+                                                   p.numel() // batch, partial.data_ptr(), sums.data_ptr(),
+                                                   _terms(c_dice, c_gul, c_atr), _lib.stream_ptr()), "loss_sums_per_sample")
+        _lib.check(lib.seunet_loss_sample_values(sums.data_ptr(), batch, float(c_dice), float(c_gul), float(c_atr),
+                                                 values.data_ptr(), _lib.stream_ptr()), "loss_sample_values")
+    return values
