@@ -437,6 +437,40 @@ int seunet_label_stats(const int* parsing, int n0, int n1, int n2, int num, unsi
                        int* status_dev, seunet_stream_t s);
 int seunet_relabel(const int* parsing, long long n, const int* lut, int nlut, int* out, seunet_stream_t s);
 
+/* ---- airway tree parsing: the reference's own parser -----------------------------------------------
+ * What ske_and_parse.py:20-65 (airway_parse) with ours_skel_parse.py:569-619 (Topology_Tree.sub / merge) needs from the device
+ * besides seunet_largest_component, seunet_skeletonize, seunet_mask_bits, seunet_mask_box, seunet_crop3d and seunet_parse_assign;
+ * its graph stage runs on the host.  Volumes are C-contiguous (n0, n1, n2) on the device, axis 2 contiguous; masks are bytes
+ * with non-zero = 1; fewer than 2^31 voxels (anything else: error).  Integer work throughout: every output is bitwise scipy's and
+ * does not depend on the order in which the device executes anything.  Nothing is allocated and no call synchronises the stream.
+ *
+ * seunet_binary_morph: skimage.morphology.binary_dilation / binary_closing with the default footprint, the cross of the 6 face
+ *   neighbours, as scipy.ndimage states them (not checked against skimage): SEUNET_MORPH_DILATE, outside the volume = 0;
+ *   SEUNET_MORPH_ERODE_BORDER0 / _BORDER1, outside = 0 / 1 (binary_erosion(border_value=...)); SEUNET_MORPH_CLOSE = DILATE then
+ *   ERODE_BORDER1, bit for bit.  out: n0*n1*n2 bytes of 0/1, may not alias volume.  workspace:
+ *   seunet_binary_morph_workspace_bytes(n0, n1, n2), caller-owned (two bit-packed copies of the volume).
+ * seunet_fill_holes: scipy.ndimage.binary_fill_holes: out = volume != 0, plus the 6-connected background that does not reach
+ *   the border of the volume: the hole-filling stage of seunet_largest_component on its own.  out: bytes of 0/1, may alias
+ *   volume.  workspace: seunet_cc_workspace_bytes(n0, n1, n2).
+ * seunet_slice_moments: out_dev = 3 device u64 {count, sum of i0, sum of i1} over the non-zero voxels of the slice [:, :, k]
+ *   (zeroed here): the exact sums behind the centroids of compute_base_vector (ours_skel_parse.py:178-183).
+ * seunet_scatter_labels: cd[lin_index[j]] = value[j] and skeleton_parse[lin_index[j]] = (value[j] != 0) for j < m, into volumes
+ *   of n voxels the caller has zeroed (ske_and_parse.py:48-62); lin_index = device int64 raster indices, value = device int32.
+ *   The caller passes every voxel once (the first writer is resolved on the host), so the device order decides nothing.  An
+ *   index outside 0..n-1 is skipped and sets status_dev (device int, zeroed here) to 1. */
+#define SEUNET_MORPH_DILATE 0
+#define SEUNET_MORPH_ERODE_BORDER0 1
+#define SEUNET_MORPH_ERODE_BORDER1 2
+#define SEUNET_MORPH_CLOSE 3
+size_t seunet_binary_morph_workspace_bytes(int n0, int n1, int n2);
+int seunet_binary_morph(const unsigned char* volume, int n0, int n1, int n2, int op, unsigned char* out, void* workspace,
+                        size_t workspace_bytes, seunet_stream_t s);
+int seunet_fill_holes(const unsigned char* volume, int n0, int n1, int n2, unsigned char* out, void* workspace, size_t workspace_bytes,
+                      seunet_stream_t s);
+int seunet_slice_moments(const unsigned char* mask, int n0, int n1, int n2, int k, unsigned long long* out_dev, seunet_stream_t s);
+int seunet_scatter_labels(const long long* lin_index_dev, const int* value_dev, long long m, long long n, int* cd,
+                          unsigned char* skeleton_parse, int* status_dev, seunet_stream_t s);
+
 /* ---- CT preprocessing: preprocessing.py:26-130 with util.py:95-152 -----------------------------
  * CT volumes are int16, C-contiguous (h, w, z) on the device (the reference's orientation after its transposes), fewer than 2^31
  * voxels; masks are bytes, non-zero = 1.

@@ -5,13 +5,14 @@ hand-written HIP kernels behind a C ABI (``include/seunet_hip.h``).  The directo
 Python identifier; import it as ``seunet_amd`` (alias module at the repo root) or via
 ``importlib.import_module("se-unet-airseg_amd")``.
 """
-from . import _lib, ddp, online, ops, optim, pipeline, postprocess, prep, preprocess
+from . import _lib, ddp, online, ops, optim, pipeline, postprocess, prep, preprocess, topology
 from .SE_UNet import CapturedForward, CATConv, DropLayer, SE_UNet, SSEConv, SSEConv2, get_model, load_reference_checkpoint
 from .optim import AdamW
 from .pipeline import (AirwayHMData3GPU, AirwayHMDataGPU, CropSegDataGPU, aug_code, crop_batch, draw_stage1_plan, draw_stage2_plan,
                        draw_stage3_plan, two_channel_volume)
-from .prep import (CandidateSet, break_weight, distance_transform_edt, hard_mining_candidates, label_adjacency, lib_weight, relabel,
-                   skeleton_parsing, skeletonize_3d, tree_parsing, tree_parsing_func)
+from .prep import (CandidateSet, airway_parse, binary_closing, binary_dilation, binary_erosion, binary_fill_holes, break_weight,
+                   distance_transform_edt, hard_mining_candidates, label_adjacency, lib_weight, relabel, skeleton_parsing, skeletonize_3d,
+                   tree_parsing, tree_parsing_func)
 from .preprocess import cut_mask, get_l, large_connected_domain26, preprocess_ct, th_2t
 from .postprocess import (MetricSums, double_threshold_iteration, evaluation_case, largest_component, maximum_3d,
                           postprocess_prediction, zero_borders)
@@ -23,4 +24,5 @@ __all__ = ["SE_UNet", "SSEConv", "SSEConv2", "CATConv", "DropLayer", "get_model"
            "general_union_loss_lib", "atr_loss", "fused_logit_loss", "fused_stage_loss", "per_sample_loss", "OnlineHardPool",
            "sliding_window_predict", "sliding_window_validate", "two_channel", "window_starts", "window_table", "AdamW", "CropSegDataGPU", "AirwayHMDataGPU", "AirwayHMData3GPU", "aug_code", "crop_batch", "draw_stage1_plan", "draw_stage2_plan", "draw_stage3_plan", "two_channel_volume", "double_threshold_iteration", "postprocess_prediction", "zero_borders", "maximum_3d", "largest_component",
            "evaluation_case", "MetricSums", "CandidateSet", "distance_transform_edt", "hard_mining_candidates", "lib_weight",
-           "break_weight", "skeletonize_3d", "skeleton_parsing", "tree_parsing_func", "label_adjacency", "tree_parsing", "relabel", "preprocess_ct", "th_2t", "get_l", "large_connected_domain26", "cut_mask"]
+           "break_weight", "skeletonize_3d", "skeleton_parsing", "tree_parsing_func", "label_adjacency", "tree_parsing", "relabel", "airway_parse", "binary_dilation",
+           "binary_erosion", "binary_closing", "binary_fill_holes", "preprocess_ct", "th_2t", "get_l", "large_connected_domain26", "cut_mask"]

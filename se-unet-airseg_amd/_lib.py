@@ -17,6 +17,7 @@ CONV_MFMA, CONV_NAIVE, CONV_MARCH, CONV_TILED = 0, 1, 2, 3
 LOSS_NSUMS = 7
 DTI_F64, DTI_F32 = 0, 1
 CC_EVALUATION, CC_MAXIMUM_3D, CC_LARGEST_FILLED = 0, 1, 2
+MORPH_DILATE, MORPH_ERODE_BORDER0, MORPH_ERODE_BORDER1, MORPH_CLOSE = 0, 1, 2, 3
 
 
 class Dims(C.Structure):
@@ -142,6 +143,11 @@ PROTOTYPES = {
     "seunet_label_stats_max_num": (_i, []),
     "seunet_label_stats": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "seunet_relabel": (_i, [_vp, _ll, _vp, _i, _vp, _vp]),
+    "seunet_binary_morph_workspace_bytes": (_sz, [_i, _i, _i]),
+    "seunet_binary_morph": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "seunet_fill_holes": (_i, [_vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "seunet_slice_moments": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "seunet_scatter_labels": (_i, [_vp, _vp, _ll, _ll, _vp, _vp, _vp, _vp]),
     "seunet_adamw_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _i, _i, _vp]),
     "seunet_net_param_count": (_i, [C.POINTER(NetDesc)]),
     "seunet_net_param_info": (_i, [C.POINTER(NetDesc), _i, C.c_char_p, _i, _ip, _ip]),

@@ -29,7 +29,8 @@ int seunet_debug_set_buffer(void* p) { seunet::g_conv_debug = reinterpret_cast<u
 int seunet_debug_upsample2_form(int dtype, int c, seunet_dims dims, int backward) { return upsample2_form(dtype, c, D(dims), backward != 0); }
 
 // diagnostic hook (not part of the public header, host only): the workspace layout of a volume operation as its launcher
-// carves it.  op: 0 cc, 1 get_l, 2 edt, 3 lib_weight, 4 break_weight, 5 skeleton_branches, 6 dti, 7 skeleton, 8 parse_assign.
+// carves it.  op: 0 cc, 1 get_l, 2 edt, 3 lib_weight, 4 break_weight, 5 skeleton_branches, 6 dti, 7 skeleton, 8 parse_assign,
+// 9 binary_morph.
 // Returns the number of sub-buffers (0: extents the op rejects, -1: no such op) and writes (offset, bytes up to the next
 // sub-buffer or the end) of the first `cap`.
 int seunet_debug_volume_layout(int op, int n0, int n1, int n2, size_t* offsets, int cap) {
@@ -47,6 +48,7 @@ int seunet_debug_volume_layout(int op, int n0, int n1, int n2, size_t* offsets, 
     case 5: branches_ws(c, n0, n1, n2); break;
     case 6: dti_ws(c, n0, n1, n2); break;
     case 7: if (!skeleton_ws(c, n0, n1, n2)) return 0; break;
+    case 9: morph_ws(c, n0, n1, n2); break;
     default: return -1;
   }
   if (c.taken > c.log_cap) return -1;
@@ -461,6 +463,26 @@ int seunet_label_stats(const int* parsing, int n0, int n1, int n2, int num, unsi
 }
 int seunet_relabel(const int* parsing, long long n, const int* lut, int nlut, int* out, seunet_stream_t s) {
   return launch_relabel(parsing, n, lut, nlut, out, S(s));
+}
+
+size_t seunet_binary_morph_workspace_bytes(int n0, int n1, int n2) {
+  if (n0 < 1 || n1 < 1 || n2 < 1) { fail("binary_morph_workspace_bytes: bad dimensions"); return 0; }
+  return binary_morph_workspace_bytes(n0, n1, n2);
+}
+int seunet_binary_morph(const unsigned char* volume, int n0, int n1, int n2, int op, unsigned char* out, void* workspace,
+                        size_t workspace_bytes, seunet_stream_t s) {
+  return launch_binary_morph(volume, n0, n1, n2, op, out, workspace, workspace_bytes, S(s));
+}
+int seunet_fill_holes(const unsigned char* volume, int n0, int n1, int n2, unsigned char* out, void* workspace, size_t workspace_bytes,
+                      seunet_stream_t s) {
+  return launch_fill_holes(volume, n0, n1, n2, out, workspace, workspace_bytes, S(s));
+}
+int seunet_slice_moments(const unsigned char* mask, int n0, int n1, int n2, int k, unsigned long long* out_dev, seunet_stream_t s) {
+  return launch_slice_moments(mask, n0, n1, n2, k, out_dev, S(s));
+}
+int seunet_scatter_labels(const long long* lin_index_dev, const int* value_dev, long long m, long long n, int* cd,
+                          unsigned char* skeleton_parse, int* status_dev, seunet_stream_t s) {
+  return launch_scatter_labels(lin_index_dev, value_dev, m, n, cd, skeleton_parse, status_dev, S(s));
 }
 
 int seunet_value_counts(const short* ct, long long n, int shift, unsigned int* counts, seunet_stream_t s) {

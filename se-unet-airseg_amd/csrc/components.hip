@@ -178,6 +178,38 @@ void cc_label26(const unsigned char* vol, int H, int W, int Z, int* L, hipStream
 
 size_t cc_workspace_bytes(int H, int W, int Z) { return measured(cc_ws, H, W, Z); }
 
+// scipy.ndimage.binary_fill_holes on a 0/1 mask, in place: label the complement with 6-connectivity, keep what reaches the border
+static int fill_holes_in_place(unsigned char* mask, int H, int W, int Z, int* L, unsigned int* flag, hipStream_t s) {
+  const long long n = (long long)H * W * Z;
+  const unsigned blocks = blocks_256(n);
+  SEUNET_HIP(hipMemsetAsync(flag, 0, (size_t)n * 4, s));
+  cc_init_kernel<true><<<blocks, 256, 0, s>>>(mask, n, Z, L);
+  cc_merge_kernel<false><<<blocks, 256, 0, s>>>(L, n, H, W, Z);
+  launch_cc_compress(L, n, s);
+  cc_border_kernel<<<blocks, 256, 0, s>>>(L, H, W, Z, flag);
+  cc_fill_kernel<<<blocks, 256, 0, s>>>(L, flag, n, mask);
+  return 0;
+}
+
+__global__ void __launch_bounds__(256)
+mask01_kernel(const unsigned char* vol, long long n, unsigned char* out) {
+  const long long i = blockIdx.x * 256ll + threadIdx.x;
+  if (i < n) out[i] = vol[i] != 0 ? 1 : 0;
+}
+
+int launch_fill_holes(const unsigned char* vol, int H, int W, int Z, unsigned char* out, void* workspace, size_t ws_bytes, hipStream_t s) {
+  SEUNET_CHECK(vol && out && workspace, "fill_holes: null argument");
+  if (volume_check("fill_holes", H, W, Z, 0, true)) return 1;
+  WsCarver carve(workspace);
+  const CcWs w = cc_ws(carve, H, W, Z);
+  SEUNET_CHECK(ws_bytes >= carve.bytes(), "fill_holes: workspace too small");
+  const long long n = (long long)H * W * Z;
+  mask01_kernel<<<blocks_256(n), 256, 0, s>>>(vol, n, out);          // (elementwise: out may alias vol)
+  if (fill_holes_in_place(out, H, W, Z, w.labels, w.counts, s)) return 1;
+  SEUNET_LAUNCH_CHECK();
+  return 0;
+}
+
 int launch_largest_component(const unsigned char* vol, int H, int W, int Z, int rule, unsigned char* out, int* status_dev,
                              void* workspace, size_t ws_bytes, hipStream_t s) {
   SEUNET_CHECK(vol && out && workspace && H >= 1 && W >= 1 && Z >= 1, "largest_component: bad argument");
@@ -204,14 +236,7 @@ int launch_largest_component(const unsigned char* vol, int H, int W, int Z, int 
   }
   cc_choose_kernel<<<1, 64, 0, s>>>(sel, rule);
   cc_mask_kernel<<<blocks, 256, 0, s>>>(L, n, sel, out);
-  if (rule >= 1) {   // binary_fill_holes (util.py:73, :163): label the complement with 6-connectivity, keep what reaches the border
-    SEUNET_HIP(hipMemsetAsync(cnt, 0, (size_t)n * 4, s));
-    cc_init_kernel<true><<<blocks, 256, 0, s>>>(out, n, Z, L);
-    cc_merge_kernel<false><<<blocks, 256, 0, s>>>(L, n, H, W, Z);
-    launch_cc_compress(L, n, s);
-    cc_border_kernel<<<blocks, 256, 0, s>>>(L, H, W, Z, cnt);
-    cc_fill_kernel<<<blocks, 256, 0, s>>>(L, cnt, n, out);
-  }
+  if (rule >= 1 && fill_holes_in_place(out, H, W, Z, L, cnt, s)) return 1;      // binary_fill_holes (util.py:73, :163)
   if (status_dev) SEUNET_HIP(hipMemcpyAsync(status_dev, &sel->status, sizeof(int), hipMemcpyDeviceToDevice, s));
   SEUNET_LAUNCH_CHECK();
   return 0;

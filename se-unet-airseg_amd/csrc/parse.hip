@@ -231,4 +231,66 @@ int launch_relabel(const int* parsing, long long n, const int* lut, int nlut, in
   return 0;
 }
 
+// ---- the reference's own parser: what its host graph stage asks of the device -------------------------
+
+// out[0..2] += count, sum of i0, sum of i1 over the non-zero voxels of slice [:, :, k]
+__global__ void __launch_bounds__(256)
+slice_moments_kernel(const unsigned char* __restrict__ mask, int n0, int n1, int n2, int k, u64* __restrict__ out) {
+  const long long rows = (long long)n0 * n1;
+  u64 cnt = 0, s0 = 0, s1 = 0;
+  for (long long r = blockIdx.x * 256ll + threadIdx.x; r < rows; r += (long long)gridDim.x * 256) {
+    if (mask[r * n2 + k] != 0) {
+      cnt += 1;
+      s0 += (u64)(r / n1);
+      s1 += (u64)(r % n1);
+    }
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    cnt += shfl_xor_settled(cnt, off);
+    s0 += shfl_xor_settled(s0, off);
+    s1 += shfl_xor_settled(s1, off);
+  }
+  if ((threadIdx.x & 63) == 0 && cnt) {
+    atomicAdd(&out[0], cnt);
+    atomicAdd(&out[1], s0);
+    atomicAdd(&out[2], s1);
+  }
+}
+
+int launch_slice_moments(const unsigned char* mask, int n0, int n1, int n2, int k, unsigned long long* out_dev, hipStream_t s) {
+  SEUNET_CHECK(mask && out_dev, "slice_moments: null argument");
+  if (volume_check("slice_moments", n0, n1, n2, 0)) return 1;
+  SEUNET_CHECK(k >= 0 && k < n2, "slice_moments: slice %d of an axis of %d", k, n2);
+  SEUNET_HIP(hipMemsetAsync(out_dev, 0, 3 * sizeof(u64), s));
+  slice_moments_kernel<<<grid_for((long long)n0 * n1), 256, 0, s>>>(mask, n0, n1, n2, k, out_dev);
+  SEUNET_LAUNCH_CHECK();
+  return 0;
+}
+
+// cd[lin[j]] = value[j], skeleton_parse[lin[j]] = value[j] != 0; an index outside 0 .. n - 1 sets *status and is skipped.  The
+// caller passes every voxel once, so no order among the lanes decides anything.
+__global__ void __launch_bounds__(256)
+scatter_labels_kernel(const long long* __restrict__ lin, const int* __restrict__ value, long long m, long long n, int* __restrict__ cd,
+                      unsigned char* __restrict__ parse, int* __restrict__ status) {
+  const long long j = blockIdx.x * 256ll + threadIdx.x;
+  if (j >= m) return;
+  const long long i = lin[j];
+  if (i < 0 || i >= n) { *status = 1; return; }
+  const int v = value[j];
+  cd[i] = v;
+  parse[i] = v != 0 ? 1 : 0;
+}
+
+int launch_scatter_labels(const long long* lin_index, const int* value, long long m, long long n, int* cd, unsigned char* skeleton_parse,
+                          int* status_dev, hipStream_t s) {
+  SEUNET_CHECK(cd && skeleton_parse && status_dev && m >= 0 && n >= 1, "scatter_labels: bad argument");
+  SEUNET_CHECK(m == 0 || (lin_index && value), "scatter_labels: null list");
+  SEUNET_CHECK(m < (1ll << 31) * 256, "scatter_labels: %lld entries", m);
+  SEUNET_HIP(hipMemsetAsync(status_dev, 0, sizeof(int), s));
+  if (m > 0) scatter_labels_kernel<<<blocks_256(m), 256, 0, s>>>(lin_index, value, m, n, cd, skeleton_parse, status_dev);
+  SEUNET_LAUNCH_CHECK();
+  return 0;
+}
+
 }  // namespace seunet

@@ -1,4 +1,4 @@
-// Shared layer of the volume operations (components.hip, lung.hip, edt.hip, parse.hip, skeleton.hip, dti.hip): their launcher
+// Shared layer of the volume operations (components.hip, lung.hip, edt.hip, parse.hip, skeleton.hip, dti.hip, morph.hip): their launcher
 // prototypes, ONE workspace layout per operation, the extent check and the voxel / wave helpers their kernels share.
 //
 // Workspace contract: every operation has a layout struct filled by one function that walks a WsCarver.  Over a null base
@@ -96,6 +96,8 @@ size_t cc_workspace_bytes(int H, int W, int Z);
 void cc_label26(const unsigned char* vol, int H, int W, int Z, int* L, hipStream_t s);   // component labels (minimum index), -1 off
 int launch_largest_component(const unsigned char* vol, int H, int W, int Z, int rule, unsigned char* out, int* status_dev,
                              void* workspace, size_t ws_bytes, hipStream_t s);
+// scipy.ndimage.binary_fill_holes: out = (vol != 0) plus the 6-connected background that does not reach the border; workspace: cc_ws
+int launch_fill_holes(const unsigned char* vol, int H, int W, int Z, unsigned char* out, void* workspace, size_t ws_bytes, hipStream_t s);
 void launch_cc_compress(int* L, long long n, hipStream_t s);                          // L[i] = root of i
 void launch_cc_count(const int* L, long long n, unsigned int* cnt, hipStream_t s);   // cnt[root] += voxels (cnt zeroed by the caller)
 size_t metric_out_bytes(int nbins);
@@ -196,6 +198,20 @@ int label_stats_max_num();
 int launch_label_stats(const int* parsing, int n0, int n1, int n2, int num, unsigned int* counts, unsigned long long* adjacency_bits,
                        int* status_dev, hipStream_t s);
 int launch_relabel(const int* parsing, long long n, const int* lut, int nlut, int* out, hipStream_t s);
+// the reference's own parser: centroid sums of one axis-2 slice, and cd / skeleton_parse from a voxel list
+int launch_slice_moments(const unsigned char* mask, int n0, int n1, int n2, int k, unsigned long long* out_dev, hipStream_t s);
+int launch_scatter_labels(const long long* lin_index, const int* value, long long m, long long n, int* cd, unsigned char* skeleton_parse,
+                          int* status_dev, hipStream_t s);
+
+// ---- binary morphology with the 6-neighbour cross (morph.hip) ---------------------------------------------------------------
+struct MorphWs { u64 *a, *b; };   // the packed volume and one step's result; rows of ceil(n2 / 64) words
+static inline MorphWs morph_ws(WsCarver& c, int n0, int n1, int n2) {
+  const size_t words = (size_t)n0 * n1 * ((n2 + 63) / 64);
+  return MorphWs{c.take<u64>(words), c.take<u64>(words)};
+}
+size_t binary_morph_workspace_bytes(int n0, int n1, int n2);
+int launch_binary_morph(const unsigned char* vol, int n0, int n1, int n2, int op, unsigned char* out, void* workspace, size_t ws_bytes,
+                        hipStream_t s);
 
 // ---- CT preprocessing (lung.hip): value counts, shift + clamp, per-slice lung field, mask combination, bounding box, crop --
 struct GetLWs {

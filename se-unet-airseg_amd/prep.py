@@ -11,8 +11,9 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, topology
 from ._volume import mask_in, out as _out, read_status, workspace
+from .postprocess import maximum_3d
 
 _BLOCK_WORDS = 8          # 512 voxels per prefix-sum block
 SKELETON_ROUND_LAUNCHES = 32   # kRoundLaunches of csrc/skeleton.hip (scripts/bench_skeleton.py counts launches with it)
@@ -479,3 +480,180 @@ def relabel(parsing, lut):
             _lib.check(_lib.load().seunet_relabel(vol.data_ptr(), vol.numel(), table.data_ptr(), table.numel(), out.data_ptr(),
                                                   _lib.stream_ptr()), "relabel")
     return _out(out, as_numpy)
+
+
+# ---- airway tree parsing: the reference's own parser (csrc/morph.hip, components.hip, parse.hip, topology.py) -----
+
+def _morph(vol, op, what):
+    n0, n1, n2 = (int(v) for v in vol.shape)
+    dev = vol.device
+    out = torch.empty((n0, n1, n2), dtype=torch.uint8, device=dev)
+    if vol.numel():
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            ws = workspace(lib.seunet_binary_morph_workspace_bytes, n0, n1, n2, device=dev, min_bytes=1)
+            _lib.check(lib.seunet_binary_morph(vol.data_ptr(), n0, n1, n2, op, out.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()), what)
+    return out
+
+
+def binary_dilation(volume):
+    """``skimage.morphology.binary_dilation(volume)`` with its default footprint, the cross of the 6 face neighbours, as
+    ``scipy.ndimage.binary_dilation`` states it (outside the volume = 0; not checked against skimage).  uint8 0/1 out; CUDA tensor
+    in -> CUDA tensor out, numpy in -> numpy out; the input is not modified."""
+    vol, as_numpy = _mask_in(volume, "volume")
+    return _out(_morph(vol, _lib.MORPH_DILATE, "binary_dilation"), as_numpy)
+
+
+def binary_erosion(volume, border_value: int = 0):
+    """``scipy.ndimage.binary_erosion(volume, border_value=...)`` with the 6-neighbour cross: outside the volume counts as
+    ``border_value`` (0 or 1)."""
+    if border_value not in (0, 1, False, True):
+        raise ValueError(f"seunet prep: binary_erosion: border_value {border_value!r} (0 or 1)")
+    vol, as_numpy = _mask_in(volume, "volume")
+    return _out(_morph(vol, _lib.MORPH_ERODE_BORDER1 if border_value else _lib.MORPH_ERODE_BORDER0, "binary_erosion"), as_numpy)
+
+
+def binary_closing(volume):
+    """``skimage.morphology.binary_closing(volume)`` with the 6-neighbour cross: ``binary_erosion(binary_dilation(volume),
+    border_value=1)``, bit for bit, in one call on the packed bits (the reading of skimage 0.21-0.24; not checked against
+    skimage)."""
+    vol, as_numpy = _mask_in(volume, "volume")
+    return _out(_morph(vol, _lib.MORPH_CLOSE, "binary_closing"), as_numpy)
+
+
+def binary_fill_holes(volume):
+    """``scipy.ndimage.binary_fill_holes(volume)``: the volume plus the 6-connected background that does not reach its border.
+    uint8 0/1 out."""
+    vol, as_numpy = _mask_in(volume, "volume")
+    n0, n1, n2 = (int(v) for v in vol.shape)
+    dev = vol.device
+    out = torch.empty((n0, n1, n2), dtype=torch.uint8, device=dev)
+    if vol.numel():
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            ws = workspace(lib.seunet_cc_workspace_bytes, n0, n1, n2, device=dev)
+            _lib.check(lib.seunet_fill_holes(vol.data_ptr(), n0, n1, n2, out.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()),
+                       "fill_holes")
+    return _out(out, as_numpy)
+
+
+def _mask_extent(vol):
+    """The 6 ints of ``seunet_mask_box`` on the host: {min, max} per axis; max = -1 for an empty mask."""
+    n0, n1, n2 = (int(v) for v in vol.shape)
+    with torch.cuda.device(vol.device):
+        box = torch.empty(6, dtype=torch.int32, device=vol.device)
+        _lib.check(_lib.load().seunet_mask_box(vol.data_ptr(), n0, n1, n2, box.data_ptr(), _lib.stream_ptr()), "mask_box")
+        return [int(v) for v in box.cpu().numpy()]
+
+
+def _mask_coords(mask):
+    """``np.argwhere(mask != 0)`` of a device volume, (m, 3) int64 in raster order: the bits are packed on the device
+    (``seunet_mask_bits``) and only the non-zero words are unpacked on the host, so a skeleton costs its own size, not the volume's."""
+    n = mask.numel()
+    with torch.cuda.device(mask.device):
+        bits = torch.empty((n + 63) // 64, dtype=torch.int64, device=mask.device)
+        _lib.check(_lib.load().seunet_mask_bits(mask.data_ptr(), n, bits.data_ptr(), _lib.stream_ptr()), "mask_bits")
+        words = bits.cpu().numpy().view(np.uint64)
+    if n % 64:
+        words[-1] &= np.uint64((1 << (n % 64)) - 1)
+    at = np.flatnonzero(words)
+    word, bit = np.nonzero(np.unpackbits(words[at].view(np.uint8).reshape(-1, 8), axis=1, bitorder="little"))
+    lin = at[word].astype(np.int64) * 64 + bit
+    return np.stack(np.unravel_index(lin, tuple(mask.shape)), axis=1).astype(np.int64)
+
+
+def _largest_in_slice(vol, k):
+    """Voxels of the largest 8-connected component of the slice ``[:, :, k]`` (0 for an empty slice)."""
+    n0, n1, n2 = (int(v) for v in vol.shape)
+    lib = _lib.load()
+    dev = vol.device
+    with torch.cuda.device(dev):
+        sl = torch.empty((n0, n1, 1), dtype=torch.uint8, device=dev)
+        _lib.check(lib.seunet_crop3d(vol.data_ptr(), 1, n0, n1, n2, _lib.int_array([0, n0, 0, n1, k, k + 1]), sl.data_ptr(),
+                                     _lib.stream_ptr()), "crop3d")
+        ws = workspace(lib.seunet_cc_workspace_bytes, n0, n1, 1, device=dev)
+        comp = torch.empty((n0, n1, 1), dtype=torch.uint8, device=dev)
+        _lib.check(lib.seunet_largest_component(sl.data_ptr(), n0, n1, 1, _lib.CC_EVALUATION, comp.data_ptr(), None, ws.data_ptr(),
+                                                ws.numel(), _lib.stream_ptr()), "largest_component")
+        return int(comp.sum(dtype=torch.int64).item())
+
+
+def slice_moments(mask, k: int):
+    """``(count, sum of i0, sum of i1)`` over the non-zero voxels of ``mask[:, :, k]``, exact Python ints (``seunet_slice_moments``)."""
+    vol, _ = _mask_in(mask, "mask")
+    n0, n1, n2 = (int(v) for v in vol.shape)
+    if not 0 <= int(k) < n2:
+        raise ValueError(f"seunet prep: slice_moments: slice {k} of an axis of {n2}")
+    with torch.cuda.device(vol.device):
+        out = torch.empty(3, dtype=torch.int64, device=vol.device)
+        _lib.check(_lib.load().seunet_slice_moments(vol.data_ptr(), n0, n1, n2, int(k), out.data_ptr(), _lib.stream_ptr()), "slice_moments")
+        return tuple(int(v) for v in out.cpu().numpy().view(np.uint64))
+
+
+def scatter_labels(lin_index, values, shape):
+    """``(cd int32, skeleton_parse uint8)`` device volumes of ``shape`` with ``cd.flat[lin_index[j]] = values[j]`` (one launch into
+    zeroed volumes; every index once).  An index outside the volume raises ValueError."""
+    n0, n1, n2 = (int(v) for v in shape)
+    lin = torch.from_numpy(np.ascontiguousarray(lin_index, dtype=np.int64)).cuda()
+    val = torch.from_numpy(np.ascontiguousarray(values, dtype=np.int32)).cuda()
+    if lin.shape != val.shape or lin.dim() != 1:
+        raise ValueError("seunet prep: scatter_labels: lin_index and values must be 1-D and of one length")
+    dev = lin.device
+    with torch.cuda.device(dev):
+        cd = torch.zeros((n0, n1, n2), dtype=torch.int32, device=dev)
+        parse = torch.zeros((n0, n1, n2), dtype=torch.uint8, device=dev)
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+        _lib.check(_lib.load().seunet_scatter_labels(_lib.ptr(lin) if lin.numel() else None, _lib.ptr(val) if val.numel() else None,
+                                                     lin.numel(), cd.numel(), cd.data_ptr(), parse.data_ptr(), status.data_ptr(),
+                                                     _lib.stream_ptr()), "scatter_labels")
+        _status(status, "airway_parse: cd: a branch voxel lies outside the volume")
+    return cd, parse
+
+
+def airway_parse_stages(label, merge_t: int = 5):
+    """``airway_parse`` with every intermediate result, as a dict: ``order``, ``label_trans``, ``skeleton``, ``B0`` / ``B`` (the
+    sorted skeleton before / after smoothing), ``mainpart``, ``table1`` / ``merged`` (branch tables before / after merging),
+    ``codes``, ``cd``, ``skeleton_parse`` and ``parsing`` (device tensors for the volumes)."""
+    lab, _ = _mask_in(label, "label")
+    n0, n1, n2 = (int(v) for v in lab.shape)
+    box = _mask_extent(lab) if lab.numel() else [0, -1] * 3
+    if box[5] < 0:
+        raise ValueError("airway_parse: orientation: the mask is empty")
+    k2, k8 = topology.orientation_slices(box[4], box[5])
+    order = topology.orientation(_largest_in_slice(lab, k2), _largest_in_slice(lab, k8))
+    closed = _morph(binary_fill_holes(_morph(lab, _lib.MORPH_DILATE, "binary_dilation")), _lib.MORPH_CLOSE, "binary_closing")
+    try:
+        lt = maximum_3d(closed)
+    except IndexError as e:
+        raise ValueError(f"airway_parse: label_trans: {e}") from None
+    skel = skeletonize_3d(lt)
+    coords = _mask_coords(skel)
+    ext = _mask_extent(lt)
+    trace = {}
+    merged, codes = topology.graph_stage(coords, (n0, n1, n2), order, (ext[4], ext[5]), lambda k: slice_moments(lt, k), merge_t, trace)
+    lin, val = topology.branch_labels(merged, (n0, n1, n2))
+    cd, parse = scatter_labels(lin, val, (n0, n1, n2))
+    parsing = _assign(parse, lab, cd)
+    trace.update(order=order, label_trans=lt, skeleton=skel, cd=cd, skeleton_parse=parse, parsing=parsing)
+    return trace
+
+
+def airway_parse(label, merge_t: int = 5, return_branches: bool = False):
+    """``ske_and_parse.airway_parse(label, merge_t)`` (ske_and_parse.py:20-65), the branch labelling the reference trains and
+    evaluates with: its own parser ``Topology_Tree.sub()`` + ``.merge()`` (ours_skel_parse.py:515-619), not the ATM'22 one of
+    ``tree_parsing``.  -> the int32 ``parsing`` volume ``evaluation_case`` takes.  ``label``: a byte mask, non-zero = 1 (what
+    ``large_connected_domain26`` returns); it is not modified.  CUDA tensor in -> CUDA tensor out, numpy in -> numpy out.
+
+    Dense stages on the GPU (orientation, dilation, hole fill, closing, ``maximum_3d``, ``skeletonize_3d``, the nearest-branch
+    assignment), the graph stage on the host on the skeleton's voxels (``topology.py``).  Both sorts of the reference are stable
+    here, and where the reference raises (an empty mask, fewer than three branches after merging, a father number past its child
+    table, a voxel outside the volume) ``ValueError`` names the stage: DESIGN.md section 3g.  ``return_branches``: also the merged
+    branch table, a list of dicts ``index``, ``fatherindex``, ``start``, ``member``, optionally ``end``, and the ``grade()`` code
+    strings ``grade`` / ``father_grade``."""
+    as_numpy = isinstance(label, np.ndarray)
+    st = airway_parse_stages(label, merge_t)
+    out = _out(st["parsing"], as_numpy)
+    if not return_branches:
+        return out
+    branches = [dict(b, grade=c, father_grade=f) for b, (c, f) in zip(st["merged"], st["codes"])]
+    return out, branches
