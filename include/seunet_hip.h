@@ -471,6 +471,50 @@ int seunet_slice_moments(const unsigned char* mask, int n0, int n1, int n2, int 
 int seunet_scatter_labels(const long long* lin_index_dev, const int* value_dev, long long m, long long n, int* cd,
                           unsigned char* skeleton_parse, int* status_dev, seunet_stream_t s);
 
+/* ---- surface meshing: prediction.py:121-149 ---------------------------------------------------------
+ * A 0/1 volume (bytes, non-zero = 1, C-contiguous (n0, n1, n2), fewer than 2^31 voxels) to an indexed triangle mesh, the mesh's
+ * vertex adjacency, Jacobi smoothing, the affine step (v - centre) * scale and binary-STL records.  The extraction rule, the
+ * vertex and face numbering and the order of every float32 operation are DESIGN.md 3h; every result is deterministic and equals
+ * tests/mesh_oracle.py bit for bit.  Equality with skimage's marching_cubes_lewiner or with VTK's smoothing is not claimed.
+ * verts are float32 (V, 3), faces int32 (F, 3); V and 3 F beyond the int32 range are an error.
+ *
+ * seunet_mesh_count: packs the volume, counts and scans; *nverts / *nfaces (HOST) receive V and F.  This call synchronises the
+ *   stream once, to read those two numbers; the caller sizes verts and faces with them.  workspace:
+ *   seunet_mesh_workspace_bytes(n0, n1, n2), caller-owned, and handed unchanged to seunet_mesh_emit.  A volume with an extent of 1
+ *   has no cells and gives V = F = 0.
+ * seunet_mesh_emit: writes verts and faces from the workspace seunet_mesh_count left, with the nverts / nfaces it returned;
+ *   level strictly between 0 and 1 (the offsets level and 1 - level are formed in double and rounded once to float32).
+ * seunet_mesh_coord_sums: sums_dev = 4 device int64 {count, sum of i0, sum of i1, sum of i2} over the non-zero voxels (zeroed
+ *   here): the exact sums behind the mean skeleton coordinate the mesh is centred on.
+ * seunet_mesh_adjacency: the neighbours of every vertex in CSR form, ascending and without repeats: indptr = nverts + 1 device
+ *   int32, indices = room for indices_capacity >= 6 F device int32 of which indptr[nverts] are written, boundary = nverts bytes,
+ *   1 where the vertex is an end of a directed face edge whose reverse no face has.  A face with an index outside 0 .. nverts - 1
+ *   is left out and sets status_dev (device int, zeroed here) to 1.  6 F beyond the int32 range is an error.  workspace:
+ *   seunet_mesh_adjacency_workspace_bytes(nverts, nfaces).
+ * seunet_mesh_smooth: n_iter sweeps x' = x + relaxation_factor * (m - x), m = (0 + the neighbours in ascending order) / degree,
+ *   per coordinate, one float32 rounding per operation; boundary vertices and vertices without neighbours stay.  indptr, indices,
+ *   boundary as seunet_mesh_adjacency wrote them.  out may not alias verts; tmp = a second (nverts, 3) buffer, needed from two
+ *   sweeps on.  n_iter = 0 copies.
+ * seunet_mesh_affine: out = (verts - centre) * scale per axis in float32; centre, scale = 3 HOST floats each (NULL: 0 / 1).
+ *   out may alias verts.
+ * seunet_mesh_stl_records: records = 50 F bytes (2-byte aligned): the unit normal of (b - a) x (c - a) (0, 0, 0 for a zero-area
+ *   triangle), the three vertices after the affine step, a zero attribute word.  With an 80-byte header and the uint32 F in front
+ *   this is a binary STL file.  A face with an index outside 0 .. nverts - 1 gives a zero record and sets status_dev to 1. */
+size_t seunet_mesh_workspace_bytes(int n0, int n1, int n2);
+int seunet_mesh_count(const unsigned char* volume, int n0, int n1, int n2, long long* nverts, long long* nfaces, void* workspace,
+                      size_t workspace_bytes, seunet_stream_t s);
+int seunet_mesh_emit(int n0, int n1, int n2, double level, long long nverts, long long nfaces, float* verts, int* faces,
+                     const void* workspace, size_t workspace_bytes, seunet_stream_t s);
+int seunet_mesh_coord_sums(const unsigned char* mask, int n0, int n1, int n2, long long* sums_dev, seunet_stream_t s);
+size_t seunet_mesh_adjacency_workspace_bytes(long long nverts, long long nfaces);
+int seunet_mesh_adjacency(const int* faces, long long nfaces, long long nverts, int* indptr, int* indices, long long indices_capacity,
+                          unsigned char* boundary, int* status_dev, void* workspace, size_t workspace_bytes, seunet_stream_t s);
+int seunet_mesh_smooth(const float* verts, long long nverts, const int* indptr, const int* indices, const unsigned char* boundary,
+                       int n_iter, float relaxation_factor, float* out, float* tmp, seunet_stream_t s);
+int seunet_mesh_affine(const float* verts, long long nverts, const float* centre, const float* scale, float* out, seunet_stream_t s);
+int seunet_mesh_stl_records(const float* verts, long long nverts, const int* faces, long long nfaces, const float* centre,
+                            const float* scale, unsigned char* records, int* status_dev, seunet_stream_t s);
+
 /* ---- CT preprocessing: preprocessing.py:26-130 with util.py:95-152 -----------------------------
  * CT volumes are int16, C-contiguous (h, w, z) on the device (the reference's orientation after its transposes), fewer than 2^31
  * voxels; masks are bytes, non-zero = 1.

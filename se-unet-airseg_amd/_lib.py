@@ -148,6 +148,15 @@ PROTOTYPES = {
     "seunet_fill_holes": (_i, [_vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "seunet_slice_moments": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "seunet_scatter_labels": (_i, [_vp, _vp, _ll, _ll, _vp, _vp, _vp, _vp]),
+    "seunet_mesh_workspace_bytes": (_sz, [_i, _i, _i]),
+    "seunet_mesh_count": (_i, [_vp, _i, _i, _i, C.POINTER(_ll), C.POINTER(_ll), _vp, _sz, _vp]),
+    "seunet_mesh_emit": (_i, [_i, _i, _i, _d, _ll, _ll, _vp, _vp, _vp, _sz, _vp]),
+    "seunet_mesh_coord_sums": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "seunet_mesh_adjacency_workspace_bytes": (_sz, [_ll, _ll]),
+    "seunet_mesh_adjacency": (_i, [_vp, _ll, _ll, _vp, _vp, _ll, _vp, _vp, _vp, _sz, _vp]),
+    "seunet_mesh_smooth": (_i, [_vp, _ll, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp]),
+    "seunet_mesh_affine": (_i, [_vp, _ll, C.POINTER(_f), C.POINTER(_f), _vp, _vp]),
+    "seunet_mesh_stl_records": (_i, [_vp, _ll, _vp, _ll, C.POINTER(_f), C.POINTER(_f), _vp, _vp, _vp]),
     "seunet_adamw_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _i, _i, _vp]),
     "seunet_net_param_count": (_i, [C.POINTER(NetDesc)]),
     "seunet_net_param_info": (_i, [C.POINTER(NetDesc), _i, C.c_char_p, _i, _ip, _ip]),

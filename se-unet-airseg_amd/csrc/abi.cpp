@@ -30,7 +30,7 @@ int seunet_debug_upsample2_form(int dtype, int c, seunet_dims dims, int backward
 
 // diagnostic hook (not part of the public header, host only): the workspace layout of a volume operation as its launcher
 // carves it.  op: 0 cc, 1 get_l, 2 edt, 3 lib_weight, 4 break_weight, 5 skeleton_branches, 6 dti, 7 skeleton, 8 parse_assign,
-// 9 binary_morph.
+// 9 binary_morph, 10 mesh.
 // Returns the number of sub-buffers (0: extents the op rejects, -1: no such op) and writes (offset, bytes up to the next
 // sub-buffer or the end) of the first `cap`.
 int seunet_debug_volume_layout(int op, int n0, int n1, int n2, size_t* offsets, int cap) {
@@ -49,6 +49,7 @@ int seunet_debug_volume_layout(int op, int n0, int n1, int n2, size_t* offsets, 
     case 6: dti_ws(c, n0, n1, n2); break;
     case 7: if (!skeleton_ws(c, n0, n1, n2)) return 0; break;
     case 9: morph_ws(c, n0, n1, n2); break;
+    case 10: if ((long long)n0 * n1 * n2 >= (1ll << 31)) return 0; mesh_ws(c, n0, n1, n2); break;
     default: return -1;
   }
   if (c.taken > c.log_cap) return -1;
@@ -483,6 +484,45 @@ int seunet_slice_moments(const unsigned char* mask, int n0, int n1, int n2, int 
 int seunet_scatter_labels(const long long* lin_index_dev, const int* value_dev, long long m, long long n, int* cd,
                           unsigned char* skeleton_parse, int* status_dev, seunet_stream_t s) {
   return launch_scatter_labels(lin_index_dev, value_dev, m, n, cd, skeleton_parse, status_dev, S(s));
+}
+
+size_t seunet_mesh_workspace_bytes(int n0, int n1, int n2) {
+  if (volume_check("mesh_workspace_bytes", n0, n1, n2, 0)) return 0;
+  return mesh_workspace_bytes(n0, n1, n2);
+}
+int seunet_mesh_count(const unsigned char* volume, int n0, int n1, int n2, long long* nverts, long long* nfaces, void* workspace,
+                      size_t workspace_bytes, seunet_stream_t s) {
+  return launch_mesh_count(volume, n0, n1, n2, nverts, nfaces, workspace, workspace_bytes, S(s));
+}
+int seunet_mesh_emit(int n0, int n1, int n2, double level, long long nverts, long long nfaces, float* verts, int* faces,
+                     const void* workspace, size_t workspace_bytes, seunet_stream_t s) {
+  return launch_mesh_emit(n0, n1, n2, level, nverts, nfaces, verts, faces, workspace, workspace_bytes, S(s));
+}
+int seunet_mesh_coord_sums(const unsigned char* mask, int n0, int n1, int n2, long long* sums_dev, seunet_stream_t s) {
+  return launch_mesh_coord_sums(mask, n0, n1, n2, sums_dev, S(s));
+}
+size_t seunet_mesh_adjacency_workspace_bytes(long long nverts, long long nfaces) {
+  if (nverts < 0 || nfaces < 0 || nverts > 0x7ffffffell || 6 * nfaces > 0x7fffffffll) {
+    fail("mesh_adjacency_workspace_bytes: bad sizes (%lld vertices, %lld faces)", nverts, nfaces);
+    return 0;
+  }
+  return mesh_adjacency_workspace_bytes(nverts, nfaces);
+}
+int seunet_mesh_adjacency(const int* faces, long long nfaces, long long nverts, int* indptr, int* indices, long long indices_capacity,
+                          unsigned char* boundary, int* status_dev, void* workspace, size_t workspace_bytes, seunet_stream_t s) {
+  return launch_mesh_adjacency(faces, nfaces, nverts, indptr, indices, indices_capacity, boundary, status_dev, workspace, workspace_bytes,
+                               S(s));
+}
+int seunet_mesh_smooth(const float* verts, long long nverts, const int* indptr, const int* indices, const unsigned char* boundary,
+                       int n_iter, float relaxation_factor, float* out, float* tmp, seunet_stream_t s) {
+  return launch_mesh_smooth(verts, nverts, indptr, indices, boundary, n_iter, relaxation_factor, out, tmp, S(s));
+}
+int seunet_mesh_affine(const float* verts, long long nverts, const float* centre, const float* scale, float* out, seunet_stream_t s) {
+  return launch_mesh_affine(verts, nverts, centre, scale, out, S(s));
+}
+int seunet_mesh_stl_records(const float* verts, long long nverts, const int* faces, long long nfaces, const float* centre,
+                            const float* scale, unsigned char* records, int* status_dev, seunet_stream_t s) {
+  return launch_mesh_stl_records(verts, nverts, faces, nfaces, centre, scale, records, status_dev, S(s));
 }
 
 int seunet_value_counts(const short* ct, long long n, int shift, unsigned int* counts, seunet_stream_t s) {

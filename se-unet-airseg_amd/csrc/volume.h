@@ -1,4 +1,4 @@
-// Shared layer of the volume operations (components.hip, lung.hip, edt.hip, parse.hip, skeleton.hip, dti.hip, morph.hip): their launcher
+// Shared layer of the volume operations (components.hip, lung.hip, edt.hip, parse.hip, skeleton.hip, dti.hip, morph.hip, mesh.hip): their launcher
 // prototypes, ONE workspace layout per operation, the extent check and the voxel / wave helpers their kernels share.
 //
 // Workspace contract: every operation has a layout struct filled by one function that walks a WsCarver.  Over a null base
@@ -251,6 +251,48 @@ static inline DtiWs dti_ws(WsCarver& c, int h, int w, int z) {
 size_t dti_workspace_bytes(int h, int w, int z);
 int launch_dti(const double* pred, int h, int w, int z, double h_thresh, double l_thresh, int pred_dtype, unsigned char* out,
                void* workspace, size_t ws_bytes, hipStream_t s);
+
+// ---- surface meshing (mesh.hip): extraction, vertex adjacency, smoothing, affine step, STL records ---------------------------
+struct MeshRec { u64 nverts, nfaces; };   // the totals the host reads once
+struct MeshWs {
+  MeshRec* rec;
+  u64* bits;                      // the packed volume; rows of ceil(n2 / 64) words, no padding
+  u64 *a0, *a1, *a2;              // per word: the voxels that own a vertex along axis 0, 1, 2
+  unsigned *vcnt, *fcnt;          // per word: vertices and triangles, then their exclusive scan inside a block of 1024 words
+  unsigned *vblk, *fblk;          // per block: its total, then the exclusive scan of the totals
+};
+static inline MeshWs mesh_ws(WsCarver& c, int n0, int n1, int n2) {
+  const size_t words = (size_t)n0 * n1 * ((n2 + 63) / 64), blocks = (words + 1023) / 1024;
+  return MeshWs{c.take<MeshRec>(1), c.take<u64>(words), c.take<u64>(words), c.take<u64>(words), c.take<u64>(words),
+                c.take<unsigned>(words), c.take<unsigned>(words), c.take<unsigned>(blocks), c.take<unsigned>(blocks)};
+}
+struct MeshAdjWs {
+  u64* total;                     // the scan's grand total (two slots)
+  unsigned* deg;                  // V + 1: list lengths, then the fill cursors, then the lengths without repeats
+  unsigned* rawptr;               // V + 1: start of every vertex's list in raw
+  unsigned* raw;                  // 6 F: (neighbour << 1) | arrives, later the sorted neighbours at the front of each list
+  unsigned* blk;                  // block totals of the scans
+};
+static inline MeshAdjWs mesh_adj_ws(WsCarver& c, long long nverts, long long nfaces) {
+  const size_t v1 = (size_t)nverts + 1;
+  return MeshAdjWs{c.take<u64>(2), c.take<unsigned>(v1), c.take<unsigned>(v1), c.take<unsigned>((size_t)nfaces * 6),
+                   c.take<unsigned>((v1 + 1023) / 1024)};
+}
+size_t mesh_workspace_bytes(int n0, int n1, int n2);
+size_t mesh_adjacency_workspace_bytes(long long nverts, long long nfaces);
+// count: pack, count, scan; synchronises once to return the totals.  emit: verts (V, 3) and faces (F, 3) from the same workspace.
+int launch_mesh_count(const unsigned char* vol, int n0, int n1, int n2, long long* nverts, long long* nfaces, void* workspace,
+                      size_t ws_bytes, hipStream_t s);
+int launch_mesh_emit(int n0, int n1, int n2, double level, long long nverts, long long nfaces, float* verts, int* faces,
+                     const void* workspace, size_t ws_bytes, hipStream_t s);
+int launch_mesh_coord_sums(const unsigned char* mask, int n0, int n1, int n2, long long* sums_dev, hipStream_t s);
+int launch_mesh_adjacency(const int* faces, long long nfaces, long long nverts, int* indptr, int* indices, long long capacity,
+                          unsigned char* boundary, int* status_dev, void* workspace, size_t ws_bytes, hipStream_t s);
+int launch_mesh_smooth(const float* verts, long long nverts, const int* indptr, const int* indices, const unsigned char* boundary,
+                       int n_iter, float relaxation, float* out, float* tmp, hipStream_t s);
+int launch_mesh_affine(const float* verts, long long nverts, const float* centre, const float* scale, float* out, hipStream_t s);
+int launch_mesh_stl_records(const float* verts, long long nverts, const int* faces, long long nfaces, const float* centre,
+                            const float* scale, unsigned char* records, int* status_dev, hipStream_t s);
 
 // ---- device helpers -------------------------------------------------------------------------------------------------------
 // raster index -> coordinates of an (n0, n1, n2) volume (n0 is not needed)
