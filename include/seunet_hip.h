@@ -515,6 +515,33 @@ int seunet_mesh_affine(const float* verts, long long nverts, const float* centre
 int seunet_mesh_stl_records(const float* verts, long long nverts, const int* faces, long long nfaces, const float* centre,
                             const float* scale, unsigned char* records, int* status_dev, seunet_stream_t s);
 
+/* ---- labelled surface meshing: ours_skel_parse.py:1101-1152, tree_parsing.py:167-196 -----------------
+ * An int32 label volume (C-contiguous (n0, n1, n2), values 0 .. num, num <= 65535, fewer than 2^31 voxels) to the meshes of all
+ * its labels in one extraction.  The mesh of label k is, bit for bit and index for index, what seunet_mesh_count / seunet_mesh_emit
+ * give for the mask "label == k"; the result is their concatenation for k = 1 .. num: verts float32 (V, 3), faces int32 (F, 3)
+ * indexing the concatenated verts, and vert_ptr / face_ptr with label k owning verts[vert_ptr[k-1] .. vert_ptr[k]) and
+ * faces[face_ptr[k-1] .. face_ptr[k]).  A grid edge between two different non-zero labels carries two vertices, one per label.
+ * Every result is deterministic and equals tests/mesh_label_oracle.py.  No launch, pass or synchronisation is per label.
+ *
+ * seunet_mesh_label_count: checks the labels, counts, scans.  num = the number of labels, or -1 for the largest label present.
+ *   *nverts, *nfaces, *num_used, *status (all HOST) receive V, F, the num in force and 0 or a sum of 1 (a negative label) and 2
+ *   (a label above num, or above 65535 with num = -1); with a non-zero status the other results mean nothing and
+ *   seunet_mesh_label_emit must not follow.  This call synchronises the stream once, to read those four numbers.  vert_ptr_dev,
+ *   face_ptr_dev: ptr_capacity device int64 each, ptr_capacity >= num + 1 (65536 with num = -1); entries 0 .. num_used are the
+ *   pointers above, left on the device for the caller to read.  workspace: seunet_mesh_label_workspace_bytes(n0, n1, n2),
+ *   caller-owned, handed unchanged to seunet_mesh_label_emit.  A volume with an extent of 1 has no cells: V = F = 0, pointers 0.
+ * seunet_mesh_label_emit: writes verts and faces with the num_used / nverts / nfaces the count call returned and the same labels
+ *   and workspace; level as in seunet_mesh_emit.  The label order comes from a stable radix sort of (label, raster index) in
+ *   sort_workspace: seunet_mesh_label_sort_bytes(nverts, nfaces), caller-owned.  V or 3 F beyond the int32 range is an error. */
+size_t seunet_mesh_label_workspace_bytes(int n0, int n1, int n2);
+size_t seunet_mesh_label_sort_bytes(long long nverts, long long nfaces);
+int seunet_mesh_label_count(const int* labels, int n0, int n1, int n2, int num, long long* nverts, long long* nfaces, int* num_used,
+                            int* status, long long* vert_ptr_dev, long long* face_ptr_dev, int ptr_capacity, void* workspace,
+                            size_t workspace_bytes, seunet_stream_t s);
+int seunet_mesh_label_emit(const int* labels, int n0, int n1, int n2, int num, double level, long long nverts, long long nfaces,
+                           float* verts, int* faces, const void* workspace, size_t workspace_bytes, void* sort_workspace,
+                           size_t sort_bytes, seunet_stream_t s);
+
 /* ---- CT preprocessing: preprocessing.py:26-130 with util.py:95-152 -----------------------------
  * CT volumes are int16, C-contiguous (h, w, z) on the device (the reference's orientation after its transposes), fewer than 2^31
  * voxels; masks are bytes, non-zero = 1.

@@ -13,7 +13,8 @@ from .pipeline import (AirwayHMData3GPU, AirwayHMDataGPU, CropSegDataGPU, aug_co
 from .prep import (CandidateSet, airway_parse, binary_closing, binary_dilation, binary_erosion, binary_fill_holes, break_weight,
                    distance_transform_edt, hard_mining_candidates, label_adjacency, lib_weight, relabel, skeleton_parsing, skeletonize_3d,
                    tree_parsing, tree_parsing_func)
-from .mesh import marching_cubes, mesh_adjacency, prediction_mesh, smooth_mesh, stl_records, transform_mesh, write_stl
+from .mesh import (LabelMeshes, branch_meshes, label_meshes, marching_cubes, mesh_adjacency, prediction_mesh, smooth_mesh, stl_records,
+                   transform_mesh, write_stl)
 from .preprocess import cut_mask, get_l, large_connected_domain26, preprocess_ct, th_2t
 from .postprocess import (MetricSums, double_threshold_iteration, evaluation_case, largest_component, maximum_3d,
                           postprocess_prediction, zero_borders)
@@ -27,4 +28,5 @@ __all__ = ["SE_UNet", "SSEConv", "SSEConv2", "CATConv", "DropLayer", "get_model"
            "evaluation_case", "MetricSums", "CandidateSet", "distance_transform_edt", "hard_mining_candidates", "lib_weight",
            "break_weight", "skeletonize_3d", "skeleton_parsing", "tree_parsing_func", "label_adjacency", "tree_parsing", "relabel", "airway_parse", "binary_dilation",
            "binary_erosion", "binary_closing", "binary_fill_holes", "preprocess_ct", "th_2t", "get_l", "large_connected_domain26", "cut_mask",
-           "marching_cubes", "smooth_mesh", "write_stl", "prediction_mesh", "mesh_adjacency", "stl_records", "transform_mesh"]
+           "marching_cubes", "smooth_mesh", "write_stl", "prediction_mesh", "mesh_adjacency", "stl_records", "transform_mesh",
+           "label_meshes", "branch_meshes", "LabelMeshes"]

@@ -30,12 +30,12 @@ int seunet_debug_upsample2_form(int dtype, int c, seunet_dims dims, int backward
 
 // diagnostic hook (not part of the public header, host only): the workspace layout of a volume operation as its launcher
 // carves it.  op: 0 cc, 1 get_l, 2 edt, 3 lib_weight, 4 break_weight, 5 skeleton_branches, 6 dti, 7 skeleton, 8 parse_assign,
-// 9 binary_morph, 10 mesh.
+// 9 binary_morph, 10 mesh, 11 mesh_label.
 // Returns the number of sub-buffers (0: extents the op rejects, -1: no such op) and writes (offset, bytes up to the next
 // sub-buffer or the end) of the first `cap`.
 int seunet_debug_volume_layout(int op, int n0, int n1, int n2, size_t* offsets, int cap) {
   if (n0 < 1 || n1 < 1 || n2 < 1) return 0;
-  size_t at[16];                       // no operation has more than 9 sub-buffers
+  size_t at[16];                       // no operation has more than 14 sub-buffers
   WsCarver c(nullptr);
   c.log = at;
   c.log_cap = 16;
@@ -50,6 +50,7 @@ int seunet_debug_volume_layout(int op, int n0, int n1, int n2, size_t* offsets, 
     case 7: if (!skeleton_ws(c, n0, n1, n2)) return 0; break;
     case 9: morph_ws(c, n0, n1, n2); break;
     case 10: if ((long long)n0 * n1 * n2 >= (1ll << 31)) return 0; mesh_ws(c, n0, n1, n2); break;
+    case 11: if ((long long)n0 * n1 * n2 >= (1ll << 31)) return 0; mesh_label_ws(c, n0, n1, n2); break;
     default: return -1;
   }
   if (c.taken > c.log_cap) return -1;
@@ -497,6 +498,29 @@ int seunet_mesh_count(const unsigned char* volume, int n0, int n1, int n2, long 
 int seunet_mesh_emit(int n0, int n1, int n2, double level, long long nverts, long long nfaces, float* verts, int* faces,
                      const void* workspace, size_t workspace_bytes, seunet_stream_t s) {
   return launch_mesh_emit(n0, n1, n2, level, nverts, nfaces, verts, faces, workspace, workspace_bytes, S(s));
+}
+size_t seunet_mesh_label_workspace_bytes(int n0, int n1, int n2) {
+  if (volume_check("mesh_label_workspace_bytes", n0, n1, n2, 0)) return 0;
+  return mesh_label_workspace_bytes(n0, n1, n2);
+}
+size_t seunet_mesh_label_sort_bytes(long long nverts, long long nfaces) {
+  if (nverts < 0 || nfaces < 0 || nverts > 0x7fffffffll || 3 * nfaces > 0x7fffffffll) {
+    fail("mesh_label_sort_bytes: bad sizes (%lld vertices, %lld faces)", nverts, nfaces);
+    return 0;
+  }
+  return mesh_label_sort_bytes(nverts, nfaces);
+}
+int seunet_mesh_label_count(const int* labels, int n0, int n1, int n2, int num, long long* nverts, long long* nfaces, int* num_used,
+                            int* status, long long* vert_ptr_dev, long long* face_ptr_dev, int ptr_capacity, void* workspace,
+                            size_t workspace_bytes, seunet_stream_t s) {
+  return launch_mesh_label_count(labels, n0, n1, n2, num, nverts, nfaces, num_used, status, vert_ptr_dev, face_ptr_dev, ptr_capacity,
+                                 workspace, workspace_bytes, S(s));
+}
+int seunet_mesh_label_emit(const int* labels, int n0, int n1, int n2, int num, double level, long long nverts, long long nfaces,
+                           float* verts, int* faces, const void* workspace, size_t workspace_bytes, void* sort_workspace,
+                           size_t sort_bytes, seunet_stream_t s) {
+  return launch_mesh_label_emit(labels, n0, n1, n2, num, level, nverts, nfaces, verts, faces, workspace, workspace_bytes,
+                                sort_workspace, sort_bytes, S(s));
 }
 int seunet_mesh_coord_sums(const unsigned char* mask, int n0, int n1, int n2, long long* sums_dev, seunet_stream_t s) {
   return launch_mesh_coord_sums(mask, n0, n1, n2, sums_dev, S(s));

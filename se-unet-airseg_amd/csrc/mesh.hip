@@ -139,8 +139,6 @@ mesh_count_kernel(const u64* __restrict__ bits, MeshGeom g, u64* __restrict__ a0
   }
 }
 
-constexpr int kScanBlock = 1024;                              // elements per workgroup of the block scan: 256 threads x 4
-
 // Exclusive scan of every block of kScanBlock elements in place; the block's total to blk.  `b` / `blk_b`: a second array scanned
 // in the same launch (null: none).
 __global__ void __launch_bounds__(256)
@@ -219,6 +217,9 @@ scan_add_kernel(const unsigned* __restrict__ a, const unsigned* __restrict__ blk
   else if (i == n) out[n] = (unsigned)total[0];
 }
 
+}  // namespace
+
+// declared in volume.h: mesh_label.hip scans with it too
 int run_scan(unsigned* a, unsigned* b, long long n, unsigned* blk_a, unsigned* blk_b, u64* total, hipStream_t s) {
   const long long nb = (n + kScanBlock - 1) / kScanBlock;
   if (nb > 0) scan_block_kernel<<<(unsigned)nb, 256, 0, s>>>(a, b, n, blk_a, blk_b);
@@ -226,6 +227,8 @@ int run_scan(unsigned* a, unsigned* b, long long n, unsigned* blk_a, unsigned* b
   SEUNET_LAUNCH_CHECK();
   return 0;
 }
+
+namespace {
 
 struct EmitArgs {
   const u64 *bits, *a0s, *a1s, *a2s;

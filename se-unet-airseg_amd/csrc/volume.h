@@ -1,4 +1,4 @@
-// Shared layer of the volume operations (components.hip, lung.hip, edt.hip, parse.hip, skeleton.hip, dti.hip, morph.hip, mesh.hip): their launcher
+// Shared layer of the volume operations (components.hip, lung.hip, edt.hip, parse.hip, skeleton.hip, dti.hip, morph.hip, mesh.hip, mesh_label.hip): their launcher
 // prototypes, ONE workspace layout per operation, the extent check and the voxel / wave helpers their kernels share.
 //
 // Workspace contract: every operation has a layout struct filled by one function that walks a WsCarver.  Over a null base
@@ -278,6 +278,11 @@ static inline MeshAdjWs mesh_adj_ws(WsCarver& c, long long nverts, long long nfa
   return MeshAdjWs{c.take<u64>(2), c.take<unsigned>(v1), c.take<unsigned>(v1), c.take<unsigned>((size_t)nfaces * 6),
                    c.take<unsigned>((v1 + 1023) / 1024)};
 }
+// Exclusive scan of a (and b, null: none) over n elements (mesh.hip): in place inside blocks of kScanBlock elements, the blocks'
+// totals to blk_a / blk_b and scanned there, the grand totals in 64 bits to total[0] / total[1].  Element i's scan value is
+// a[i] + blk_a[i / kScanBlock].  No atomics.
+constexpr int kScanBlock = 1024;          // elements per workgroup of the block scan: 256 threads x 4
+int run_scan(unsigned* a, unsigned* b, long long n, unsigned* blk_a, unsigned* blk_b, u64* total, hipStream_t s);
 size_t mesh_workspace_bytes(int n0, int n1, int n2);
 size_t mesh_adjacency_workspace_bytes(long long nverts, long long nfaces);
 // count: pack, count, scan; synchronises once to return the totals.  emit: verts (V, 3) and faces (F, 3) from the same workspace.
@@ -293,6 +298,56 @@ int launch_mesh_smooth(const float* verts, long long nverts, const int* indptr, 
 int launch_mesh_affine(const float* verts, long long nverts, const float* centre, const float* scale, float* out, hipStream_t s);
 int launch_mesh_stl_records(const float* verts, long long nverts, const int* faces, long long nfaces, const float* centre,
                             const float* scale, unsigned char* records, int* status_dev, hipStream_t s);
+
+// ---- labelled surface meshing (mesh_label.hip): every label's mesh of an int32 label volume in one extraction ----------------
+constexpr int kMeshLabelMax = 65535;      // labels are 16-bit sort keys: two radix digits
+struct MeshLabelRec { u64 nverts, nfaces; int max_label, status; };   // what the host reads once; status: 1 negative, 2 too large
+struct MeshLabelWs {
+  MeshLabelRec* rec;
+  u64 *vb0, *vb1, *vb2;           // per word: bit planes of the vertex count (0 .. 6) of each of its voxels
+  unsigned *vcnt, *fcnt;          // per word: vertex and triangle items, then their exclusive scan inside a block of 1024 words
+  unsigned char* active;          // per word: 1 where the word has an item at all; the emit passes leave the others at once
+  unsigned *vblk, *fblk;          // per block: its total, then the exclusive scan of the totals
+  unsigned *vhist, *fhist;        // kMeshLabelMax + 1 each: items per label, then their exclusive scan inside a block
+  unsigned *hvblk, *hfblk;        // the block totals of the two label scans
+  u64* htotal;                    // their grand totals (two slots)
+};
+static inline MeshLabelWs mesh_label_ws(WsCarver& c, int n0, int n1, int n2) {
+  const size_t words = (size_t)n0 * n1 * ((n2 + 63) / 64), blocks = (words + kScanBlock - 1) / kScanBlock;
+  const size_t labels = kMeshLabelMax + 1, label_blocks = labels / kScanBlock;
+  return MeshLabelWs{c.take<MeshLabelRec>(1), c.take<u64>(words), c.take<u64>(words), c.take<u64>(words),
+                     c.take<unsigned>(words), c.take<unsigned>(words), c.take<unsigned char>(words), c.take<unsigned>(blocks),
+                     c.take<unsigned>(blocks), c.take<unsigned>(labels), c.take<unsigned>(labels), c.take<unsigned>(label_blocks),
+                     c.take<unsigned>(label_blocks), c.take<u64>(2)};
+}
+// what the label sort of the emit call needs besides: sized by the totals the count call returned
+constexpr int kSortBlock = 1024;          // items per workgroup of a radix pass: 4 waves x 4 rounds x 64 lanes
+struct MeshLabelSortWs {
+  u64* total;                     // the scan's grand total (two slots, not read)
+  unsigned *vperm, *fperm;        // V / F: position of every raster-order item in label-major order
+  unsigned short *vkey, *fkey;    // V / F: the label of every raster-order item
+  unsigned short* key2;           // max(V, F): keys after the first of two passes
+  unsigned* idx2;                 //            and the raster index they came from
+  unsigned* hist;                 // 256 digits x sort blocks, digit-major; scanned in place
+  unsigned* hblk;                 // block totals of that scan
+};
+static inline MeshLabelSortWs mesh_label_sort_ws(WsCarver& c, long long nverts, long long nfaces) {
+  const size_t v = (size_t)nverts, f = (size_t)nfaces, m = std::max(v, f);
+  const size_t bins = 256 * ((m + kSortBlock - 1) / kSortBlock);
+  return MeshLabelSortWs{c.take<u64>(2), c.take<unsigned>(v), c.take<unsigned>(f), c.take<unsigned short>(v),
+                         c.take<unsigned short>(f), c.take<unsigned short>(m), c.take<unsigned>(m), c.take<unsigned>(bins),
+                         c.take<unsigned>((bins + kScanBlock - 1) / kScanBlock)};
+}
+size_t mesh_label_workspace_bytes(int n0, int n1, int n2);
+size_t mesh_label_sort_bytes(long long nverts, long long nfaces);
+// count: label check, count, scans; synchronises once to return the totals, the label count and the status.  vert_ptr_dev /
+// face_ptr_dev: ptr_capacity device int64 each, entry k = items of the labels 1 .. k.  emit: verts and faces in label order.
+int launch_mesh_label_count(const int* labels, int n0, int n1, int n2, int num, long long* nverts, long long* nfaces, int* num_used,
+                            int* status, long long* vert_ptr_dev, long long* face_ptr_dev, int ptr_capacity, void* workspace,
+                            size_t ws_bytes, hipStream_t s);
+int launch_mesh_label_emit(const int* labels, int n0, int n1, int n2, int num, double level, long long nverts, long long nfaces,
+                           float* verts, int* faces, const void* workspace, size_t ws_bytes, void* sort_workspace, size_t sort_bytes,
+                           hipStream_t s);
 
 // ---- device helpers -------------------------------------------------------------------------------------------------------
 // raster index -> coordinates of an (n0, n1, n2) volume (n0 is not needed)

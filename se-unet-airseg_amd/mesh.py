@@ -10,19 +10,23 @@ interior cases differ) and the smoothing is ``n_iter`` Jacobi sweeps with fixed 
 boundary handling are not reproduced).  Equality with skimage or VTK is not claimed; every result equals tests/mesh_oracle.py bit
 for bit and is deterministic.
 
+``label_meshes`` / ``branch_meshes`` (csrc/mesh_label.hip) make the meshes of all the labels of a ``parsing``
+volume in one extraction -- the per-branch models of the reference's tree tools (ours_skel_parse.py:1101-1152) -- each label's
+mesh bit for bit ``marching_cubes(parsing == k)``; tests/mesh_label_oracle.py states the concatenation.
+
 CUDA tensors in -> CUDA tensors out, numpy arrays in -> numpy arrays out; there is no CPU path."""
 from __future__ import annotations
 
 import ctypes as C
 import struct
-from typing import Optional, Sequence, Tuple
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib
 from ._volume import mask_in, out as _out, read_status, workspace
-from .prep import _vol, skeletonize_3d
+from .prep import _labels_in, _vol, skeletonize_3d
 
 _PREFIX = "seunet mesh"
 
@@ -104,6 +108,104 @@ def marching_cubes(volume, level: float = 0.95):
             _lib.check(lib.seunet_mesh_emit(n0, n1, n2, level, nv.value, nf.value, verts.data_ptr(), faces.data_ptr(), ws.data_ptr(),
                                             ws.numel(), _lib.stream_ptr()), "mesh_emit")
     return _out(verts, as_numpy), _out(faces, as_numpy)
+
+
+# ---- every label's mesh of a parsing volume ----------------------------------------------------------------------------------------
+
+MAX_LABELS = 65535
+_INT32_MAX = 2 ** 31 - 1
+
+
+class LabelMeshes(NamedTuple):
+    """The meshes of the labels 1 .. num, concatenated in label order: label k owns ``verts[vert_ptr[k-1]:vert_ptr[k]]`` and
+    ``faces[face_ptr[k-1]:face_ptr[k]]``; ``faces`` index the concatenated ``verts``.  ``vert_ptr`` / ``face_ptr``: host numpy
+    int64 of length num + 1."""
+    verts: object
+    faces: object
+    vert_ptr: np.ndarray
+    face_ptr: np.ndarray
+
+    @property
+    def num(self) -> int:
+        return len(self.vert_ptr) - 1
+
+    def mesh(self, k: int):
+        """``(verts_k, faces_k)`` of label k (1 .. num), the faces indexing ``verts_k``: what ``marching_cubes(parsing == k)``
+        gives.  Slices, no copy of the vertices."""
+        k = int(k)
+        if not 1 <= k <= self.num:
+            raise IndexError(f"{_PREFIX}: label {k} outside 1 .. {self.num}")
+        v0, v1 = int(self.vert_ptr[k - 1]), int(self.vert_ptr[k])
+        f0, f1 = int(self.face_ptr[k - 1]), int(self.face_ptr[k])
+        faces = self.faces[f0:f1]
+        return self.verts[v0:v1], (faces - np.int32(v0) if isinstance(faces, np.ndarray) else faces - v0)
+
+
+def label_meshes(parsing, num: Optional[int] = None, level: float = 0.95) -> LabelMeshes:
+    """The mesh of every label of an integer label volume (CUDA tensor int32 / int64 / int16 / uint8 or numpy array of any integer
+    dtype, shape (n0, n1, n2), values 0 .. num, 0 = background; non-contiguous is fine) in one extraction: label k's mesh is
+    bit for bit ``marching_cubes(parsing == k, level)``, and the result is their concatenation for k = 1 .. ``num`` (see
+    ``LabelMeshes``).  ``num=None``: the largest label present, found on the device.  A grid edge between two different non-zero
+    labels carries one vertex for each of them.  A label without voxels, a volume with an extent of 1 and a volume without labels
+    give empty slices.  ValueError: a negative label, a label above an explicit ``num``, more than 65535 labels, ``V`` or ``3 F``
+    beyond int32.  The sizes and the two pointer arrays are read after the call's one synchronise."""
+    level = _level(level)
+    if num is not None:
+        num = int(num)
+        if not 0 <= num <= MAX_LABELS:
+            raise ValueError(f"{_PREFIX}: label_meshes: num must lie in 0 .. {MAX_LABELS}, got {num}")
+    lab, as_numpy = _labels_in(parsing, "parsing")
+    n0, n1, n2 = (int(v) for v in lab.shape)
+    dev = lab.device
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        if lab.numel() == 0:
+            n = num or 0
+            empty = LabelMeshes(torch.empty((0, 3), dtype=torch.float32, device=dev), torch.empty((0, 3), dtype=torch.int32, device=dev),
+                                np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64))
+            return empty._replace(verts=_out(empty.verts, as_numpy), faces=_out(empty.faces, as_numpy))
+        cap = MAX_LABELS + 1 if num is None else num + 1
+        ptrs = torch.empty((2, cap), dtype=torch.int64, device=dev)
+        ws = workspace(lib.seunet_mesh_label_workspace_bytes, n0, n1, n2, device=dev, what=f"{_PREFIX}: label_meshes")
+        nv, nf, used, status = C.c_longlong(0), C.c_longlong(0), C.c_int(0), C.c_int(0)
+        _lib.check(lib.seunet_mesh_label_count(lab.data_ptr(), n0, n1, n2, -1 if num is None else num, C.byref(nv), C.byref(nf),
+                                               C.byref(used), C.byref(status), ptrs[0].data_ptr(), ptrs[1].data_ptr(), cap,
+                                               ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "mesh_label_count")
+        if status.value & 1:
+            raise ValueError(f"{_PREFIX}: label_meshes: `parsing` holds a negative label")
+        if status.value & 2:
+            raise ValueError(f"{_PREFIX}: label_meshes: `parsing` holds a label above " +
+                             (f"{MAX_LABELS}, the most labels one call takes" if num is None else f"num = {num}"))
+        V, F, n = nv.value, nf.value, used.value
+        if V > _INT32_MAX or 3 * F > _INT32_MAX:
+            raise ValueError(f"{_PREFIX}: label_meshes: {V} vertices / {F} faces: V or 3 F exceeds the int32 index range")
+        host_ptrs = ptrs[:, :n + 1].cpu().numpy()              # the stream is idle after the count call's synchronise
+        verts = torch.empty((V, 3), dtype=torch.float32, device=dev)
+        faces = torch.empty((F, 3), dtype=torch.int32, device=dev)
+        if V or F:
+            sort_ws = workspace(lib.seunet_mesh_label_sort_bytes, V, F, device=dev, what=f"{_PREFIX}: label_meshes")
+            _lib.check(lib.seunet_mesh_label_emit(lab.data_ptr(), n0, n1, n2, n, level, V, F, verts.data_ptr(), faces.data_ptr(),
+                                                  ws.data_ptr(), ws.numel(), sort_ws.data_ptr(), sort_ws.numel(), _lib.stream_ptr()),
+                       "mesh_label_emit")
+    return LabelMeshes(_out(verts, as_numpy), _out(faces, as_numpy), np.ascontiguousarray(host_ptrs[0]),
+                       np.ascontiguousarray(host_ptrs[1]))
+
+
+def branch_meshes(parsing, spacing=None, centre=None, num: Optional[int] = None, level: float = 0.95, smooth: bool = True,
+                  n_iter: int = 20, relaxation_factor: float = 0.15) -> LabelMeshes:
+    """The per-branch models of the reference's tree tool (ours_skel_parse.py:1110-1119, ``sub_model``) for all branches at once,
+    in its order of steps: ``label_meshes(parsing, num, level)``, ``transform_mesh(verts, centre, spacing)`` (``(v - centre) *
+    spacing``; the reference uses one centre ``o`` for the whole tree -- ``mean_coordinate`` gives it -- and both None is the
+    ATM'22 tool's variant without centring, tree_parsing.py:167-176), then ``smooth_mesh`` with the reference's relaxation factor
+    0.15.  The labels' meshes share no vertex, so the one smoothing call equals smoothing every label's mesh on its own bit for
+    bit.  ``write_stl(path, *meshes.mesh(k))`` writes one branch."""
+    m = label_meshes(parsing, num, level)
+    verts = m.verts
+    if centre is not None or spacing is not None:
+        verts = transform_mesh(verts, centre, spacing)
+    if smooth:
+        verts = smooth_mesh(verts, m.faces, n_iter, relaxation_factor)
+    return m._replace(verts=verts)
 
 
 # ---- adjacency and smoothing ----------------------------------------------------------------------------------------------------
