@@ -542,6 +542,32 @@ int seunet_mesh_label_emit(const int* labels, int n0, int n1, int n2, int num, d
                            float* verts, int* faces, const void* workspace, size_t workspace_bytes, void* sort_workspace,
                            size_t sort_bytes, seunet_stream_t s);
 
+/* ---- branch morphometry: the numbers per branch of a labelled airway tree ---------------------------
+ * The reference measures nothing per branch; the definition is this comment, restated in numpy by tests/morphometry_oracle.py.
+ * parsing: int32 label volume, C-contiguous (n0, n1, n2), values 0 .. num with 0 = background, fewer than 2^31 voxels,
+ * num <= seunet_label_stats_max_num() = 4095 (anything else: error).  skeleton: bytes, non-zero = set.  sqdist: the int32 squared
+ * distance of seunet_edt, or NULL: r2_sum, r2_min and r2_max keep their empty values then.  A labelled skeleton voxel is one with
+ * skeleton != 0 and 1 <= parsing <= num.  Integer work throughout: every output is deterministic and does not depend on the
+ * order in which the device executes anything.  No launch, pass or synchronisation is per label; nothing is allocated, no
+ * workspace is needed and the call does not synchronise the stream.
+ *
+ * seunet_branch_stats: device arrays indexed by label value 0 .. num, all written here (row 0 holds the empty values):
+ *   voxels int64[num + 1]: voxels with parsing == k.  coord_sum int64[num + 1][3]: the sums of i0, i1, i2 over them.  box_min,
+ *   box_max int32[num + 1][3]: their inclusive bounding box; a label without voxels has box_min = (n0, n1, n2), box_max = (-1, -1, -1).
+ *   skeleton_voxels int64[num + 1]: labelled skeleton voxels of label k.  links int64[num + 1][13]: counted links whose two ends both
+ *   carry label k, by offset class.  cross_links int64[num + 1][13]: counted links with one end of label k and the other end of a
+ *   different label >= 1; such a link is counted once in each of the two rows.  r2_sum int64[num + 1], r2_min / r2_max
+ *   int32[num + 1]: sum, minimum and maximum of sqdist over the labelled skeleton voxels of k; empty: 0, INT32_MAX, -1.
+ *   Links: the 13 offset classes are the offsets d of {-1, 0, 1}^3 lexicographically above (0, 0, 0) in ascending order (class 0 =
+ *   (0, 0, 1), class 1 = (0, 1, -1), ..., class 12 = (1, 1, 1)).  A pair (p, p + d) of labelled skeleton voxels inside the volume is
+ *   a counted link unless, for some proper non-empty subset of the non-zero components of d, p + (that part of d) is a labelled
+ *   skeleton voxel of any label: face links always count, an edge diagonal is dropped when one of its 2 intermediate voxels is
+ *   occupied, a corner diagonal when one of its 6 is.
+ *   status_dev (device int): 1 if a parsing value outside 0..num was met (that voxel is ignored everywhere), 0 otherwise. */
+int seunet_branch_stats(const int* parsing, const unsigned char* skeleton, const int* sqdist, int n0, int n1, int n2, int num,
+                        long long* voxels, long long* coord_sum, int* box_min, int* box_max, long long* skeleton_voxels, long long* links,
+                        long long* cross_links, long long* r2_sum, int* r2_min, int* r2_max, int* status_dev, seunet_stream_t s);
+
 /* ---- CT preprocessing: preprocessing.py:26-130 with util.py:95-152 -----------------------------
  * CT volumes are int16, C-contiguous (h, w, z) on the device (the reference's orientation after its transposes), fewer than 2^31
  * voxels; masks are bytes, non-zero = 1.

@@ -155,6 +155,7 @@ PROTOTYPES = {
     "seunet_mesh_label_sort_bytes": (_sz, [_ll, _ll]),
     "seunet_mesh_label_count": (_i, [_vp, _i, _i, _i, _i, C.POINTER(_ll), C.POINTER(_ll), _ip, _ip, _vp, _vp, _i, _vp, _sz, _vp]),
     "seunet_mesh_label_emit": (_i, [_vp, _i, _i, _i, _i, _d, _ll, _ll, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "seunet_branch_stats": (_i, [_vp, _vp, _vp, _i, _i, _i, _i] + [_vp] * 11 + [_vp]),
     "seunet_mesh_coord_sums": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "seunet_mesh_adjacency_workspace_bytes": (_sz, [_ll, _ll]),
     "seunet_mesh_adjacency": (_i, [_vp, _ll, _ll, _vp, _vp, _ll, _vp, _vp, _vp, _sz, _vp]),

@@ -522,6 +522,14 @@ int seunet_mesh_label_emit(const int* labels, int n0, int n1, int n2, int num, d
   return launch_mesh_label_emit(labels, n0, n1, n2, num, level, nverts, nfaces, verts, faces, workspace, workspace_bytes,
                                 sort_workspace, sort_bytes, S(s));
 }
+int seunet_branch_stats(const int* parsing, const unsigned char* skeleton, const int* sqdist, int n0, int n1, int n2, int num,
+                        long long* voxels, long long* coord_sum, int* box_min, int* box_max, long long* skeleton_voxels, long long* links,
+                        long long* cross_links, long long* r2_sum, int* r2_min, int* r2_max, int* status_dev, seunet_stream_t s) {
+  return launch_branch_stats(parsing, skeleton, sqdist, n0, n1, n2, num,
+                             BranchStatsOut{voxels, coord_sum, box_min, box_max, skeleton_voxels, links, cross_links, r2_sum, r2_min,
+                                            r2_max, status_dev},
+                             S(s));
+}
 int seunet_mesh_coord_sums(const unsigned char* mask, int n0, int n1, int n2, long long* sums_dev, seunet_stream_t s) {
   return launch_mesh_coord_sums(mask, n0, n1, n2, sums_dev, S(s));
 }

@@ -1,4 +1,4 @@
-// Shared layer of the volume operations (components.hip, lung.hip, edt.hip, parse.hip, skeleton.hip, dti.hip, morph.hip, mesh.hip, mesh_label.hip): their launcher
+// Shared layer of the volume operations (components.hip, lung.hip, edt.hip, parse.hip, skeleton.hip, dti.hip, morph.hip, mesh.hip, mesh_label.hip, morphometry.hip): their launcher
 // prototypes, ONE workspace layout per operation, the extent check and the voxel / wave helpers their kernels share.
 //
 // Workspace contract: every operation has a layout struct filled by one function that walks a WsCarver.  Over a null base
@@ -348,6 +348,19 @@ int launch_mesh_label_count(const int* labels, int n0, int n1, int n2, int num, 
 int launch_mesh_label_emit(const int* labels, int n0, int n1, int n2, int num, double level, long long nverts, long long nfaces,
                            float* verts, int* faces, const void* workspace, size_t ws_bytes, void* sort_workspace, size_t sort_bytes,
                            hipStream_t s);
+
+// ---- branch morphometry (morphometry.hip): per-label integer tables of a parsing volume, its skeleton and the squared EDT -----
+// Device arrays indexed by label value 0 .. num (include/seunet_hip.h, seunet_branch_stats).  No workspace: the tables are the
+// only memory the passes write.
+struct BranchStatsOut {
+  long long *voxels, *coord_sum;            // [num + 1], [num + 1][3]
+  int *box_min, *box_max;                   // [num + 1][3] each
+  long long *skeleton_voxels, *links, *cross_links, *r2_sum;   // [num + 1], [num + 1][13], [num + 1][13], [num + 1]
+  int *r2_min, *r2_max;                     // [num + 1] each
+  int* status;
+};
+int launch_branch_stats(const int* parsing, const unsigned char* skeleton, const int* sqdist, int n0, int n1, int n2, int num,
+                        BranchStatsOut out, hipStream_t s);
 
 // ---- device helpers -------------------------------------------------------------------------------------------------------
 // raster index -> coordinates of an (n0, n1, n2) volume (n0 is not needed)

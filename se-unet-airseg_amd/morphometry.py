@@ -1,0 +1,262 @@
+"""Branch morphometry: the table of numbers per branch that a labelled airway tree is made for.
+
+``branch_stats`` (csrc/morphometry.hip) reduces a ``parsing`` volume, its ``skeleton`` and the integer squared EDT to integer tables
+per label in two streaming passes on the GPU, with no launch, pass or synchronise per label; ``branch_tree`` turns the face
+adjacency of ``label_adjacency`` into parent / generation on the host; ``branch_morphometry`` joins them into a ``BranchTable`` with
+lengths, volumes and radii in float64.  The reference has no such function: the definition is the docstrings here and
+include/seunet_hip.h, restated in plain numpy by tests/morphometry_oracle.py, and the integer tables equal that oracle bit for bit."""
+from __future__ import annotations
+
+import dataclasses
+from typing import Dict, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib, prep
+
+_PREFIX = "seunet morphometry"
+
+# the 13 link classes: the offsets of {-1, 0, 1}^3 lexicographically above (0, 0, 0), ascending
+LINK_OFFSETS = tuple((d0, d1, d2) for d0 in (-1, 0, 1) for d1 in (-1, 0, 1) for d2 in (-1, 0, 1) if (d0, d1, d2) > (0, 0, 0))
+
+# the integer tables of seunet_branch_stats: name -> (dtype, columns); device layout: all int64 tables, then all int32 tables
+_TABLES = (("voxels", np.int64, 1), ("coord_sum", np.int64, 3), ("skeleton_voxels", np.int64, 1), ("links", np.int64, 13),
+           ("cross_links", np.int64, 13), ("r2_sum", np.int64, 1), ("box_min", np.int32, 3), ("box_max", np.int32, 3),
+           ("r2_min", np.int32, 1), ("r2_max", np.int32, 1))
+_ARG_ORDER = ("voxels", "coord_sum", "box_min", "box_max", "skeleton_voxels", "links", "cross_links", "r2_sum", "r2_min", "r2_max")
+INT32_MAX = int(np.iinfo(np.int32).max)
+
+
+def _sqdist_in(a, name):
+    if isinstance(a, np.ndarray):
+        if a.ndim != 3:
+            raise ValueError(f"{_PREFIX}: `{name}` must be (n0, n1, n2), got {tuple(a.shape)}")
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).cuda()
+    if not isinstance(a, torch.Tensor) or not a.is_cuda:
+        raise RuntimeError(f"{_PREFIX}: `{name}` must be a CUDA tensor resident on the GPU (there is no CPU path)")
+    if a.dim() != 3:
+        raise ValueError(f"{_PREFIX}: `{name}` must be (n0, n1, n2), got {tuple(a.shape)}")
+    if a.dtype != torch.int32:
+        raise TypeError(f"{_PREFIX}: `{name}` has dtype {a.dtype}; expected the int32 squared distance "
+                        "(distance_transform_edt(..., return_sqdist=True))")
+    return a.contiguous()
+
+
+def _empty_tables(num: int, shape) -> Dict[str, np.ndarray]:
+    out = {}
+    for name, dtype, cols in _TABLES:
+        out[name] = np.zeros((num, cols) if cols > 1 else (num,), dtype=dtype)
+    out["box_min"][:] = np.asarray(shape, dtype=np.int32)
+    out["box_max"][:] = -1
+    out["r2_min"][:] = INT32_MAX
+    out["r2_max"][:] = -1
+    return out
+
+
+def _branch_stats(vol, skel, sq, num: int) -> Dict[str, np.ndarray]:
+    """The tables of ``branch_stats`` for device inputs that are already checked, rows 1..num."""
+    lib = _lib.load()
+    cap = int(lib.seunet_label_stats_max_num())
+    if not 0 <= num <= cap:
+        raise ValueError(f"{_PREFIX}: labels up to {cap} are supported, got num = {num}")
+    shape = tuple(int(v) for v in vol.shape)
+    if vol.numel() == 0:
+        return _empty_tables(num, shape)
+    rows = num + 1
+    dev = vol.device
+    with torch.cuda.device(dev):
+        # one buffer of 8-byte words: the int64 tables, the int32 tables (two values per word), the status word
+        at, words = {}, 0
+        for name, dtype, cols in _TABLES:
+            at[name] = words
+            words += (rows * cols * np.dtype(dtype).itemsize + 7) // 8
+        buf = torch.empty(words + 1, dtype=torch.int64, device=dev)
+        base = buf.data_ptr()
+        _lib.check(lib.seunet_branch_stats(vol.data_ptr(), skel.data_ptr(), _lib.ptr(sq), *shape, num,
+                                           *(base + 8 * at[name] for name in _ARG_ORDER), base + 8 * words, _lib.stream_ptr()),
+                   "branch_stats")
+        host = buf.cpu().numpy()                             # the one copy back; it carries the status
+    if int(host[words:].view(np.int32)[0]) != 0:
+        raise ValueError(f"{_PREFIX}: the volume holds a label outside 0..{num}")
+    out = {}
+    for name, dtype, cols in _TABLES:
+        t = host[at[name]:].view(dtype)[:rows * cols]
+        out[name] = (t.reshape(rows, cols) if cols > 1 else t)[1:].copy()
+    return out
+
+
+def _inputs(parsing, skeleton, sqdist):
+    vol, as_numpy = prep._labels_in(parsing, "parsing")
+    skel = None
+    if skeleton is not None:
+        skel, _ = prep._mask_in(skeleton, "skeleton")
+        prep._same(vol, skel, "parsing", "skeleton")
+    sq = None
+    if sqdist is not None:
+        sq = _sqdist_in(sqdist, "sqdist")
+        prep._same(vol, sq, "parsing", "sqdist")
+    return vol, skel, sq, as_numpy
+
+
+def branch_stats(parsing, skeleton, num: Optional[int] = None, sqdist=None) -> Dict[str, np.ndarray]:
+    """The integer tables of ``seunet_branch_stats`` as a dict of numpy arrays with one row per label 1..num (row k - 1 = label k):
+
+    ``voxels`` int64[num]; ``coord_sum`` int64[num, 3], the sums of i0, i1, i2; ``box_min`` / ``box_max`` int32[num, 3], the inclusive
+    bounding box (a label without voxels: the volume's shape / -1); ``skeleton_voxels`` int64[num], the voxels with ``skeleton != 0``
+    and that label; ``links`` int64[num, 13], links between two skeleton voxels of the label by offset class (``LINK_OFFSETS``);
+    ``cross_links`` int64[num, 13], links to a skeleton voxel of another label >= 1, counted in both labels' rows; ``r2_sum`` int64[num],
+    ``r2_min`` / ``r2_max`` int32[num], sum, minimum and maximum of ``sqdist`` over the label's skeleton voxels (none, or
+    ``sqdist=None``: 0, INT32_MAX, -1).
+
+    A link joins two skeleton voxels with labels in 1..num whose offset d is one of the 13 classes, unless a voxel p + (a proper
+    non-empty part of d's non-zero components) is such a skeleton voxel too: the diagonal across an L-shaped corner is not counted.
+
+    ``parsing``: integer labels 0..num; ``skeleton``: 0/1 mask; ``sqdist``: int32, ``distance_transform_edt(..., return_sqdist=True)``.
+    CUDA tensors or numpy arrays; the inputs are not modified.  ``num=None`` takes ``int(parsing.max())``, which reads the device
+    once more; otherwise the call ends in one copy back that carries the status, with no synchronise before it.  ValueError: a label
+    outside 0..num, ``num`` above 4095, mismatched shapes."""
+    vol, skel, sq, _ = _inputs(parsing, skeleton, sqdist)
+    if skel is None:
+        raise ValueError(f"{_PREFIX}: branch_stats needs the skeleton")
+    if num is None:
+        num = max(int(vol.max()), 0) if vol.numel() else 0
+    return _branch_stats(vol, skel, sq, int(num))
+
+
+def branch_tree(counts, adjacency) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The branch tree from the face adjacency, on the host.  ``counts``: voxels of the labels 1..num; ``adjacency``: (num, num),
+    non-zero where two labels meet across a face (both as ``label_adjacency`` returns them).  The root is the label with the most
+    voxels, the lowest such label on a tie.  Generations go breadth-first by levels, a level in ascending label order; a label's
+    parent is the first label to reach it.  -> ``(parent, generation, n_children)``, int32[num] indexed by label - 1: ``parent`` holds
+    label values, 0 for the root and -1 for a label that is empty or not reachable from the root; ``generation`` is 0 at the
+    root and -1 where ``parent`` is -1."""
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+    num = counts.size
+    adj = np.asarray(adjacency).reshape(num, num) != 0
+    parent = np.full(num, -1, dtype=np.int32)
+    generation = np.full(num, -1, dtype=np.int32)
+    n_children = np.zeros(num, dtype=np.int32)
+    if num == 0 or counts.max() <= 0:
+        return parent, generation, n_children
+    root = int(np.argmax(counts))                            # the first of the maxima
+    parent[root], generation[root] = 0, 0
+    level = [root]
+    while level:
+        reached = []
+        for cur in level:                                    # ascending
+            for child in np.flatnonzero(adj[cur] | adj[:, cur]):
+                if generation[child] < 0 and counts[child] > 0:
+                    parent[child] = cur + 1
+                    generation[child] = generation[cur] + 1
+                    n_children[cur] += 1
+                    reached.append(int(child))
+        level = sorted(reached)
+    return parent, generation, n_children
+
+
+def link_lengths(spacing: Sequence[float]) -> np.ndarray:
+    """float64[13]: the length of a link of each class under ``spacing``, sqrt(sum_a (d_a s_a)^2)."""
+    s = np.asarray(spacing, dtype=np.float64).reshape(3)
+    return np.sqrt(((np.asarray(LINK_OFFSETS, dtype=np.float64) * s) ** 2).sum(axis=1))
+
+
+@dataclasses.dataclass
+class BranchTable:
+    """One row per label 1..num (index k - 1 = label k).  Integer columns: those of ``branch_stats``.  float64 columns: ``volume``,
+    ``centroid`` (num, 3), ``length`` and ``radius_equivalent`` in the units of ``spacing``; ``radius_inscribed_rms`` / ``_min`` /
+    ``_max`` in VOXEL units of the unit-sampling EDT, which convert to the units of ``spacing`` by one factor only when the spacing
+    is isotropic.  Tree columns: ``parent`` (label value, 0 root, -1 none), ``generation``, ``n_children``, ``is_leaf``.  Whole tree:
+    ``n_branches`` (labels with voxels), ``n_leaves``, ``total_length``, ``max_generation`` (-1 without a root),
+    ``branches_per_generation`` (int64[max_generation + 1])."""
+    num: int
+    spacing: Tuple[float, float, float]
+    voxels: np.ndarray
+    coord_sum: np.ndarray
+    box_min: np.ndarray
+    box_max: np.ndarray
+    skeleton_voxels: np.ndarray
+    links: np.ndarray
+    cross_links: np.ndarray
+    r2_sum: np.ndarray
+    r2_min: np.ndarray
+    r2_max: np.ndarray
+    volume: np.ndarray
+    centroid: np.ndarray
+    length: np.ndarray
+    radius_equivalent: np.ndarray
+    radius_inscribed_rms: np.ndarray
+    radius_inscribed_min: np.ndarray
+    radius_inscribed_max: np.ndarray
+    parent: np.ndarray
+    generation: np.ndarray
+    n_children: np.ndarray
+    is_leaf: np.ndarray
+    n_branches: int
+    n_leaves: int
+    total_length: float
+    max_generation: int
+    branches_per_generation: np.ndarray
+
+    def to_dict(self) -> dict:
+        return {f.name: getattr(self, f.name) for f in dataclasses.fields(self)}
+
+    @classmethod
+    def from_stats(cls, stats: Dict[str, np.ndarray], adjacency, spacing: Sequence[float] = (1.0, 1.0, 1.0)) -> "BranchTable":
+        """The derived columns from the integer tables of ``branch_stats`` and a (num, num) face adjacency; host only."""
+        s = np.asarray(spacing, dtype=np.float64).reshape(3)
+        if not (np.all(np.isfinite(s)) and np.all(s > 0)):
+            raise ValueError(f"{_PREFIX}: spacing must be three positive numbers, got {tuple(spacing)}")
+        voxels = np.asarray(stats["voxels"], dtype=np.int64)
+        num = int(voxels.size)
+        skv = np.asarray(stats["skeleton_voxels"], dtype=np.int64)
+        ell = link_lengths(s)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            volume = voxels.astype(np.float64) * (s[0] * s[1] * s[2])
+            centroid = np.where(voxels[:, None] > 0, stats["coord_sum"].astype(np.float64) / voxels[:, None] * s, np.nan)
+            length = (stats["links"].astype(np.float64) * ell).sum(axis=1) + 0.5 * (stats["cross_links"].astype(np.float64) * ell).sum(axis=1)
+            radius_equivalent = np.where(length > 0, np.sqrt(volume / (np.pi * length)), np.nan)
+            measured = (skv > 0) & (np.asarray(stats["r2_max"]) >= 0)        # r2_max stays -1 without sqdist
+            rms = np.where(measured, np.sqrt(stats["r2_sum"].astype(np.float64) / skv), np.nan)
+            rmin = np.where(measured, np.sqrt(np.where(measured, stats["r2_min"], 0).astype(np.float64)), np.nan)
+            rmax = np.where(measured, np.sqrt(np.where(measured, stats["r2_max"], 0).astype(np.float64)), np.nan)
+        parent, generation, n_children = branch_tree(voxels, adjacency)
+        is_leaf = (generation >= 0) & (n_children == 0)
+        max_generation = int(generation.max()) if num else -1
+        per_generation = np.bincount(generation[generation >= 0], minlength=max_generation + 1).astype(np.int64)
+        return cls(num=num, spacing=tuple(float(v) for v in s), **{name: np.asarray(stats[name]) for name, _, _ in _TABLES},
+                   volume=volume, centroid=centroid, length=length, radius_equivalent=radius_equivalent, radius_inscribed_rms=rms,
+                   radius_inscribed_min=rmin, radius_inscribed_max=rmax, parent=parent, generation=generation, n_children=n_children,
+                   is_leaf=is_leaf, n_branches=int((voxels > 0).sum()), n_leaves=int(is_leaf.sum()), total_length=float(length.sum()),
+                   max_generation=max_generation, branches_per_generation=per_generation)
+
+
+def branch_morphometry(parsing, skeleton=None, spacing: Sequence[float] = (1.0, 1.0, 1.0), num: Optional[int] = None,
+                       sqdist=None) -> BranchTable:
+    """The per-branch table of a ``parsing`` volume (``tree_parsing`` or ``airway_parse``): ``BranchTable``.
+
+    ``volume = voxels * s0 s1 s2``; ``centroid = coord_sum / voxels * spacing`` (nan for a label without voxels);
+    ``length = sum_c links[:, c] l_c + 1/2 sum_c cross_links[:, c] l_c`` with ``l_c = sqrt(sum_a (d_a s_a)^2)``: the half share of a
+    link between two branches closes the gap between them without counting it twice; ``radius_equivalent =
+    sqrt(volume / (pi length))``, the radius of the cylinder of that volume and length, correct under anisotropic spacing, nan where
+    the length is 0; ``radius_inscribed_rms / _min / _max = sqrt(r2_sum / skeleton_voxels), sqrt(r2_min), sqrt(r2_max)``: the distance
+    from the centreline to the wall in VOXEL units of the unit-sampling EDT (nan for a label without skeleton voxels), which is a
+    length in the units of ``spacing`` only after multiplying by an isotropic spacing; an EDT with sampling is not offered.  The tree
+    columns come from ``branch_tree`` on the face adjacency of ``seunet_label_stats``.
+
+    ``skeleton=None`` thins ``parsing != 0`` with ``skeletonize_3d``; ``sqdist=None`` takes the squared EDT of ``parsing != 0`` (a
+    volume without a background voxel has none: ValueError).  ``num=None``: ``int(parsing.max())``.  CUDA tensors or numpy arrays in,
+    numpy columns out; the inputs are not modified."""
+    vol, skel, sq, _ = _inputs(parsing, skeleton, sqdist)
+    if num is None:
+        num = max(int(vol.max()), 0) if vol.numel() else 0
+    num = int(num)
+    if skel is None or sq is None:
+        mask = (vol != 0).to(torch.uint8)
+        if skel is None:
+            skel = prep.skeletonize_3d(mask)
+        if sq is None and vol.numel():
+            sq = prep.distance_transform_edt(mask, return_distances=False, return_sqdist=True)
+    stats = _branch_stats(vol, skel, sq, num)
+    _, adjacency = prep._label_stats(vol, num)
+    return BranchTable.from_stats(stats, adjacency[1:, 1:], spacing)
