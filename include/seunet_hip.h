@@ -8,9 +8,12 @@
  *   - every function returns 0 on success, non-zero on error (message: seunet_last_error(), thread
  *     local); nothing throws across the ABI; every tensor and workspace is caller-owned and the
  *     launches themselves neither allocate nor synchronise;
+ *   - all device work of a call (kernels, memsets, copies) is ordered on its stream argument and on nothing else, and a call
+ *     that returns host values (pass counts, status words, counts, boxes) waits for that stream only;
  *   - what the library keeps per process, all of it created lazily on first need and none of it per call:
- *       (1) per device, one 4-KB page of zeros (hipMalloc + hipMemset, i.e. one device synchronisation, the first time
- *           a kernel that pads through it runs on that device -- or up front by seunet_init);
+ *       (1) per device, one 4-KB page of zeros (hipMalloc + hipMemset + a wait for the null stream, so the zeros are in
+ *           memory before any stream reads them: one device synchronisation, the first time a kernel that pads through it
+ *           runs on that device -- or up front by seunet_init);
  *       (2) per kernel instantiation, a bit mask of the devices on which hipFuncSetAttribute (LDS above 64 KB) has run;
  *       (3) the opt-in seunet_prof_* recorder (process-wide, off by default; the per-launch-group timer of bench.py).
  *     Apart from these everything is parameterised by (pointers, stream) and calls are re-entrant across threads and

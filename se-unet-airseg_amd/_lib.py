@@ -228,6 +228,8 @@ def int_array(vals: Sequence[int]) -> C.Array:
 
 
 def stream_ptr() -> int:
+    """The ``hipStream_t`` every library call is given: ``torch.cuda.current_stream()`` of the current device, read at call time
+    on the calling thread (so a ``torch.cuda.stream(...)`` block, and the stream autograd restores for a backward, apply)."""
     import torch
     return torch.cuda.current_stream().cuda_stream
 

@@ -78,6 +78,9 @@ int configure_kernel_lds(unsigned long long& mask, const void* fn, int bytes) {
 
 // ---- a per-device page of zeros: source of padding voxels / channels for the weight-gradient LDS-DMA -------------
 // (one hipMalloc + hipMemset per device for the life of the process, instead of a fill kernel in every launch)
+// The kernels that read the page run on the caller's stream, which may be a non-blocking one that the null stream's work is
+// not ordered with.  So the memset is followed, still under the lock, by a wait for the null stream it was issued on: the
+// pointer is published (and handed to any thread) only after the zeros are in memory, whatever stream reads them next.
 const void* device_zero_page() {
   static std::mutex mu;
   static void* page[64] = {};
@@ -87,7 +90,7 @@ const void* device_zero_page() {
   if (page[dev] == nullptr) {
     void* p = nullptr;
     if (hipMalloc(&p, 4096) != hipSuccess) return nullptr;
-    if (hipMemset(p, 0, 4096) != hipSuccess) { (void)hipFree(p); return nullptr; }
+    if (hipMemset(p, 0, 4096) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) { (void)hipFree(p); return nullptr; }
     page[dev] = p;
   }
   return page[dev];
