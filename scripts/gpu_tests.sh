@@ -63,7 +63,18 @@ if [ $rc -le 1 ]; then
 else
   echo "ops run crashed or timed out (rc=$rc): net and layer tests skipped"
 fi
-# exit status = the worst of the six runs (a crash / timeout / GPU fault is a failure, not a skip)
+rc7=0
+if [ $rc -le 1 ] && [ $rc2 -le 1 ] && [ $rc3 -le 1 ] && [ $rc4 -le 1 ] && [ $rc5 -le 1 ] && [ $rc6 -le 1 ]; then
+  # every 16-bit pass at the ends of its number range and on non-finite input (measured: 3 s + 7 s on an MI355X box)
+  rng_log=$(mktemp)
+  timeout -k 10 90 python -m pytest tests/test_conv_range_gpu.py tests/test_epilogue_range_gpu.py -m gpu -q -s -p no:cacheprovider > "$rng_log" 2>&1
+  rc7=$?
+  echo "range rc=$rc7"; grep -E -A10 "bit patterns differ|beyond the bound|that the plant reaches are finite" "$rng_log" | cut -c1-200 | head -60
+  grep -E "passed|failed|FAILED|Error" "$rng_log" | tail -20
+  rm -f "$rng_log"
+fi
+# exit status = the worst of the seven runs (a crash / timeout / GPU fault is a failure, not a skip)
+[ $rc7 -gt $rc ] && rc=$rc7
 [ $rc2 -gt $rc ] && rc=$rc2
 [ $rc3 -gt $rc ] && rc=$rc3
 [ $rc4 -gt $rc ] && rc=$rc4

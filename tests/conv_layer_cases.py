@@ -74,10 +74,11 @@ def storage(dtype):
     return torch.bfloat16 if dtype == "bf16" else torch.float16
 
 
-def ints(shape, lo, hi, seed):
-    """Seeded integers in [lo, hi] as int8 on the GPU (the CPU reference reads a copy of the same values)."""
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    return torch.randint(lo, hi + 1, shape, generator=g, device="cuda", dtype=torch.int8)
+def ints(shape, lo, hi, seed, device="cuda"):
+    """Seeded integers in [lo, hi] as int8 on the GPU (the CPU reference reads a copy of the same values).
+    (device="cpu": the CPU generator's draw instead, for data a host test has to see as well -- tests/range_cases.py)"""
+    g = torch.Generator(device=device).manual_seed(seed)
+    return torch.randint(lo, hi + 1, shape, generator=g, device=device, dtype=torch.int8)
 
 
 _cache = {}
@@ -163,13 +164,16 @@ def conv_ref(x, w, b, taps, dil):
 # ---------------------------------------------------------------------------------------------------
 # forward (+ InstanceNorm statistics)
 # ---------------------------------------------------------------------------------------------------
-def forward_data(c, seed):
+def forward_data(c, seed, device="cuda", nonzero_w=False):
+    """(nonzero_w: weights of 0 become 1, for operands that hold an infinity -- tests/range_cases.py)"""
     n, d, h, w = c["dims"]
     k = 3 if c["taps"] == 27 else 1
-    x = ints((n, sum(c["src_c"]), d, h, w), -3, 3, seed)
+    x = ints((n, sum(c["src_c"]), d, h, w), -3, 3, seed, device)
     x[:, c["cin"]:] = 0                                  # ec1: the logical 2 of the 8 packed channels
-    wt = ints((c["cout"], c["cin"], k, k, k), -3, 3, seed + 1).float().cpu()
-    b = ints((c["cout"],), -3, 3, seed + 2).float().cpu() if c["taps"] == 27 else None     # (the aggregation convs have no bias)
+    wt = ints((c["cout"], c["cin"], k, k, k), -3, 3, seed + 1, device).float().cpu()
+    if nonzero_w:
+        wt[wt == 0] = 1.0
+    b = ints((c["cout"],), -3, 3, seed + 2, device).float().cpu() if c["taps"] == 27 else None     # (the aggregation convs have no bias)
     ref = conv_ref(x[:, :c["cin"]].cpu().float(), wt, b, c["taps"], c["dilation"])
     mean = torch.stack([r.double().mean(dim=(1, 2, 3)) for r in ref])
     var = torch.stack([r.double().var(dim=(1, 2, 3), unbiased=False) for r in ref])
@@ -215,15 +219,17 @@ def forward_case(S, cfg, case):
 # ---------------------------------------------------------------------------------------------------
 # data gradient
 # ---------------------------------------------------------------------------------------------------
-def dgrad_data(c, seed):
+def dgrad_data(c, seed, device="cuda", nonzero_w=False):
     n, d, h, w = c["dims"]
     k = 3 if c["taps"] == 27 else 1
     cin = sum(c["src_c"])
-    dy = ints((n, c["cout"], d, h, w), -3, 3, seed)
-    wt = ints((c["cout"], cin, k, k, k), -3, 3, seed + 1).float().cpu()
+    dy = ints((n, c["cout"], d, h, w), -3, 3, seed, device)
+    wt = ints((c["cout"], cin, k, k, k), -3, 3, seed + 1, device).float().cpu()
+    if nonzero_w:
+        wt[wt == 0] = 1.0
     # the transposed convolution as a convolution with the transposed, mirrored weight (exact in f32 like the forward)
     ref = conv_ref(dy.cpu().float(), wt.transpose(0, 1).flip(2, 3, 4).contiguous(), None, c["taps"], c["dilation"])
-    prev = ints((n, cin, d, h, w), -3, 3, seed + 2)
+    prev = ints((n, cin, d, h, w), -3, 3, seed + 2, device)
     return dy, wt, ref, prev
 
 
@@ -294,12 +300,12 @@ def dgrad_case(S, cfg, case):
 # ---------------------------------------------------------------------------------------------------
 # weight gradient
 # ---------------------------------------------------------------------------------------------------
-def wgrad_data(c, seed):
+def wgrad_data(c, seed, device="cuda"):
     n, d, h, w = c["dims"]
     k = 3 if c["taps"] == 27 else 1
-    x = ints((n, sum(c["src_c"]), d, h, w), -1, 1, seed)
+    x = ints((n, sum(c["src_c"]), d, h, w), -1, 1, seed, device)
     x[:, c["cin"]:] = 0
-    dy = ints((n, c["cout"], d, h, w), -1, 1, seed + 1)
+    dy = ints((n, c["cout"], d, h, w), -1, 1, seed + 1, device)
     pad = c["dilation"] if k == 3 else 0
     ref = torch.nn.grad.conv3d_weight(x[:, :c["cin"]].cpu().float(), (c["cout"], c["cin"], k, k, k), dy.cpu().float(),
                                       padding=pad, dilation=c["dilation"] if k == 3 else 1)

@@ -138,6 +138,28 @@ def f64(t):
     return t.detach().double().cuda()
 
 
+GRAD_CLIP = 0.9375          # 15/16: times 2^16 it is 61440, below fp16's 65504
+
+
+def scale_grad(t, grad_scale, clip=GRAD_CLIP):
+    """An incoming gradient for the number-range tests (tests/test_epilogue_range_gpu.py): rounded to multiples of 2^-4, then
+    times ``grad_scale``, an exact power of two, in the tensor's own type.  With 2^-20 the values are multiples of 2^-24 below
+    2^-14: exact fp16 subnormals, which the assert states.  With a scale of 1 and above (the overflow-on-store runs) a 16-bit
+    gradient is first clamped to +-clip, so that it stays finite up to 2^16 (clip = 15/16) while the pass's results cross
+    65520: with the Gaussian tails of ``act`` no power of two does both.  (The gated blocks attenuate g_e -- two sigmoid gates --
+    so their runs clamp it to 2^-10 and let the f32 level gradient, which is not clamped, carry draw across 65520 at up to 2^25.)  None leaves the tensor as it is."""
+    if grad_scale is None:
+        return t
+    q = (t.float() * 16).round() / 16
+    if grad_scale >= 1 and t.element_size() == 2:
+        q = q.clamp(-clip, clip)
+    out = (q * grad_scale).to(t.dtype)
+    assert bool(out.isfinite().all()) and torch.equal(out.double(), q.double() * grad_scale), "the scaled gradient is not exact in its type"
+    if grad_scale == 2.0 ** -20:
+        assert float(q.abs().max()) < 64 and float(out.abs().max()) < 2.0 ** -14 and bool((out != 0).any())
+    return out
+
+
 def report(got, ref, bound, what):
     """Asserts |got - ref| <= bound element by element and prints the largest error / bound ratio.  The comparison is written
     so that a NaN (or an infinity) the kernel left anywhere fails it: NaN <= bound is false."""
@@ -260,7 +282,7 @@ def gate_stats_and_forward(S, cfg, case):
             report(maps[with_drop][i].reshape(V), ref, R.sum_bound(S_, 8 + lgl, R.KE(C) + 5), f"{name} {dtype} level map[{i}] drop={with_drop}")
 
 
-def gate_backward(S, cfg, case):
+def gate_backward(S, cfg, case, grad_scale=None, store_check=None, grad_clip=GRAD_CLIP):
     """The form training runs: sse_bwd_kernel<.., LEVEL = true> with g_e and g_level (level 0: laid out as the logit gradient
     (N, 1, D, H, W)), finalised by seunet_gate_bwd_finalize as the network does -- and by stats_finalize + pgrad_reduce, which
     share the device code and must give the same bits."""
@@ -274,6 +296,7 @@ def gate_backward(S, cfg, case):
     g = gen(seed_of(name, dtype, "bwd"))
     g_e = act((n, d, h, w, C), dtype, g, centre=0.2)
     gl = torch.randn((n, 1, d, h, w), generator=g, device="cuda") * 0.5 + 0.1
+    g_e, gl = scale_grad(g_e, grad_scale, grad_clip), scale_grad(gl, grad_scale)
     args = (raw, t["mean"], t["rstd"], p["w_se"], p["w_se2"], p["w_side"], p["b_side"], SLOPE)
     kw = dict(g_e=g_e, g_level=gl, head_w=head_w, drop=drop, drop_stride=p["nch"])
     out = S.gate_epilogue_bwd(*args, **kw, fused_finalize=True)
@@ -302,7 +325,7 @@ def gate_backward(S, cfg, case):
         m1, m2, rs = f64(out["m1"][i]), f64(out["m2"][i]), f64(t["rstd"][i])
         ref = R.in_backward(bw["dxh"], fw["xh"], rs, m1, m2)
         A = rs * (ab["dxh"] + m1.abs() + (fw["xh"] * m2).abs())
-        report(out["draw"][i].reshape(V, C), ref, R.element_bound(ref, A, KD + 6, dtype), f"{name} {dtype} draw[{i}]")
+        (store_check or report)(out["draw"][i].reshape(V, C), ref, R.element_bound(ref, A, KD + 6, dtype), f"{name} {dtype} draw[{i}]")
         for k in ("dw_se", "dw_se2", "dw_side", "db_side", "dhead_w"):
             tot[k] = tot.get(k, 0) + bw[k]
             tot_abs[k] = tot_abs.get(k, 0) + ab[k]
@@ -358,7 +381,7 @@ def x_block(S, cfg, name, dtype, kind):
     return shared((cfg.key, "x", name, dtype, kind), make)
 
 
-def aggregation_x_pool_forward_and_backward(S, cfg, case):
+def aggregation_x_pool_forward_and_backward(S, cfg, case, grad_scale=None, store_check=None):
     """The encoder aggregation block as the network runs it: x-branch statistics from the input's moments, the kernel that also
     writes the pooled tensor and the arg-max words, and both backward passes with the pooled gradient added on the fly.  The
     cases named np2-* have extents that are not powers of two and differ per axis (the multiply-high divisions of the routing)."""
@@ -383,6 +406,7 @@ def aggregation_x_pool_forward_and_backward(S, cfg, case):
     g = gen(seed_of(name, dtype, kind, "bwd"))
     g_out = act((n, d, h, w, C), dtype, g, centre=0.2)
     g_pool = act((n, d // 2, h // 2, w // 2, C), dtype, g, centre=0.2)
+    g_out, g_pool = scale_grad(g_out, grad_scale), scale_grad(g_pool, grad_scale)
     res = S.cat_epilogue_bwd_x(g_out, raw, t["mean"], t["rstd"], x_in, w2, 2, t["mean2"], t["rstd2"], t["mom"], SLOPE, EPS,
                                pool_argmax=words, pool_g=g_pool)
     T = thread_chain((n, d, h, w), C)
@@ -423,7 +447,7 @@ def aggregation_x_pool_forward_and_backward(S, cfg, case):
         m1, m2 = f64(res["m1"][i]), f64(res["m2"][i])
         ref = R.in_backward(bw["d1"], xh, rs, m1, m2)
         A = rs * (bw["d1_abs"] + m1.abs() + (xh * m2).abs())
-        report(res["dx"][i].reshape(V, C), ref, R.element_bound(ref, A, 8, dtype), f"{name} {dtype} {kind} dx[{i}]")
+        (store_check or report)(res["dx"][i].reshape(V, C), ref, R.element_bound(ref, A, 8, dtype), f"{name} {dtype} {kind} dx[{i}]")
         # dW2 in float64 from float64 statistics of the x-branch (the kernel forms it in f64 from the sums S_k = sum dxhat2 x_k,
         # sum dxhat2 and the input's moments); its tolerance propagates the sum bounds of those three sums through
         # dW2_i = rs (A_i - rs^2 (wa A_0 + wb A_1)(wa C_0i + wb C_1i)),  A_k = S_k - mean(x_k) sum dxhat2
@@ -456,7 +480,7 @@ def aggregation_x_pool_forward_and_backward(S, cfg, case):
         assert flag_share < 1e-5, flag_share
 
 
-def aggregation_one_branch(S, cfg, case):
+def aggregation_one_branch(S, cfg, case, grad_scale=None, store_check=None):
     """ec123, dc22, dc42: cat_epilogue_fwd / cat_epilogue_bwd without a second branch."""
     name, dtype = case
     b = cfg.BLOCKS[name]
@@ -464,7 +488,7 @@ def aggregation_one_branch(S, cfg, case):
     C, V = b["C"], d * h * w
     g = gen(seed_of(name, dtype))
     raw = act((n, d, h, w, C), dtype, g, centre=0.8)
-    g_out = act((n, d, h, w, C), dtype, g, centre=0.2)
+    g_out = scale_grad(act((n, d, h, w, C), dtype, g, centre=0.2), grad_scale)
     mean, rstd = check_stats(S, raw, f"{name} {dtype}")
     out = S.cat_epilogue_fwd(raw, mean, rstd, slope=SLOPE)
     dx, _ = S.cat_epilogue_bwd(g_out, raw, mean, rstd, slope=SLOPE)
@@ -481,7 +505,7 @@ def aggregation_one_branch(S, cfg, case):
         e1, e2 = R.sum_bound(dd.abs().mean(0), L, 2 + 1), R.sum_bound((dd * xh).abs().mean(0), L, 5 + 1)
         ref = R.in_backward(dd, xh, rs, m1, m2)
         A = rs * (dd.abs() + m1.abs() + (xh * m2).abs())
-        report(dx[i].reshape(V, C), ref, R.element_bound(ref, A, 7, dtype) + rs * (e1 + xh.abs() * e2), f"{name} {dtype} dx[{i}]")
+        (store_check or report)(dx[i].reshape(V, C), ref, R.element_bound(ref, A, 7, dtype) + rs * (e1 + xh.abs() * e2), f"{name} {dtype} dx[{i}]")
 
 
 # ---- max-pool ------------------------------------------------------------------------------------------------------------------
@@ -494,13 +518,15 @@ def maxpool_forward(S, case):
         same(got[i].float(), want, f"maxpool_fwd after {name} {dtype} [{i}]")
 
 
-def maxpool_backward(S, case):
-    """g_in (+)= the pooled gradient at the first maximum of every window: round_T(g + prev) formed in f32 is exact."""
+def maxpool_backward(S, case, grad_scale=None, shares=None):
+    """g_in (+)= the pooled gradient at the first maximum of every window: round_T(g + prev) formed in f32 is exact.
+    (shares: a list that receives, per sample, the share of the expected elements that are inf -- the overflow-on-store runs)"""
     name, C, (n, d, h, w), dtype, acc = case
     g = gen(seed_of("poolb", name, dtype))
     t = levels((n, d, h, w, C), dtype, g, 6)             # ties included
     g_out = act((n, d // 2, h // 2, w // 2, C), dtype, g)
     prev = act((n, d, h, w, C), dtype, g)
+    g_out, prev = scale_grad(g_out, grad_scale), scale_grad(prev, grad_scale)
     got = S.maxpool_bwd(t, g_out, prev.clone() if acc else None)
     for i in range(n):
         _, first, _ = R.pool_first_max(t[i].float())
@@ -509,6 +535,8 @@ def maxpool_backward(S, case):
         want = R.unpool_windows(win, d, h, w)
         if acc:
             want = (want + prev[i].float()).to(R.storage(dtype)).float()
+        if shares is not None:
+            shares.append(float(want.isinf().double().mean()))
         same(got[i].float(), want, f"maxpool_bwd after {name} {dtype} accumulate={acc} [{i}]")
 
 
@@ -526,20 +554,21 @@ def upsample_forward(S, case):
         report(got[i], ref, R.element_bound(ref, A, 10, dtype, U * R.lambda_term(x.abs())), f"upsample2_fwd into {name} {dtype} [{i}]")
 
 
-def upsample_backward(S, case):
+def upsample_backward(S, case, grad_scale=None, store_check=None):
     """The marching kernel reduces y (weight 2 roundings, product, <= 5 additions), x (2, 1, <= 6) and z (2, 1, <= 6) and adds
     the previous gradient once: 27.  A: the adjoint applied to |g|, plus |previous|; R.lambda_term as in the forward."""
     name, C, (n, d, h, w), dtype, acc = case
     g = gen(seed_of("upb", name, dtype))
     g_out = act((n, 2 * d, 2 * h, 2 * w, C), dtype, g)
     prev = act((n, d, h, w, C), dtype, g)
+    g_out, prev = scale_grad(g_out, grad_scale), scale_grad(prev, grad_scale)
     got = S.upsample2_bwd(g_out, prev.clone() if acc else None)
     for i in range(n):
         x = g_out[i].double()
         ref, A = R.upsample(x, transpose=True), R.upsample(x.abs(), transpose=True)
         if acc:
             ref, A = ref + prev[i].double(), A + prev[i].double().abs()
-        report(got[i], ref, R.element_bound(ref, A, 27, dtype, U * R.lambda_term(x.abs(), transpose=True)), f"upsample2_bwd out of {name} {dtype} accumulate={acc} [{i}]")
+        (store_check or report)(got[i], ref, R.element_bound(ref, A, 27, dtype, U * R.lambda_term(x.abs(), transpose=True)), f"upsample2_bwd out of {name} {dtype} accumulate={acc} [{i}]")
 
 
 # ---- heads ---------------------------------------------------------------------------------------------------------------------
@@ -563,11 +592,11 @@ def head_forward(S, cfg, nlevels):
         report(pred[i, 0], ref, R.sum_bound(S_, 4, 10) + lam, f"head_fwd {nlevels} levels [{i}]")
 
 
-def head_backward(S, cfg, nlevels):
+def head_backward(S, cfg, nlevels, grad_scale=None):
     """Three axis passes per level, each a chain of up to T_l taps (weight 2 roundings, product 1): L = 3 T_l, K = 9.  The bias
     gradient's partials are all f64: 1 ulp of f32 at the float64 sum."""
     n, D = cfg.batch, cfg.extent
-    g_pred = torch.randn((n, 1, D, D, D), generator=gen(seed_of("headb", nlevels)), device="cuda") + 0.1
+    g_pred = scale_grad(torch.randn((n, 1, D, D, D), generator=gen(seed_of("headb", nlevels)), device="cuda") + 0.1, grad_scale)
     lv, gb = S.head_bwd(g_pred, nlevels)
     tot = g_pred.double().sum()
     report(gb, tot.reshape(1), R.ulp32(tot).reshape(1) + g_pred.numel() * 2.0 ** -53 * g_pred.double().abs().sum().reshape(1), "head_bwd bias gradient")
