@@ -380,6 +380,16 @@ int seunet_metric_sums(const unsigned char* pred, const unsigned char* label, co
 size_t seunet_edt_workspace_bytes(int n0, int n1, int n2);
 int seunet_edt(const unsigned char* volume, int n0, int n1, int n2, int* sqdist, double* dist, int* indices, int* status_dev,
                void* workspace, size_t workspace_bytes, seunet_stream_t s);
+/* seunet_edt_sampling: scipy.ndimage.distance_transform_edt(volume, sampling=(s0, s1, s2), return_indices=True): the nearest ZERO
+ *   voxel of every voxel when voxel (i0, i1, i2) lies at (i0 s0, i1 s1, i2 s2).  scipy's feature transform in float64, operation
+ *   by operation with no fused multiply-add; s0, s1, s2 positive and finite (anything else: error), passed
+ *   by value.  Outputs (each optional, NULL = skip): dist float64 = sqrt((dt_0^2 + dt_1^2) + dt_2^2) with
+ *   dt_a = (double)(index_a - coordinate_a) * s_a, bitwise scipy's; indices int32 (3, n0, n1, n2), bitwise scipy's, ties included;
+ *   lin int32, the linear index (i0 n1 + i1) n2 + i2 of the feature.  status_dev and a volume with no zero voxel: as seunet_edt.
+ *   All work is ordered on s; the call does not synchronise.  workspace: seunet_edt_sampling_workspace_bytes (8 bytes per voxel). */
+size_t seunet_edt_sampling_workspace_bytes(int n0, int n1, int n2);
+int seunet_edt_sampling(const unsigned char* volume, int n0, int n1, int n2, double s0, double s1, double s2, double* dist, int* indices,
+                        int* lin, int* status_dev, void* workspace, size_t workspace_bytes, seunet_stream_t s);
 int seunet_mask_bits(const unsigned char* mask, long long n, unsigned long long* bits, seunet_stream_t s);
 int seunet_hard_mining_masks(const unsigned char* label, const unsigned char* skeleton, const unsigned char* pred, int n0, int n1,
                              int n2, unsigned long long* skeleton_bits, unsigned long long* small_bits, seunet_stream_t s);
@@ -570,6 +580,18 @@ int seunet_mesh_label_emit(const int* labels, int n0, int n1, int n2, int num, d
 int seunet_branch_stats(const int* parsing, const unsigned char* skeleton, const int* sqdist, int n0, int n1, int n2, int num,
                         long long* voxels, long long* coord_sum, int* box_min, int* box_max, long long* skeleton_voxels, long long* links,
                         long long* cross_links, long long* r2_sum, int* r2_min, int* r2_max, int* status_dev, seunet_stream_t s);
+/* seunet_branch_wall_stats: the distance from the centreline to the wall per label under the voxel spacing (s0, s1, s2), positive
+ *   and finite, by value.  indices: int32 (3, n0, n1, n2), the feature transform of seunet_edt_sampling with the same spacing
+ *   (-1: no feature).  One streaming pass over skeleton; parsing and indices are read at set skeleton voxels only.  Over the
+ *   labelled skeleton voxels of label k that have a feature (device arrays indexed by label value 0 .. num, all written here):
+ *   wall_count int64[num + 1]: their number.  offset_sq_sum int64[num + 1][3]: the sums of (index_a - coordinate_a)^2 per axis a.
+ *   wall_sq_min / wall_sq_max float64[num + 1]: minimum and maximum of (dt_0^2 + dt_1^2) + dt_2^2 with
+ *   dt_a = (double)(index_a - coordinate_a) * s_a, every product and sum rounded on its own; none: +inf and 0.0.
+ *   Deterministic: integer sums, and minima / maxima taken on the bit patterns of non-negative doubles.
+ *   status_dev (device int): 1 if a skeleton voxel's parsing value is outside 0..num (that voxel is ignored), 0 otherwise. */
+int seunet_branch_wall_stats(const int* parsing, const unsigned char* skeleton, const int* indices, int n0, int n1, int n2, int num,
+                             double s0, double s1, double s2, long long* wall_count, long long* offset_sq_sum, double* wall_sq_min,
+                             double* wall_sq_max, int* status_dev, seunet_stream_t s);
 
 /* ---- CT preprocessing: preprocessing.py:26-130 with util.py:95-152 -----------------------------
  * CT volumes are int16, C-contiguous (h, w, z) on the device (the reference's orientation after its transposes), fewer than 2^31

@@ -15,7 +15,7 @@ from .prep import (CandidateSet, airway_parse, binary_closing, binary_dilation, 
                    tree_parsing, tree_parsing_func)
 from .mesh import (LabelMeshes, branch_meshes, label_meshes, marching_cubes, mesh_adjacency, prediction_mesh, smooth_mesh, stl_records,
                    transform_mesh, write_stl)
-from .morphometry import BranchTable, branch_morphometry, branch_stats, branch_tree
+from .morphometry import BranchTable, branch_morphometry, branch_stats, branch_tree, branch_wall_distance
 from .preprocess import cut_mask, get_l, large_connected_domain26, preprocess_ct, th_2t
 from .postprocess import (MetricSums, double_threshold_iteration, evaluation_case, largest_component, maximum_3d,
                           postprocess_prediction, zero_borders)
@@ -30,4 +30,4 @@ __all__ = ["SE_UNet", "SSEConv", "SSEConv2", "CATConv", "DropLayer", "get_model"
            "break_weight", "skeletonize_3d", "skeleton_parsing", "tree_parsing_func", "label_adjacency", "tree_parsing", "relabel", "airway_parse", "binary_dilation",
            "binary_erosion", "binary_closing", "binary_fill_holes", "preprocess_ct", "th_2t", "get_l", "large_connected_domain26", "cut_mask",
            "marching_cubes", "smooth_mesh", "write_stl", "prediction_mesh", "mesh_adjacency", "stl_records", "transform_mesh",
-           "label_meshes", "branch_meshes", "LabelMeshes", "branch_stats", "branch_tree", "branch_morphometry", "BranchTable"]
+           "label_meshes", "branch_meshes", "LabelMeshes", "branch_stats", "branch_tree", "branch_morphometry", "BranchTable", "branch_wall_distance"]

@@ -128,6 +128,8 @@ PROTOTYPES = {
     "seunet_dti": (_i, [_vp, _i, _i, _i, C.c_double, C.c_double, _i, _vp, _vp, _sz, _vp]),
     "seunet_edt_workspace_bytes": (_sz, [_i, _i, _i]),
     "seunet_edt": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "seunet_edt_sampling_workspace_bytes": (_sz, [_i, _i, _i]),
+    "seunet_edt_sampling": (_i, [_vp, _i, _i, _i, _d, _d, _d, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "seunet_mask_bits": (_i, [_vp, _ll, _vp, _vp]),
     "seunet_hard_mining_masks": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "seunet_lib_weight_workspace_bytes": (_sz, [_i, _i, _i]),
@@ -156,6 +158,7 @@ PROTOTYPES = {
     "seunet_mesh_label_count": (_i, [_vp, _i, _i, _i, _i, C.POINTER(_ll), C.POINTER(_ll), _ip, _ip, _vp, _vp, _i, _vp, _sz, _vp]),
     "seunet_mesh_label_emit": (_i, [_vp, _i, _i, _i, _i, _d, _ll, _ll, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "seunet_branch_stats": (_i, [_vp, _vp, _vp, _i, _i, _i, _i] + [_vp] * 11 + [_vp]),
+    "seunet_branch_wall_stats": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _d, _d, _d, _vp, _vp, _vp, _vp, _vp, _vp]),
     "seunet_mesh_coord_sums": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "seunet_mesh_adjacency_workspace_bytes": (_sz, [_ll, _ll]),
     "seunet_mesh_adjacency": (_i, [_vp, _ll, _ll, _vp, _vp, _ll, _vp, _vp, _vp, _sz, _vp]),

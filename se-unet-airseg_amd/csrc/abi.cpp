@@ -30,7 +30,7 @@ int seunet_debug_upsample2_form(int dtype, int c, seunet_dims dims, int backward
 
 // diagnostic hook (not part of the public header, host only): the workspace layout of a volume operation as its launcher
 // carves it.  op: 0 cc, 1 get_l, 2 edt, 3 lib_weight, 4 break_weight, 5 skeleton_branches, 6 dti, 7 skeleton, 8 parse_assign,
-// 9 binary_morph, 10 mesh, 11 mesh_label.
+// 9 binary_morph, 10 mesh, 11 mesh_label, 12 edt_sampling.
 // Returns the number of sub-buffers (0: extents the op rejects, -1: no such op) and writes (offset, bytes up to the next
 // sub-buffer or the end) of the first `cap`.
 int seunet_debug_volume_layout(int op, int n0, int n1, int n2, size_t* offsets, int cap) {
@@ -51,6 +51,7 @@ int seunet_debug_volume_layout(int op, int n0, int n1, int n2, size_t* offsets, 
     case 9: morph_ws(c, n0, n1, n2); break;
     case 10: if ((long long)n0 * n1 * n2 >= (1ll << 31)) return 0; mesh_ws(c, n0, n1, n2); break;
     case 11: if ((long long)n0 * n1 * n2 >= (1ll << 31)) return 0; mesh_label_ws(c, n0, n1, n2); break;
+    case 12: edt_sampling_ws(c, n0, n1, n2); break;
     default: return -1;
   }
   if (c.taken > c.log_cap) return -1;
@@ -407,6 +408,15 @@ int seunet_edt(const unsigned char* volume, int n0, int n1, int n2, int* sqdist,
                void* workspace, size_t workspace_bytes, seunet_stream_t s) {
   return launch_edt(volume, n0, n1, n2, sqdist, dist, indices, status_dev, workspace, workspace_bytes, S(s));
 }
+size_t seunet_edt_sampling_workspace_bytes(int n0, int n1, int n2) {
+  if (n0 < 1 || n1 < 1 || n2 < 1) { fail("edt_sampling_workspace_bytes: bad dimensions"); return 0; }
+  return edt_sampling_workspace_bytes(n0, n1, n2);
+}
+int seunet_edt_sampling(const unsigned char* volume, int n0, int n1, int n2, double s0, double s1, double s2, double* dist, int* indices,
+                        int* lin, int* status_dev, void* workspace, size_t workspace_bytes, seunet_stream_t s) {
+  return launch_edt_sampling(volume, n0, n1, n2, s0, s1, s2, EdtSamplingOut{dist, indices, lin}, status_dev, workspace, workspace_bytes,
+                             S(s));
+}
 int seunet_mask_bits(const unsigned char* mask, long long n, unsigned long long* bits, seunet_stream_t s) {
   return launch_mask_bits(mask, n, bits, S(s));
 }
@@ -529,6 +539,12 @@ int seunet_branch_stats(const int* parsing, const unsigned char* skeleton, const
                              BranchStatsOut{voxels, coord_sum, box_min, box_max, skeleton_voxels, links, cross_links, r2_sum, r2_min,
                                             r2_max, status_dev},
                              S(s));
+}
+int seunet_branch_wall_stats(const int* parsing, const unsigned char* skeleton, const int* indices, int n0, int n1, int n2, int num,
+                             double s0, double s1, double s2, long long* wall_count, long long* offset_sq_sum, double* wall_sq_min,
+                             double* wall_sq_max, int* status_dev, seunet_stream_t s) {
+  return launch_branch_wall_stats(parsing, skeleton, indices, n0, n1, n2, num, s0, s1, s2,
+                                  BranchWallOut{wall_count, offset_sq_sum, wall_sq_min, wall_sq_max, status_dev}, S(s));
 }
 int seunet_mesh_coord_sums(const unsigned char* mask, int n0, int n1, int n2, long long* sums_dev, seunet_stream_t s) {
   return launch_mesh_coord_sums(mask, n0, n1, n2, sums_dev, S(s));

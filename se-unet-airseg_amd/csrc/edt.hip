@@ -154,6 +154,15 @@ edt_pass_kernel(const short* __restrict__ in0, const short* __restrict__ in1, in
 
 size_t edt_workspace_bytes(int n0, int n1, int n2) { return measured(edt_ws, n0, n1, n2); }
 
+// pass 0 with its status preset; shared with the passes in float64 of edt_sampling.hip, whose pass 0 is this one
+int run_edt_pass0(const unsigned char* vol, bool invert, int n0, int n1, int n2, short* f0, int* status_dev, hipStream_t s) {
+  if (status_dev) SEUNET_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(status_dev), 1, 1, s));
+  const long long plane = (long long)n1 * n2;
+  if (invert) edt_pass0_kernel<true><<<blocks_256(plane), 256, 0, s>>>(vol, n0, plane, f0, status_dev);
+  else edt_pass0_kernel<false><<<blocks_256(plane), 256, 0, s>>>(vol, n0, plane, f0, status_dev);
+  return 0;
+}
+
 int run_edt(const unsigned char* vol, bool invert, int n0, int n1, int n2, EdtOut o, int* status_dev, void* workspace, size_t ws_bytes,
             hipStream_t s) {
   SEUNET_CHECK(vol && workspace, "edt: null argument");
@@ -161,10 +170,7 @@ int run_edt(const unsigned char* vol, bool invert, int n0, int n1, int n2, EdtOu
   WsCarver carve(workspace);
   const EdtWs w = edt_ws(carve, n0, n1, n2);
   SEUNET_CHECK(ws_bytes >= carve.bytes(), "edt: workspace too small");
-  if (status_dev) SEUNET_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(status_dev), 1, 1, s));
-  const long long plane = (long long)n1 * n2;
-  if (invert) edt_pass0_kernel<true><<<blocks_256(plane), 256, 0, s>>>(vol, n0, plane, w.f0, status_dev);
-  else edt_pass0_kernel<false><<<blocks_256(plane), 256, 0, s>>>(vol, n0, plane, w.f0, status_dev);
+  if (run_edt_pass0(vol, invert, n0, n1, n2, w.f0, status_dev, s)) return 1;
   const long long l1 = (long long)n0 * n2, l2 = (long long)n0 * n1;
   edt_pass_kernel<1><<<blocks_256(l1), 256, 0, s>>>(w.f0, nullptr, n0, n1, n2, w.spos, w.sr, w.fa, w.fb, o);
   edt_pass_kernel<2><<<blocks_256(l2), 256, 0, s>>>(w.fa, w.fb, n0, n1, n2, w.spos, w.sr, nullptr, nullptr, o);

@@ -305,4 +305,124 @@ int launch_branch_stats(const int* parsing, const unsigned char* skeleton, const
   return 0;
 }
 
+// ---- wall distance pass ---------------------------------------------------------------------------------------
+// Per label, over its skeleton voxels that have a feature in `indices` (the feature transform of the EDT with spacing): their
+// count, the exact sums of the squared index offsets per axis, and the minimum / maximum of the squared physical distance
+// (dt_0^2 + dt_1^2) + dt_2^2 with dt_a = (double)(index_a - coordinate_a) * s_a, each product and sum rounded on its own as numpy
+// does.  Integer sums, and minima / maxima of non-negative doubles through their bit patterns (br_maxf_kernel of edt.hip): no order
+// of execution shows in a result.
+
+__global__ void __launch_bounds__(256)
+branch_wall_init_kernel(BranchWallOut o, int num) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k == 0) *o.status = 0;
+  if (k > num) return;
+  o.wall_count[k] = 0;
+  for (int a = 0; a < 3; ++a) o.offset_sq_sum[3 * k + a] = 0;
+  o.wall_sq_min[k] = __builtin_huge_val();
+  o.wall_sq_max[k] = 0.0;
+}
+
+struct WallTables { u64 *count, *sq_sum, *sq_min, *sq_max; };
+
+// One voxel per lane, i valid where `set`; called by whole waves.  A label outside 0 .. num sets the status and is ignored.
+__device__ __forceinline__ void wall_step(const int* __restrict__ parsing, const int* __restrict__ indices, long long n, int n1, int n2,
+                                          int num, double s0, double s1, double s2, long long i, bool set, const WallTables& t,
+                                          int* __restrict__ status) {
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x & 63;
+  int a = 0;
+  u64 q[3] = {0ull, 0ull, 0ull};
+  u64 bits = 0;                                          // the squared distance as its bit pattern
+  if (set) {
+    a = parsing[i];
+    if (a < 0 || a > num) { *status = 1; a = 0; }
+    const int j0 = a > 0 ? indices[i] : -1;
+    if (j0 < 0) a = 0;                                   // a voxel without a feature is not measured
+    else {
+      const Vox3 p = vox3(i, n1, n2);
+      const int d0 = j0 - p.i0, d1 = indices[i + n] - p.i1, d2 = indices[i + 2 * n] - p.i2;
+      q[0] = (u64)((long long)d0 * d0);
+      q[1] = (u64)((long long)d1 * d1);
+      q[2] = (u64)((long long)d2 * d2);
+      const double t0 = (double)d0 * s0, t1 = (double)d1 * s1, t2 = (double)d2 * s2;
+      bits = __builtin_bit_cast(u64, (t0 * t0 + t1 * t1) + t2 * t2);
+    }
+  }
+  // wave-uniform from here: one label of the wave at a time, reduced over the lanes that hold it
+  u64 pending = __ballot(a > 0);
+  while (pending) {
+    const int first = __builtin_ctzll(pending);
+    const int label = dpp_settle(__shfl(a, first, 64));
+    const bool mine = a == label;
+    const u64 holders = __ballot(mine);
+    u64 sum[3], lo = mine ? bits : ~0ull, hi = mine ? bits : 0ull;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) sum[k] = mine ? q[k] : 0ull;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) sum[k] += shfl_xor_settled(sum[k], off);
+      lo = std::min(lo, shfl_xor_settled(lo, off));
+      hi = std::max(hi, shfl_xor_settled(hi, off));
+    }
+    if (lane == first) {
+      atomicAdd(&t.count[label], lanes(holders));
+#pragma unroll
+      for (int k = 0; k < 3; ++k)
+        if (sum[k]) atomicAdd(&t.sq_sum[3 * label + k], sum[k]);
+      if (t.sq_min[label] > lo) atomicMin(&t.sq_min[label], lo);
+      if (t.sq_max[label] < hi) atomicMax(&t.sq_max[label], hi);
+    }
+    pending &= ~holders;
+  }
+}
+
+// the skeleton stream of branch_skeleton_kernel: 16 bytes per lane from 16-byte aligned addresses, `parsing` and `indices` at set
+// voxels only
+__global__ void __launch_bounds__(256)
+branch_wall_kernel(const int* __restrict__ parsing, const unsigned char* __restrict__ skel, const int* __restrict__ indices, int n0,
+                   int n1, int n2, int num, double s0, double s1, double s2, int skew, BranchWallOut o) {
+  const long long n = (long long)n0 * n1 * n2, stream = n + skew;
+  const unsigned char* const aligned = skel - skew;
+  const WallTables t{reinterpret_cast<u64*>(o.wall_count), reinterpret_cast<u64*>(o.offset_sq_sum), reinterpret_cast<u64*>(o.wall_sq_min),
+                     reinterpret_cast<u64*>(o.wall_sq_max)};
+  for (long long base = blockIdx.x * 4096ll; base < stream; base += (long long)gridDim.x * 4096) {
+    const long long at = base + 16ll * threadIdx.x;
+    u64 half[2] = {0ull, 0ull};
+    if (at >= skew && at + 16 <= stream) {
+      const uint4 w = *reinterpret_cast<const uint4*>(aligned + at);
+      half[0] = (u64)w.y << 32 | w.x;
+      half[1] = (u64)w.w << 32 | w.z;
+    } else {                                             // the ends of the volume: byte by byte, nothing outside it is read
+      for (int b = 0; b < 16; ++b)
+        if (at + b >= skew && at + b < stream) half[b >> 3] |= (u64)aligned[at + b] << (8 * (b & 7));
+    }
+    if (__ballot((half[0] | half[1]) != 0) == 0) continue;   // (wave-uniform)
+#pragma unroll 1
+    for (int b = 0; b < 16; ++b) {
+      const bool set = ((b < 8 ? half[0] : half[1]) >> (8 * (b & 7)) & 0xffull) != 0;
+      if (__ballot(set) == 0) continue;                  // (wave-uniform)
+      wall_step(parsing, indices, n, n1, n2, num, s0, s1, s2, at + b - skew, set, t, o.status);
+    }
+  }
+}
+
+int launch_branch_wall_stats(const int* parsing, const unsigned char* skeleton, const int* indices, int n0, int n1, int n2, int num,
+                             double s0, double s1, double s2, BranchWallOut o, hipStream_t s) {
+  SEUNET_CHECK(parsing && skeleton && indices && o.wall_count && o.offset_sq_sum && o.wall_sq_min && o.wall_sq_max && o.status,
+               "branch_wall_stats: null argument");
+  if (volume_check("branch_wall_stats", n0, n1, n2, 0)) return 1;
+  SEUNET_CHECK(num >= 0 && num <= label_stats_max_num(), "branch_wall_stats: num %d: labels 0 .. %d are supported", num,
+               label_stats_max_num());
+  SEUNET_CHECK(s0 > 0.0 && s1 > 0.0 && s2 > 0.0 && s0 < HUGE_VAL && s1 < HUGE_VAL && s2 < HUGE_VAL,
+               "branch_wall_stats: the sampling must be three positive finite numbers, got (%g, %g, %g)", s0, s1, s2);
+  const long long n = (long long)n0 * n1 * n2;
+  branch_wall_init_kernel<<<blocks_256(num + 1), 256, 0, s>>>(o, num);
+  const int skew = (int)(reinterpret_cast<uintptr_t>(skeleton) & 15);
+  branch_wall_kernel<<<grid_for((n + skew + 15) / 16), 256, 0, s>>>(parsing, skeleton, indices, n0, n1, n2, num, s0, s1, s2, skew, o);
+  SEUNET_LAUNCH_CHECK();
+  return 0;
+}
+
 }  // namespace seunet

@@ -1,4 +1,4 @@
-// Shared layer of the volume operations (components.hip, lung.hip, edt.hip, parse.hip, skeleton.hip, dti.hip, morph.hip, mesh.hip, mesh_label.hip, morphometry.hip): their launcher
+// Shared layer of the volume operations (components.hip, lung.hip, edt.hip, edt_sampling.hip, parse.hip, skeleton.hip, dti.hip, morph.hip, mesh.hip, mesh_label.hip, morphometry.hip): their launcher
 // prototypes, ONE workspace layout per operation, the extent check and the voxel / wave helpers their kernels share.
 //
 // Workspace contract: every operation has a layout struct filled by one function that walks a WsCarver.  Over a null base
@@ -160,6 +160,27 @@ struct EdtOut {            // what the last pass of the feature transform writes
 // invert = false: sites are the zero voxels (distance_transform_edt(vol)); true: the non-zero ones (EDT of 1 - vol)
 int run_edt(const unsigned char* vol, bool invert, int n0, int n1, int n2, EdtOut o, int* status_dev, void* workspace, size_t ws_bytes,
             hipStream_t s);
+// pass 0 alone: f0 = coordinate along axis 0 of the nearest site of each column (-1: none); status_dev (optional) = 1 without a site
+int run_edt_pass0(const unsigned char* vol, bool invert, int n0, int n1, int n2, short* f0, int* status_dev, hipStream_t s);
+
+// ---- EDT with voxel spacing (edt_sampling.hip): pass 0 of edt.hip, then passes 1 and 2 in float64 ---------------------------
+struct EdtSamplingWs {
+  short *f0, *fa, *fb;    // as EdtWs
+  short* spos;            // the stack of each line: positions only (the off-line terms are recomputed from the features)
+};
+static inline EdtSamplingWs edt_sampling_ws(WsCarver& c, int n0, int n1, int n2) {
+  const size_t n = (size_t)n0 * n1 * n2;
+  return EdtSamplingWs{c.take<short>(n), c.take<short>(n), c.take<short>(n), c.take<short>(n)};
+}
+struct EdtSamplingOut {    // what the last pass writes (each part optional)
+  double* dist;
+  int* indices;            // (3, n0, n1, n2)
+  int* lin;                // linear index of the feature
+};
+size_t edt_sampling_workspace_bytes(int n0, int n1, int n2);
+int launch_edt_sampling(const unsigned char* vol, int n0, int n1, int n2, double s0, double s1, double s2, EdtSamplingOut o,
+                        int* status_dev, void* workspace, size_t ws_bytes, hipStream_t s);
+
 int launch_mask_bits(const unsigned char* mask, long long n, unsigned long long* bits, hipStream_t s);
 int launch_hm_candidates(const unsigned char* label, const unsigned char* skel, const unsigned char* pred, int n0, int n1, int n2,
                          unsigned long long* skel_bits, unsigned long long* small_bits, hipStream_t s);
@@ -361,6 +382,14 @@ struct BranchStatsOut {
 };
 int launch_branch_stats(const int* parsing, const unsigned char* skeleton, const int* sqdist, int n0, int n1, int n2, int num,
                         BranchStatsOut out, hipStream_t s);
+// the distance from the skeleton to the wall per label, from the feature transform of the EDT with spacing (edt_sampling.hip)
+struct BranchWallOut {
+  long long *wall_count, *offset_sq_sum;    // [num + 1], [num + 1][3]
+  double *wall_sq_min, *wall_sq_max;        // [num + 1] each, reduced as their 64-bit patterns
+  int* status;
+};
+int launch_branch_wall_stats(const int* parsing, const unsigned char* skeleton, const int* indices, int n0, int n1, int n2, int num,
+                             double s0, double s1, double s2, BranchWallOut out, hipStream_t s);
 
 // ---- device helpers -------------------------------------------------------------------------------------------------------
 // raster index -> coordinates of an (n0, n1, n2) volume (n0 is not needed)

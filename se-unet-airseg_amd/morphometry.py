@@ -4,7 +4,11 @@
 per label in two streaming passes on the GPU, with no launch, pass or synchronise per label; ``branch_tree`` turns the face
 adjacency of ``label_adjacency`` into parent / generation on the host; ``branch_morphometry`` joins them into a ``BranchTable`` with
 lengths, volumes and radii in float64.  The reference has no such function: the definition is the docstrings here and
-include/seunet_hip.h, restated in plain numpy by tests/morphometry_oracle.py, and the integer tables equal that oracle bit for bit."""
+include/seunet_hip.h, restated in plain numpy by tests/morphometry_oracle.py, and the integer tables equal that oracle bit for bit.
+
+``branch_wall_distance`` reduces the feature transform of the EDT with voxel spacing over the skeleton in one
+more streaming pass: the distance from the centreline to the wall per branch as a length, which ``branch_morphometry(...,
+inscribed="physical")`` puts into the table; its tables equal tests/wall_distance_oracle.py bit for bit."""
 from __future__ import annotations
 
 import dataclasses
@@ -124,6 +128,84 @@ def branch_stats(parsing, skeleton, num: Optional[int] = None, sqdist=None) -> D
     return _branch_stats(vol, skel, sq, int(num))
 
 
+WALL_TABLES = ("wall_count", "offset_sq_sum", "wall_sq_min", "wall_sq_max")
+
+
+def _indices_in(a, vol, name="indices"):
+    if isinstance(a, np.ndarray):
+        a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(vol.device)
+    if not isinstance(a, torch.Tensor) or not a.is_cuda:
+        raise RuntimeError(f"{_PREFIX}: `{name}` must be a CUDA tensor resident on the GPU (there is no CPU path)")
+    if a.dtype != torch.int32:
+        raise TypeError(f"{_PREFIX}: `{name}` has dtype {a.dtype}; expected the int32 indices of "
+                        "distance_transform_edt(..., return_indices=True, sampling=spacing)")
+    if tuple(a.shape) != (3,) + tuple(vol.shape):
+        raise ValueError(f"{_PREFIX}: `{name}` shape {tuple(a.shape)} is not (3,) + `parsing`'s {tuple(vol.shape)}")
+    if a.device != vol.device:
+        raise ValueError(f"{_PREFIX}: `{name}` is on {a.device}, `parsing` on {vol.device}")
+    return a.contiguous()
+
+
+def _empty_wall(num: int) -> Dict[str, np.ndarray]:
+    return {"wall_count": np.zeros(num, np.int64), "offset_sq_sum": np.zeros((num, 3), np.int64),
+            "wall_sq_min": np.full(num, np.inf, np.float64), "wall_sq_max": np.zeros(num, np.float64)}
+
+
+def _branch_wall(vol, skel, ind, s, num: int) -> Dict[str, np.ndarray]:
+    """The tables of ``branch_wall_distance`` for device inputs that are already checked, rows 1..num."""
+    lib = _lib.load()
+    cap = int(lib.seunet_label_stats_max_num())
+    if not 0 <= num <= cap:
+        raise ValueError(f"{_PREFIX}: labels up to {cap} are supported, got num = {num}")
+    if vol.numel() == 0:
+        return _empty_wall(num)
+    rows = num + 1
+    dev = vol.device
+    with torch.cuda.device(dev):
+        # one buffer of 8-byte words: wall_count, offset_sq_sum (3 per row), wall_sq_min, wall_sq_max, the status word
+        buf = torch.empty(6 * rows + 1, dtype=torch.int64, device=dev)
+        base = buf.data_ptr()
+        _lib.check(lib.seunet_branch_wall_stats(vol.data_ptr(), skel.data_ptr(), ind.data_ptr(), *(int(v) for v in vol.shape), num,
+                                                s[0], s[1], s[2], base, base + 8 * rows, base + 8 * 4 * rows, base + 8 * 5 * rows,
+                                                base + 8 * 6 * rows, _lib.stream_ptr()), "branch_wall_stats")
+        host = buf.cpu().numpy()                             # the one copy back; it carries the status
+    if int(host[6 * rows:].view(np.int32)[0]) != 0:
+        raise ValueError(f"{_PREFIX}: the volume holds a label outside 0..{num}")
+    return {"wall_count": host[1:rows].copy(), "offset_sq_sum": host[rows:4 * rows].reshape(rows, 3)[1:].copy(),
+            "wall_sq_min": host[4 * rows:5 * rows].view(np.float64)[1:].copy(),
+            "wall_sq_max": host[5 * rows:6 * rows].view(np.float64)[1:].copy()}
+
+
+def branch_wall_distance(parsing, skeleton, spacing, num: Optional[int] = None, indices=None) -> Dict[str, np.ndarray]:
+    """The distance from the centreline to the wall per branch under the voxel ``spacing`` (a positive number or three of them), as a
+    dict of numpy arrays with one row per label 1..num, over the label's skeleton voxels that have a feature in ``indices``:
+
+    ``wall_count`` int64[num], their number; ``offset_sq_sum`` int64[num, 3], the exact sums of ``(index_a - coordinate_a)**2`` per
+    axis; ``wall_sq_min`` / ``wall_sq_max`` float64[num], minimum and maximum of ``(dt_0**2 + dt_1**2) + dt_2**2`` with
+    ``dt_a = float64(index_a - coordinate_a) * spacing[a]``, which is the square of ``distance_transform_edt(..., sampling=spacing)``
+    there before the root (none: +inf and 0.0).  All four are deterministic and equal tests/wall_distance_oracle.py bit for bit.
+
+    ``indices``: int32 (3, n0, n1, n2), ``distance_transform_edt(mask, return_indices=True, sampling=spacing)``; None computes it
+    for ``parsing != 0`` (a volume without a background voxel has none: ValueError).  One streaming pass over ``skeleton``
+    (``seunet_branch_wall_stats``) and one copy back that carries the status; ``parsing`` is read at skeleton voxels only, so a
+    label outside 0..num is a ValueError when a skeleton voxel carries it.  ``num=None``: ``int(parsing.max())``.  CUDA tensors or
+    numpy arrays; the inputs are not modified."""
+    s = prep.normalize_sampling(spacing, "spacing")
+    vol, skel, _, _ = _inputs(parsing, skeleton, None)
+    if skel is None:
+        raise ValueError(f"{_PREFIX}: branch_wall_distance needs the skeleton")
+    if num is None:
+        num = max(int(vol.max()), 0) if vol.numel() else 0
+    num = int(num)
+    if indices is not None:
+        ind = _indices_in(indices, vol)
+    elif vol.numel():
+        _, ind, _ = prep._edt_sampling((vol != 0).to(torch.uint8), s, False, True)
+    else:
+        ind = None
+    return _branch_wall(vol, skel, ind, s, num)
+
+
 def branch_tree(counts, adjacency) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """The branch tree from the face adjacency, on the host.  ``counts``: voxels of the labels 1..num; ``adjacency``: (num, num),
     non-zero where two labels meet across a face (both as ``label_adjacency`` returns them).  The root is the label with the most
@@ -166,7 +248,8 @@ class BranchTable:
     """One row per label 1..num (index k - 1 = label k).  Integer columns: those of ``branch_stats``.  float64 columns: ``volume``,
     ``centroid`` (num, 3), ``length`` and ``radius_equivalent`` in the units of ``spacing``; ``radius_inscribed_rms`` / ``_min`` /
     ``_max`` in VOXEL units of the unit-sampling EDT, which convert to the units of ``spacing`` by one factor only when the spacing
-    is isotropic.  Tree columns: ``parent`` (label value, 0 root, -1 none), ``generation``, ``n_children``, ``is_leaf``.  Whole tree:
+    is isotropic -- or, where the tables of ``branch_wall_distance`` are given (``wall_count``, ``offset_sq_sum``, ``wall_sq_min``,
+    ``wall_sq_max``; None otherwise), in the units of ``spacing`` from the EDT with that spacing.  Tree columns: ``parent`` (label value, 0 root, -1 none), ``generation``, ``n_children``, ``is_leaf``.  Whole tree:
     ``n_branches`` (labels with voxels), ``n_leaves``, ``total_length``, ``max_generation`` (-1 without a root),
     ``branches_per_generation`` (int64[max_generation + 1])."""
     num: int
@@ -197,13 +280,20 @@ class BranchTable:
     total_length: float
     max_generation: int
     branches_per_generation: np.ndarray
+    wall_count: Optional[np.ndarray] = None
+    offset_sq_sum: Optional[np.ndarray] = None
+    wall_sq_min: Optional[np.ndarray] = None
+    wall_sq_max: Optional[np.ndarray] = None
 
     def to_dict(self) -> dict:
         return {f.name: getattr(self, f.name) for f in dataclasses.fields(self)}
 
     @classmethod
-    def from_stats(cls, stats: Dict[str, np.ndarray], adjacency, spacing: Sequence[float] = (1.0, 1.0, 1.0)) -> "BranchTable":
-        """The derived columns from the integer tables of ``branch_stats`` and a (num, num) face adjacency; host only."""
+    def from_stats(cls, stats: Dict[str, np.ndarray], adjacency, spacing: Sequence[float] = (1.0, 1.0, 1.0),
+                   wall: Optional[Dict[str, np.ndarray]] = None) -> "BranchTable":
+        """The derived columns from the integer tables of ``branch_stats`` and a (num, num) face adjacency; host only.  ``wall``: the
+        tables of ``branch_wall_distance`` for the same ``spacing``; the inscribed radii are then ``sqrt((s0^2 sum d0^2 + s1^2 sum d1^2
+        + s2^2 sum d2^2) / wall_count)``, ``sqrt(wall_sq_min)`` and ``sqrt(wall_sq_max)``, nan where ``wall_count`` is 0."""
         s = np.asarray(spacing, dtype=np.float64).reshape(3)
         if not (np.all(np.isfinite(s)) and np.all(s > 0)):
             raise ValueError(f"{_PREFIX}: spacing must be three positive numbers, got {tuple(spacing)}")
@@ -220,6 +310,14 @@ class BranchTable:
             rms = np.where(measured, np.sqrt(stats["r2_sum"].astype(np.float64) / skv), np.nan)
             rmin = np.where(measured, np.sqrt(np.where(measured, stats["r2_min"], 0).astype(np.float64)), np.nan)
             rmax = np.where(measured, np.sqrt(np.where(measured, stats["r2_max"], 0).astype(np.float64)), np.nan)
+            if wall is not None:
+                wall = {k: np.asarray(wall[k]) for k in WALL_TABLES}
+                count = wall["wall_count"].astype(np.int64)
+                measured = count > 0
+                sq = wall["offset_sq_sum"].astype(np.float64)
+                rms = np.where(measured, np.sqrt((s[0] * s[0] * sq[:, 0] + s[1] * s[1] * sq[:, 1] + s[2] * s[2] * sq[:, 2]) / count), np.nan)
+                rmin = np.where(measured, np.sqrt(np.where(measured, wall["wall_sq_min"], 0.0)), np.nan)
+                rmax = np.where(measured, np.sqrt(np.where(measured, wall["wall_sq_max"], 0.0)), np.nan)
         parent, generation, n_children = branch_tree(voxels, adjacency)
         is_leaf = (generation >= 0) & (n_children == 0)
         max_generation = int(generation.max()) if num else -1
@@ -228,11 +326,11 @@ class BranchTable:
                    volume=volume, centroid=centroid, length=length, radius_equivalent=radius_equivalent, radius_inscribed_rms=rms,
                    radius_inscribed_min=rmin, radius_inscribed_max=rmax, parent=parent, generation=generation, n_children=n_children,
                    is_leaf=is_leaf, n_branches=int((voxels > 0).sum()), n_leaves=int(is_leaf.sum()), total_length=float(length.sum()),
-                   max_generation=max_generation, branches_per_generation=per_generation)
+                   max_generation=max_generation, branches_per_generation=per_generation, **(wall or {}))
 
 
 def branch_morphometry(parsing, skeleton=None, spacing: Sequence[float] = (1.0, 1.0, 1.0), num: Optional[int] = None,
-                       sqdist=None) -> BranchTable:
+                       sqdist=None, inscribed: str = "voxel") -> BranchTable:
     """The per-branch table of a ``parsing`` volume (``tree_parsing`` or ``airway_parse``): ``BranchTable``.
 
     ``volume = voxels * s0 s1 s2``; ``centroid = coord_sum / voxels * spacing`` (nan for a label without voxels);
@@ -241,22 +339,39 @@ def branch_morphometry(parsing, skeleton=None, spacing: Sequence[float] = (1.0, 
     sqrt(volume / (pi length))``, the radius of the cylinder of that volume and length, correct under anisotropic spacing, nan where
     the length is 0; ``radius_inscribed_rms / _min / _max = sqrt(r2_sum / skeleton_voxels), sqrt(r2_min), sqrt(r2_max)``: the distance
     from the centreline to the wall in VOXEL units of the unit-sampling EDT (nan for a label without skeleton voxels), which is a
-    length in the units of ``spacing`` only after multiplying by an isotropic spacing; an EDT with sampling is not offered.  The tree
-    columns come from ``branch_tree`` on the face adjacency of ``seunet_label_stats``.
+    length in the units of ``spacing`` only after multiplying by an isotropic spacing; ``inscribed="physical"`` gives them in the
+    units of ``spacing`` under any spacing.  The tree columns come from ``branch_tree`` on the face adjacency of
+    ``seunet_label_stats``.
+
+    ``inscribed="physical"``: the three inscribed radii come from ``branch_wall_distance`` on the EDT of ``parsing != 0`` with
+    ``sampling=spacing``: ``radius_inscribed_rms = sqrt((s0^2 sum d0^2 + s1^2 sum d1^2 + s2^2 sum d2^2) / wall_count)``, ``_min =
+    sqrt(wall_sq_min)``, ``_max = sqrt(wall_sq_max)`` (nan where ``wall_count`` is 0); the table carries ``wall_count``,
+    ``offset_sq_sum``, ``wall_sq_min`` and ``wall_sq_max`` (None in voxel mode); ``r2_sum`` / ``r2_min`` / ``r2_max`` keep their
+    empty values (0, INT32_MAX, -1), and passing ``sqdist`` is a ValueError.
 
     ``skeleton=None`` thins ``parsing != 0`` with ``skeletonize_3d``; ``sqdist=None`` takes the squared EDT of ``parsing != 0`` (a
     volume without a background voxel has none: ValueError).  ``num=None``: ``int(parsing.max())``.  CUDA tensors or numpy arrays in,
     numpy columns out; the inputs are not modified."""
+    if inscribed not in ("voxel", "physical"):
+        raise ValueError(f"{_PREFIX}: inscribed must be 'voxel' or 'physical', got {inscribed!r}")
+    physical = inscribed == "physical"
+    if physical and sqdist is not None:
+        raise ValueError(f"{_PREFIX}: `sqdist` is the unit-sampling squared distance; it is not used with inscribed='physical'")
+    s = prep.normalize_sampling(spacing, "spacing") if physical else None
     vol, skel, sq, _ = _inputs(parsing, skeleton, sqdist)
     if num is None:
         num = max(int(vol.max()), 0) if vol.numel() else 0
     num = int(num)
+    ind = None
     if skel is None or sq is None:
         mask = (vol != 0).to(torch.uint8)
         if skel is None:
             skel = prep.skeletonize_3d(mask)
-        if sq is None and vol.numel():
+        if physical and vol.numel():
+            _, ind, _ = prep._edt_sampling(mask, s, False, True)
+        elif sq is None and vol.numel():
             sq = prep.distance_transform_edt(mask, return_distances=False, return_sqdist=True)
     stats = _branch_stats(vol, skel, sq, num)
+    wall = _branch_wall(vol, skel, ind, s, num) if physical else None
     _, adjacency = prep._label_stats(vol, num)
-    return BranchTable.from_stats(stats, adjacency[1:, 1:], spacing)
+    return BranchTable.from_stats(stats, adjacency[1:, 1:], spacing, wall)

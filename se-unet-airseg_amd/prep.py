@@ -41,15 +41,56 @@ def _status(status, what):
         raise ValueError(f"seunet prep: {what}")
 
 
+def normalize_sampling(sampling, what: str = "sampling") -> Tuple[float, float, float]:
+    """``sampling`` as three float64 values, like scipy's ``_normalize_sequence``: a scalar is repeated over the three axes, a
+    sequence must have length 3.  ValueError for any other length and for values that are not positive and finite."""
+    s = np.asarray(sampling, dtype=np.float64)
+    if s.ndim == 0:
+        s = np.repeat(s, 3)
+    if s.shape != (3,):
+        raise ValueError(f"seunet prep: `{what}` must be a number or a sequence of 3 numbers, got shape {s.shape}")
+    if not (np.all(np.isfinite(s)) and np.all(s > 0)):
+        raise ValueError(f"seunet prep: `{what}` must be positive and finite, got {tuple(float(v) for v in s)}")
+    return tuple(float(v) for v in s)
+
+
+def _edt_sampling(vol, s, want_dist: bool, want_indices: bool, want_lin: bool = False):
+    """The sampled EDT of a checked device mask: (dist, indices, lin), None where not wanted.  ValueError without a zero voxel."""
+    n0, n1, n2 = (int(v) for v in vol.shape)
+    lib = _lib.load()
+    dev = vol.device
+    with torch.cuda.device(dev):
+        ws = workspace(lib.seunet_edt_sampling_workspace_bytes, n0, n1, n2, device=dev, min_bytes=1)
+        dist = torch.empty((n0, n1, n2), dtype=torch.float64, device=dev) if want_dist else None
+        ind = torch.empty((3, n0, n1, n2), dtype=torch.int32, device=dev) if want_indices else None
+        lin = torch.empty((n0, n1, n2), dtype=torch.int32, device=dev) if want_lin else None
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+        _lib.check(lib.seunet_edt_sampling(vol.data_ptr(), n0, n1, n2, s[0], s[1], s[2], _lib.ptr(dist), _lib.ptr(ind), _lib.ptr(lin),
+                                           status.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "edt_sampling")
+        _status(status, "distance_transform_edt: the volume has no zero voxel (the distance is undefined)")
+    return dist, ind, lin
+
+
 def distance_transform_edt(volume: torch.Tensor, return_distances: bool = True, return_indices: bool = False,
-                           return_sqdist: bool = False):
-    """``scipy.ndimage.distance_transform_edt(volume, return_indices=...)`` with unit sampling, on the GPU: for every voxel
-    the distance to the nearest zero voxel.  ``dist`` (float64) and ``indices`` (int32, (3, n0, n1, n2)) are bitwise
+                           return_sqdist: bool = False, *, sampling=None):
+    """``scipy.ndimage.distance_transform_edt(volume, sampling=..., return_indices=...)`` on the GPU: for every voxel the
+    distance to the nearest zero voxel.  ``dist`` (float64) and ``indices`` (int32, (3, n0, n1, n2)) are bitwise
     scipy's, ties included; ``sqdist`` is the int32 squared distance.  Returns the requested outputs in the order
-    (sqdist, dist, indices), a single tensor when one is requested.  A volume with no zero voxel raises ValueError."""
+    (sqdist, dist, indices), a single tensor when one is requested.  A volume with no zero voxel raises ValueError.
+
+    ``sampling=None``: unit sampling, the integer passes of csrc/edt.hip.  ``sampling`` a positive finite number or three of them:
+    the voxel spacing along each axis, scipy's feature transform in float64 (csrc/edt_sampling.hip, DESIGN.md section 3k);
+    ``dist`` is then in the units of ``sampling``, and ``return_sqdist`` is a ValueError (there is no integer squared distance)."""
     vol = _vol(volume, "volume")
     if not (return_distances or return_indices or return_sqdist):
         raise ValueError("seunet prep: at least one of return_distances / return_indices / return_sqdist must be set")
+    if sampling is not None:
+        s = normalize_sampling(sampling)
+        if return_sqdist:
+            raise ValueError("seunet prep: return_sqdist is the integer squared distance of unit sampling; it is not defined with `sampling`")
+        dist, ind, _ = _edt_sampling(vol, s, bool(return_distances), bool(return_indices))
+        out = tuple(t for t in (dist, ind) if t is not None)
+        return out[0] if len(out) == 1 else out
     n0, n1, n2 = (int(v) for v in vol.shape)
     lib = _lib.load()
     dev = vol.device
