@@ -3,6 +3,7 @@
 #include "seunet_common.h"
 #include "epilogue.h"
 #include "volume.h"
+#include "wgrad.h"
 #include "../../include/seunet_hip.h"
 
 using namespace seunet;

@@ -5,6 +5,7 @@
 // layout is recomputed by the backward call).
 #include "seunet_common.h"
 #include "epilogue.h"
+#include "wgrad.h"
 #include "../../include/seunet_hip.h"
 
 #include <algorithm>
@@ -15,6 +16,30 @@
 #include <vector>
 
 namespace seunet {
+
+// kernel routing, the part other files call (wgrad.h): the non-streaming weight gradient's kernel by size.  The rest of the
+// routing is Plan::route below.
+ConvKernel wgrad_kernel(int dtype, int taps, int dil, const SrcList& x, int cin_logical, int cout, Dims d, long long src_dist) {
+  if (taps == 1) {
+    // where the whole-GEMM 1x1x1 kernel beats the tiled kernel (isolated launches): many (ci, co) combos there, i.e. many
+    // re-reads -- ec63 (8 combos, 1 M voxels) 0.104 vs 0.165 ms, 192 -> 128 channels (24 combos, 131 k voxels) 0.051 vs 0.085 ms;
+    // not dc42 (2 combos: 0.059 vs 0.039 ms) nor dc22 (8 combos but 131 k voxels: 0.033 vs 0.023 ms, four chunks per workgroup do
+    // not amortise the pipeline fill).  (ec93 is 192 -> 64 at width 1: 12 combos on 131 k voxels, on dc22's side, and not a form
+    // wgrad_1x1.hip instantiates.)
+    const int combos = cdiv(cin_logical, 32) * cdiv(cout, 32);
+    const long long nv = (long long)d.N * d.vox();
+    const bool pays = combos >= 16 || (combos >= 8 && nv >= 500000);
+    return pays && wgrad_1x1_supported(dtype, x, cin_logical, cout) ? ConvKernel::Wgrad1x1 : ConvKernel::Tiled;
+  }
+  // where the marching kernel beats the tiled kernel (isolated launches, 4 samples): the fine levels (rows of >= 32 voxels,
+  // >= 48^3); every dilation-2 layer down to 16^3 (the tiled kernel works on parity sub-lattices there: 32^3 64 -> 64 0.057 vs
+  // 0.080 ms, 16^3 128 -> 128 0.058 vs 0.075 ms); 256-channel inputs (dc1 at width 2: 0.118 vs 0.134 ms; 128 at width 1).  Dilation 1 with <= 128 input
+  // channels on the coarse levels is a tie and stays where it was.
+  const bool fine = d.W >= 32 && (long long)d.D * d.H * d.W >= 48LL * 48 * 48;
+  const bool pays = fine || dil == 2 || cin_logical >= 256;
+  return pays && wgrad_march_supported(dtype, taps, dil, x, cin_logical, cout, d, src_dist) ? ConvKernel::March : ConvKernel::Tiled;
+}
+
 namespace {
 
 // ---------------------------------------------------------------------------------------------------
@@ -132,7 +157,7 @@ constexpr int kNumOps = sizeof(kOps) / sizeof(kOps[0]);
 inline bool is_input(int t) { return t <= T_X2; }
 
 // ---------------------------------------------------------------------------------------------------
-// kernel routing: which kernel runs each pass of each conv (Plan::route, and wgrad_kernel below for the non-streaming weight
+// kernel routing: which kernel runs each pass of each conv (Plan::route, and wgrad_kernel above for the non-streaming weight
 // gradient).  The packed weights, the statistics slots, the workspace and the dispatch all follow from that one choice.
 // ---------------------------------------------------------------------------------------------------
 // levels on which the marching conv pays: full 32-voxel rows and enough (y, x) patches x planes for one workgroup per CU
@@ -152,44 +177,6 @@ int conv_slots(ConvKernel k, const Dims& dm, int taps, int dil, int cin, int cou
     default: return conv_stats_tiles(dm, taps, dil);
   }
 }
-
-}  // namespace
-
-ConvKernel wgrad_kernel(int dtype, int taps, int dil, const SrcList& x, int cin_logical, int cout, Dims d, long long src_dist) {
-  if (taps == 1) {
-    // where the whole-GEMM 1x1x1 kernel beats the tiled kernel (isolated launches): many (ci, co) combos there, i.e. many
-    // re-reads -- ec63 (8 combos, 1 M voxels) 0.104 vs 0.165 ms, 192 -> 128 channels (24 combos, 131 k voxels) 0.051 vs 0.085 ms;
-    // not dc42 (2 combos: 0.059 vs 0.039 ms) nor dc22 (8 combos but 131 k voxels: 0.033 vs 0.023 ms, four chunks per workgroup do
-    // not amortise the pipeline fill).  (ec93 is 192 -> 64 at width 1: 12 combos on 131 k voxels, on dc22's side, and not a form
-    // wgrad_1x1.hip instantiates.)
-    const int combos = cdiv(cin_logical, 32) * cdiv(cout, 32);
-    const long long nv = (long long)d.N * d.vox();
-    const bool pays = combos >= 16 || (combos >= 8 && nv >= 500000);
-    return pays && wgrad_1x1_supported(dtype, x, cin_logical, cout) ? ConvKernel::Wgrad1x1 : ConvKernel::Tiled;
-  }
-  // where the marching kernel beats the tiled kernel (isolated launches, 4 samples): the fine levels (rows of >= 32 voxels,
-  // >= 48^3); every dilation-2 layer down to 16^3 (the tiled kernel works on parity sub-lattices there: 32^3 64 -> 64 0.057 vs
-  // 0.080 ms, 16^3 128 -> 128 0.058 vs 0.075 ms); 256-channel inputs (dc1 at width 2: 0.118 vs 0.134 ms; 128 at width 1).  Dilation 1 with <= 128 input
-  // channels on the coarse levels is a tie and stays where it was.
-  const bool fine = d.W >= 32 && (long long)d.D * d.H * d.W >= 48LL * 48 * 48;
-  const bool pays = fine || dil == 2 || cin_logical >= 256;
-  return pays && wgrad_march_supported(dtype, taps, dil, x, cin_logical, cout, d, src_dist) ? ConvKernel::March : ConvKernel::Tiled;
-}
-
-int run_wgrad(ConvKernel k, int dtype, int taps, int dil, const SrcList& x, int cin_logical, const void* dy, int cout, float* dw,
-              void* workspace, size_t ws_bytes, Dims d, hipStream_t s) {
-  switch (k) {
-    case ConvKernel::Naive: return launch_wgrad_naive(dtype, taps, dil, x, cin_logical, dy, cout, dw, d, s);
-    case ConvKernel::Tiled: return launch_wgrad(dtype, taps, dil, x, cin_logical, dy, cout, dw, workspace, ws_bytes, d, s);
-    case ConvKernel::Stream:
-      return launch_wgrad_stream(dtype, dil, x.ptr[0], x.C[0], cin_logical, dy, cout, cout, dw, workspace, ws_bytes, d, s);
-    case ConvKernel::March: return launch_wgrad_march(dtype, taps, dil, x, cin_logical, dy, cout, dw, workspace, ws_bytes, d, s);
-    case ConvKernel::Wgrad1x1: return launch_wgrad_1x1(dtype, x, cin_logical, dy, cout, dw, workspace, ws_bytes, d, s);
-  }
-  return fail("wgrad: unknown kernel %d", (int)k);
-}
-
-namespace {
 
 // ---------------------------------------------------------------------------------------------------
 // workspace plan

@@ -307,37 +307,9 @@ int launch_conv_march_pack_multi(int dtype, const MarchPackJob* jobs, int n, hip
 int launch_conv_march(int dtype, int dil, const SrcList& src, const void* wpack, const float* bias, const DstList& dst, double* stats,
                       Dims d, hipStream_t s);
 
-// streaming small-channel weight gradient (wgrad_stream.hip)
-bool wgrad_stream_supported(int dtype, int taps, int dil, int x_c, int dy_c);
-size_t wgrad_stream_workspace_bytes(int x_c, int dy_c, int dil, Dims d);
-int launch_wgrad_stream(int dtype, int dil, const void* x, int x_c, int cin_w, const void* dy, int dy_c, int cout_w, float* dw,
-                        void* workspace, size_t ws_bytes, Dims d, hipStream_t s);
-
-// weight gradient (wgrad.hip).  The workspace serves whichever weight-gradient kernel the layer is routed to: the most any of
-// them needs for these channels (the tiled kernel's slabs, wgrad_1x1_workspace_bytes, wgrad_march_workspace_bytes)
-static constexpr int WG_TILED_SLABS = 512;   // slabs of the tiled kernel over all (ci, co) combos: two workgroups per CU
-size_t wgrad_workspace_bytes(int taps, int cin, int cout);
-int launch_wgrad(int dtype, int taps, int dil, const SrcList& x, int cin_logical, const void* dy,
-                 int cout, float* dw_torch, void* workspace, size_t ws_bytes, Dims d, hipStream_t s);
-// marching weight gradient (wgrad_march.hip); src_dist: byte distance between the two sources of x (32-bit reach)
-bool wgrad_march_supported(int dtype, int taps, int dil, const SrcList& x, int cin_logical, int cout, Dims d, long long src_dist);
-int launch_wgrad_march(int dtype, int taps, int dil, const SrcList& x, int cin_logical, const void* dy, int cout,
-                       float* dw, void* workspace, size_t ws_bytes, Dims d, hipStream_t s);
-size_t wgrad_march_workspace_bytes(int taps, int cin, int cout);   // its bound for any volume; 0 for channels it does not take
-// 1x1x1 weight gradient of the aggregation convolutions (wgrad_1x1.hip)
-bool wgrad_1x1_supported(int dtype, const SrcList& x, int cin_logical, int cout);
-int launch_wgrad_1x1(int dtype, const SrcList& x, int cin_logical, const void* dy, int cout, float* dw, void* workspace,
-                     size_t ws_bytes, Dims d, hipStream_t s);
-size_t wgrad_1x1_workspace_bytes(int cin, int cout);               // its bound for any volume
-int launch_wgrad_naive(int dtype, int taps, int dil, const SrcList& x, int cin_logical,
-                       const void* dy, int cout, float* dw_torch, Dims d, hipStream_t s);
+// weight gradients (wgrad.hip, wgrad_march.hip, wgrad_1x1.hip, wgrad_stream.hip): wgrad.h
 // the kernel of each conv pass: chosen in one place, net.cpp (kernel routing)
 enum class ConvKernel { Naive, Tiled, Stream, March, Wgrad1x1 };
-// the non-streaming weight gradient's choice by size (the network plan and seunet_conv3d_wgrad); src_dist as above
-ConvKernel wgrad_kernel(int dtype, int taps, int dil, const SrcList& x, int cin_logical, int cout, Dims d, long long src_dist);
-// weight gradient on kernel k (Stream: one source, dy with cout channels)
-int run_wgrad(ConvKernel k, int dtype, int taps, int dil, const SrcList& x, int cin_logical, const void* dy, int cout, float* dw,
-              void* workspace, size_t ws_bytes, Dims d, hipStream_t s);
 
 // normalisation / gates / cat (epilogue.hip, gate.hip, cat.hip): epilogue.h
 

@@ -15,11 +15,13 @@
 //               4-voxel x 16-channel block -> conflict-free), tap shifts only move the row address (tap base register +
 //               immediate).  The phase is pipelined by hand: fragments are requested two MFMAs ahead.
 //               f32 : v_mfma_f32_32x32x2_f32 (K-step = 2 voxels, one element per lane, plain loads)
-//   output      each workgroup stores its accumulators once to a slab (1x1x1: after summing its four waves in LDS); a
-//               second kernel sums the slabs 16-way parallel in a fixed order (deterministic, no atomics, f64) straight
-//               into the PyTorch (Cout,Cin,3,3,3) layout
+//   output      each workgroup stores its accumulators once to a slab (1x1x1: after summing its four waves in LDS); the
+//               family's shared reduction (wgrad.h) sums the slabs in a fixed order in f64 straight into the PyTorch
+//               (Cout,Cin,3,3,3) layout
+// This file also holds what enumerates the whole family: wgrad_workspace_bytes (the bound) and run_wgrad (the dispatch).
 #include "seunet_common.h"
 #include "mfma.h"
+#include "wgrad.h"
 #include <climits>
 #include <cstdlib>
 
@@ -372,38 +374,16 @@ wgrad_kernel(WgArgs a) {
 #endif
 }
 
-// dW (PyTorch layout) = fixed-order sum of the slabs.  A 256-thread block owns 16 consecutive slab elements
-// (tap, ci, co); its 16 thread groups each sum every 16th slab (64-B coalesced reads, 16-fold shorter dependent
-// chains than one thread per element: that version averaged 37 us per launch, ~1 ms per training step), and the 16
-// partial sums are combined in a fixed order through LDS.  f64 throughout; deterministic, no atomics.
-__global__ void __launch_bounds__(256)
-wgrad_reduce_kernel(const float* __restrict__ slab, int nslab, int taps, int cin_w, int cout_w, int co_tiles,
-                    float* __restrict__ dw) {
-  const int per = taps * 1024;
-  const int el = threadIdx.x & 15, part = threadIdx.x >> 4;
-  const int e = blockIdx.x * 16 + el;             // element inside one slab (per is a multiple of 16)
-  const int combo = blockIdx.y;
-  const float* p = slab + (size_t)combo * nslab * per + e;
-  double s0 = 0.0, s1 = 0.0;
-  int k = part;
-  for (; k + 16 < nslab; k += 32) {
-    s0 += (double)p[(size_t)k * per];
-    s1 += (double)p[(size_t)(k + 16) * per];
-  }
-  if (k < nslab) s0 += (double)p[(size_t)k * per];
-  __shared__ double red[16][17];
-  red[part][el] = s0 + s1;
-  __syncthreads();
-  if (part == 0) {
-    double t = red[0][el];
-#pragma unroll
-    for (int q = 1; q < 16; ++q) t += red[q][el];
+// element e = (tap, ci, co) of a slab of the 32 x 32 combo -> dW (cout_w, cin_w, taps)
+struct WgMap {
+  int taps, cin_w, cout_w, co_tiles;
+  __device__ long long operator()(int combo, int e) const {
     const int tap = e >> 10, ci = (combo / co_tiles) * 32 + ((e >> 5) & 31), co = (combo % co_tiles) * 32 + (e & 31);
-    if (ci < cin_w && co < cout_w) dw[((size_t)co * cin_w + ci) * taps + tap] = (float)t;
+    return ci < cin_w && co < cout_w ? (long long)(((size_t)co * cin_w + ci) * taps + tap) : -1;
   }
-}
+};
 
-// persistent workgroups per (ci, co) combo == slabs the reduce kernel has to sum; ~2 resident workgroups per CU in total
+// persistent workgroups per (ci, co) combo == slabs the reduction has to sum; ~2 resident workgroups per CU in total
 static inline int wgrad_groups(int combos, int total_tiles) {
   int g = WG_TILED_SLABS / combos;   // two resident workgroups per CU
   if (g < 16) g = 16;
@@ -412,17 +392,31 @@ static inline int wgrad_groups(int combos, int total_tiles) {
   if (g < 1) g = 1;
   return g;
 }
-static size_t wgrad_tiled_bytes(int taps, int combos, int groups) {
-  return 256 + (size_t)combos * groups * taps * 1024 * sizeof(float);   // 256 zero bytes + slabs
+static WgSlabs wgrad_tiled_slabs(int taps, int combos, int groups) {   // one slab of taps x 32 x 32 per workgroup
+  return {WG_SLAB_PREFIX, (size_t)combos * groups, (size_t)taps * 1024};
 }
 
 // one workspace serves whichever weight-gradient kernel the layer is routed to: the most any of them asks for these channels,
 // whatever the volume (each term is defined next to the launcher that checks it)
 size_t wgrad_workspace_bytes(int taps, int cin, int cout) {
   const int combos = cdiv(cin, 32) * cdiv(cout, 32);
-  const size_t tiled = wgrad_tiled_bytes(taps, combos, wgrad_groups(combos, INT_MAX));
+  const size_t tiled = wgrad_tiled_slabs(taps, combos, wgrad_groups(combos, INT_MAX)).bytes();
   const size_t other = taps == 1 ? wgrad_1x1_workspace_bytes(cin, cout) : wgrad_march_workspace_bytes(taps, cin, cout);
   return tiled > other ? tiled : other;
+}
+
+// weight gradient on kernel k: the dispatch over the same family
+int run_wgrad(ConvKernel k, int dtype, int taps, int dil, const SrcList& x, int cin_logical, const void* dy, int cout, float* dw,
+              void* workspace, size_t ws_bytes, Dims d, hipStream_t s) {
+  switch (k) {
+    case ConvKernel::Naive: return launch_wgrad_naive(dtype, taps, dil, x, cin_logical, dy, cout, dw, d, s);
+    case ConvKernel::Tiled: return launch_wgrad(dtype, taps, dil, x, cin_logical, dy, cout, dw, workspace, ws_bytes, d, s);
+    case ConvKernel::Stream:
+      return launch_wgrad_stream(dtype, dil, x.ptr[0], x.C[0], cin_logical, dy, cout, cout, dw, workspace, ws_bytes, d, s);
+    case ConvKernel::March: return launch_wgrad_march(dtype, taps, dil, x, cin_logical, dy, cout, dw, workspace, ws_bytes, d, s);
+    case ConvKernel::Wgrad1x1: return launch_wgrad_1x1(dtype, x, cin_logical, dy, cout, dw, workspace, ws_bytes, d, s);
+  }
+  return fail("wgrad: unknown kernel %d", (int)k);
 }
 
 template <typename T, int TAPS, int DIL, int NW>
@@ -456,13 +450,11 @@ int launch_wgrad(int dtype, int taps, int dil, const SrcList& x, int cin_logical
   SEUNET_CHECK(taps == 1 || dil == 1 || dil == 2, "wgrad: dilation %d unsupported", dil);
   SEUNET_CHECK(x.n >= 1 && x.n <= 3, "wgrad: 1..3 sources");
   SEUNET_CHECK(cout % 8 == 0 && cin_logical >= 1 && cin_logical <= x.total(), "wgrad: bad channel counts");
-  SEUNET_CHECK(ws_bytes >= wgrad_workspace_bytes(taps, cin_logical, cout), "wgrad: workspace too small");
   WgArgs a{};
   wg_sources(a, x, cin_logical);
   a.dy = dy; a.cout = cout;
   a.zero = device_zero_page();
   SEUNET_CHECK(a.zero != nullptr, "wgrad: cannot allocate the device zero page");
-  a.slab = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(workspace) + 256);
   a.N = d.N; a.D = d.D; a.H = d.H; a.W = d.W;
   const int tz = dtype_size(dtype) == 2 ? WgTile<bf16_t>::TZ : WgTile<float>::TZ;
   const int ty = dtype_size(dtype) == 2 ? WgTile<bf16_t>::TY : WgTile<float>::TY;
@@ -472,6 +464,8 @@ int launch_wgrad(int dtype, int taps, int dil, const SrcList& x, int cin_logical
   a.debug = g_conv_debug;
   const int combos = cdiv(cin_logical, 32) * a.co_tiles;
   const int G = wgrad_groups(combos, a.tx * a.ty * a.tz * st * st * st * d.N);
+  a.slab = wgrad_tiled_slabs(taps, combos, G).base(workspace, ws_bytes);
+  SEUNET_CHECK(a.slab != nullptr, "wgrad: workspace too small");
   dim3 grid(G, combos);
   int e;
   SEUNET_DTYPE_SWITCH(dtype, {
@@ -480,10 +474,7 @@ int launch_wgrad(int dtype, int taps, int dil, const SrcList& x, int cin_logical
     else e = wgrad_launch_one<T, 27, 2, 4>(a, grid, s);
   });
   if (e) return e;
-  wgrad_reduce_kernel<<<dim3(taps * 1024 / 16, combos), 256, 0, s>>>(a.slab, G, taps, cin_logical, cout,
-                                                                            a.co_tiles, dw);
-  SEUNET_LAUNCH_CHECK();
-  return 0;
+  return launch_wgrad_reduce(a.slab, G, taps * 1024, combos, WgMap{taps, cin_logical, cout, a.co_tiles}, dw, s);
 }
 
 // ------------------------------------------------------------------------------------------------

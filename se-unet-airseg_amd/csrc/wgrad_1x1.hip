@@ -11,10 +11,11 @@
 //   * the four waves split the 16-channel input blocks, every wave pairs its blocks with all output blocks:
 //     v_mfma_f32_16x16x32, A = dY^T (16 channels x 32 voxels), B = X (32 voxels x 16 channels), both through
 //     ds_read_b64_tr_b16; accumulators (<= 24 pairs per wave) live in registers for the whole launch;
-//   * one slab per workgroup, fixed-order f64 slab sum (deterministic, no atomics).
+//   * one slab per workgroup, summed by the family's shared reduction (wgrad.h).
 #include "seunet_common.h"
 #include "lds_dma.h"
 #include "mfma.h"
+#include "wgrad.h"
 #include <cstdlib>
 
 namespace seunet {
@@ -176,34 +177,17 @@ wgrad_1x1_kernel(W1Args a) {
     for (int k = 0; k < NCOB; ++k) *reinterpret_cast<f32x4*>(out + (c * NCOB + k) * 256) = acc[c][k];
 }
 
-// sum of the slabs, 16-way parallel in a fixed order, f64 -> dw (cout, cin)
-__global__ void __launch_bounds__(256)
-wgrad_1x1_reduce_kernel(const float* __restrict__ slab, int nslab, int cibw, int ncob, int cin, float* __restrict__ dw) {
-  const int per = W1_NW * cibw * ncob * 256;
-  const int el = threadIdx.x & 15, part = threadIdx.x >> 4;
-  const int e = blockIdx.x * 16 + el;
-  const float* ptr = slab + e;
-  double s0 = 0.0, s1 = 0.0;
-  int k = part;
-  for (; k + 16 < nslab; k += 32) {
-    s0 += (double)ptr[(size_t)k * per];
-    s1 += (double)ptr[(size_t)(k + 16) * per];
-  }
-  if (k < nslab) s0 += (double)ptr[(size_t)k * per];
-  __shared__ double red[16][17];
-  red[part][el] = s0 + s1;
-  __syncthreads();
-  if (part == 0) {
-    double t = red[0][el];
-#pragma unroll
-    for (int j = 1; j < 16; ++j) t += red[j][el];
+// element e = (wave, input block, output block, lane, component) of a slab (one combo: all channels) -> dW (cout, cin)
+struct W1Map {
+  int cibw, ncob, cin;
+  __device__ long long operator()(int, int e) const {
     const int comp = e & 3, lane = (e >> 2) & 63, pair = e >> 8;
     const int kk = pair % ncob, c = (pair / ncob) % cibw, wave = pair / (ncob * cibw);
     const int co = kk * 16 + 4 * (lane >> 4) + comp;
     const int ci = (wave * cibw + c) * 16 + (lane & 15);
-    if (ci < cin) dw[(size_t)co * cin + ci] = (float)t;
+    return ci < cin ? (long long)((size_t)co * cin + ci) : -1;
   }
-}
+};
 
 struct W1Cfg { int cibw, ncob, ch, nst; };
 static bool wgrad_1x1_cfg(int dtype, const SrcList& x, int cin_logical, int cout, W1Cfg& c) {
@@ -239,7 +223,7 @@ bool wgrad_1x1_supported(int dtype, const SrcList& x, int cin_logical, int cout)
 // and the workspace bound rounds other channel counts up.
 static constexpr int W1_MAX_WG = 256;                     // one workgroup per CU
 static size_t w1_slab_floats(int cin, int cout) { return (size_t)W1_NW * cdiv(cin, 64) * cdiv(cout, 16) * 256; }
-static size_t w1_bytes(int groups, int cin, int cout) { return 256 + (size_t)groups * w1_slab_floats(cin, cout) * sizeof(float); }   // 256 B reserved + slabs
+static WgSlabs w1_slabs(int groups, int cin, int cout) { return {WG_SLAB_PREFIX, (size_t)groups, w1_slab_floats(cin, cout)}; }
 struct W1Cut { long long nvox; int nchunk, groups; };
 static W1Cut w1_cut(const W1Cfg& c, Dims d) {
   W1Cut m;
@@ -248,7 +232,7 @@ static W1Cut w1_cut(const W1Cfg& c, Dims d) {
   m.groups = m.nchunk < W1_MAX_WG ? m.nchunk : W1_MAX_WG;
   return m;
 }
-size_t wgrad_1x1_workspace_bytes(int cin, int cout) { return w1_bytes(W1_MAX_WG, cin, cout); }
+size_t wgrad_1x1_workspace_bytes(int cin, int cout) { return w1_slabs(W1_MAX_WG, cin, cout).bytes(); }
 
 template <typename T, int CIBW, int NCOB, int CH>
 static int wgrad_1x1_launch(const W1Args& a, int grid, int lds, hipStream_t s) {
@@ -265,14 +249,15 @@ int launch_wgrad_1x1(int dtype, const SrcList& x, int cin_logical, const void* d
   SEUNET_CHECK(wgrad_1x1_cfg(dtype, x, cin_logical, cout, c),
                "wgrad_1x1: 16-bit tensors, 1..3 sources of 32 or 64 channels (64, 128 or 192 together), 32 / 64 / 128 output channels only");
   const W1Cut cut = w1_cut(c, d);
-  SEUNET_CHECK(ws_bytes >= w1_bytes(cut.groups, cin_logical, cout), "wgrad_1x1: workspace too small");
+  const WgSlabs slabs = w1_slabs(cut.groups, cin_logical, cout);
   W1Args a{};
+  a.slab = slabs.base(workspace, ws_bytes);
+  SEUNET_CHECK(a.slab != nullptr, "wgrad_1x1: workspace too small");
   for (int i = 0; i < 3; ++i) { a.src[i] = i < x.n ? x.ptr[i] : nullptr; a.srcC[i] = i < x.n ? x.C[i] : 0; }
   a.nsrc = x.n;
   a.dy = dy; a.cout = cout;
   a.zero = device_zero_page();
   SEUNET_CHECK(a.zero != nullptr, "wgrad_1x1: cannot allocate the device zero page");
-  a.slab = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(workspace) + 256);
   a.nvox = cut.nvox;
   a.nchunk = cut.nchunk;
   const int grid = cut.groups;
@@ -288,9 +273,7 @@ int launch_wgrad_1x1(int dtype, const SrcList& x, int cin_logical, const void* d
     else e = wgrad_1x1_launch<T, 3, 8, 64>(a, grid, lds, s);
   });
   if (e) return e;
-  wgrad_1x1_reduce_kernel<<<(unsigned)(w1_slab_floats(cin_logical, cout) / 16), 256, 0, s>>>(a.slab, grid, c.cibw, c.ncob, cin_logical, dw);
-  SEUNET_LAUNCH_CHECK();
-  return 0;
+  return launch_wgrad_reduce(a.slab, grid, (int)slabs.per, 1, W1Map{c.cibw, c.ncob, cin_logical}, dw, s);
 }
 
 }  // namespace seunet

@@ -17,10 +17,11 @@
 //     counted wait (lds_dma.h), one raw s_barrier per step; 16-byte pieces XOR-swizzled by x on the DMA source side so that the
 //     transposing reads touch every bank once; a dY plane outside the march is a zero plane in the LDS (no branches);
 //   * workgroups are persistent over their (sample, patch, z-segment) items; one slab of accumulators per workgroup, summed
-//     by a second kernel in a fixed order in f64 (deterministic, no atomics) into the PyTorch (Cout, Cin, 3, 3, 3) layout.
+//     by the family's shared reduction (wgrad.h) into the PyTorch (Cout, Cin, 3, 3, 3) layout.
 #include "seunet_common.h"
 #include "lds_dma.h"
 #include "mfma.h"
+#include "wgrad.h"
 #include <cstdlib>
 
 namespace seunet {
@@ -321,37 +322,18 @@ wgrad_march_kernel(WmArgs a) {
     for (int t = 0; t < 27; ++t) *reinterpret_cast<f32x4*>(out + (k * 27 + t) * 256) = acc[k][t];
 }
 
-// sum of the slabs, 16-way parallel in a fixed order, f64 -> dw (cout, cin, 27)
-__global__ void __launch_bounds__(256)
-wgrad_march_reduce_kernel(const float* __restrict__ slab, int nslab, int ncb, int pw, int xc, int yc, int nco,
-                          int cin_w, float* __restrict__ dw) {
-  const int per = WM_NW * pw * 27 * 256;
-  const int el = threadIdx.x & 15, part = threadIdx.x >> 4;
-  const int e = blockIdx.x * 16 + el;
-  const int combo = blockIdx.y;
-  const float* ptr = slab + (size_t)combo * nslab * per + e;
-  double s0 = 0.0, s1 = 0.0;
-  int k = part;
-  for (; k + 16 < nslab; k += 32) {
-    s0 += (double)ptr[(size_t)k * per];
-    s1 += (double)ptr[(size_t)(k + 16) * per];
-  }
-  if (k < nslab) s0 += (double)ptr[(size_t)k * per];
-  __shared__ double red[16][17];
-  red[part][el] = s0 + s1;
-  __syncthreads();
-  if (part == 0) {
-    double t = red[0][el];
-#pragma unroll
-    for (int j = 1; j < 16; ++j) t += red[j][el];
+// element e = (pair, tap, lane, component) of a slab of the (xc x yc)-channel combo -> dW (cout, cin_w, 27); no channel padding
+struct WmMap {
+  int ncb, pw, xc, yc, nco, cin_w;
+  __device__ long long operator()(int combo, int e) const {
     const int comp = e & 3, lane = (e >> 2) & 63, tap = (e >> 8) % 27, pair = e / (27 * 256);
     const int wave = pair / pw, kk = pair % pw;
     const int cib = wave % ncb, cob = (wave / ncb) * pw + kk;
     const int co = (combo % nco) * yc + cob * 16 + 4 * (lane >> 4) + comp;
     const int ci = (combo / nco) * xc + cib * 16 + (lane & 15);
-    dw[((size_t)co * cin_w + ci) * 27 + tap] = (float)t;
+    return (long long)(((size_t)co * cin_w + ci) * 27 + tap);
   }
-}
+};
 
 struct WmCfg { int ncb, nob; };
 static WmCfg wm_blocks(int cin, int cout) {   // 16-channel blocks (input, output) of a workgroup
@@ -368,7 +350,7 @@ struct WmCut {
   int xc, yc, pw, nco, combos, gmax;
   int nyb, nxb, nseg, zsteps, items, groups;
   size_t slab_floats() const { return (size_t)WM_NW * pw * 27 * 256; }
-  size_t bytes(int g) const { return 256 + (size_t)combos * g * slab_floats() * sizeof(float); }   // 256 B reserved + slabs
+  WgSlabs slabs(int g) const { return {WG_SLAB_PREFIX, (size_t)combos * g, slab_floats()}; }       // g workgroups per combo
 };
 static WmCut wm_channels(const WmCfg& c, int cin, int cout) {
   WmCut m{};
@@ -391,15 +373,17 @@ static WmCut wm_cut(const WmCfg& c, int cin, int cout, Dims d, int dil) {
   return m;
 }
 // The most this kernel asks of the workspace that wgrad_workspace_bytes() sizes.  It never exceeds the tiled kernel's need for
-// the same channels, so it does not move that size.  In slabs of the tiled kernel (27 x 32 x 32 floats, one per workgroup and
-// 32 x 32 combo): a marching slab is pw of them and covers pw of those combos, so a marching launch of m combos fills at most
-// pw * m * (WM_MAX_WG / m) of them, or pw * m when m > WM_MAX_WG; the tiled kernel on the same pw * m combos keeps
-// pw * m * max(16, WG_TILED_SLABS / (pw * m)), and pw <= 2 (WmGeo).
-static_assert(WM_NW * 256 == 32 * 32 && 2 * WM_MAX_WG <= WG_TILED_SLABS, "a marching launch fits the tiled kernel's slabs");
+// the same channels, so it does not move that size.  Both are WgSlabs with the same prefix (wgrad.h), so it is a matter of
+// floats; in slabs of the tiled kernel (27 x 32 x 32 floats, one per workgroup and 32 x 32 combo): a marching slab is pw of
+// them and covers pw of those combos, so a marching launch of m combos fills at most pw * m * (WM_MAX_WG / m) of them, or
+// pw * m when m > WM_MAX_WG; the tiled kernel on the same pw * m combos keeps pw * m * max(16, WG_TILED_SLABS / (pw * m)),
+// and pw <= 2 (WmGeo).
+static_assert(WM_NW * 256 == 32 * 32 && 2 * WM_MAX_WG <= WG_TILED_SLABS,
+              "a marching launch's WgSlabs fit those of the tiled kernel for the same channels");
 size_t wgrad_march_workspace_bytes(int taps, int cin, int cout) {
   if (taps != 27 || cin < 32 || cout < 32 || cin % 32 || cout % 32) return 0;      // (never routed here: wgrad_march_cfg)
   const WmCut m = wm_channels(wm_blocks(cin, cout), cin, cout);
-  return m.bytes(m.gmax);
+  return m.slabs(m.gmax).bytes();
 }
 static bool wgrad_march_cfg(int dtype, int taps, int dil, const SrcList& x, int cin_logical, int cout, Dims d, long long src_dist, WmCfg& c) {
   if (dtype_size(dtype) != 2 || taps != 27 || (dil != 1 && dil != 2)) return false;
@@ -438,11 +422,11 @@ int launch_wgrad_march(int dtype, int taps, int dil, const SrcList& x, int cin_l
   SEUNET_CHECK(wgrad_march_cfg(dtype, taps, dil, x, cin_logical, cout, d, x.gap(), c),
                "wgrad_march: 16-bit 3x3x3 layers with 32k input and 32k output channels (one tensor or two equal halves) only");
   const WmCut cut = wm_cut(c, cin_logical, cout, d, dil);
-  SEUNET_CHECK(ws_bytes >= cut.bytes(cut.groups), "wgrad_march: workspace too small");
   WmArgs a{};
+  a.slab = cut.slabs(cut.groups).base(workspace, ws_bytes);
+  SEUNET_CHECK(a.slab != nullptr, "wgrad_march: workspace too small");
   a.src0 = x.ptr[0]; a.src1 = x.n > 1 ? x.ptr[1] : nullptr; a.srcC = x.C[0]; a.nsrc = x.n;
   a.dy = dy; a.cout = cout;
-  a.slab = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(workspace) + 256);
   a.N = d.N; a.D = d.D; a.H = d.H; a.W = d.W;
   a.nyb = cut.nyb; a.nxb = cut.nxb; a.nseg = cut.nseg; a.zsteps = cut.zsteps;
   a.nco = cut.nco; a.items = cut.items;
@@ -457,10 +441,8 @@ int launch_wgrad_march(int dtype, int taps, int dil, const SrcList& x, int cin_l
     else e = wgrad_march_launch<T, 2, 2, 2>(a, grid, s);
   });
   if (e) return e;
-  const dim3 rgrid((unsigned)(cut.slab_floats() / 16), cut.combos);
-  wgrad_march_reduce_kernel<<<rgrid, 256, 0, s>>>(a.slab, cut.groups, c.ncb, cut.pw, cut.xc, cut.yc, cut.nco, cin_logical, dw);
-  SEUNET_LAUNCH_CHECK();
-  return 0;
+  return launch_wgrad_reduce(a.slab, cut.groups, (int)cut.slab_floats(), cut.combos,
+                             WmMap{c.ncb, cut.pw, cut.xc, cut.yc, cut.nco, cin_logical}, dw, s);
 }
 
 }  // namespace seunet

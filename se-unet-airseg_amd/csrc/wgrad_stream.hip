@@ -12,10 +12,11 @@
 //     exactly that from the unmodified images;
 //   * 8 waves = 2 groups of (dy, dx, channel-block) units x 4 row pairs; every wave keeps its 16 x 16 accumulators in
 //     registers for the whole march; at the end the four row-pair partials are summed through LDS in a fixed order and the
-//     workgroup writes ONE compact slab [27][ci][co]; a second kernel sums the slabs (f64, fixed order: deterministic).
+//     workgroup writes ONE compact slab [27][ci][co]; the family's shared reduction (wgrad.h) sums the slabs.
 #include "seunet_common.h"
 #include "lds_dma.h"
 #include "mfma.h"
+#include "wgrad.h"
 
 namespace seunet {
 
@@ -60,11 +61,7 @@ wgrad_stream_kernel(WsArgs a) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int grp = wave & 1, rp = wave >> 1;                        // A-unit group, row pair (rows 2 rp, 2 rp + 1)
-  int t;
-  {
-    const int nt = gridDim.x, b = blockIdx.x, q = nt >> 3, r = nt & 7, xcd = b & 7;
-    t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-  }
+  const int t = xcd_contiguous_tile((int)blockIdx.x, (int)gridDim.x);
   const int xb = t % a.nxb, yb = t / a.nxb;
   const int seg = blockIdx.y / DIL, pz = blockIdx.y % DIL;
   const int n = blockIdx.z;
@@ -256,30 +253,14 @@ wgrad_stream_kernel(WsArgs a) {
   }
 }
 
-// dW (PyTorch (cout, cin_w, 3, 3, 3)) = f64 fixed-order sum of the slabs; 16 slab elements per block, 16 partial sums each
-__global__ void __launch_bounds__(256)
-wgrad_stream_reduce_kernel(const float* __restrict__ slab, int nslab, int per, int cin, int cout, int cin_w, int cout_w,
-                           float* __restrict__ dw) {
-  const int el = threadIdx.x & 15, part = threadIdx.x >> 4;
-  const int e = blockIdx.x * 16 + el;
-  double s0 = 0.0, s1 = 0.0;
-  if (e < per) {
-    const float* p = slab + e;
-    int k = part;
-    for (; k + 16 < nslab; k += 32) { s0 += (double)p[(size_t)k * per]; s1 += (double)p[(size_t)(k + 16) * per]; }
-    if (k < nslab) s0 += (double)p[(size_t)k * per];
-  }
-  __shared__ double red[16][17];
-  red[part][el] = s0 + s1;
-  __syncthreads();
-  if (part == 0 && e < per) {
-    double tsum = red[0][el];
-#pragma unroll
-    for (int q = 1; q < 16; ++q) tsum += red[q][el];
+// element e = (tap, ci, co) of a slab [27][cin][cout] (one combo) -> dW (cout_w, cin_w, 3, 3, 3)
+struct WsMap {
+  int cin, cout, cin_w, cout_w;
+  __device__ long long operator()(int, int e) const {
     const int co = e % cout, ci = (e / cout) % cin, tap = e / (cout * cin);
-    if (ci < cin_w && co < cout_w) dw[((size_t)co * cin_w + ci) * 27 + tap] = (float)tsum;
+    return ci < cin_w && co < cout_w ? (long long)(((size_t)co * cin_w + ci) * 27 + tap) : -1;
   }
-}
+};
 
 static bool ws_shape_ok(int cin, int cout, int dil) {
   if (cin == 32 && cout == 16) return dil == 1;          // (dilation 2 would need 161 KB of LDS)
@@ -310,9 +291,8 @@ static WsCut ws_cut(Dims d, int dil) {
   c.nzseg = cdiv(c.planes, c.zsteps);
   return c;
 }
-size_t wgrad_stream_workspace_bytes(int x_c, int dy_c, int dil, Dims d) {
-  return (size_t)ws_cut(d, dil).slabs() * (27 * x_c * dy_c) * sizeof(float);
-}
+static WgSlabs ws_slabs(const WsCut& c, int x_c, int dy_c) { return {0, (size_t)c.slabs(), (size_t)(27 * x_c * dy_c)}; }   // no prefix
+size_t wgrad_stream_workspace_bytes(int x_c, int dy_c, int dil, Dims d) { return ws_slabs(ws_cut(d, dil), x_c, dy_c).bytes(); }
 
 template <typename T, int CIN, int COUT, int DIL>
 static int ws_launch_t(const WsArgs& a, dim3 grid, hipStream_t s) {
@@ -336,12 +316,12 @@ int launch_wgrad_stream(int dtype, int dil, const void* x, int x_c, int cin_w, c
   SEUNET_CHECK(wgrad_stream_supported(dtype, 27, dil, x_c, dy_c), "wgrad_stream: unsupported shape (%d x %d channels, dilation %d)", x_c, dy_c, dil);
   SEUNET_CHECK(x && dy && dw && workspace && cin_w >= 1 && cin_w <= x_c && cout_w >= 1 && cout_w <= dy_c, "wgrad_stream: bad argument");
   const WsCut cut = ws_cut(d, dil);
-  const int per = 27 * x_c * dy_c;                       // floats per slab
-  SEUNET_CHECK(ws_bytes >= (size_t)cut.slabs() * per * sizeof(float), "wgrad_stream: workspace too small");
+  const WgSlabs slabs = ws_slabs(cut, x_c, dy_c);
+  WsArgs a{};
+  a.x = x; a.dy = dy; a.slab = slabs.base(workspace, ws_bytes);
+  SEUNET_CHECK(a.slab != nullptr, "wgrad_stream: workspace too small");
   SEUNET_CHECK((long long)d.D * d.H * d.W * (x_c > dy_c ? x_c : dy_c) * 2 < 0xFFFFFFFFll,
                "wgrad_stream: one sample exceeds the 32-bit buffer offsets of this kernel");
-  WsArgs a{};
-  a.x = x; a.dy = dy; a.slab = reinterpret_cast<float*>(workspace);
   a.N = d.N; a.D = d.D; a.H = d.H; a.W = d.W;
   a.zsteps = cut.zsteps; a.nzseg = cut.nzseg; a.nyb = cut.nyb; a.nxb = cut.nxb;
   SEUNET_CHECK(d.N <= 65535, "wgrad_stream: batch too large");
@@ -353,9 +333,7 @@ int launch_wgrad_stream(int dtype, int dil, const void* x, int x_c, int cin_w, c
   else if (x_c == 16 && dy_c == 32) e = dil == 1 ? ws_launch<16, 32, 1>(dtype, a, grid, s) : ws_launch<16, 32, 2>(dtype, a, grid, s);
   else if (x_c == 32 && dy_c == 16) e = ws_launch<32, 16, 1>(dtype, a, grid, s);
   if (e) return e;
-  wgrad_stream_reduce_kernel<<<cdiv(per, 16), 256, 0, s>>>(a.slab, cut.slabs(), per, x_c, dy_c, cin_w, cout_w, dw);
-  SEUNET_LAUNCH_CHECK();
-  return 0;
+  return launch_wgrad_reduce(a.slab, cut.slabs(), (int)slabs.per, 1, WsMap{x_c, dy_c, cin_w, cout_w}, dw, s);
 }
 
 }  // namespace seunet

@@ -265,6 +265,52 @@ def test_conv_weight_gradient_march_refuses_unserved_layers(S):
         S.conv3d_wgrad([x], dy, 16, 32, 27, 1, S._lib.CONV_MARCH)
 
 
+SLAB_COUNT_CASES = [  # (kernel, source channels, cout, taps, (n, d, h, w), slabs per combo)
+    ("tiled", 64, 32, 27, (1, 4, 8, 32), 4), ("tiled", 64, 32, 27, (1, 8, 20, 32), 20), ("tiled", 64, 32, 27, (1, 16, 20, 32), 40),
+    ("march", 64, 64, 27, (1, 4, 16, 32), 4), ("march", 64, 64, 27, (1, 4, 80, 32), 20), ("march", 64, 64, 27, (1, 16, 80, 32), 40),
+    ("1x1", 64, 32, 1, (1, 4, 4, 32), 4), ("1x1", 64, 32, 1, (1, 4, 20, 32), 20), ("1x1", 64, 32, 1, (1, 8, 20, 32), 40),
+    ("stream", 16, 16, 27, (1, 4, 16, 32), 2), ("stream", 16, 16, 27, (1, 16, 80, 32), 20), ("stream", 16, 16, 27, (1, 32, 80, 32), 40),
+]
+
+
+@pytest.mark.parametrize("case", SLAB_COUNT_CASES, ids=lambda c: f"{c[0]}-{c[5]}slabs")
+def test_conv_weight_gradient_slab_counts(S, case):
+    """The slab reduction that the four weight-gradient kernels share (csrc/wgrad.h), BITWISE, in its three regimes by the slab
+    count n of a combo: n <= 16 (some of the 16 thread groups add nothing), 17 <= n <= 32 (some groups run the two-chain loop, the
+    others only the tail), n > 32 and no multiple of 32 (loop and tail).  bf16 storage, operands in {-1, 0, 1}: every sum is at
+    most the voxel count, <= 32 * 80 * 32 = 81 920 < 2^17, exact in f32 in any order, so ``torch.nn.grad.conv3d_weight`` on the
+    CPU is an exact reference.  One source, dilation 1.  n follows from the cut functions:
+
+    tiled (wgrad.hip, 64 -> 32: 2 x 1 = 2 combos of 32 x 32): wgrad_groups = min(max(16, 512 / 2), tiles) = min(256, tiles), tiles of
+      2 x 4 x 32 (z, y, x) in 16-bit storage: (4, 8, 32) -> 2 * 2 * 1 = 4; (8, 20, 32) -> 4 * 5 * 1 = 20; (16, 20, 32) -> 8 * 5 * 1 = 40.
+    march (wgrad_march.hip, 64 -> 64: wm_blocks = {4, 2}, a workgroup holds 64 x 32 channels, 2 pairs per wave, 1 x 2 = 2 combos,
+      gmax = 256 / 2 = 128): items = 4-row patches x z segments, and the planes are split in two while items < 128 and a half
+      keeps >= 8 planes: (4, 16, 32) -> 4 patches x 1 = 4; (4, 80, 32) -> 20 x 1 = 20; (16, 80, 32) -> 20 x 2 segments of 8 planes = 40;
+      groups = min(items, 128) = items.
+    1x1 (wgrad_1x1.hip, 64 -> 32: 1 input block per wave, 2 output blocks, a stage of (64 + 32) * 2 * 128 B = 24 KB, four stages:
+      chunks of 128 voxels): groups = min(chunks, 256): 4 * 4 * 32 / 128 = 4; 4 * 20 * 32 / 128 = 20; 8 * 20 * 32 / 128 = 40.
+    stream (wgrad_stream.hip, 16 -> 16): patches of 8 x 32 (y, x); z segments = min(ceil(256 / patches), ceil(planes / 8)), re-cut
+      to equal lengths: (4, 16, 32) -> 2 patches x 1 = 2; (16, 80, 32) -> 10 x 2 = 20; (32, 80, 32) -> 10 x 4 = 40; asserted below
+      from the workspace size, which is n slabs of 27 * 16 * 16 floats."""
+    from conv_layer_cases import assert_same, ints
+    kernel, cin, cout, taps, (n, d, h, w), nslab = case
+    k = 3 if taps == 27 else 1
+    x, dy = ints((n, cin, d, h, w), -1, 1, 4000 + nslab), ints((n, cout, d, h, w), -1, 1, 4100 + nslab)
+    ref = torch.nn.grad.conv3d_weight(x.cpu().float(), (cout, cin, k, k, k), dy.cpu().float(), padding=1 if k == 3 else 0)
+    xc, dyc = S.to_cl(x.float(), "bf16"), S.to_cl(dy.float(), "bf16")
+    if kernel == "stream":
+        nbytes = S._lib.load().seunet_conv3d_wgrad_stream_workspace_bytes(cin, cout, 1, S._dims_cl(dyc))
+        assert nbytes == nslab * 27 * 16 * 16 * 4, (nbytes, nslab)
+        run = lambda: S.conv3d_wgrad_stream(xc, dyc, cin, cout, 1)
+    else:
+        impl = S._lib.CONV_TILED if kernel == "tiled" else S._lib.CONV_MARCH
+        run = lambda: S.conv3d_wgrad([xc], dyc, cin, cout, taps, 1, impl)
+    what = f"weight gradient on the {kernel} kernel, {cin} -> {cout} channels, {(n, d, h, w)}, {nslab} slabs per combo"
+    dw = run()
+    assert_same(dw.cpu(), ref, what, axes=("co", "ci", "tap"))
+    assert_same(run(), dw, what + ": second run against the first", axes=("co", "ci", "tap"))
+
+
 def _block_ref(raw, w_se, w_se2, w_side, b_side, slope=0.01):
     e = F.leaky_relu(F.instance_norm(raw), slope)
     e = e * torch.sigmoid(F.conv3d(e, w_se))
