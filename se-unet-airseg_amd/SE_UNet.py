@@ -378,9 +378,8 @@ class SE_UNet(nn.Module):
         b, _, d, h, w = x.shape
         desc = make_desc(b, self.in_channel, self.n_classes, d, h, w, self.width_mult, _lib.dtype_code(self.act_dtype),
                          self.conv_impl, self.negative_slope)
-        level = {"ec1": 0, "ec2": 0, "ec3": 0, "ec33": 0, "dc5": 0, "dc6": 0, "ec4": 1, "ec5": 1, "ec6": 1, "ec63": 1, "dc3": 1,
-                 "dc4": 1, "dc42": 1, "ec7": 2, "ec8": 2, "ec9": 2, "ec93": 2, "dc1": 2, "dc2": 2, "dc22": 2, "ec10": 3, "ec11": 3,
-                 "ec12": 3, "ec123": 3, "x33": 0, "x63": 1, "x93": 2}   # (x-branches: raw / mean / rstd only)
+        # (an x-branch is on its block's level; it has raw / mean / rstd only)
+        level = {n: c["level"] for c in conv_plan(desc) for n in (c["name"], c["x_name"]) if n}
         with torch.cuda.device(x.device):
             nbytes = lib.seunet_net_workspace_bytes(C.byref(desc))
             ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)

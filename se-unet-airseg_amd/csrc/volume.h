@@ -16,7 +16,8 @@ typedef unsigned long long u64;
 // workgroups of a one-thread-per-item pass of 256-thread blocks (grid_for clamps to 4096 workgroups for grid-stride passes)
 static inline unsigned blocks_256(long long n) { return (unsigned)((n + 255) / 256); }
 
-// Bump carver over a device workspace, the sibling of Plan::take in net.cpp.  A null base measures: take() returns null and
+// Bump carver over a device workspace, the sibling of Plan::take in net.cpp (which hands out offsets of a workspace it never sees,
+// and logs a name with each: seunet_debug_net_layout).  A null base measures: take() returns null and
 // only the offset advances.  `log` (the layout report only; null in queries and launchers) receives the offset of every take.
 struct WsCarver {
   unsigned char* base;
