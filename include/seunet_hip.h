@@ -279,6 +279,16 @@ int seunet_pool_gather(const int* slots_host, int n, int capacity, long long vox
 int seunet_adamw_step(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
                       const long long* counts, int n_tensors, double lr, double beta1, double beta2, double eps,
                       double weight_decay, int step, int maximize, seunet_stream_t s);
+/* The same step behind a device flag: when *skip_flag (a DEVICE int, written earlier on the stream by a backward pass whose
+ * scaled fp16 gradients overflowed) is non-zero, parameters and both moments keep their bits and every tensor's device count
+ * skipped[i] (one f32 holding a whole number) grows by one; otherwise the step is applied with the bias corrections of the
+ * tensor's EFFECTIVE step steps[i] - *skipped[i] (steps: HOST array, state['step'] after the increment).  Nothing is read on
+ * the host.  table: DEVICE scratch of 2 * n_tensors floats, fully written before it is read (prior contents do not matter).
+ * The flag is only read: the caller clears it on the stream after the last call of an optimizer step. */
+int seunet_adamw_step_gated(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                            const long long* counts, const int* steps, float* const* skipped, int n_tensors, double lr,
+                            double beta1, double beta2, double eps, double weight_decay, int maximize, const int* skip_flag,
+                            float* table, seunet_stream_t s);
 
 /* ---- input pipeline: one resident case -> the tensors of a training step, in one launch ------------------
  * Replaces, for a mini-batch of crops: crop extraction (data.py:645-664, :85-252), the two HU windows (data.py:667-677,

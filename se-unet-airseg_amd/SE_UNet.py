@@ -25,8 +25,12 @@ fp16 storage (BASELINE configs[4]) needs what the reference never had: the Dice 
 per voxel, below half precision's normal range, so the activation gradients are carried multiplied by a STATIC
 ``loss_scale`` (default 65536 for fp16, 1 otherwise; a build-side extension, attribute ``model.loss_scale``): the incoming
 logit gradients are multiplied by it, the parameter gradients divided by it, nothing else changes.  A backward pass whose
-scaled gradients overflow (inf / NaN in the flat gradient buffer) yields zero gradients and increments the device counter
-``model.overflow_steps`` (no host synchronisation; lower ``model.loss_scale`` when it is ever non-zero).
+scaled gradients overflow (inf / NaN in the flat gradient buffer) yields zero gradients, increments the device counter
+``model.overflow_steps`` and sets the device flag ``model.overflow_pending`` (no host synchronisation; lower
+``model.loss_scale`` when the counter is ever non-zero).  Zero gradients alone do not drop the step: AdamW would still decay
+the weights, shrink both moments, advance its bias corrections and move the weights along the stale momentum.
+``seunet_amd.AdamW(..., overflow_gate=model)`` reads the flag on the device and makes that ``step()`` a true no-op
+(optim.py); with another optimizer, read ``overflow_steps`` on the host and leave ``optimizer.step()`` out yourself.
 """
 from __future__ import annotations
 
@@ -231,7 +235,7 @@ class _SEUNetFunction(torch.autograd.Function):
         ctx.plist, ctx.drop = plist, (drop1, drop2)
         ctx.dead = meta["dead"]
         ctx.loss_scale = float(meta.get("loss_scale", 1.0))
-        ctx.overflow = meta.get("overflow")
+        ctx.overflow, ctx.pending = meta.get("overflow"), meta.get("pending")
         ctx.names, ctx.grad_sync = meta.get("names"), meta.get("grad_sync")
         ctx.input_grad = bool(meta.get("input_grad", False))
         return pred0, pred1
@@ -280,10 +284,12 @@ class _SEUNetFunction(torch.autograd.Function):
                 sync.exchange(flat, split, ev)
             if ctx.loss_scale != 1.0:
                 # a scaled activation gradient beyond half precision's range turns into inf / NaN in the flat buffer: such a step
-                # is dropped (zero gradients) and counted on the device, with no host synchronisation -- the caller reads
+                # yields zero gradients, is counted on the device and raises ``model.overflow_pending``, the flag that makes the gated
+                # ``seunet_amd.AdamW`` skip its next step -- all with no host synchronisation; the caller reads
                 # ``model.overflow_steps`` when it wants to (and lowers ``model.loss_scale`` if it ever becomes non-zero).
-                # Without ``grad_sync`` (``ddp.allreduce_gradients`` after the backward) the decision is per rank: a rank that
-                # overflowed contributes zeros to the sum; the ranks still apply the same update.
+                # Without ``grad_sync`` the decision made HERE is per rank: ``ddp.allreduce_gradients(..., gate=model)`` after the
+                # backward then reduces the flag over the group (MAX), so that every rank zeroes its gradients, counts the
+                # step and skips it together; without ``gate=`` a rank that overflowed merely contributes zeros to the sum.
                 # (with an input gradient the decision covers it too: both are kept, unscaled, or both zeroed.  grad_x is per rank,
                 # so under data parallelism an overflow of grad_x alone drops the step on that rank only)
                 ok = torch.isfinite(flat).all()
@@ -293,6 +299,8 @@ class _SEUNetFunction(torch.autograd.Function):
                 flat.copy_(torch.where(ok, flat * (1.0 / ctx.loss_scale), torch.zeros((), dtype=flat.dtype, device=dev)))
                 if ctx.overflow is not None:
                     ctx.overflow.add_((~ok).to(ctx.overflow.dtype))
+                if ctx.pending is not None:     # sticky: only the optimizer step that consumes it clears it
+                    ctx.pending.bitwise_or_((~ok).to(ctx.pending.dtype))
         ctx.ws = None
         return (grad_x, None, None, None) + tuple(grads)
 
@@ -313,6 +321,7 @@ class SE_UNet(nn.Module):
         self.conv_impl = _default_conv_impl() if conv_impl is None else conv_impl
         self.loss_scale = 65536.0 if _lib.dtype_code(self.act_dtype) == _lib.F16 else 1.0
         self.overflow_steps = None    # device counter of backward passes dropped because a scaled gradient left half precision's range
+        self.overflow_pending = None  # device int32 flag: a backward since the last gated optimizer step overflowed (optim.AdamW)
         self.batchnorm, self.bias, self.out_channel2, self.sigmoid_output = False, True, 2, 0
         m = width_mult
         # registration order == reference SE_UNet.py:108-153 (state_dict / parameters() order)
@@ -481,7 +490,8 @@ class SE_UNet(nn.Module):
         if self.loss_scale != 1.0:
             if self.overflow_steps is None or self.overflow_steps.device != x.device:
                 self.overflow_steps = torch.zeros((), dtype=torch.int64, device=x.device)
-            meta["overflow"] = self.overflow_steps
+                self.overflow_pending = torch.zeros((), dtype=torch.int32, device=x.device)
+            meta["overflow"], meta["pending"] = self.overflow_steps, self.overflow_pending
         if not self._registry_checked:
             self._check_registry(make_desc(b, self.in_channel, self.n_classes, x.shape[2], x.shape[3], x.shape[4],
                                            self.width_mult, meta["dtype"], self.conv_impl, self.negative_slope))

@@ -166,6 +166,8 @@ PROTOTYPES = {
     "seunet_mesh_affine": (_i, [_vp, _ll, C.POINTER(_f), C.POINTER(_f), _vp, _vp]),
     "seunet_mesh_stl_records": (_i, [_vp, _ll, _vp, _ll, C.POINTER(_f), C.POINTER(_f), _vp, _vp, _vp]),
     "seunet_adamw_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _i, _i, _vp]),
+    "seunet_adamw_step_gated": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                                     _i, _vp, _vp, _vp]),
     "seunet_net_param_count": (_i, [C.POINTER(NetDesc)]),
     "seunet_net_param_info": (_i, [C.POINTER(NetDesc), _i, C.c_char_p, _i, _ip, _ip]),
     "seunet_net_workspace_bytes": (_sz, [C.POINTER(NetDesc)]),

@@ -638,5 +638,14 @@ int seunet_adamw_step(float* const* params, const float* const* grads, float* co
   return launch_adamw(params, grads, exp_avg, exp_avg_sq, counts, n_tensors, lr, beta1, beta2, eps, weight_decay, step,
                       maximize, S(s));
 }
+int seunet_adamw_step_gated(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                            const long long* counts, const int* steps, float* const* skipped, int n_tensors, double lr,
+                            double beta1, double beta2, double eps, double weight_decay, int maximize, const int* skip_flag,
+                            float* table, seunet_stream_t s) {
+  SEUNET_CHECK(n_tensors == 0 || (params && grads && exp_avg && exp_avg_sq && counts && steps && skipped && table),
+               "adamw_step_gated: bad argument");
+  return launch_adamw_gated(params, grads, exp_avg, exp_avg_sq, counts, steps, skipped, n_tensors, lr, beta1, beta2, eps,
+                            weight_decay, maximize, skip_flag, table, S(s));
+}
 
 }  // extern "C"

@@ -353,6 +353,9 @@ int launch_window_finalize(const double* acc, int X, int Y, int Z, int cube, int
 int launch_adamw(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
                  const long long* counts, int n, double lr, double beta1, double beta2, double eps, double weight_decay,
                  int step, int maximize, hipStream_t s);
+int launch_adamw_gated(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                       const long long* counts, const int* steps, float* const* skipped, int n, double lr, double beta1,
+                       double beta2, double eps, double weight_decay, int maximize, const int* flag, float* table, hipStream_t s);
 // raises a kernel's dynamic-LDS limit once per (instantiation, device): under a lock, the device's bit is set on success only
 int configure_kernel_lds(unsigned long long& mask, const void* fn, int bytes);
 const void* device_zero_page();   // >= 256 zero bytes on the current device (allocated once per device, never freed)

@@ -113,22 +113,47 @@ class GradSync:
         return out
 
 
-def allreduce_gradients(params: Iterable[torch.nn.Parameter], group=None, average: bool = False) -> int:
+def _reduce_gate(gate, group):
+    """Make the fp16 overflow decision global: MAX of the ranks' pending flags, in place.  ``gate`` is the ``SE_UNet`` (its
+    ``overflow_pending`` flag; its ``overflow_steps`` counter then also counts a step that only another rank overflowed) or the
+    flag tensor itself.  Returns the device boolean 'keep the summed gradients', or None when there
+    is no flag (no fp16 forward so far).  No host synchronisation of its own."""
+    flag = gate if torch.is_tensor(gate) else getattr(gate, "overflow_pending", None)
+    if flag is None:
+        return None
+    local = flag.clone()
+    dist.all_reduce(flag, op=dist.ReduceOp.MAX, group=group)
+    counter = None if torch.is_tensor(gate) else getattr(gate, "overflow_steps", None)
+    if counter is not None:
+        counter.add_(((flag != 0) & (local == 0)).to(counter.dtype))
+    return flag == 0
+
+
+def allreduce_gradients(params: Iterable[torch.nn.Parameter], group=None, average: bool = False, gate=None) -> int:
     """Sum (or average) the gradients of ``params`` across ranks with one collective.  Returns the number of
-    elements reduced.  Parameters without a gradient (the dead ``dc62`` block) are skipped on every rank alike."""
+    elements reduced.  Parameters without a gradient (the dead ``dc62`` block) are skipped on every rank alike.
+
+    ``gate`` (fp16 storage; the model, or its ``overflow_pending`` flag): the overflow decision of the backward pass is per
+    rank here, so it is reduced over the group as well (MAX).  When any rank overflowed, every rank is left with zero gradients
+    and a raised flag, and the gated ``seunet_amd.AdamW`` skips the step on all of them; pass it on every rank or on none."""
     grads = [p.grad for p in params if p.grad is not None]
     if not grads or not dist.is_initialized() or dist.get_world_size(group) == 1:
         return sum(g.numel() for g in grads)
+    keep = None if gate is None else _reduce_gate(gate, group)
     flat = _flat_view(grads)
     if flat is not None:
         dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)
         if average:
             flat.div_(dist.get_world_size(group))
+        if keep is not None:
+            flat.copy_(torch.where(keep, flat, torch.zeros((), dtype=flat.dtype, device=flat.device)))
         return flat.numel()
     bucket = torch.cat([g.reshape(-1) for g in grads])
     dist.all_reduce(bucket, op=dist.ReduceOp.SUM, group=group)
     if average:
         bucket.div_(dist.get_world_size(group))
+    if keep is not None:
+        bucket = torch.where(keep, bucket, torch.zeros((), dtype=bucket.dtype, device=bucket.device))
     off = 0
     for g in grads:
         g.copy_(bucket[off:off + g.numel()].view_as(g))

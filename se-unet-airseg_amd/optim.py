@@ -5,6 +5,15 @@ Drop-in for the reference's ``torch.optim.AdamW(model.parameters(), lr=0.0001)``
 ``torch.optim.lr_scheduler.MultiStepLR`` at train.py:189-191 and ``state_dict()`` keep working), but one native
 multi-tensor launch sequence per step (``seunet_adamw_step``, csrc/optim.hip) instead of PyTorch's per-op foreach
 kernels.  There is no CPU path: parameters must be contiguous float32 CUDA tensors.
+
+Overflow gate (fp16 storage): ``AdamW(..., overflow_gate=model)`` or ``opt.bind_overflow_gate(model)`` makes the step behind a
+backward pass whose scaled gradients overflowed a true no-op -- parameters, ``exp_avg`` and ``exp_avg_sq`` keep their bits and
+later bias corrections count applied steps only.  The gate is ``model.overflow_pending``, a device int32 flag that ``SE_UNet``'s
+backward sets (and never clears) on an overflow; it is looked up at ``step()`` time, read by the kernels in stream order with
+no host synchronisation (``seunet_adamw_step_gated``), and cleared by ``step()`` once consumed -- so with gradient accumulation
+one overflowing backward skips the step that follows.  ``state['step']`` still counts every ``step()`` call; the per-tensor
+device count ``state['skipped']`` (a whole number held in an f32, so that ``load_state_dict`` leaves it as it is) is what the
+kernels subtract.  A gate that does not exist yet or never will (no forward so far; bf16 / fp32 storage) runs the ungated code.
 """
 import ctypes as C
 from typing import Iterable, Tuple
@@ -18,7 +27,7 @@ class AdamW(torch.optim.Optimizer):
     """torch.optim.AdamW semantics (decoupled weight decay, bias correction, no amsgrad) on the HIP library."""
 
     def __init__(self, params: Iterable, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 1e-2, amsgrad: bool = False, *, maximize: bool = False):
+                 weight_decay: float = 1e-2, amsgrad: bool = False, *, maximize: bool = False, overflow_gate=None):
         if amsgrad:
             raise ValueError("seunet AdamW: amsgrad is not implemented (the reference never enables it)")
         if not 0.0 <= lr:
@@ -31,6 +40,19 @@ class AdamW(torch.optim.Optimizer):
             raise ValueError(f"Invalid weight_decay value: {weight_decay}")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False,
                                       maximize=maximize))
+        self._overflow_gate = overflow_gate
+
+    def bind_overflow_gate(self, gate) -> None:
+        """``gate``: an ``SE_UNet`` (its ``overflow_pending`` flag is looked up at every ``step()``), a device int32 tensor of one
+        element (non-zero = skip the next step; ``step()`` clears it), or None for the ungated step."""
+        self._overflow_gate = gate
+
+    def _skip_flag(self):
+        gate = self._overflow_gate
+        flag = gate if gate is None or torch.is_tensor(gate) else getattr(gate, "overflow_pending", None)
+        if flag is not None and not (flag.is_cuda and flag.dtype == torch.int32 and flag.numel() == 1):
+            raise RuntimeError("seunet AdamW: the overflow gate must be one int32 element on the GPU")
+        return flag
 
     def _init_group_state(self, group):
         """exp_avg / exp_avg_sq of a group live in one flat buffer each (views per parameter)."""
@@ -57,6 +79,7 @@ class AdamW(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         lib = _lib.load()
+        flag = self._skip_flag()
         for group in self.param_groups:
             self._init_group_state(group)
             by_step = {}
@@ -72,6 +95,9 @@ class AdamW(torch.optim.Optimizer):
                 st["step"] += 1
                 by_step.setdefault(int(st["step"].item()), []).append((p, g if g.is_contiguous() else g.contiguous(), st))
             beta1, beta2 = group["betas"]
+            if flag is not None and by_step:
+                self._gated_group_step(lib, group, by_step, flag)
+                continue
             for step, items in by_step.items():
                 n = len(items)
                 pa, ga, ma, va = ((C.c_void_p * n)() for _ in range(4))
@@ -84,4 +110,34 @@ class AdamW(torch.optim.Optimizer):
                     _lib.check(lib.seunet_adamw_step(pa, ga, ma, va, cnt, n, float(group["lr"]), float(beta1), float(beta2),
                                                      float(group["eps"]), float(group["weight_decay"]), step,
                                                      int(bool(group["maximize"])), _lib.stream_ptr()), "adamw_step")
+        if flag is not None:
+            flag.zero_()        # consumed (stream-ordered behind the kernels that read it)
         return loss
+
+    def _gated_group_step(self, lib, group, by_step, flag):
+        """All tensors of the group in one call: each carries its own step and skipped count, the kernels decide."""
+        items = [(step, *it) for step, its in by_step.items() for it in its]
+        n = len(items)
+        dev = items[0][1].device
+        if flag.device != dev:
+            raise RuntimeError(f"seunet AdamW: the overflow gate is on {flag.device} but the parameters are on {dev}")
+        new = [st for _, _, _, st in items if "skipped" not in st]
+        if new:
+            flat = torch.zeros(len(new), dtype=torch.float32, device=dev)
+            for i, st in enumerate(new):
+                st["skipped"] = flat[i]
+        pa, ga, ma, va, sa = ((C.c_void_p * n)() for _ in range(5))
+        cnt, steps = (C.c_longlong * n)(), (C.c_int * n)()
+        for i, (step, p, g, st) in enumerate(items):
+            sk = st["skipped"]
+            if not (sk.is_cuda and sk.dtype == torch.float32 and sk.numel() == 1 and sk.device == dev):
+                raise RuntimeError("seunet AdamW: state['skipped'] must be one float32 element on the parameter's device")
+            pa[i], ga[i] = p.data_ptr(), g.data_ptr()
+            ma[i], va[i], sa[i] = st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), sk.data_ptr()
+            cnt[i], steps[i] = p.numel(), step
+        beta1, beta2 = group["betas"]
+        with torch.cuda.device(dev):
+            table = torch.empty(2 * n, dtype=torch.float32, device=dev)     # step_size, 1/sqrt(bc2) per tensor: written by the prepare kernel
+            _lib.check(lib.seunet_adamw_step_gated(pa, ga, ma, va, cnt, steps, sa, n, float(group["lr"]), float(beta1), float(beta2),
+                                                   float(group["eps"]), float(group["weight_decay"]), int(bool(group["maximize"])),
+                                                   flag.data_ptr(), table.data_ptr(), _lib.stream_ptr()), "adamw_step_gated")

@@ -764,6 +764,7 @@ def test_bf16_mode_trains_like_fp32_mode(A, orc):
             opt.step()
             losses.append(float(loss.detach()))
         curves[dtype] = np.array(losses)
+        print(f"overflow_steps[{dtype}] =", None if m.overflow_steps is None else int(m.overflow_steps))     # (no loss scale: no counter)
     f, h = curves["fp32"], curves["bf16"]
     print("loss curve fp32:", np.round(f[::5], 4), "bf16:", np.round(h[::5], 4), "max |diff| %.4f" % np.abs(f - h).max())
     assert np.isfinite(f).all() and np.isfinite(h).all()
@@ -1161,7 +1162,7 @@ def test_fp16_mode_trains(A, orc):
     img = torch.rand(2, 2, 64, 64, 64, generator=g)
     label = (img[:, 0:1] > 0.97).float()
     x, lab = img.cuda(), label.cuda()
-    curves = {}
+    curves, overflow = {}, {}
     for dtype in ("fp32", "fp16"):
         m = build(A, orc, 2, dtype)
         opt = A.AdamW(m.parameters(), lr=1e-3)
@@ -1174,6 +1175,9 @@ def test_fp16_mode_trains(A, orc):
             opt.step()
             losses.append(float(loss.detach()))
         curves[dtype] = np.array(losses)
+        overflow[dtype] = None if m.overflow_steps is None else int(m.overflow_steps)
+    print("overflow_steps:", overflow)
+    assert overflow == {"fp32": None, "fp16": 0}       # no step of the fp16 curve was one with zero gradients (no loss scale: no counter)
     f, h = curves["fp32"], curves["fp16"]
     print("loss curve fp32:", np.round(f[::5], 4), "fp16:", np.round(h[::5], 4), "max |diff| %.4f" % np.abs(f - h).max())
     assert np.isfinite(h).all() and h[-1] < h[0] - 0.05 and np.abs(f - h).max() <= 5e-3

@@ -318,6 +318,38 @@ def test_adamw_four_steps(A):
         np.testing.assert_allclose(host(exp_avg_sq[i]), want["exp_avg_sq"][i], rtol=2e-6, atol=3e-7 * float(np.abs(want["exp_avg_sq"][i]).max()))
 
 
+def test_adamw_four_steps_gated_with_a_skip_at_step_two(A):
+    """The gated step (``overflow_gate=``) over dirty scratch: the step-size table is ``torch.empty`` scratch that the prepare
+    kernel writes before the main kernel reads it, the skipped-step counts are ``torch.zeros``; neither may depend on the fill,
+    and nothing is written beside them, the flag or the moments.  Against the oracle run on steps one, three and four."""
+    import adamw_oracle as ao
+    g = torch.Generator().manual_seed(7)
+    shapes = [(5,), (1,), (257, 9), (1024,), (1025,), (2049,)]       # one element below, at and above the 1024-element block
+    init = [torch.randn(s, generator=g) * 0.1 for s in shapes]
+    grads = [[torch.randn(s, generator=g) * 1e-3 for s in shapes] for _ in range(4)]
+
+    def op():
+        params = [torch.nn.Parameter(dev(t)) for t in init]
+        flag = dev(torch.zeros((), dtype=torch.int32))
+        opt = A.AdamW(params, lr=1e-4, overflow_gate=flag)
+        for t in range(4):
+            for p, gr in zip(params, grads[t]):
+                p.grad = dev(gr)
+            if t == 1:
+                flag.bitwise_or_(torch.ones_like(flag))              # (the way an overflowing backward raises it)
+            opt.step()
+            check()
+        return ([p.detach() for p in params], [opt.state[p]["exp_avg"] for p in params], [opt.state[p]["exp_avg_sq"] for p in params],
+                [opt.state[p]["skipped"] for p in params], flag)
+    params, exp_avg, exp_avg_sq, skipped, flag = three_fills(op, "AdamW gated")
+    assert int(flag) == 0 and [float(v) for v in skipped] == [1.0] * len(shapes)
+    want = ao.run([t.numpy() for t in init], [[gr.numpy() for gr in grads[t]] for t in (0, 2, 3)], [1e-4] * 3)
+    for i, p in enumerate(params):
+        np.testing.assert_allclose(host(p), want["params"][i], rtol=2e-7, atol=1e-9)
+        for got, key in ((exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+            np.testing.assert_allclose(host(got[i]), want[key][i], rtol=2e-6, atol=3e-7 * float(np.abs(want[key][i]).max()))
+
+
 # ---- losses ------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("stage", (1, 2, 3))
 def test_fused_stage_loss(A, stage):

@@ -454,6 +454,35 @@ def test_adamw_four_steps(A):
         np.testing.assert_allclose(host(exp_avg_sq[i]), want["exp_avg_sq"][i], rtol=2e-6, atol=3e-7 * float(np.abs(want["exp_avg_sq"][i]).max()))
 
 
+def test_adamw_four_steps_gated_with_a_skip_at_step_two(A):
+    """The gated step (``overflow_gate=``): the flag an overflowing backward would raise arrives with the other inputs, behind
+    the delay (poison: another step is skipped), and the prepare kernel, its table and the flag's reset are on the caller's
+    stream.  Against the oracle run on steps one, three and four."""
+    import adamw_oracle as ao
+    k = len(ADAMW_SHAPES)
+    raised = lambda *steps: [torch.tensor([int(s in steps) for s in range(4)], dtype=torch.int32)]
+
+    def op(*t):
+        params = [torch.nn.Parameter(v) for v in t[:k]]
+        flag = torch.zeros((), dtype=torch.int32, device="cuda")
+        opt = A.AdamW(params, lr=1e-4, overflow_gate=flag)
+        for s in range(4):
+            for i, p in enumerate(params):
+                p.grad = t[k * (s + 1) + i]
+            flag.bitwise_or_(t[-1][s])
+            opt.step()
+        return ([p.detach() for p in params], [opt.state[p]["exp_avg"] for p in params], [opt.state[p]["exp_avg_sq"] for p in params],
+                [opt.state[p]["skipped"] for p in params], flag)
+    real = _adamw_inputs(7) + raised(1)
+    (params, exp_avg, exp_avg_sq, skipped, flag), _ = both(real, _adamw_inputs(7 + POISON) + raised(2), op, "AdamW gated", True)
+    assert int(flag) == 0 and [float(v) for v in skipped] == [1.0] * k
+    want = ao.run([v.numpy() for v in real[:k]], [[v.numpy() for v in real[k * (s + 1):k * (s + 2)]] for s in (0, 2, 3)], [1e-4] * 3)
+    for i, p in enumerate(params):
+        np.testing.assert_allclose(host(p), want["params"][i], rtol=2e-7, atol=1e-9)
+        for got, key in ((exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+            np.testing.assert_allclose(host(got[i]), want[key][i], rtol=2e-6, atol=3e-7 * float(np.abs(want[key][i]).max()))
+
+
 def _psl_inputs(seed):
     g = torch.Generator().manual_seed(seed)
     shape = (4, 1, 6, 9, 40)
