@@ -255,7 +255,10 @@ class _SEUNetFunction(torch.autograd.Function):
             if ctx.loss_scale != 1.0:       # fp16 storage: keep the activation gradients inside half precision's range
                 g0, g1 = g0 * ctx.loss_scale, g1 * ctx.loss_scale
             # all live parameter gradients are views of ONE flat buffer (one RCCL all-reduce under data parallelism)
-            flat, grads, split = alloc_flat_grads(ctx.plist, ctx.dead, dev, ctx.names)
+            # (a frozen parameter, requires_grad False, is treated like the dead block: no space, a null pointer, and the native
+            # walk does not compute its gradient)
+            skip = [dd or not ctx.needs_input_grad[4 + i] for i, dd in enumerate(ctx.dead)]
+            flat, grads, split = alloc_flat_grads(ctx.plist, skip, dev, ctx.names)
             garr = _lib.ptr_array(grads)
             parr = _lib.ptr_array(ctx.plist)
             sync = ctx.grad_sync

@@ -5,6 +5,7 @@
 // instead of read, its statistics come from the input's second moments, and its weight gradient is formed from sums of the
 // backward pass A (XR / XW template modes below).
 #include "epilogue.h"
+#include "wgrad.h"
 #include <type_traits>
 
 namespace seunet {
@@ -372,11 +373,10 @@ xbranch_stats_kernel(const double* __restrict__ partial, int slots, const float*
 // (the mean(dxhat2) term drops out against sum_v xc_i = 0).  The cancellation between A_i and its projection on w happens in
 // f64 here; the f32 inputs of the sums (dxhat2 = g or slope * g, x) enter only through products that are exact in f64.
 // One block per output channel; fixed summation order (slots within a sample, then samples): bitwise reproducible.
-__global__ void __launch_bounds__(256)
-xw_finalize_kernel(const double* __restrict__ xw_partial, const double* __restrict__ stat_partial2, int slots, int C, int N,
-                   const double* __restrict__ moments, const float* __restrict__ w2, int ic, double eps, float* __restrict__ dw) {
+__device__ __forceinline__ void
+xw_finalize_body(int c, const double* __restrict__ xw_partial, const double* __restrict__ stat_partial2, int slots, int C, int N,
+                 const double* __restrict__ moments, const float* __restrict__ w2, int ic, double eps, float* __restrict__ dw) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int c = blockIdx.x;
   __shared__ double red[4][3];
   const double wa = (double)w2[c * ic], wb = ic > 1 ? (double)w2[c * ic + 1] : 0.0;
   double g0 = 0.0, g1 = 0.0;
@@ -414,6 +414,26 @@ xw_finalize_kernel(const double* __restrict__ xw_partial, const double* __restri
     dw[c * ic] = (float)g0;
     if (ic > 1) dw[c * ic + 1] = (float)g1;
   }
+}
+__global__ void __launch_bounds__(256)
+xw_finalize_kernel(const double* __restrict__ xw_partial, const double* __restrict__ stat_partial2, int slots, int C, int N,
+                   const double* __restrict__ moments, const float* __restrict__ w2, int ic, double eps, float* __restrict__ dw) {
+  xw_finalize_body(blockIdx.x, xw_partial, stat_partial2, slots, C, N, moments, w2, ic, eps, dw);
+}
+// what follows pass A of an aggregation block, in ONE launch (the gated block's gate_bwd_finalize_kernel is the model): blocks
+// [0, N*C) the first branch's two means, the next nb2 = N*C or 0 the second branch's, the next nxw = C or 0 the recomputed
+// x-branch's weight gradient, and any blocks past those the rider (wgrad.h).  Pass B waits for the means alone: they come first.
+__global__ void __launch_bounds__(256)
+cat_bwd_finalize_kernel(const double* __restrict__ partial, const double* __restrict__ partial2, int slots, int C, int N,
+                        double inv_count, float* __restrict__ m1, float* __restrict__ m2, float* __restrict__ m1b,
+                        float* __restrict__ m2b, int nb2, int nxw, const double* __restrict__ xw_partial,
+                        const double* __restrict__ moments, const float* __restrict__ w2, int ic, double eps, float* __restrict__ dw,
+                        WgReduceJob rider) {
+  const int b = blockIdx.x, nb = N * C;
+  if (b < nb) stats_finalize_body(b, partial, slots, C, inv_count, 0.f, 1, m1, m2);
+  else if (b < nb + nb2) stats_finalize_body(b - nb, partial2, slots, C, inv_count, 0.f, 1, m1b, m2b);
+  else if (b < nb + nb2 + nxw) xw_finalize_body(b - nb - nb2, xw_partial, partial2, slots, C, N, moments, w2, ic, eps, dw);
+  else wgrad_reduce_body(rider, b - nb - nb2 - nxw);
 }
 
 // diagnostic (seunet_net_read_tensor): the x-branch's raw values, recomputed by the same device function as the aggregation
@@ -568,6 +588,21 @@ int launch_cat_xgrad_finalize(const double* xw_partial, const double* stat_parti
                               int C, int in_channel, int N, float eps, float* dw, hipStream_t s) {
   SEUNET_CHECK(in_channel >= 1 && in_channel <= 2, "cat_xgrad_finalize: in_channel %d (1 or 2)", in_channel);
   xw_finalize_kernel<<<C, 256, 0, s>>>(xw_partial, stat_partial2, slots, C, N, moments, w2, in_channel, (double)eps, dw);
+  SEUNET_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_cat_bwd_finalize(const double* stat_partial, const double* stat_partial2, int slots, int C, int N, long long count,
+                            float* m1, float* m2, float* m1b, float* m2b, const CatXwFinalize& xw, hipStream_t s,
+                            const WgReduceJob* rider) {
+  SEUNET_CHECK(stat_partial && m1 && m2 && (!stat_partial2 || (m1b && m2b)), "cat_bwd_finalize: missing argument");
+  SEUNET_CHECK(!xw.dw || (stat_partial2 && xw.xw_partial && xw.moments && xw.w2 && xw.in_channel >= 1 && xw.in_channel <= 2),
+               "cat_bwd_finalize: the x-branch weight gradient needs the second branch's sums and in_channel 1 or 2");
+  const WgReduceJob job = rider ? *rider : WgReduceJob{};
+  const int nb2 = stat_partial2 ? N * C : 0, nxw = xw.dw ? C : 0;
+  cat_bwd_finalize_kernel<<<N * C + nb2 + nxw + job.blocks(), 256, 0, s>>>(
+      stat_partial, stat_partial2, slots, C, N, 1.0 / (double)count, m1, m2, m1b, m2b, nb2, nxw, xw.xw_partial, xw.moments, xw.w2,
+      xw.in_channel, (double)xw.eps, xw.dw, job);
   SEUNET_LAUNCH_CHECK();
   return 0;
 }

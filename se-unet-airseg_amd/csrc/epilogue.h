@@ -14,6 +14,9 @@
 namespace seunet {
 
 // ---- launchers and their arguments -----------------------------------------------------------------------------------
+// A finalize launch between pass A and pass B can carry a rider: the slab reduction of an earlier weight gradient (wgrad.h,
+// WgReduceJob) as extra workgroups after its own.  Null: none.
+struct WgReduceJob;
 int epi_partials(Dims d);         // partial slots per sample used by the epilogue kernels
 int launch_channel_stats(int dtype, const void* t, int C, double* partial, Dims d, hipStream_t s);
 int launch_stats_finalize(const double* partial, int slots, int C, int N, long long count,
@@ -55,7 +58,7 @@ int launch_sse_bwd_apply(int dtype, const GateBlock& b, const SseBwdIn& g, const
                          hipStream_t s);
 int launch_gate_bwd_finalize(const double* stat_partial, int slots, int C, int N, long long count, float* m1, float* m2,
                              const float* pgrad_partial, int records, float* dw_se, float* dw_se2, float* dw_side,
-                             float* db_side, float* dhead_w, hipStream_t s);
+                             float* db_side, float* dhead_w, hipStream_t s, const WgReduceJob* rider = nullptr);
 int launch_pgrad_reduce(const float* pgrad_partial, int records, int C, float* dw_se,
                         float* dw_se2, float* dw_side, float* db_side, float* dhead_w,
                         hipStream_t s);
@@ -95,6 +98,13 @@ int launch_xbranch_stats(const double* partial, int slots, const float* w2, int 
                          float eps, float* mean2, float* rstd2, double* moments_out, hipStream_t s);
 int launch_cat_xgrad_finalize(const double* xw_partial, const double* stat_partial2, int slots, const double* moments, const float* w2,
                               int C, int in_channel, int N, float eps, float* dw, hipStream_t s);
+// What follows pass A of an aggregation block, in ONE launch: the two means of the first branch (stat_partial -> m1, m2), those
+// of the second (stat_partial2 -> m1b, m2b; null = one branch), the recomputed x-branch's weight gradient (xw.dw null = not
+// asked for; what launch_cat_xgrad_finalize computes), then the rider.
+struct CatXwFinalize { const double* xw_partial; const double* moments; const float* w2; int in_channel; float eps; float* dw; };
+int launch_cat_bwd_finalize(const double* stat_partial, const double* stat_partial2, int slots, int C, int N, long long count,
+                            float* m1, float* m2, float* m1b, float* m2b, const CatXwFinalize& xw, hipStream_t s,
+                            const WgReduceJob* rider = nullptr);
 int launch_xbranch_values(int dtype, const void* x_in, const float* w2, int C, int in_channel, float* out_ncdhw, Dims d, hipStream_t s);   // diagnostic
 
 // ---- device steps ----------------------------------------------------------------------------------------------------

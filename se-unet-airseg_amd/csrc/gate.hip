@@ -2,6 +2,7 @@
 //     raw conv output -> InstanceNorm -> LeakyReLU -> spatial gate(s) -> e ; side = conv1x1(e)
 // and its backward (two-phase InstanceNorm backward).  Thread mapping and the steps shared with cat.hip: epilogue.h.
 #include "epilogue.h"
+#include "wgrad.h"
 
 namespace seunet {
 
@@ -326,13 +327,18 @@ pgrad_reduce_kernel(const float* __restrict__ pg, int records, int C, float* dw_
   pgrad_reduce_body(blockIdx.x, pg, records, C, dw_se, dw_se2, dw_side, db_side, dhead_w);
 }
 // what follows pass A of a gated block, in ONE launch: the two means of the InstanceNorm backward (blocks [0, N*C)) and the
-// parameter-gradient records (the remaining blocks) -- two dependent 5-us launches on the critical path otherwise
+// parameter-gradient records (the next cdiv(4 * C + 4, 4) blocks) -- two dependent 5-us launches on the critical path otherwise.
+// Any blocks past those are riders: the slab reduction of the weight gradient that ran before this block's pass A (wgrad.h),
+// which nothing in this launch depends on and which depends on nothing in it.  The statistics blocks, which pass B waits
+// for, come first in the grid and so dispatch first.
 __global__ void __launch_bounds__(256)
 gate_bwd_finalize_kernel(const double* __restrict__ partial, int slots, int C, int N, double inv_count, float* __restrict__ m1,
                          float* __restrict__ m2, const float* __restrict__ pg, int records, float* dw_se, float* dw_se2,
-                         float* dw_side, float* db_side, float* dhead_w) {
+                         float* dw_side, float* db_side, float* dhead_w, WgReduceJob rider) {
+  const int own = N * C + (4 * C + 4 + 3) / 4;   // (the launcher's grid without riders)
   if ((int)blockIdx.x < N * C) stats_finalize_body(blockIdx.x, partial, slots, C, inv_count, 0.f, 1, m1, m2);
-  else pgrad_reduce_body((int)blockIdx.x - N * C, pg, records, C, dw_se, dw_se2, dw_side, db_side, dhead_w);
+  else if ((int)blockIdx.x < own) pgrad_reduce_body((int)blockIdx.x - N * C, pg, records, C, dw_se, dw_se2, dw_side, db_side, dhead_w);
+  else wgrad_reduce_body(rider, (int)blockIdx.x - own);
 }
 
 int launch_sse_fwd(int dtype, const GateBlock& b, void* e_out, const SseHead& head, Dims d, hipStream_t s) {
@@ -383,9 +389,10 @@ int launch_sse_bwd_apply(int dtype, const GateBlock& b, const SseBwdIn& g, const
 
 int launch_gate_bwd_finalize(const double* stat_partial, int slots, int C, int N, long long count, float* m1, float* m2,
                              const float* pgrad_partial, int records, float* dw_se, float* dw_se2, float* dw_side,
-                             float* db_side, float* dhead_w, hipStream_t s) {
-  gate_bwd_finalize_kernel<<<N * C + cdiv(4 * C + 4, 4), 256, 0, s>>>(stat_partial, slots, C, N, 1.0 / (double)count, m1, m2,
-                                                                     pgrad_partial, records, dw_se, dw_se2, dw_side, db_side, dhead_w);
+                             float* db_side, float* dhead_w, hipStream_t s, const WgReduceJob* rider) {
+  const WgReduceJob job = rider ? *rider : WgReduceJob{};
+  gate_bwd_finalize_kernel<<<N * C + cdiv(4 * C + 4, 4) + job.blocks(), 256, 0, s>>>(
+      stat_partial, slots, C, N, 1.0 / (double)count, m1, m2, pgrad_partial, records, dw_se, dw_se2, dw_side, db_side, dhead_w, job);
   SEUNET_LAUNCH_CHECK();
   return 0;
 }

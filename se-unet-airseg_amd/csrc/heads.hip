@@ -340,6 +340,26 @@ __global__ void __launch_bounds__(1024) sum_stage2_wide_kernel(const double* __r
   }
 }
 
+// The same sum by one 256-thread block, bit for bit: thread t stands for the four threads t, t + 256, t + 512, t + 768 of the
+// 1024 (same lane, waves t / 64 + 4 j), so every thread-strided sum, every wave butterfly and the 16-wave order are the same.
+__device__ __forceinline__ void sum_stage2_wide_by_256(const double* __restrict__ partial, int n, float* __restrict__ out) {
+  __shared__ double w[16];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    double s = 0.0;
+    for (int i = threadIdx.x + 256 * j; i < n; i += 1024) s += partial[i];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) s += shfl_xor_settled(s, off);
+    if ((threadIdx.x & 63) == 0) w[(threadIdx.x >> 6) + 4 * j] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+    for (int k = 0; k < 16; ++k) t += w[k];
+    out[0] = (float)t;
+  }
+}
+
 // ---------------- launchers -----------------------------------------------------------------------
 int launch_side_upsample(const float* side, int C, int scale, float* out, int c_total, int c_off, Dims dl,
                          hipStream_t s) {
@@ -369,10 +389,16 @@ int launch_head_fwd(const float* const* level_maps, int nlevels, const float* bi
   return 0;
 }
 
-// the y- (or z-) passes of all coarse levels of one head in ONE launch: blockIdx.y = job (one per level)
+// the y- (or z-) passes of all coarse levels of one head in ONE launch: blockIdx.y = job (one per level).  The y launch has
+// one more row when the bias gradient is asked for: its first block sums the x pass's bias partials (nothing waits for that
+// sum, and it waits for the x pass alone), the others return.
 struct AxisJob { const float* in; float* out; int I, O; long long inner, total; };
-struct AxisJobs { AxisJob j[3]; };
+struct AxisJobs { AxisJob j[3]; int njobs; const double* bias_part; int bias_n; float* g_bias; };
 __global__ void __launch_bounds__(256) up_transpose_axis_multi_kernel(AxisJobs jobs) {
+  if ((int)blockIdx.y >= jobs.njobs) {
+    if (blockIdx.x == 0) sum_stage2_wide_by_256(jobs.bias_part, jobs.bias_n, jobs.g_bias);
+    return;
+  }
   const AxisJob jb = jobs.j[blockIdx.y];
   if (jb.total == 0) return;
   const float rs = ac_scale(jb.I, jb.O);
@@ -454,11 +480,14 @@ int launch_head_bwd(const float* g_pred, float* const* g_levels, int nlevels, fl
     max_z = tz > max_z ? tz : max_z;
     ++njobs;
   }
+  jy.njobs = jz.njobs = njobs;
   if (njobs) {
-    up_transpose_axis_multi_kernel<<<dim3((unsigned)grid_for(max_y), (unsigned)njobs), 256, 0, s>>>(jy);
+    if (g_bias) { jy.bias_part = part; jy.bias_n = nblk; jy.g_bias = g_bias; }
+    up_transpose_axis_multi_kernel<<<dim3((unsigned)grid_for(max_y), (unsigned)njobs + (g_bias ? 1 : 0)), 256, 0, s>>>(jy);
     up_transpose_axis_multi_kernel<<<dim3((unsigned)grid_for(max_z), (unsigned)njobs), 256, 0, s>>>(jz);
+  } else if (g_bias) {   // (no coarse level: the sum is a launch of its own)
+    sum_stage2_wide_kernel<<<1, 1024, 0, s>>>(part, nblk, g_bias);
   }
-  if (g_bias) sum_stage2_wide_kernel<<<1, 1024, 0, s>>>(part, nblk, g_bias);
   SEUNET_LAUNCH_CHECK();
   return 0;
 }

@@ -3,6 +3,7 @@
 //
 //   max-pool      reference SE_UNet.py:131-133 (nn.MaxPool3d 2/2)
 #include "seunet_common.h"
+#include "wgrad.h"
 
 namespace seunet {
 
@@ -148,18 +149,23 @@ int launch_maxpool_bwd(int dtype, const void* in, const void* g_out, int C, void
 }
 
 // zero several small f32 arrays with ONE launch (the identically-zero conv1.bias gradients of a backward pass: a
-// hipMemsetAsync each is a 5-us fill kernel, thirty times per step)
+// hipMemsetAsync each is a 5-us fill kernel, thirty times per step).  The first launch can carry a rider (wgrad.h: the last
+// weight gradient's slab reduction, at the end of the backward walk) as the blocks past its own; n = 0 with a rider is that
+// reduction alone.
 struct ZeroList { float* ptr[48]; int count[48]; int n; };
-__global__ void multi_zero_kernel(ZeroList z) {
+__global__ void __launch_bounds__(256) multi_zero_kernel(ZeroList z, WgReduceJob rider) {
+  if ((int)blockIdx.x >= z.n) { wgrad_reduce_body(rider, (int)blockIdx.x - z.n); return; }
   float* p = z.ptr[blockIdx.x];
   for (int i = threadIdx.x; i < z.count[blockIdx.x]; i += blockDim.x) p[i] = 0.f;
 }
-int launch_multi_zero(float* const* ptrs, const int* counts, int n, hipStream_t s) {
-  for (int base = 0; base < n; base += 48) {
+int launch_multi_zero(float* const* ptrs, const int* counts, int n, hipStream_t s, const WgReduceJob* rider) {
+  WgReduceJob job = rider ? *rider : WgReduceJob{};
+  for (int base = 0; base < n || job.blocks() > 0; base += 48) {
     ZeroList z{};
     z.n = n - base < 48 ? n - base : 48;
     for (int i = 0; i < z.n; ++i) { z.ptr[i] = ptrs[base + i]; z.count[i] = counts[base + i]; }
-    multi_zero_kernel<<<z.n, 256, 0, s>>>(z);
+    multi_zero_kernel<<<z.n + job.blocks(), 256, 0, s>>>(z, job);
+    job = WgReduceJob{};
   }
   SEUNET_LAUNCH_CHECK();
   return 0;

@@ -42,6 +42,9 @@ ConvKernel wgrad_kernel(int dtype, int taps, int dil, const SrcList& x, int cin_
 
 namespace {
 
+// diagnostic switch (seunet_debug_net_wgrad_defer): off = every weight gradient of the backward walk reduces its slabs at once
+bool g_wgrad_defer = true;
+
 // ---------------------------------------------------------------------------------------------------
 // the graph
 // ---------------------------------------------------------------------------------------------------
@@ -665,6 +668,24 @@ struct Exec {
 
   float* gpar(int op, PField f) const { const int k = kG.prm[op].at[f]; return k < 0 ? nullptr : grads[k]; }
 
+  // The slab reduction of the last weight gradient, not yet launched (wgrad.h).  Nothing reads a weight gradient inside the
+  // walk, so the reduction need not sit between wgrad(L) and dgrad(L): it rides the next finalize launch of the walk
+  // (take_pending: gated_backward, cat_backward; the last one rides the zeroing launch after the walk) as extra workgroups.
+  // It has to run before the next weight gradient overwrites wgrad_ws and before decoder_done is recorded: flush_pending.
+  WgReduceJob pending;
+  WgReduceJob* defer() { return g_wgrad_defer ? &pending : nullptr; }
+  WgReduceJob take_pending() { const WgReduceJob j = pending; pending = WgReduceJob{}; return j; }
+  int flush_pending() {
+    if (pending.blocks() == 0) return 0;
+    mark("wgrad:flush");
+    return launch_wgrad_reduce(take_pending(), s);
+  }
+  // one weight gradient of the walk into the shared workspace
+  int walk_wgrad(ConvKernel k, int taps, int dil, const SrcList& x, int cin, const void* dy, int cout, float* gw, const Dims& dm) {
+    if (int e = flush_pending()) return e;   // (only a second weight gradient of one op finds one: the materialised x-branch's)
+    return run_wgrad(k, p.d.dtype, taps, dil, x, cin, dy, cout, gw, at(p.wgrad_ws), p.wgrad_ws_bytes, dm, s, defer());
+  }
+
   // gradient w.r.t. the raw conv output is in grad[dst]; produce weight gradient and input gradients
   int conv_backward(const Op& c) {
     const OpDesc& o = c.o;
@@ -672,8 +693,7 @@ struct Exec {
     const SrcList x = srcs(c.i);
     if (float* gw = gpar(c.i, P_CONV1_W)) {
       mark("wgrad:", o.name);
-      if (int e = run_wgrad(r.wgrad, p.d.dtype, r.taps, o.dil, x, r.cin, at(p.grad[o.dst]), r.cout, gw, at(p.wgrad_ws),
-                            p.wgrad_ws_bytes, c.dm, s)) return e;
+      if (int e = walk_wgrad(r.wgrad, r.taps, o.dil, x, r.cin, at(p.grad[o.dst]), r.cout, gw, c.dm)) return e;
     }
     if (!r.need_dgrad) return 0;
     const SrcList gsrc{{at(p.grad[o.dst])}, {r.cout}, 1};
@@ -728,9 +748,10 @@ struct Exec {
     mark("epi_bwd:", o.name);   // pass A: f64 sums + parameter-gradient records
     if (int e = launch_sse_bwd_sums(p.d.dtype, blk, g, hd, SseSums{dat(p.stats), fat(p.pgrad)}, c.dm, s)) return e;
     mark("stats");
+    const WgReduceJob rider = take_pending();
     if (int e = launch_gate_bwd_finalize(dat(p.stats), P_slots, c.r.cout, c.dm.N, c.dm.vox(), fat(p.m1), fat(p.m2), fat(p.pgrad),
                                          c.dm.N * P_slots, gpar(c.i, P_SE), gpar(c.i, P_SE2), gpar(c.i, P_CONV2_W),
-                                         gpar(c.i, P_CONV2_B), g_head, s)) return e;
+                                         gpar(c.i, P_CONV2_B), g_head, s, &rider)) return e;
     mark("in_bwd:", o.name);    // pass B: recompute dxhat, apply the InstanceNorm backward, store draw over g_e
     if (int e = launch_sse_bwd_apply(p.d.dtype, blk, g, hd, SseApply{fat(p.m1), fat(p.m2), at(p.grad[o.dst])}, c.dm, s)) return e;
     written[o.dst] = true;
@@ -755,13 +776,11 @@ struct Exec {
     mark("cat_bwd:", o.name);   // pass A; a recomputed x-branch also sums what its weight gradient is formed from
     const CatSums sums{dat(p.stats), dat(p.stats2), recomputed && gxw ? dat(p.xwp) : nullptr};
     if (int e = launch_cat_bwd_sums(p.d.dtype, blk, g_out, pool, sums, c.dm, s)) return e;
-    mark("stats");
-    if (recomputed && gxw)
-      if (int e = launch_cat_xgrad_finalize(dat(p.xwp), dat(p.stats2), P_slots, dat(r.xtot), blk.b.w2, r.cout, p.d.in_channel, c.dm.N,
-                                            p.d.eps, gxw, s)) return e;
-    if (int e = launch_stats_finalize(dat(p.stats), P_slots, r.cout, c.dm.N, c.dm.vox(), 0.f, 1, fat(p.m1), fat(p.m2), s)) return e;
-    if (two)
-      if (int e = launch_stats_finalize(dat(p.stats2), P_slots, r.cout, c.dm.N, c.dm.vox(), 0.f, 1, fat(p.m1b), fat(p.m2b), s)) return e;
+    mark("stats");   // one launch: both branches' means, the recomputed x-branch's weight gradient, the pending slab reduction
+    const CatXwFinalize xwf{dat(p.xwp), dat(r.xtot), blk.b.w2, p.d.in_channel, p.d.eps, recomputed ? gxw : nullptr};
+    const WgReduceJob rider = take_pending();
+    if (int e = launch_cat_bwd_finalize(dat(p.stats), two ? dat(p.stats2) : nullptr, P_slots, r.cout, c.dm.N, c.dm.vox(), fat(p.m1),
+                                        fat(p.m2), fat(p.m1b), fat(p.m2b), xwf, s, &rider)) return e;
     // pass B: draw over g_out; a stored x-branch's draw goes to gx, a recomputed one adds its input-gradient term on the fly
     mark("in_bwd:", o.name);
     CatApply ap{fat(p.m1), fat(p.m2), fat(p.m1b), fat(p.m2b), at(p.grad[o.dst]), two && !recomputed ? at(p.gx) : nullptr, nullptr, 0};
@@ -774,8 +793,7 @@ struct Exec {
       }
       if (gxw) {
         mark("wgrad:", o.xname);
-        if (int e = run_wgrad(r.x_wgrad, p.d.dtype, 1, 1, xbranch_src(o), p.d.in_channel, at(p.gx), r.cout, gxw, at(p.wgrad_ws),
-                              p.wgrad_ws_bytes, c.dm, s)) return e;
+        if (int e = walk_wgrad(r.x_wgrad, 1, 1, xbranch_src(o), p.d.in_channel, at(p.gx), r.cout, gxw, c.dm)) return e;
       }
     }
     return conv_backward(c);
@@ -823,6 +841,7 @@ struct Exec {
       if (decoder_done && i == kG.first_up) {
         // the walk is in reverse forward order: everything after up0 (the decoder) has been differentiated.  Its parameter
         // gradients are final from here on (the heads' weights are not: the encoder blocks still add to dc0_0)
+        if (int e = flush_pending()) return e;
         SEUNET_HIP(hipEventRecord(decoder_done, s));
       }
       const Op c = op(i);
@@ -830,9 +849,10 @@ struct Exec {
       if (int e = k == OP_GATED ? gated_backward(c) : k == OP_CAT ? cat_backward(c) : k == OP_POOL ? pool_backward(c) : up_backward(c))
         return e;
     }
-    if (!zero_ptrs.empty()) {
+    if (!zero_ptrs.empty() || pending.blocks() > 0) {   // with the last weight gradient's slab reduction as its rider
       mark("stats");
-      if (int e = launch_multi_zero(zero_ptrs.data(), zero_counts.data(), (int)zero_ptrs.size(), s)) return e;
+      const WgReduceJob rider = take_pending();
+      if (int e = launch_multi_zero(zero_ptrs.data(), zero_counts.data(), (int)zero_ptrs.size(), s, &rider)) return e;
     }
     if (grad_x) {
       // grad_x = convT_ec1(draw_ec1) + gx_0 + unpool_0(gx_1); ec1's pass B left draw_ec1 in grad[T_E0]
@@ -888,6 +908,15 @@ int seunet_debug_net_layout(const seunet_net_desc* desc, int index, char* name, 
   *offset = t.off;
   *bytes = t.bytes;
   return 0;
+}
+
+// Diagnostic (process-global, not in the public header): on (the default) = the backward walk defers each weight gradient's
+// slab reduction into the next finalize launch; off = every weight gradient reduces at once, in a launch of its own.  The two
+// give the same bits (tests/test_wgrad_deferred_gpu.py).  Returns the previous setting.
+int seunet_debug_net_wgrad_defer(int on) {
+  const int was = g_wgrad_defer ? 1 : 0;
+  g_wgrad_defer = on != 0;
+  return was;
 }
 
 int seunet_net_forward(const seunet_net_desc* desc, const float* const* params, const float* x, const float* drop1,

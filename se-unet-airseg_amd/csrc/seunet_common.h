@@ -327,7 +327,8 @@ int launch_upsample2_fwd(int dtype, const void* in, int C, void* out, Dims din, 
 int launch_upsample2_bwd(int dtype, const void* g_out, int C, void* g_in, int accumulate,
                          Dims din, hipStream_t s);
 int upsample2_form(int dtype, int C, Dims din, bool backward);   // the form of the pass's cut: 0 gather, 1 tiled, 2 march
-int launch_multi_zero(float* const* ptrs, const int* counts, int n, hipStream_t s);   // (layout.hip)
+struct WgReduceJob;   // (wgrad.h)
+int launch_multi_zero(float* const* ptrs, const int* counts, int n, hipStream_t s, const WgReduceJob* rider = nullptr);   // (layout.hip)
 // n_classes > 1: the general head path (classes.hip)
 int class_max();
 int class_grad_records(Dims d);

@@ -374,15 +374,6 @@ wgrad_kernel(WgArgs a) {
 #endif
 }
 
-// element e = (tap, ci, co) of a slab of the 32 x 32 combo -> dW (cout_w, cin_w, taps)
-struct WgMap {
-  int taps, cin_w, cout_w, co_tiles;
-  __device__ long long operator()(int combo, int e) const {
-    const int tap = e >> 10, ci = (combo / co_tiles) * 32 + ((e >> 5) & 31), co = (combo % co_tiles) * 32 + (e & 31);
-    return ci < cin_w && co < cout_w ? (long long)(((size_t)co * cin_w + ci) * taps + tap) : -1;
-  }
-};
-
 // persistent workgroups per (ci, co) combo == slabs the reduction has to sum; ~2 resident workgroups per CU in total
 static inline int wgrad_groups(int combos, int total_tiles) {
   int g = WG_TILED_SLABS / combos;   // two resident workgroups per CU
@@ -405,16 +396,26 @@ size_t wgrad_workspace_bytes(int taps, int cin, int cout) {
   return tiled > other ? tiled : other;
 }
 
+// the slab reduction as a launch of its own: the immediate path of every launcher, and the network walk's flushes
+__global__ void __launch_bounds__(256) wgrad_reduce_kernel(WgReduceJob job) { wgrad_reduce_body(job, blockIdx.x); }
+
+int launch_wgrad_reduce(const WgReduceJob& job, hipStream_t s) {
+  if (job.blocks() == 0) return 0;
+  wgrad_reduce_kernel<<<job.blocks(), 256, 0, s>>>(job);
+  SEUNET_LAUNCH_CHECK();
+  return 0;
+}
+
 // weight gradient on kernel k: the dispatch over the same family
 int run_wgrad(ConvKernel k, int dtype, int taps, int dil, const SrcList& x, int cin_logical, const void* dy, int cout, float* dw,
-              void* workspace, size_t ws_bytes, Dims d, hipStream_t s) {
+              void* workspace, size_t ws_bytes, Dims d, hipStream_t s, WgReduceJob* defer) {
   switch (k) {
     case ConvKernel::Naive: return launch_wgrad_naive(dtype, taps, dil, x, cin_logical, dy, cout, dw, d, s);
-    case ConvKernel::Tiled: return launch_wgrad(dtype, taps, dil, x, cin_logical, dy, cout, dw, workspace, ws_bytes, d, s);
+    case ConvKernel::Tiled: return launch_wgrad(dtype, taps, dil, x, cin_logical, dy, cout, dw, workspace, ws_bytes, d, s, defer);
     case ConvKernel::Stream:
-      return launch_wgrad_stream(dtype, dil, x.ptr[0], x.C[0], cin_logical, dy, cout, cout, dw, workspace, ws_bytes, d, s);
-    case ConvKernel::March: return launch_wgrad_march(dtype, taps, dil, x, cin_logical, dy, cout, dw, workspace, ws_bytes, d, s);
-    case ConvKernel::Wgrad1x1: return launch_wgrad_1x1(dtype, x, cin_logical, dy, cout, dw, workspace, ws_bytes, d, s);
+      return launch_wgrad_stream(dtype, dil, x.ptr[0], x.C[0], cin_logical, dy, cout, cout, dw, workspace, ws_bytes, d, s, defer);
+    case ConvKernel::March: return launch_wgrad_march(dtype, taps, dil, x, cin_logical, dy, cout, dw, workspace, ws_bytes, d, s, defer);
+    case ConvKernel::Wgrad1x1: return launch_wgrad_1x1(dtype, x, cin_logical, dy, cout, dw, workspace, ws_bytes, d, s, defer);
   }
   return fail("wgrad: unknown kernel %d", (int)k);
 }
@@ -445,7 +446,7 @@ static void wg_sources(WgArgs& a, const SrcList& x, int cin_logical) {   // the 
 // x: input activation (may be a concatenation), cin_logical leading channels carry weights;
 // dy: gradient w.r.t. the raw conv output, [N][V][cout]; dw: (cout, cin_logical, taps) f32, overwritten.
 int launch_wgrad(int dtype, int taps, int dil, const SrcList& x, int cin_logical, const void* dy, int cout,
-                 float* dw, void* workspace, size_t ws_bytes, Dims d, hipStream_t s) {
+                 float* dw, void* workspace, size_t ws_bytes, Dims d, hipStream_t s, WgReduceJob* defer) {
   SEUNET_CHECK(taps == 27 || taps == 1, "wgrad: taps=%d unsupported", taps);
   SEUNET_CHECK(taps == 1 || dil == 1 || dil == 2, "wgrad: dilation %d unsupported", dil);
   SEUNET_CHECK(x.n >= 1 && x.n <= 3, "wgrad: 1..3 sources");
@@ -474,7 +475,7 @@ int launch_wgrad(int dtype, int taps, int dil, const SrcList& x, int cin_logical
     else e = wgrad_launch_one<T, 27, 2, 4>(a, grid, s);
   });
   if (e) return e;
-  return launch_wgrad_reduce(a.slab, G, taps * 1024, combos, WgMap{taps, cin_logical, cout, a.co_tiles}, dw, s);
+  return finish_wgrad(a.slab, G, taps * 1024, combos, WgMap{taps, cin_logical, cout, a.co_tiles}, dw, defer, s);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -177,18 +177,6 @@ wgrad_1x1_kernel(W1Args a) {
     for (int k = 0; k < NCOB; ++k) *reinterpret_cast<f32x4*>(out + (c * NCOB + k) * 256) = acc[c][k];
 }
 
-// element e = (wave, input block, output block, lane, component) of a slab (one combo: all channels) -> dW (cout, cin)
-struct W1Map {
-  int cibw, ncob, cin;
-  __device__ long long operator()(int, int e) const {
-    const int comp = e & 3, lane = (e >> 2) & 63, pair = e >> 8;
-    const int kk = pair % ncob, c = (pair / ncob) % cibw, wave = pair / (ncob * cibw);
-    const int co = kk * 16 + 4 * (lane >> 4) + comp;
-    const int ci = (wave * cibw + c) * 16 + (lane & 15);
-    return ci < cin ? (long long)((size_t)co * cin + ci) : -1;
-  }
-};
-
 struct W1Cfg { int cibw, ncob, ch, nst; };
 static bool wgrad_1x1_cfg(int dtype, const SrcList& x, int cin_logical, int cout, W1Cfg& c) {
   if (dtype_size(dtype) != 2 || x.n < 1 || x.n > 3 || cin_logical != x.total()) return false;
@@ -244,7 +232,7 @@ static int wgrad_1x1_launch(const W1Args& a, int grid, int lds, hipStream_t s) {
 }
 
 int launch_wgrad_1x1(int dtype, const SrcList& x, int cin_logical, const void* dy, int cout, float* dw, void* workspace,
-                     size_t ws_bytes, Dims d, hipStream_t s) {
+                     size_t ws_bytes, Dims d, hipStream_t s, WgReduceJob* defer) {
   W1Cfg c;
   SEUNET_CHECK(wgrad_1x1_cfg(dtype, x, cin_logical, cout, c),
                "wgrad_1x1: 16-bit tensors, 1..3 sources of 32 or 64 channels (64, 128 or 192 together), 32 / 64 / 128 output channels only");
@@ -273,7 +261,7 @@ int launch_wgrad_1x1(int dtype, const SrcList& x, int cin_logical, const void* d
     else e = wgrad_1x1_launch<T, 3, 8, 64>(a, grid, lds, s);
   });
   if (e) return e;
-  return launch_wgrad_reduce(a.slab, grid, (int)slabs.per, 1, W1Map{c.cibw, c.ncob, cin_logical}, dw, s);
+  return finish_wgrad(a.slab, grid, (int)slabs.per, 1, W1Map{c.cibw, c.ncob, cin_logical}, dw, defer, s);
 }
 
 }  // namespace seunet

@@ -322,19 +322,6 @@ wgrad_march_kernel(WmArgs a) {
     for (int t = 0; t < 27; ++t) *reinterpret_cast<f32x4*>(out + (k * 27 + t) * 256) = acc[k][t];
 }
 
-// element e = (pair, tap, lane, component) of a slab of the (xc x yc)-channel combo -> dW (cout, cin_w, 27); no channel padding
-struct WmMap {
-  int ncb, pw, xc, yc, nco, cin_w;
-  __device__ long long operator()(int combo, int e) const {
-    const int comp = e & 3, lane = (e >> 2) & 63, tap = (e >> 8) % 27, pair = e / (27 * 256);
-    const int wave = pair / pw, kk = pair % pw;
-    const int cib = wave % ncb, cob = (wave / ncb) * pw + kk;
-    const int co = (combo % nco) * yc + cob * 16 + 4 * (lane >> 4) + comp;
-    const int ci = (combo / nco) * xc + cib * 16 + (lane & 15);
-    return (long long)(((size_t)co * cin_w + ci) * 27 + tap);
-  }
-};
-
 struct WmCfg { int ncb, nob; };
 static WmCfg wm_blocks(int cin, int cout) {   // 16-channel blocks (input, output) of a workgroup
   if (cin % 64 == 0) return {4, 2};
@@ -417,7 +404,7 @@ static int wgrad_march_launch(const WmArgs& a, dim3 grid, hipStream_t s) {
 }
 
 int launch_wgrad_march(int dtype, int taps, int dil, const SrcList& x, int cin_logical, const void* dy, int cout,
-                       float* dw, void* workspace, size_t ws_bytes, Dims d, hipStream_t s) {
+                       float* dw, void* workspace, size_t ws_bytes, Dims d, hipStream_t s, WgReduceJob* defer) {
   WmCfg c;
   SEUNET_CHECK(wgrad_march_cfg(dtype, taps, dil, x, cin_logical, cout, d, x.gap(), c),
                "wgrad_march: 16-bit 3x3x3 layers with 32k input and 32k output channels (one tensor or two equal halves) only");
@@ -441,8 +428,8 @@ int launch_wgrad_march(int dtype, int taps, int dil, const SrcList& x, int cin_l
     else e = wgrad_march_launch<T, 2, 2, 2>(a, grid, s);
   });
   if (e) return e;
-  return launch_wgrad_reduce(a.slab, cut.groups, (int)cut.slab_floats(), cut.combos,
-                             WmMap{c.ncb, cut.pw, cut.xc, cut.yc, cut.nco, cin_logical}, dw, s);
+  return finish_wgrad(a.slab, cut.groups, (int)cut.slab_floats(), cut.combos,
+                      WmMap{c.ncb, cut.pw, cut.xc, cut.yc, cut.nco, cin_logical}, dw, defer, s);
 }
 
 }  // namespace seunet

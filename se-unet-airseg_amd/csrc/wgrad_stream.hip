@@ -253,15 +253,6 @@ wgrad_stream_kernel(WsArgs a) {
   }
 }
 
-// element e = (tap, ci, co) of a slab [27][cin][cout] (one combo) -> dW (cout_w, cin_w, 3, 3, 3)
-struct WsMap {
-  int cin, cout, cin_w, cout_w;
-  __device__ long long operator()(int, int e) const {
-    const int co = e % cout, ci = (e / cout) % cin, tap = e / (cout * cin);
-    return ci < cin_w && co < cout_w ? (long long)(((size_t)co * cin_w + ci) * 27 + tap) : -1;
-  }
-};
-
 static bool ws_shape_ok(int cin, int cout, int dil) {
   if (cin == 32 && cout == 16) return dil == 1;          // (dilation 2 would need 161 KB of LDS)
   return (cin == 8 && (cout == 8 || cout == 16)) || (cin == 16 && cout == 32) || (cin == 16 && cout == 16);
@@ -312,7 +303,7 @@ static int ws_launch(int dtype, const WsArgs& a, dim3 grid, hipStream_t s) {
 // x: [N][D][H][W][x_c] (x_c = 8 | 16 | 32, cin_w leading channels carry weights); dy: [N][D][H][W][dy_c];
 // dw: (cout_w, cin_w, 3, 3, 3) f32, overwritten.
 int launch_wgrad_stream(int dtype, int dil, const void* x, int x_c, int cin_w, const void* dy, int dy_c, int cout_w, float* dw,
-                        void* workspace, size_t ws_bytes, Dims d, hipStream_t s) {
+                        void* workspace, size_t ws_bytes, Dims d, hipStream_t s, WgReduceJob* defer) {
   SEUNET_CHECK(wgrad_stream_supported(dtype, 27, dil, x_c, dy_c), "wgrad_stream: unsupported shape (%d x %d channels, dilation %d)", x_c, dy_c, dil);
   SEUNET_CHECK(x && dy && dw && workspace && cin_w >= 1 && cin_w <= x_c && cout_w >= 1 && cout_w <= dy_c, "wgrad_stream: bad argument");
   const WsCut cut = ws_cut(d, dil);
@@ -333,7 +324,7 @@ int launch_wgrad_stream(int dtype, int dil, const void* x, int x_c, int cin_w, c
   else if (x_c == 16 && dy_c == 32) e = dil == 1 ? ws_launch<16, 32, 1>(dtype, a, grid, s) : ws_launch<16, 32, 2>(dtype, a, grid, s);
   else if (x_c == 32 && dy_c == 16) e = ws_launch<32, 16, 1>(dtype, a, grid, s);
   if (e) return e;
-  return launch_wgrad_reduce(a.slab, cut.slabs(), (int)slabs.per, 1, WsMap{x_c, dy_c, cin_w, cout_w}, dw, s);
+  return finish_wgrad(a.slab, cut.slabs(), (int)slabs.per, 1, WsMap{x_c, dy_c, cin_w, cout_w}, dw, defer, s);
 }
 
 }  // namespace seunet
