@@ -243,6 +243,35 @@ int seunet_loss_sums_per_sample(const float* pred, int apply_sigmoid, const floa
 int seunet_loss_sample_values(const double* sums, int batch, double c_dice, double c_gul, double c_atr, float* values,
                               seunet_stream_t s);
 
+/* ---- soft skeleton, soft clDice loss (Shit et al., CVPR 2021) and the hard clDice counts (csrc/cldice.hip; the definition
+ * is tests/cldice_oracle.py) ------------------------------------------------------------------------------------------------
+ * Tensors are `volumes` independent (n0, n1, n2) float32 volumes back to back; pooling never crosses from one into the next.
+ * iters: 0 .. 16.  Every call orders all of its work on s and none synchronises the host.
+ *   seunet_soft_skeleton: out = S_iters of x, bit for bit the float32 oracle's.  save != 0 also fills the workspace with what
+ *     seunet_cldice_backward reads (the workspace then belongs to that pair of calls; the backward leaves the saved state as
+ *     it is, so it can run again).  workspace: seunet_cldice_workspace_bytes with the same arguments (host only; 0 + error
+ *     for an empty shape or bad iters).
+ *   seunet_cldice_sums: sums[4] (f64) = sum S(p) t, sum S(p), sum S(t) p, sum S(t) over n voxels, formed in float64 in a fixed
+ *     order; partial: seunet_cldice_partial_doubles() doubles of scratch.  Under data parallelism the caller all-reduces the
+ *     four sums before the next two calls.
+ *   seunet_cldice_value: value[0] = f32(1 - 2 tprec tsens / (tprec + tsens)), tprec = (sums[0] + smooth) / (sums[1] + smooth),
+ *     tsens = (sums[2] + smooth) / (sums[3] + smooth); scalars (optional, f64[2]) = dL/dtprec, dL/dtsens.
+ *   seunet_cldice_backward: grad = g_dev[0] * dL/dpred for the prediction whose saving forward filled `workspace`, by the
+ *     recorded arg-min / arg-max choices, in gather form (no float atomics: the same bits every run).
+ *   seunet_cldice_counts: counts[4] (u64) = |S_P and V_L|, |S_P|, |S_L and V_P|, |S_L| of four uint8 masks (non-zero = 1). */
+size_t seunet_cldice_workspace_bytes(long long volumes, int n0, int n1, int n2, int iters, int save);
+int seunet_cldice_partial_doubles(void);
+int seunet_soft_skeleton(const float* x, long long volumes, int n0, int n1, int n2, int iters, float* out, int save, void* workspace,
+                         size_t workspace_bytes, seunet_stream_t s);
+int seunet_cldice_sums(const float* skel_pred, const float* target, const float* skel_target, const float* pred, long long n,
+                       double* partial, double* sums, seunet_stream_t s);
+int seunet_cldice_value(const double* sums, double smooth, float* value, double* scalars, seunet_stream_t s);
+int seunet_cldice_backward(const float* target, const float* skel_target, const double* sums, double smooth, const float* g_dev,
+                           long long volumes, int n0, int n1, int n2, int iters, float* grad, void* workspace, size_t workspace_bytes,
+                           seunet_stream_t s);
+int seunet_cldice_counts(const unsigned char* skel_pred, const unsigned char* label, const unsigned char* skel_label,
+                         const unsigned char* pred, long long n, unsigned long long* counts, seunet_stream_t s);
+
 /* ---- online hard mining: the sample pool of save_data_online / save_data_online3 (train.py:78-138) and OnlineHMData /
  * OnlineHMData3 (data.py:586-630) in HBM ----------------------------------------------------------------------------------
  * The pool keeps the `capacity` samples with the largest key.  All of it is caller-owned device memory:

@@ -97,7 +97,14 @@ PROTOTYPES = {
     "seunet_loss_sample_partial_floats": (_i, [_i]),
     "seunet_loss_sums_per_sample": (_i, [_vp, _i, _vp, _vp, _vp, _i, _ll, _vp, _vp, _i, _vp]),
     "seunet_loss_sample_values": (_i, [_vp, _i, _d, _d, _d, _vp, _vp]),
-    "seunet_pool_select": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp]),
+    "seunet_cldice_workspace_bytes": (_sz, [_ll, _i, _i, _i, _i, _i]),
+    "seunet_cldice_partial_doubles": (_i, []),
+    "seunet_soft_skeleton": (_i, [_vp, _ll, _i, _i, _i, _i, _vp, _i, _vp, _sz, _vp]),
+    "seunet_cldice_sums": (_i, [_vp, _vp, _vp, _vp, _ll, _vp, _vp, _vp]),
+    "seunet_cldice_value": (_i, [_vp, _d, _vp, _vp, _vp]),
+    "seunet_cldice_backward": (_i, [_vp, _vp, _vp, _d, _vp, _ll, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "seunet_cldice_counts": (_i, [_vp, _vp, _vp, _vp, _ll, _vp, _vp]),
+    "seunet_pool_select":(_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     "seunet_pool_scatter": (_i, [_vp, _i, _i, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "seunet_pool_gather": (_i, [_ip, _i, _i, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "seunet_xbranch_moment_slots": (_i, [Dims]),

@@ -320,6 +320,34 @@ int seunet_loss_sample_values(const double* sums, int batch, double c_dice, doub
   return launch_loss_sample_values(sums, batch, c_dice, c_gul, c_atr, values, S(s));
 }
 
+size_t seunet_cldice_workspace_bytes(long long volumes, int n0, int n1, int n2, int iters, int save) {
+  if (volumes < 1 || n0 < 1 || n1 < 1 || n2 < 1) { fail("cldice_workspace_bytes: empty shape (%lld volumes of (%d, %d, %d))", volumes, n0, n1, n2); return 0; }
+  if (iters < 0 || iters > kCldiceMaxIters) { fail("cldice_workspace_bytes: iters=%d (0..%d)", iters, kCldiceMaxIters); return 0; }
+  if ((long long)n0 * n1 * n2 >= (1ll << 31) / volumes) { fail("cldice_workspace_bytes: fewer than 2^31 voxels in all supported"); return 0; }
+  return cldice_workspace_bytes(volumes, n0, n1, n2, iters, save != 0);
+}
+int seunet_cldice_partial_doubles(void) { return cldice_partial_doubles(); }
+int seunet_soft_skeleton(const float* x, long long volumes, int n0, int n1, int n2, int iters, float* out, int save, void* workspace,
+                         size_t workspace_bytes, seunet_stream_t s) {
+  return launch_soft_skeleton(x, volumes, n0, n1, n2, iters, out, save != 0, workspace, workspace_bytes, S(s));
+}
+int seunet_cldice_sums(const float* skel_pred, const float* target, const float* skel_target, const float* pred, long long n,
+                       double* partial, double* sums, seunet_stream_t s) {
+  return launch_cldice_sums(skel_pred, target, skel_target, pred, n, partial, sums, S(s));
+}
+int seunet_cldice_value(const double* sums, double smooth, float* value, double* scalars, seunet_stream_t s) {
+  return launch_cldice_value(sums, smooth, value, scalars, S(s));
+}
+int seunet_cldice_backward(const float* target, const float* skel_target, const double* sums, double smooth, const float* g_dev,
+                           long long volumes, int n0, int n1, int n2, int iters, float* grad, void* workspace, size_t workspace_bytes,
+                           seunet_stream_t s) {
+  return launch_cldice_backward(target, skel_target, sums, smooth, g_dev, volumes, n0, n1, n2, iters, grad, workspace, workspace_bytes, S(s));
+}
+int seunet_cldice_counts(const unsigned char* skel_pred, const unsigned char* label, const unsigned char* skel_label,
+                         const unsigned char* pred, long long n, unsigned long long* counts, seunet_stream_t s) {
+  return launch_cldice_counts(skel_pred, label, skel_label, pred, n, counts, S(s));
+}
+
 int seunet_pool_select(const float* new_keys, int batch, float* keys, long long* seq, long long* state, int capacity, int* slots_out,
                        seunet_stream_t s) {
   return launch_pool_select(new_keys, batch, keys, seq, state, capacity, slots_out, S(s));

@@ -1,4 +1,4 @@
-// Shared layer of the volume operations (components.hip, lung.hip, edt.hip, edt_sampling.hip, parse.hip, skeleton.hip, dti.hip, morph.hip, mesh.hip, mesh_label.hip, morphometry.hip): their launcher
+// Shared layer of the volume operations (components.hip, lung.hip, edt.hip, edt_sampling.hip, parse.hip, skeleton.hip, dti.hip, morph.hip, mesh.hip, mesh_label.hip, morphometry.hip, cldice.hip): their launcher
 // prototypes, ONE workspace layout per operation, the extent check and the voxel / wave helpers their kernels share.
 //
 // Workspace contract: every operation has a layout struct filled by one function that walks a WsCarver.  Over a null base
@@ -391,6 +391,35 @@ struct BranchWallOut {
 };
 int launch_branch_wall_stats(const int* parsing, const unsigned char* skeleton, const int* indices, int n0, int n1, int n2, int num,
                              double s0, double s1, double s2, BranchWallOut out, hipStream_t s);
+
+// ---- soft skeleton / soft clDice loss / hard clDice counts (cldice.hip) -----------------------------------------------------
+// `volumes` independent (n0, n1, n2) volumes back to back; n = volumes n0 n1 n2 voxels.  A forward that keeps no state needs
+// the two E buffers only.  A saving forward (the loss's prediction branch) also fills the chains the backward reads; the
+// backward writes `a` and reuses e0 / e1 for its running gradient, so the saved state survives it.
+constexpr int kCldiceMaxIters = 16;
+struct CldiceWs {
+  float *e0, *e1;         // E_{j+1} of odd / even j (forward); dL/dE_j in turn (backward)
+  float* d;               // iters + 1 volumes: d_j = relu(E_j - O_j)
+  float* s;               // iters volumes: S_0 .. S_{iters-1} (S_iters is the forward's output)
+  float* a;               // iters + 1 volumes: dL/dd_j, masked (backward)
+  unsigned char* code;    // iters + 1 volumes: arg-min of E_{j+1} (bits 0-2), arg-max of O_j (bits 3-7)
+};
+static inline CldiceWs cldice_ws(WsCarver& c, long long volumes, int n0, int n1, int n2, int iters, bool save) {
+  const size_t n = (size_t)volumes * n0 * n1 * n2, k = save ? (size_t)iters + 1 : 0;
+  return CldiceWs{c.take<float>(n), c.take<float>(n), c.take<float>(k * n), c.take<float>(save ? (size_t)iters * n : 0),
+                  c.take<float>(k * n), c.take<unsigned char>(k * n)};
+}
+size_t cldice_workspace_bytes(long long volumes, int n0, int n1, int n2, int iters, bool save);
+int cldice_partial_doubles();
+int launch_soft_skeleton(const float* x, long long volumes, int n0, int n1, int n2, int iters, float* out, bool save, void* workspace,
+                         size_t ws_bytes, hipStream_t s);
+int launch_cldice_sums(const float* sp, const float* t, const float* st, const float* p, long long n, double* partial, double* sums,
+                       hipStream_t s);
+int launch_cldice_value(const double* sums, double smooth, float* value, double* scal, hipStream_t s);
+int launch_cldice_backward(const float* t, const float* st, const double* sums, double smooth, const float* g_dev, long long volumes,
+                           int n0, int n1, int n2, int iters, float* grad, void* workspace, size_t ws_bytes, hipStream_t s);
+int launch_cldice_counts(const unsigned char* sp, const unsigned char* vl, const unsigned char* sl, const unsigned char* vp, long long n,
+                         unsigned long long* counts, hipStream_t s);
 
 // ---- device helpers -------------------------------------------------------------------------------------------------------
 // raster index -> coordinates of an (n0, n1, n2) volume (n0 is not needed)

@@ -192,3 +192,108 @@ def per_sample_loss(pred, target, weight=None, skel=None, c_dice=0.0, c_gul=1.0,
         _lib.check(lib.seunet_loss_sample_values(sums.data_ptr(), batch, float(c_dice), float(c_gul), float(c_atr),
                                                  values.data_ptr(), _lib.stream_ptr()), "loss_sample_values")
     return values
+
+
+# ---- soft skeleton and soft clDice (csrc/cldice.hip; the definition is tests/cldice_oracle.py) ---------------------------------
+CLDICE_MAX_ITERS = 16
+
+
+def _cldice_args(name, x, iters):
+    if isinstance(iters, bool) or not isinstance(iters, int) or not 0 <= iters <= CLDICE_MAX_ITERS:
+        raise ValueError(f"{name}: iters={iters!r} must be an integer from 0 to {CLDICE_MAX_ITERS}")
+    if x.dim() < 3 or x.numel() == 0:
+        raise ValueError(f"{name}: shape {tuple(x.shape)}: the last three axes are the volume, and none may be empty")
+
+
+def _need_gpu(name, *tensors):
+    for t in tensors:
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f"{name} needs GPU tensors (no CPU fallback; the CPU oracle is tests/cldice_oracle.py)")
+
+
+def _skeleton(xf, iters, save):
+    """(S_iters, workspace) of a contiguous float32 CUDA tensor; with ``save`` the workspace holds what the backward reads."""
+    lib = _lib.load()
+    n0, n1, n2 = (int(v) for v in xf.shape[-3:])
+    volumes = xf.numel() // (n0 * n1 * n2)
+    with torch.cuda.device(xf.device):
+        nbytes = lib.seunet_cldice_workspace_bytes(volumes, n0, n1, n2, iters, int(save))
+        if nbytes == 0:
+            raise RuntimeError(f"libseunet_hip cldice_workspace_bytes: {_lib.last_error()}")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=xf.device)
+        out = torch.empty_like(xf)
+        _lib.check(lib.seunet_soft_skeleton(xf.data_ptr(), volumes, n0, n1, n2, iters, out.data_ptr(), int(save), ws.data_ptr(),
+                                            nbytes, _lib.stream_ptr()), "soft_skeleton")
+    return out, ws
+
+
+def soft_skeleton(x, iters: int = 3):
+    """The soft skeleton of clDice (iterated min- / max-pooling, tests/cldice_oracle.py) of every volume of ``x``: the last
+    three axes are the volume, every leading index is a volume of its own.  float32 tensor of ``x``'s shape, bit for bit the
+    float32 oracle's.  Outside autograd; nothing is waited for."""
+    _cldice_args("soft_skeleton", x, iters)
+    _need_gpu("soft_skeleton", x)
+    return _skeleton(x.detach().contiguous().float(), iters, False)[0]
+
+
+def _cldice_sums(sp, t, st, p):
+    lib = _lib.load()
+    with torch.cuda.device(p.device):
+        partial = torch.empty(lib.seunet_cldice_partial_doubles(), dtype=torch.float64, device=p.device)
+        sums = torch.empty(4, dtype=torch.float64, device=p.device)
+        _lib.check(lib.seunet_cldice_sums(sp.data_ptr(), t.data_ptr(), st.data_ptr(), p.data_ptr(), p.numel(), partial.data_ptr(),
+                                          sums.data_ptr(), _lib.stream_ptr()), "cldice_sums")
+    return sums
+
+
+class _SoftClDice(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target, iters, smooth, target_skeleton, group):
+        p = pred.detach().contiguous().float()
+        t = target.detach().to(p.device, torch.float32).contiguous()
+        sp, ws = _skeleton(p, iters, True)
+        st = _skeleton(t, iters, False)[0] if target_skeleton is None else target_skeleton.detach().to(p.device, torch.float32).contiguous()
+        sums = _cldice_sums(sp, t, st, p)
+        _reduce(sums, group)
+        value = torch.empty((), dtype=torch.float32, device=p.device)
+        with torch.cuda.device(p.device):
+            _lib.check(_lib.load().seunet_cldice_value(sums.data_ptr(), float(smooth), value.data_ptr(), None, _lib.stream_ptr()),
+                       "cldice_value")
+        ctx.saved = (t, st, sums, ws)
+        ctx.args = (int(iters), float(smooth), pred.shape)
+        return value
+
+    @staticmethod
+    def backward(ctx, g):
+        t, st, sums, ws = ctx.saved
+        iters, smooth, shape = ctx.args
+        n0, n1, n2 = (int(v) for v in t.shape[-3:])
+        with torch.cuda.device(t.device):
+            gs = g.detach().reshape(1).to(t.device, torch.float32).contiguous()
+            grad = torch.empty_like(t)
+            _lib.check(_lib.load().seunet_cldice_backward(t.data_ptr(), st.data_ptr(), sums.data_ptr(), smooth, gs.data_ptr(),
+                                                          t.numel() // (n0 * n1 * n2), n0, n1, n2, iters, grad.data_ptr(),
+                                                          ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "cldice_backward")
+        return grad.reshape(shape), None, None, None, None, None
+
+
+def soft_cldice_loss(pred, target, iters: int = 3, smooth: float = 1.0, target_skeleton=None, group=None):
+    """Soft clDice loss (Shit et al., CVPR 2021; tests/cldice_oracle.py): ``1 - 2 tprec tsens / (tprec + tsens)`` with
+    ``tprec = (sum S(pred) target + smooth) / (sum S(pred) + smooth)``, ``tsens = (sum S(target) pred + smooth) / (sum S(target) +
+    smooth)``, sums over the WHOLE batch like the other losses here.  Takes *probabilities* (apply ``torch.sigmoid`` first, as
+    for ``dice_loss``) and a target of the same shape; the last three axes are the volume.  float32 scalar that supports
+    ``.backward()`` with respect to ``pred``.  ``target_skeleton``: a cached ``soft_skeleton(target, iters)``.  ``group=``: the
+    four sums are all-reduced before the ratio is formed, as ``dice_loss`` does with its sums.
+
+    Where voxels of a pooling window hold the SAME value (binary or saturated probabilities) the gradient follows the first
+    minimum in the order (d-1, d, d+1, h-1, h+1, w-1, w+1) and the first maximum in raster order of the 3x3x3 box; torch
+    autograd's choice on such ties differs.  On distinct values the gradient does not depend on any tie rule.  Deterministic:
+    no float atomics, the same bits every run; nothing is waited for in forward or backward."""
+    _cldice_args("soft_cldice_loss", pred, iters)
+    if tuple(target.shape) != tuple(pred.shape):
+        raise ValueError(f"soft_cldice_loss: target of shape {tuple(target.shape)} for a prediction of shape {tuple(pred.shape)}")
+    if target_skeleton is not None and tuple(target_skeleton.shape) != tuple(pred.shape):
+        raise ValueError(f"soft_cldice_loss: target_skeleton of shape {tuple(target_skeleton.shape)} for a prediction of shape "
+                         f"{tuple(pred.shape)}")
+    _need_gpu("soft_cldice_loss", pred, target, target_skeleton)
+    return _SoftClDice.apply(pred, target, iters, smooth, target_skeleton, group)

@@ -220,3 +220,32 @@ def evaluation_case(pred, label, skeleton, parsing, nbins: int = 4096):
     spe = specificity_calculation(None, None, sums=s)
     pre = precision_calculation(None, None, sums=s)
     return td, bd, dsc, pre, sen, spe
+
+
+def cldice_score(pred_mask, label_mask, pred_skeleton=None, label_skeleton=None, return_parts: bool = False):
+    """The hard clDice score (Shit et al., CVPR 2021) of two binary volumes: ``tprec = |S_P and V_L| / |S_P|``, ``tsens = |S_L and
+    V_P| / |S_L|``, ``2 tprec tsens / (tprec + tsens)`` in float64.  Missing skeletons come from ``skeletonize_3d``; the four
+    counts are exact integers from one counting pass on the device (``seunet_cldice_counts``), read back once.  A ratio whose
+    skeleton is empty counts as 0, and so does the score when both ratios are 0 (never nan: tests/cldice_oracle.py says why).
+    numpy arrays or CUDA tensors of any dtype (non-zero = 1).  ``return_parts``: ``(score, tprec, tsens, counts)``."""
+    from .prep import skeletonize_3d
+    vp, _ = _as_u8_cuda(pred_mask, "cldice_score")
+    vl, _ = _as_u8_cuda(label_mask, "cldice_score")
+    if vp.dim() != 3 or vl.shape != vp.shape:
+        raise ValueError(f"cldice_score expects two 3-D volumes of one shape, got {tuple(vp.shape)} and {tuple(vl.shape)}")
+    if vp.numel() == 0:
+        raise ValueError("cldice_score: empty volume")
+    sp = skeletonize_3d(vp) if pred_skeleton is None else _as_u8_cuda(pred_skeleton, "cldice_score")[0]
+    sl = skeletonize_3d(vl) if label_skeleton is None else _as_u8_cuda(label_skeleton, "cldice_score")[0]
+    for t in (sp, sl):
+        if t.shape != vp.shape:
+            raise ValueError(f"cldice_score: a skeleton of shape {tuple(t.shape)} for masks of shape {tuple(vp.shape)}")
+    with torch.cuda.device(vp.device):
+        counts = torch.empty(4, dtype=torch.int64, device=vp.device)
+        _lib.check(_lib.load().seunet_cldice_counts(sp.data_ptr(), vl.data_ptr(), sl.data_ptr(), vp.data_ptr(), vp.numel(),
+                                                    counts.data_ptr(), _lib.stream_ptr()), "cldice_counts")
+    c = [int(v) for v in counts.cpu().tolist()]
+    tprec = np.float64(c[0]) / np.float64(c[1]) if c[1] else np.float64(0.0)
+    tsens = np.float64(c[2]) / np.float64(c[3]) if c[3] else np.float64(0.0)
+    score = float(2.0 * tprec * tsens / (tprec + tsens)) if tprec + tsens != 0 else 0.0
+    return (score, float(tprec), float(tsens), tuple(c)) if return_parts else score
