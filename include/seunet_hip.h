@@ -632,6 +632,49 @@ int seunet_branch_wall_stats(const int* parsing, const unsigned char* skeleton, 
                              double s0, double s1, double s2, long long* wall_count, long long* offset_sq_sum, double* wall_sq_min,
                              double* wall_sq_max, int* status_dev, seunet_stream_t s);
 
+/* ---- surface distances: Hausdorff distance, its percentiles, ASSD and surface Dice in the units of the spacing --
+ * The reference computes none of them; the definition is this comment, restated in numpy by tests/surface_oracle.py.
+ * a, b: two 0/1 volumes (bytes, non-zero = 1, C-contiguous (n0, n1, n2), extents <= 32767, fewer than 2^31 voxels).
+ * border(M) = M and not binary_erosion(M) with the 6-neighbour cross, one iteration, outside the volume = 0 (a set voxel on a face
+ * of the volume is a border voxel; MedPy's surface distances with connectivity 1).  d_AB: for every border voxel of A in raster
+ * order, sqrt((dt_0^2 + dt_1^2) + dt_2^2) with dt_k = (double)(index_k - coordinate_k) * s_k to the border voxel of B that
+ * scipy.ndimage.distance_transform_edt(~border(B), sampling = s) selects, every product and sum rounded on its own: scipy's float64
+ * distances bit for bit.  d_BA is the mirror image.  dist = d_AB (n_a values) followed by d_BA (n_b values).  Every result is
+ * deterministic and does not depend on the order in which the device executes anything: integer atomics and fixed-shape sums only.
+ *
+ * seunet_surface_count: packs both masks, forms both borders, counts and scans.  *n_a, *n_b (HOST) receive the numbers of border
+ *   voxels and box (6 HOST ints) = {lo0, hi0, lo1, hi1, lo2, hi2}, the bounding box of the non-zero voxels of a or b, high ends
+ *   exclusive ({n0, 0, n1, 0, n2, 0} when both are empty).  This call synchronises the stream once, to read those numbers.
+ *   workspace: seunet_surface_workspace_bytes(n0, n1, n2), caller-owned, and handed unchanged to seunet_surface_emit.
+ * seunet_surface_emit: writes dist (n_a + n_b float64, at most 2^31 - 1) and, unless NULL, voxel (n_a + n_b int32: each border
+ *   voxel's linear index in the volume) with the box, n_a and n_b the count call returned; n_a and n_b >= 1 (a mask without voxels
+ *   has no surface distances: error).  The distance transforms run inside the box only, which gives the distances of the full
+ *   volume bit for bit.  s0, s1, s2: the voxel spacing, positive and finite.  emit_workspace:
+ *   seunet_surface_emit_workspace_bytes(hi0 - lo0, hi1 - lo1, hi2 - lo2) (13 bytes per voxel of the box).  Does not synchronise.
+ * seunet_surface_summary: out_dev (seunet_surface_summary_bytes(ntol) device bytes, 8-byte aligned) receives, as 64-bit words,
+ *   {count_a, count_b, max_a, max_b, sum_a, sum_b, le_a[ntol], le_b[ntol]}: the maxima and sums are float64 (0.0 for an empty
+ *   direction), le_x[q] = the number of distances of the direction <= tol[q]; tol: ntol <= 8 HOST doubles.  The sums are formed by
+ *   a tree whose shape depends on n_a and n_b alone (the same bits on every run); the bytes behind the record hold its partials.
+ * seunet_select_ranks: exact order statistics of float64 device values, FINITE AND NON-NEGATIVE (they are ordered by their 64-bit
+ *   patterns).  Request r (nranks <= 8; seg_begin, seg_end, rank: HOST arrays) asks for the element of rank rank[r] (0 = smallest)
+ *   among values[seg_begin[r] .. seg_end[r]); segments may overlap; out_dev[r] (device float64) receives it.  A radix select, eight
+ *   passes of eight bits for all requests together, without a host round trip between passes; the values are not modified.
+ *   n <= 2^31 - 1.  workspace: seunet_select_ranks_workspace_bytes(nranks).
+ * None of the last three calls synchronises; all work is ordered on s. */
+size_t seunet_surface_workspace_bytes(int n0, int n1, int n2);
+int seunet_surface_count(const unsigned char* a, const unsigned char* b, int n0, int n1, int n2, long long* n_a, long long* n_b, int* box,
+                         void* workspace, size_t workspace_bytes, seunet_stream_t s);
+size_t seunet_surface_emit_workspace_bytes(int b0, int b1, int b2);
+int seunet_surface_emit(int n0, int n1, int n2, const int* box, double s0, double s1, double s2, long long n_a, long long n_b,
+                        double* dist, int* voxel, const void* count_workspace, size_t count_workspace_bytes, void* emit_workspace,
+                        size_t emit_workspace_bytes, seunet_stream_t s);
+size_t seunet_surface_summary_bytes(int ntol);
+int seunet_surface_summary(const double* dist, long long n_a, long long n_b, const double* tol, int ntol, void* out_dev,
+                           seunet_stream_t s);
+size_t seunet_select_ranks_workspace_bytes(int nranks);
+int seunet_select_ranks(const double* values, long long n, const long long* seg_begin, const long long* seg_end, const long long* rank,
+                        int nranks, double* out_dev, void* workspace, size_t workspace_bytes, seunet_stream_t s);
+
 /* ---- CT preprocessing: preprocessing.py:26-130 with util.py:95-152 -----------------------------
  * CT volumes are int16, C-contiguous (h, w, z) on the device (the reference's orientation after its transposes), fewer than 2^31
  * voxels; masks are bytes, non-zero = 1.

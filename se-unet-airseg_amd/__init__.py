@@ -17,8 +17,8 @@ from .mesh import (LabelMeshes, branch_meshes, label_meshes, marching_cubes, mes
                    transform_mesh, write_stl)
 from .morphometry import BranchTable, branch_morphometry, branch_stats, branch_tree, branch_wall_distance
 from .preprocess import cut_mask, get_l, large_connected_domain26, preprocess_ct, th_2t
-from .postprocess import (MetricSums, cldice_score, double_threshold_iteration, evaluation_case, largest_component, maximum_3d,
-                          postprocess_prediction, zero_borders)
+from .postprocess import (MetricSums, SurfaceMetrics, cldice_score, double_threshold_iteration, evaluation_case, largest_component,
+                          maximum_3d, order_statistics, postprocess_prediction, surface_distances, surface_metrics, zero_borders)
 from .losses import atr_loss, dice_loss, fused_logit_loss, fused_stage_loss, general_union_loss_lib, per_sample_loss, soft_cldice_loss, soft_skeleton
 from .online import OnlineHardPool
 from .sliding_window import sliding_window_predict, sliding_window_validate, two_channel, window_starts, window_table
@@ -31,4 +31,4 @@ __all__ = ["SE_UNet", "SSEConv", "SSEConv2", "CATConv", "DropLayer", "get_model"
            "binary_erosion", "binary_closing", "binary_fill_holes", "preprocess_ct", "th_2t", "get_l", "large_connected_domain26", "cut_mask",
            "marching_cubes", "smooth_mesh", "write_stl", "prediction_mesh", "mesh_adjacency", "stl_records", "transform_mesh",
            "label_meshes", "branch_meshes", "LabelMeshes", "branch_stats", "branch_tree", "branch_morphometry", "BranchTable", "branch_wall_distance",
-           "soft_skeleton", "soft_cldice_loss", "cldice_score"]
+           "soft_skeleton", "soft_cldice_loss", "cldice_score", "surface_distances", "order_statistics", "surface_metrics", "SurfaceMetrics"]

@@ -166,6 +166,14 @@ PROTOTYPES = {
     "seunet_mesh_label_emit": (_i, [_vp, _i, _i, _i, _i, _d, _ll, _ll, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "seunet_branch_stats": (_i, [_vp, _vp, _vp, _i, _i, _i, _i] + [_vp] * 11 + [_vp]),
     "seunet_branch_wall_stats": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _d, _d, _d, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "seunet_surface_workspace_bytes": (_sz, [_i, _i, _i]),
+    "seunet_surface_count": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(_ll), C.POINTER(_ll), _ip, _vp, _sz, _vp]),
+    "seunet_surface_emit_workspace_bytes": (_sz, [_i, _i, _i]),
+    "seunet_surface_emit": (_i, [_i, _i, _i, _ip, _d, _d, _d, _ll, _ll, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "seunet_surface_summary_bytes": (_sz, [_i]),
+    "seunet_surface_summary": (_i, [_vp, _ll, _ll, C.POINTER(_d), _i, _vp, _vp]),
+    "seunet_select_ranks_workspace_bytes": (_sz, [_i]),
+    "seunet_select_ranks": (_i, [_vp, _ll, C.POINTER(_ll), C.POINTER(_ll), C.POINTER(_ll), _i, _vp, _vp, _sz, _vp]),
     "seunet_mesh_coord_sums": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "seunet_mesh_adjacency_workspace_bytes": (_sz, [_ll, _ll]),
     "seunet_mesh_adjacency": (_i, [_vp, _ll, _ll, _vp, _vp, _ll, _vp, _vp, _vp, _sz, _vp]),

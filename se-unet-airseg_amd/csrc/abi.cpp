@@ -31,7 +31,7 @@ int seunet_debug_upsample2_form(int dtype, int c, seunet_dims dims, int backward
 
 // diagnostic hook (not part of the public header, host only): the workspace layout of a volume operation as its launcher
 // carves it.  op: 0 cc, 1 get_l, 2 edt, 3 lib_weight, 4 break_weight, 5 skeleton_branches, 6 dti, 7 skeleton, 8 parse_assign,
-// 9 binary_morph, 10 mesh, 11 mesh_label, 12 edt_sampling.
+// 9 binary_morph, 10 mesh, 11 mesh_label, 12 edt_sampling, 13 surface (count), 14 surface_emit (extents of the box).
 // Returns the number of sub-buffers (0: extents the op rejects, -1: no such op) and writes (offset, bytes up to the next
 // sub-buffer or the end) of the first `cap`.
 int seunet_debug_volume_layout(int op, int n0, int n1, int n2, size_t* offsets, int cap) {
@@ -53,6 +53,8 @@ int seunet_debug_volume_layout(int op, int n0, int n1, int n2, size_t* offsets, 
     case 10: if ((long long)n0 * n1 * n2 >= (1ll << 31)) return 0; mesh_ws(c, n0, n1, n2); break;
     case 11: if ((long long)n0 * n1 * n2 >= (1ll << 31)) return 0; mesh_label_ws(c, n0, n1, n2); break;
     case 12: edt_sampling_ws(c, n0, n1, n2); break;
+    case 13: if ((long long)n0 * n1 * n2 >= (1ll << 31)) return 0; surface_ws(c, n0, n1, n2); break;
+    case 14: if ((long long)n0 * n1 * n2 >= (1ll << 31)) return 0; surface_emit_ws(c, n0, n1, n2); break;
     default: return -1;
   }
   if (c.taken > c.log_cap) return -1;
@@ -574,6 +576,40 @@ int seunet_branch_wall_stats(const int* parsing, const unsigned char* skeleton, 
                              double* wall_sq_max, int* status_dev, seunet_stream_t s) {
   return launch_branch_wall_stats(parsing, skeleton, indices, n0, n1, n2, num, s0, s1, s2,
                                   BranchWallOut{wall_count, offset_sq_sum, wall_sq_min, wall_sq_max, status_dev}, S(s));
+}
+size_t seunet_surface_workspace_bytes(int n0, int n1, int n2) {
+  if (volume_check("surface_workspace_bytes", n0, n1, n2, kEdtMaxExtent)) return 0;
+  return surface_workspace_bytes(n0, n1, n2);
+}
+int seunet_surface_count(const unsigned char* a, const unsigned char* b, int n0, int n1, int n2, long long* n_a, long long* n_b, int* box,
+                         void* workspace, size_t workspace_bytes, seunet_stream_t s) {
+  return launch_surface_count(a, b, n0, n1, n2, n_a, n_b, box, workspace, workspace_bytes, S(s));
+}
+size_t seunet_surface_emit_workspace_bytes(int b0, int b1, int b2) {
+  if (volume_check("surface_emit_workspace_bytes", b0, b1, b2, kEdtMaxExtent)) return 0;
+  return surface_emit_workspace_bytes(b0, b1, b2);
+}
+int seunet_surface_emit(int n0, int n1, int n2, const int* box, double s0, double s1, double s2, long long n_a, long long n_b,
+                        double* dist, int* voxel, const void* count_workspace, size_t count_workspace_bytes, void* emit_workspace,
+                        size_t emit_workspace_bytes, seunet_stream_t s) {
+  return launch_surface_emit(n0, n1, n2, box, s0, s1, s2, n_a, n_b, dist, voxel, count_workspace, count_workspace_bytes, emit_workspace,
+                             emit_workspace_bytes, S(s));
+}
+size_t seunet_surface_summary_bytes(int ntol) {
+  if (ntol < 0 || ntol > kSurfaceMaxTol) { fail("surface_summary_bytes: %d tolerances: 0 .. %d are supported", ntol, kSurfaceMaxTol); return 0; }
+  return surface_summary_bytes(ntol);
+}
+int seunet_surface_summary(const double* dist, long long n_a, long long n_b, const double* tol, int ntol, void* out_dev,
+                           seunet_stream_t s) {
+  return launch_surface_summary(dist, n_a, n_b, tol, ntol, out_dev, S(s));
+}
+size_t seunet_select_ranks_workspace_bytes(int nranks) {
+  if (nranks < 1 || nranks > kSelectMaxRanks) { fail("select_ranks_workspace_bytes: %d requests: 1 .. %d are supported", nranks, kSelectMaxRanks); return 0; }
+  return select_ranks_workspace_bytes(nranks);
+}
+int seunet_select_ranks(const double* values, long long n, const long long* seg_begin, const long long* seg_end, const long long* rank,
+                        int nranks, double* out_dev, void* workspace, size_t workspace_bytes, seunet_stream_t s) {
+  return launch_select_ranks(values, n, seg_begin, seg_end, rank, nranks, out_dev, workspace, workspace_bytes, S(s));
 }
 int seunet_mesh_coord_sums(const unsigned char* mask, int n0, int n1, int n2, long long* sums_dev, seunet_stream_t s) {
   return launch_mesh_coord_sums(mask, n0, n1, n2, sums_dev, S(s));

@@ -1,4 +1,4 @@
-// Shared layer of the volume operations (components.hip, lung.hip, edt.hip, edt_sampling.hip, parse.hip, skeleton.hip, dti.hip, morph.hip, mesh.hip, mesh_label.hip, morphometry.hip, cldice.hip): their launcher
+// Shared layer of the volume operations (components.hip, lung.hip, edt.hip, edt_sampling.hip, parse.hip, skeleton.hip, dti.hip, morph.hip, mesh.hip, mesh_label.hip, morphometry.hip, cldice.hip, surface.hip): their launcher
 // prototypes, ONE workspace layout per operation, the extent check and the voxel / wave helpers their kernels share.
 //
 // Workspace contract: every operation has a layout struct filled by one function that walks a WsCarver.  Over a null base
@@ -420,6 +420,62 @@ int launch_cldice_backward(const float* t, const float* st, const double* sums, 
                            int n0, int n1, int n2, int iters, float* grad, void* workspace, size_t ws_bytes, hipStream_t s);
 int launch_cldice_counts(const unsigned char* sp, const unsigned char* vl, const unsigned char* sl, const unsigned char* vp, long long n,
                          unsigned long long* counts, hipStream_t s);
+
+// ---- surface distances (surface.hip): border extraction, distances in raster order, their summary, order statistics -----------
+constexpr int kSurfaceMaxTol = 8;         // tolerances per summary call
+constexpr int kSelectMaxRanks = 8;        // requests per select call
+struct SurfaceRec {                       // what the host reads once
+  u64 n_a, n_b;                           // border voxels of A and of B: the scan's two totals
+  int hi[3], from_end[3];                 // box of A | B as maxima: exclusive high end, extent - low end; all 0 = empty
+};
+struct SurfaceWs {
+  SurfaceRec* rec;
+  u64 *bits_a, *bits_b;                   // the packed masks; rows of ceil(n2 / 64) words, zero tails
+  u64 *border_a, *border_b;               // their border voxels
+  unsigned *cnt_a, *cnt_b;                // per word: border voxels, then their exclusive scan inside a block of 1024 words
+  unsigned *blk_a, *blk_b;                // per block: its total, then the exclusive scan of the totals
+};
+static inline SurfaceWs surface_ws(WsCarver& c, int n0, int n1, int n2) {
+  const size_t words = (size_t)n0 * n1 * ((n2 + 63) / 64), blocks = (words + kScanBlock - 1) / kScanBlock;
+  return SurfaceWs{c.take<SurfaceRec>(1), c.take<u64>(words), c.take<u64>(words), c.take<u64>(words), c.take<u64>(words),
+                   c.take<unsigned>(words), c.take<unsigned>(words), c.take<unsigned>(blocks), c.take<unsigned>(blocks)};
+}
+struct SurfaceEmitWs {                    // on the extents of the box; used by one direction after the other
+  unsigned char* sites;                   // 0 at the other mask's border voxels, 1 elsewhere: the EDT's input
+  int* lin;                               // linear index in the box of every voxel's feature
+  EdtSamplingWs edt;                      // one whole workspace of the EDT with spacing: edt_bytes from edt.f0 on
+  size_t edt_bytes;
+};
+static inline SurfaceEmitWs surface_emit_ws(WsCarver& c, int b0, int b1, int b2) {
+  const size_t n = (size_t)b0 * b1 * b2;
+  SurfaceEmitWs w;
+  w.sites = c.take<unsigned char>(n);
+  w.lin = c.take<int>(n);
+  w.edt_bytes = edt_sampling_workspace_bytes(b0, b1, b2);
+  WsCarver edt(c.take<unsigned char>(w.edt_bytes));
+  w.edt = edt_sampling_ws(edt, b0, b1, b2);
+  return w;
+}
+struct SelectState { u64 prefix[kSelectMaxRanks], rank[kSelectMaxRanks]; };   // per request: digits chosen so far, rank among the rest
+struct SelectWs {
+  SelectState* state;
+  unsigned* hist;                         // nranks x 256: this pass's digit histogram of every request
+};
+static inline SelectWs select_ws(WsCarver& c, int nranks) { return SelectWs{c.take<SelectState>(1), c.take<unsigned>((size_t)nranks * 256)}; }
+size_t surface_workspace_bytes(int n0, int n1, int n2);
+size_t surface_emit_workspace_bytes(int b0, int b1, int b2);
+size_t surface_summary_bytes(int ntol);
+size_t select_ranks_workspace_bytes(int nranks);
+// count: pack, borders, counts, box, scan; synchronises once to return the totals and the box {lo0, hi0, lo1, hi1, lo2, hi2}.
+// emit: dist[0 .. n_a) and dist[n_a .. n_a + n_b) (voxel: the same places, optional) from the count workspace, on the box.
+int launch_surface_count(const unsigned char* a, const unsigned char* b, int n0, int n1, int n2, long long* n_a, long long* n_b, int* box,
+                         void* workspace, size_t ws_bytes, hipStream_t s);
+int launch_surface_emit(int n0, int n1, int n2, const int* box, double s0, double s1, double s2, long long n_a, long long n_b,
+                        double* dist, int* voxel, const void* count_workspace, size_t count_bytes, void* emit_workspace, size_t emit_bytes,
+                        hipStream_t s);
+int launch_surface_summary(const double* dist, long long n_a, long long n_b, const double* tol, int ntol, void* out_dev, hipStream_t s);
+int launch_select_ranks(const double* values, long long n, const long long* seg_begin, const long long* seg_end, const long long* rank,
+                        int nranks, double* out_dev, void* workspace, size_t ws_bytes, hipStream_t s);
 
 // ---- device helpers -------------------------------------------------------------------------------------------------------
 // raster index -> coordinates of an (n0, n1, n2) volume (n0 is not needed)

@@ -9,7 +9,9 @@ the default; "float32" = train.py / test.py).
 The reference's version is a pure-Python triple loop over every voxel with 26 neighbour look-ups (hours for a 512^3
 volume); here it is ``seunet_dti`` (csrc/dti.hip), which reproduces the single raster-order sweep bit for bit.
 There is no CPU path."""
-from typing import Union
+import ctypes as C
+import dataclasses
+from typing import Tuple, Union
 
 import numpy as np
 import torch
@@ -249,3 +251,194 @@ def cldice_score(pred_mask, label_mask, pred_skeleton=None, label_skeleton=None,
     tsens = np.float64(c[2]) / np.float64(c[3]) if c[3] else np.float64(0.0)
     score = float(2.0 * tprec * tsens / (tprec + tsens)) if tprec + tsens != 0 else 0.0
     return (score, float(tprec), float(tsens), tuple(c)) if return_parts else score
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Boundary metrics in the units of the voxel spacing: surface distances, order statistics, HD / ASSD / NSD
+# ----------------------------------------------------------------------------------------------------------------------
+SELECT_MAX_RANKS = 8
+SURFACE_MAX_TOLERANCES = 8
+
+
+@dataclasses.dataclass(frozen=True)
+class SurfaceMetrics:
+    """What ``surface_metrics`` returns; distances in the units of ``spacing``.  ``hd``: the Hausdorff distance, the largest
+    surface distance of either direction.  ``hd_percentile``: the larger of the two directions' ``percentile``-th percentiles;
+    ``hd_percentile_pooled``: the percentile of both directions' distances together (MedPy's ``hd95``).  ``asd_ab`` / ``asd_ba``:
+    the mean distance from the first mask's surface to the second's and back; ``assd``: the mean over both.  ``nsd``: per
+    tolerance, the fraction of all surface voxels within it (surface Dice).  ``n_a`` / ``n_b``: the surface voxels."""
+    hd: float
+    hd_percentile: float
+    hd_percentile_pooled: float
+    asd_ab: float
+    asd_ba: float
+    assd: float
+    nsd: Tuple[float, ...]
+    n_a: int
+    n_b: int
+
+
+def _surface_masks(a, b, what):
+    ta, as_numpy = _as_u8_cuda(a, what)
+    tb, _ = _as_u8_cuda(b, what)
+    if ta.dim() != 3 or tb.shape != ta.shape:
+        raise ValueError(f"{what}: the two masks must be 3-D volumes of one shape, got {tuple(ta.shape)} and {tuple(tb.shape)}")
+    if ta.numel() == 0:
+        raise ValueError(f"{what}: empty volume")
+    if tb.device != ta.device:
+        raise ValueError(f"{what}: the two masks are on different devices")
+    return ta, tb, as_numpy
+
+
+def _surface_count(ta, tb):
+    """The count call: (n_a, n_b, box, workspace)."""
+    lib = _lib.load()
+    n0, n1, n2 = (int(v) for v in ta.shape)
+    ws = workspace(lib.seunet_surface_workspace_bytes, n0, n1, n2, device=ta.device, what="seunet surface")
+    n_a, n_b, box = C.c_longlong(0), C.c_longlong(0), (C.c_int * 6)()
+    _lib.check(lib.seunet_surface_count(ta.data_ptr(), tb.data_ptr(), n0, n1, n2, C.byref(n_a), C.byref(n_b), box, ws.data_ptr(),
+                                        ws.numel(), _lib.stream_ptr()), "surface_count")
+    return int(n_a.value), int(n_b.value), box, ws
+
+
+def _surface_emit(ta, s, n_a, n_b, box, ws, want_voxels):
+    lib = _lib.load()
+    n0, n1, n2 = (int(v) for v in ta.shape)
+    dev = ta.device
+    ews = workspace(lib.seunet_surface_emit_workspace_bytes, box[1] - box[0], box[3] - box[2], box[5] - box[4], device=dev,
+                    what="seunet surface")
+    dist = torch.empty(n_a + n_b, dtype=torch.float64, device=dev)
+    voxels = torch.empty(n_a + n_b, dtype=torch.int32, device=dev) if want_voxels else None
+    _lib.check(lib.seunet_surface_emit(n0, n1, n2, box, s[0], s[1], s[2], n_a, n_b, dist.data_ptr(), _lib.ptr(voxels), ws.data_ptr(),
+                                       ws.numel(), ews.data_ptr(), ews.numel(), _lib.stream_ptr()), "surface_emit")
+    return dist, voxels
+
+
+def surface_distances(a, b, spacing=(1, 1, 1), return_voxels: bool = False):
+    """The surface distances of two masks (numpy arrays or CUDA tensors of any dtype, non-zero = 1, one 3-D shape) under the
+    voxel ``spacing`` (a positive number or three): ``(D, n_a, n_b)``.  ``D`` is float64: for each of the ``n_a`` border voxels
+    of ``a`` in raster order the distance to the nearest border voxel of ``b``, then the ``n_b`` distances of ``b``'s border
+    voxels to ``a``'s.  A border voxel is a set voxel with one of its six neighbours unset or outside the volume; the distances
+    are ``scipy.ndimage.distance_transform_edt(~border, sampling=spacing)`` read at the other border, bit for bit
+    (tests/surface_oracle.py).  ``return_voxels``: also the int32 linear index in the volume of each of the ``n_a + n_b`` border
+    voxels.  numpy in -> numpy out; CUDA tensors in -> CUDA tensors out.  ValueError when a mask has no voxel."""
+    from .prep import normalize_sampling
+    s = normalize_sampling(spacing, "spacing")
+    ta, tb, as_numpy = _surface_masks(a, b, "seunet surface_distances")
+    with torch.cuda.device(ta.device):
+        n_a, n_b, box, ws = _surface_count(ta, tb)
+        if n_a == 0 or n_b == 0:
+            raise ValueError(f"seunet surface_distances: a mask without voxels has no surface distances ({n_a} and {n_b} surface voxels)")
+        dist, voxels = _surface_emit(ta, s, n_a, n_b, box, ws, return_voxels)
+    res = (_out(dist, as_numpy), n_a, n_b)
+    return res + (_out(voxels, as_numpy),) if return_voxels else res
+
+
+def _select_ranks(values, ranks, segments, out):
+    """``seunet_select_ranks`` into ``out`` (a float64 device vector of len(ranks))."""
+    lib = _lib.load()
+    k = len(ranks)
+    arr = lambda v: (C.c_longlong * k)(*[int(x) for x in v])
+    ws = workspace(lib.seunet_select_ranks_workspace_bytes, k, device=values.device, what="seunet order_statistics")
+    _lib.check(lib.seunet_select_ranks(values.data_ptr(), values.numel(), arr([b for b, _ in segments]), arr([e for _, e in segments]),
+                                       arr(ranks), k, out.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "select_ranks")
+
+
+def order_statistics(values, ranks, segments=None):
+    """Exact order statistics on the device.  ``values``: a float64 CUDA vector of FINITE, NON-NEGATIVE numbers (they are ordered by
+    their bit patterns; it is not modified).  ``ranks``: up to 8 ints; ``segments``: per rank a ``(begin, end)`` pair (default: all
+    of ``values``), which may overlap.  Returns a float64 CUDA vector: entry r is the element of rank ``ranks[r]`` (0 = smallest)
+    of ``values[begin_r:end_r]``, the value ``sort`` would put there.  A radix select (csrc/surface.hip): no sort, no host round
+    trip, and the call does not wait for the device."""
+    if not (isinstance(values, torch.Tensor) and values.is_cuda and values.dtype == torch.float64 and values.dim() == 1):
+        raise ValueError("seunet order_statistics: `values` must be a 1-D float64 CUDA tensor")
+    values = values.contiguous()
+    n = values.numel()
+    ranks = [int(r) for r in ranks]
+    if not 1 <= len(ranks) <= SELECT_MAX_RANKS:
+        raise ValueError(f"seunet order_statistics: `ranks` must hold 1 .. {SELECT_MAX_RANKS} ranks, got {len(ranks)}")
+    segments = [(0, n)] * len(ranks) if segments is None else [(int(b), int(e)) for b, e in segments]
+    if len(segments) != len(ranks):
+        raise ValueError(f"seunet order_statistics: {len(segments)} `segments` for {len(ranks)} ranks")
+    for r, (b, e) in zip(ranks, segments):
+        if not 0 <= b < e <= n:
+            raise ValueError(f"seunet order_statistics: `segments`: [{b}, {e}) is empty or outside the {n} values")
+        if not 0 <= r < e - b:
+            raise ValueError(f"seunet order_statistics: `ranks`: rank {r} outside a segment of {e - b}")
+    with torch.cuda.device(values.device):
+        out = torch.empty(len(ranks), dtype=torch.float64, device=values.device)
+        _select_ranks(values, ranks, segments, out)
+    return out
+
+
+def _percentile_ranks(n: int, q: float):
+    """The two ranks and the weight of numpy's default (linear) percentile of ``n`` values: ``(lo, hi, g)`` in numpy's own
+    float64 arithmetic (numpy 2.2, ``_quantile``: virtual index ``(n - 1) * (q / 100)``)."""
+    vi = np.multiply(np.float64(n - 1), np.true_divide(np.float64(q), np.float64(100)))
+    lo = np.floor(vi)
+    g = np.subtract(vi, lo)
+    lo = int(lo)
+    return lo, min(lo + 1, n - 1), g
+
+
+def _percentile_lerp(a, b, g):
+    """numpy's ``_lerp``: ``a + (b - a) * g``, replaced by ``b - (b - a) * (1 - g)`` where ``g >= 0.5``."""
+    a, b, g = np.float64(a), np.float64(b), np.float64(g)
+    diff = np.subtract(b, a)
+    return np.subtract(b, np.multiply(diff, np.subtract(np.float64(1), g))) if g >= 0.5 else np.add(a, np.multiply(diff, g))
+
+
+def surface_metrics(pred, label, spacing=(1, 1, 1), percentile: float = 95.0, tolerances=(1.0,), empty: str = "raise") -> SurfaceMetrics:
+    """The boundary metrics of two masks (as ``surface_distances`` takes them) in the units of ``spacing``: Hausdorff distance,
+    its ``percentile``-th percentile per direction and pooled (MedPy's ``hd95``), average (symmetric) surface distances and the
+    surface Dice at each of up to 8 ``tolerances`` -- see ``SurfaceMetrics``.  Percentiles are numpy's default (linear)
+    ``np.percentile`` of the float64 distances, exactly: the order statistics come from a radix select on the device, the
+    interpolation is numpy's arithmetic on the host.  Maxima and counts are exact; the means are float64 sums of a fixed shape
+    (the same bits on every run).  Border extraction, distance transforms on the bounding box, gather, summary and select all
+    run on the device (csrc/surface.hip); the host waits twice: for the sizes, and for one small record of results.
+    ``empty``: a mask without voxels raises ValueError (``"raise"``, like MedPy) or gives ``inf`` for every distance and 0.0 for
+    every ``nsd`` entry (``"inf"``)."""
+    from .prep import normalize_sampling
+    s = normalize_sampling(spacing, "spacing")
+    q = float(percentile)
+    if not 0.0 <= q <= 100.0:
+        raise ValueError(f"seunet surface_metrics: `percentile` must lie in [0, 100], got {percentile!r}")
+    tol = [float(t) for t in np.atleast_1d(np.asarray(tolerances, dtype=np.float64))]
+    if len(tol) > SURFACE_MAX_TOLERANCES or any(not t >= 0.0 for t in tol):
+        raise ValueError(f"seunet surface_metrics: `tolerances` must be at most {SURFACE_MAX_TOLERANCES} non-negative numbers, got {tolerances!r}")
+    if empty not in ("raise", "inf"):
+        raise ValueError(f"seunet surface_metrics: `empty` must be 'raise' or 'inf', got {empty!r}")
+    ta, tb, _ = _surface_masks(pred, label, "seunet surface_metrics")
+    lib = _lib.load()
+    dev = ta.device
+    ntol = len(tol)
+    with torch.cuda.device(dev):
+        n_a, n_b, box, ws = _surface_count(ta, tb)
+        if n_a == 0 or n_b == 0:
+            if empty == "raise":
+                raise ValueError(f"seunet surface_metrics: a mask without voxels has no surface distances ({n_a} and {n_b} surface voxels)")
+            inf = float("inf")
+            return SurfaceMetrics(inf, inf, inf, inf, inf, inf, (0.0,) * ntol, n_a, n_b)
+        dist, _ = _surface_emit(ta, s, n_a, n_b, box, ws, False)
+        n = n_a + n_b
+        parts = [(0, n_a), (n_a, n), (0, n)]                      # d_AB, d_BA, both
+        pr = [_percentile_ranks(e - b, q) for b, e in parts]
+        # one record: six order statistics, then the summary (its partial sums stay on the device)
+        head = 8 * (6 + 6 + 2 * ntol)
+        rec = torch.empty(48 + int(lib.seunet_surface_summary_bytes(ntol)), dtype=torch.uint8, device=dev)
+        _select_ranks(dist, [r for lo, hi, _ in pr for r in (lo, hi)], [p for p in parts for _ in (0, 1)], rec[:48].view(torch.float64))
+        _lib.check(lib.seunet_surface_summary(dist.data_ptr(), n_a, n_b, (C.c_double * max(ntol, 1))(*tol), ntol, rec[48:].data_ptr(),
+                                              _lib.stream_ptr()), "surface_summary")
+        raw = rec[:head].cpu().numpy()
+    stat = raw[:48].view(np.float64)
+    words = raw[48:].view(np.uint64)
+    assert int(words[0]) == n_a and int(words[1]) == n_b
+    mx = words[2:4].view(np.float64)
+    sums = words[4:6].view(np.float64)
+    le = words[6:].astype(np.int64).reshape(2, ntol)
+    pct = [_percentile_lerp(stat[2 * i], stat[2 * i + 1], pr[i][2]) for i in range(3)]
+    return SurfaceMetrics(hd=float(max(mx[0], mx[1])), hd_percentile=float(max(pct[0], pct[1])), hd_percentile_pooled=float(pct[2]),
+                          asd_ab=float(sums[0] / np.float64(n_a)), asd_ba=float(sums[1] / np.float64(n_b)),
+                          assd=float((sums[0] + sums[1]) / np.float64(n)),
+                          nsd=tuple(float(np.float64(int(le[0, k]) + int(le[1, k])) / np.float64(n)) for k in range(ntol)),
+                          n_a=n_a, n_b=n_b)
