@@ -233,9 +233,7 @@ cldice_sums_kernel(const float* __restrict__ sp, const float* __restrict__ t, co
   __shared__ double red[4][4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    double v = s[k];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += shfl_xor_settled(v, off);
+    const double v = wave_sum(s[k]);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = v;
   }
   __syncthreads();
@@ -251,8 +249,7 @@ cldice_sums_final_kernel(const double* __restrict__ partial, double* __restrict_
   const int k = threadIdx.x >> 6, lane = threadIdx.x & 63;
   double s = 0.0;
   for (int b = lane; b < SUM_BLOCKS; b += 64) s += partial[b * 4 + k];
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) s += shfl_xor_settled(s, off);
+  s = wave_sum(s);
   if (lane == 0) sums[k] = s;
 }
 
@@ -362,9 +359,7 @@ cldice_counts_kernel(const unsigned char* __restrict__ sp, const unsigned char* 
   }
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    int v = (int)c[k];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += shfl_xor_settled(v, off);
+    const int v = wave_sum((int)c[k]);
     if ((threadIdx.x & 63) == 0 && v != 0) atomicAdd(&counts[k], (u64)v);      // integer adds: exact in any order
   }
 }

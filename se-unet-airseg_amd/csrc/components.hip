@@ -268,9 +268,7 @@ metric_sums_kernel(const unsigned char* __restrict__ pred, const unsigned char* 
   }
 #pragma unroll
   for (int q = 0; q < 5; ++q) {
-    u64 v = s[q];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += shfl_xor_settled(v, off);
+    const u64 v = wave_sum(s[q]);
     if ((threadIdx.x & 63) == 0 && v) atomicAdd(&sums[q], v);
   }
   mx = wave_max(mx);

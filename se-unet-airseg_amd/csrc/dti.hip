@@ -9,7 +9,7 @@
 // neighbours add nothing new) is on AT THAT MOMENT: neighbours earlier in raster order have their updated value, later
 // ones their original value.  The result depends on that visiting order, so it is reproduced exactly:
 //
-//   * rows (i, j) are bit-packed along k (64 voxels per word).  Inside a row the sweep is the carry recurrence
+//   * rows (i, j) are bit-packed along k (bitvol.h; the result leaves through unpack_bits).  Inside a row the sweep is the carry recurrence
 //         g[k] = a[k] | (weak[k] & g[k-1]),   a = strong | (weak & (ext | strong[k+1]))
 //     where ext ORs the (k-1, k, k+1) bits of the 8 neighbouring rows; the recurrence is exactly the carry chain of the
 //     integer addition a + (a | weak), so a row of 64 voxels costs a few 64-bit operations;
@@ -23,12 +23,13 @@ namespace seunet {
 
 // strong / weak masks, bit-packed along k.  One thread per (row, word).
 __global__ void __launch_bounds__(256)
-dti_pack_kernel(const double* __restrict__ pred, long long rows, int z, int nw, double hs, double ls, int f32,
-                u64* __restrict__ strong, u64* __restrict__ weak) {
+dti_pack_kernel(const double* __restrict__ pred, BitGeom geom, double hs, double ls, int f32, u64* __restrict__ strong,
+                u64* __restrict__ weak) {
   const long long idx = blockIdx.x * 256ll + threadIdx.x;
-  if (idx >= rows * nw) return;
-  const long long row = idx / nw;
-  const int m = (int)(idx % nw);
+  if (idx >= geom.words) return;
+  const int z = geom.n2;
+  const long long row = idx / geom.W;
+  const int m = (int)(idx % geom.W);
   const double* p = pred + row * z;
   u64 s = 0, w = 0;
   const int k1 = (m * 64 + 64 < z) ? m * 64 + 64 : z;
@@ -48,12 +49,12 @@ dti_pack_kernel(const double* __restrict__ pred, long long rows, int z, int nw, 
 __device__ __forceinline__ u64 dti_dilate(const u64* __restrict__ g, int m, int nw) {
   const u64 x = g[m];
   const u64 xl = m > 0 ? g[m - 1] : 0ull, xr = m + 1 < nw ? g[m + 1] : 0ull;
-  return x | (x << 1) | (xl >> 63) | (x >> 1) | (xr << 63);
+  return x | shift_down(x, xl) | shift_up(x, xr);
 }
 
 // the raster sweep, one workgroup, one thread per row of the current wavefront
-__global__ void __launch_bounds__(1024)
-dti_sweep_kernel(u64* g, const u64* __restrict__ weak, int h, int w, int nw) {
+__global__ void __launch_bounds__(1024) dti_sweep_kernel(u64* g, const u64* __restrict__ weak, BitGeom geom) {
+  const int h = geom.n0, w = geom.n1, nw = geom.W;
   const int steps = 2 * (h - 1) + (w - 1) + 1;
   for (int t = 0; t < steps; ++t) {
     int i_lo = (t - (w - 1) + 1) / 2;
@@ -77,7 +78,7 @@ dti_sweep_kernel(u64* g, const u64* __restrict__ weak, int h, int w, int nw) {
           }
         const u64 s = row[m], wk = wrow[m];
         const u64 s_next = m + 1 < nw ? row[m + 1] : 0ull;             // k+1 of this row: not visited yet -> original
-        const u64 a = s | (wk & (ext | (s >> 1) | (s_next << 63)));
+        const u64 a = s | (wk & (ext | shift_up(s, s_next)));
         const u64 p = a | wk;
         const u64 sum = a + p;
         const u64 c1 = sum < a ? 1ull : 0ull;
@@ -92,15 +93,6 @@ dti_sweep_kernel(u64* g, const u64* __restrict__ weak, int h, int w, int nw) {
   }
 }
 
-__global__ void __launch_bounds__(256)
-dti_unpack_kernel(const u64* __restrict__ g, long long rows, int z, int nw, unsigned char* __restrict__ out) {
-  const long long idx = blockIdx.x * 256ll + threadIdx.x;
-  if (idx >= rows * z) return;
-  const long long row = idx / z;
-  const int k = (int)(idx % z);
-  out[idx] = (unsigned char)((g[row * nw + (k >> 6)] >> (k & 63)) & 1ull);
-}
-
 size_t dti_workspace_bytes(int h, int w, int z) { return measured(dti_ws, h, w, z); }
 
 int launch_dti(const double* pred, int h, int w, int z, double h_thresh, double l_thresh, int pred_dtype, unsigned char* out,
@@ -110,14 +102,13 @@ int launch_dti(const double* pred, int h, int w, int z, double h_thresh, double 
   WsCarver carve(workspace);
   const DtiWs ws = dti_ws(carve, h, w, z);
   SEUNET_CHECK(ws_bytes >= carve.bytes(), "dti: workspace too small");
-  const int nw = (z + 63) / 64;
-  const long long rows = (long long)h * w;
+  const BitGeom geom = bit_geom(h, w, z);
   u64 *g = ws.g, *weak = ws.weak;
   double hs = h_thresh * 255.0, ls = l_thresh * 255.0;         // (h_thresh*255, l_thresh*255 in float64, prediction.py:20,28)
   if (pred_dtype == 1) { hs = (double)(float)hs; ls = (double)(float)ls; }   // weak python scalars adopt the array's float32
-  dti_pack_kernel<<<blocks_256(rows * nw), 256, 0, s>>>(pred, rows, z, nw, hs, ls, pred_dtype, g, weak);
-  dti_sweep_kernel<<<1, 1024, 0, s>>>(g, weak, h, w, nw);
-  dti_unpack_kernel<<<blocks_256(rows * z), 256, 0, s>>>(g, rows, z, nw, out);
+  dti_pack_kernel<<<blocks_256(geom.words), 256, 0, s>>>(pred, geom, hs, ls, pred_dtype, g, weak);
+  dti_sweep_kernel<<<1, 1024, 0, s>>>(g, weak, geom);
+  unpack_bits(g, geom, out, s);
   SEUNET_LAUNCH_CHECK();
   return 0;
 }

@@ -6,8 +6,8 @@
 // triangulation or with VTK's smoothing is not claimed; the definition implemented here is written out in DESIGN.md 3h and,
 // executably, in tests/mesh_oracle.py, and every result below equals that oracle bit for bit.
 //
-// Extraction.  The volume is packed into bits along the last axis, 64 voxels per word (bit b of word w of a row = voxel 64 w + b,
-// zero past the row's end).  One wavefront works on one word, one lane per voxel / cell:
+// Extraction.  The volume is bit-packed along the last axis (bitvol.h; pack_bits and run_scan are that
+// layer's).  One wavefront works on one word, one lane per voxel / cell:
 //   count  the three masks of owned vertices of the word (voxel differs from its +1 neighbour along axis 0 / 1 / 2) are word
 //          operations, their popcounts the word's vertex count; a lane's cell configuration comes from the words of the 2 x 2
 //          neighbouring rows, its triangle count from the table, the word's total from ballots of the count's three bits.  A word
@@ -29,36 +29,9 @@ namespace seunet {
 
 namespace {
 
-struct MeshTable {
-  unsigned char count[256];
-  unsigned char edges[256][3 * SEUNET_MESH_MAX_TRIS];
-};
-constexpr MeshTable make_mesh_table() {
-  MeshTable t{};
-  for (int c = 0; c < 256; ++c) {
-    t.count[c] = kMeshTriCount[c];
-    for (int k = 0; k < 3 * SEUNET_MESH_MAX_TRIS; ++k) t.edges[c][k] = kMeshTriEdges[c][k];
-  }
-  return t;
-}
 __constant__ MeshTable kTable = make_mesh_table();
 
-struct MeshGeom {
-  int n0, n1, n2, W;          // W = words per row
-  long long words;            // n0 * n1 * W
-};
-
 // ---- extraction ----------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) mesh_pack_kernel(const unsigned char* __restrict__ vol, MeshGeom g, u64* __restrict__ bits) {
-  const long long t = (blockIdx.x * 256ll + threadIdx.x) >> 6;
-  if (t >= g.words) return;                                  // whole wavefronts leave together
-  const int lane = threadIdx.x & 63;
-  const int k = (int)(t % g.W) * 64 + lane;
-  const bool fg = k < g.n2 && vol[(t / g.W) * g.n2 + k] != 0;
-  const u64 m = __ballot(fg);
-  if (lane == 0) bits[t] = m;
-}
-
 // What a wavefront needs of the 2 x 2 rows around its word: the four words, each shifted down by one voxel (bit b = voxel b + 1,
 // bit 63 from the next word), and the lanes whose voxel has a +1 neighbour along axis 2.
 struct CellWords {
@@ -69,7 +42,7 @@ struct CellWords {
   bool flat;                  // all eight are all-0 or all-1: no vertex, no triangle
 };
 
-__device__ __forceinline__ CellWords load_cell_words(const u64* __restrict__ bits, const MeshGeom& g, long long t) {
+__device__ __forceinline__ CellWords load_cell_words(const u64* __restrict__ bits, const BitGeom& g, long long t) {
   CellWords c;
   const int w = (int)(t % g.W);
   const long long row = t / g.W;
@@ -86,12 +59,11 @@ __device__ __forceinline__ CellWords load_cell_words(const u64* __restrict__ bit
   const u64 x01 = more && c.has1 ? bits[t + d1 + 1] : 0ull;
   const u64 x10 = more && c.has0 ? bits[t + d0 + 1] : 0ull;
   const u64 x11 = more && c.has0 && c.has1 ? bits[t + d0 + d1 + 1] : 0ull;
-  c.s00 = (c.m00 >> 1) | (x00 << 63);
-  c.s01 = (c.m01 >> 1) | (x01 << 63);
-  c.s10 = (c.m10 >> 1) | (x10 << 63);
-  c.s11 = (c.m11 >> 1) | (x11 << 63);
-  const int left = g.n2 - 1 - 64 * w;                        // voxels of this word that have a successor in the row
-  c.valid2 = left >= 64 ? ~0ull : (left <= 0 ? 0ull : ((1ull << left) - 1ull));
+  c.s00 = shift_up(c.m00, x00);
+  c.s01 = shift_up(c.m01, x01);
+  c.s10 = shift_up(c.m10, x10);
+  c.s11 = shift_up(c.m11, x11);
+  c.valid2 = shift_up(tail_mask(g, w), more ? 1ull : 0ull);  // the voxels whose successor is a voxel of the row
   const u64 any = c.m00 | c.m01 | c.m10 | c.m11 | ((x00 | x01 | x10 | x11) & 1ull);
   const u64 all = c.m00 & c.m01 & c.m10 & c.m11;
   c.flat = any == 0ull || (all == ~0ull && (x00 & x01 & x10 & x11 & 1ull) != 0ull);
@@ -116,7 +88,7 @@ __device__ __forceinline__ int cell_triangles(const CellWords& c, int lane, int&
 }
 
 __global__ void __launch_bounds__(256)
-mesh_count_kernel(const u64* __restrict__ bits, MeshGeom g, u64* __restrict__ a0s, u64* __restrict__ a1s, u64* __restrict__ a2s,
+mesh_count_kernel(const u64* __restrict__ bits, BitGeom g, u64* __restrict__ a0s, u64* __restrict__ a1s, u64* __restrict__ a2s,
                   unsigned* __restrict__ vcnt, unsigned* __restrict__ fcnt) {
   const long long t = (blockIdx.x * 256ll + threadIdx.x) >> 6;
   if (t >= g.words) return;
@@ -128,7 +100,7 @@ mesh_count_kernel(const u64* __restrict__ bits, MeshGeom g, u64* __restrict__ a0
     owned_masks(c, a0, a1, a2);
     int cfg;
     const int n = cell_triangles(c, lane, cfg);
-    nf = (unsigned)(__popcll(__ballot(n & 1)) + 2 * __popcll(__ballot(n & 2)) + 4 * __popcll(__ballot(n & 4)));
+    nf = (unsigned)ballot_sum<3>(n);
   }
   if (lane == 0) {
     a0s[t] = a0;
@@ -138,97 +110,6 @@ mesh_count_kernel(const u64* __restrict__ bits, MeshGeom g, u64* __restrict__ a0
     fcnt[t] = nf;
   }
 }
-
-// Exclusive scan of every block of kScanBlock elements in place; the block's total to blk.  `b` / `blk_b`: a second array scanned
-// in the same launch (null: none).
-__global__ void __launch_bounds__(256)
-scan_block_kernel(unsigned* __restrict__ a, unsigned* __restrict__ b, long long n, unsigned* __restrict__ blk_a,
-                  unsigned* __restrict__ blk_b) {
-  __shared__ unsigned sh[2][256];
-  const int tid = threadIdx.x;
-  const long long at = blockIdx.x * (long long)kScanBlock + tid * 4;
-  for (int which = 0; which < 2; ++which) {
-    unsigned* p = which ? b : a;
-    if (!p) break;                                           // uniform
-    unsigned v[4], sum = 0u;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      v[q] = at + q < n ? p[at + q] : 0u;
-      sum += v[q];
-    }
-    sh[0][tid] = sum;
-    __syncthreads();
-    int cur = 0;
-    for (int off = 1; off < 256; off <<= 1) {                // Hillis-Steele, double-buffered
-      sh[cur ^ 1][tid] = sh[cur][tid] + (tid >= off ? sh[cur][tid - off] : 0u);
-      cur ^= 1;
-      __syncthreads();
-    }
-    unsigned run = sh[cur][tid] - sum;                       // exclusive
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      if (at + q < n) p[at + q] = run;
-      run += v[q];
-    }
-    if (tid == 255) (which ? blk_b : blk_a)[blockIdx.x] = sh[cur][255];
-    __syncthreads();
-  }
-}
-
-// One workgroup: exclusive scan of the block totals in place (32 bits kept: an index the callers use fits, see the launchers'
-// checks), the grand totals in 64 bits to total[0] (a) and total[1] (b).
-__global__ void __launch_bounds__(1024)
-scan_top_kernel(unsigned* __restrict__ blk_a, unsigned* __restrict__ blk_b, long long nb, u64* __restrict__ total) {
-  __shared__ u64 sh[2][1024];
-  __shared__ u64 carry;
-  const int tid = threadIdx.x;
-  for (int which = 0; which < 2; ++which) {
-    unsigned* p = which ? blk_b : blk_a;
-    if (!p) break;
-    if (tid == 0) carry = 0ull;
-    __syncthreads();
-    for (long long c = 0; c < nb; c += 1024) {
-      const u64 v = c + tid < nb ? (u64)p[c + tid] : 0ull;
-      sh[0][tid] = v;
-      __syncthreads();
-      int cur = 0;
-      for (int off = 1; off < 1024; off <<= 1) {
-        sh[cur ^ 1][tid] = sh[cur][tid] + (tid >= off ? sh[cur][tid - off] : 0ull);
-        cur ^= 1;
-        __syncthreads();
-      }
-      const u64 before = carry;
-      if (c + tid < nb) p[c + tid] = (unsigned)(before + sh[cur][tid] - v);
-      __syncthreads();                                       // everyone has read carry
-      if (tid == 1023) carry = before + sh[cur][1023];
-      __syncthreads();
-    }
-    if (tid == 0) total[which] = carry;
-    __syncthreads();
-  }
-}
-
-// out[i] = a[i] + blk[i / kScanBlock] for i < n, out[n] = the total: the plain exclusive-scan array (CSR pointers)
-__global__ void __launch_bounds__(256)
-scan_add_kernel(const unsigned* __restrict__ a, const unsigned* __restrict__ blk, long long n, const u64* __restrict__ total,
-                unsigned* __restrict__ out) {
-  const long long i = blockIdx.x * 256ll + threadIdx.x;
-  if (i < n) out[i] = a[i] + blk[i / kScanBlock];
-  else if (i == n) out[n] = (unsigned)total[0];
-}
-
-}  // namespace
-
-// declared in volume.h: mesh_label.hip scans with it too
-int run_scan(unsigned* a, unsigned* b, long long n, unsigned* blk_a, unsigned* blk_b, u64* total, hipStream_t s) {
-  const long long nb = (n + kScanBlock - 1) / kScanBlock;
-  if (nb > 0) scan_block_kernel<<<(unsigned)nb, 256, 0, s>>>(a, b, n, blk_a, blk_b);
-  scan_top_kernel<<<1, 1024, 0, s>>>(blk_a, blk_b, nb, total);
-  SEUNET_LAUNCH_CHECK();
-  return 0;
-}
-
-namespace {
 
 struct EmitArgs {
   const u64 *bits, *a0s, *a1s, *a2s;
@@ -246,7 +127,7 @@ __device__ __forceinline__ void put_vertex(const EmitArgs& e, long long idx, flo
 }
 
 // index of the vertex on cube edge `edge` of the cell at (i, j, k)
-__device__ __forceinline__ int edge_vertex(const EmitArgs& e, const MeshGeom& g, int i, int j, int k, int edge) {
+__device__ __forceinline__ int edge_vertex(const EmitArgs& e, const BitGeom& g, int i, int j, int k, int edge) {
   const int axis = edge >> 2, du = (edge >> 1) & 1, dv = edge & 1;
   const int d0 = axis == 0 ? 0 : du, d1 = axis == 0 ? du : (axis == 1 ? 0 : dv), d2 = axis == 2 ? 0 : dv;
   const int kk = k + d2;
@@ -260,7 +141,7 @@ __device__ __forceinline__ int edge_vertex(const EmitArgs& e, const MeshGeom& g,
   return (int)id;
 }
 
-__global__ void __launch_bounds__(256) mesh_emit_kernel(EmitArgs e, MeshGeom g) {
+__global__ void __launch_bounds__(256) mesh_emit_kernel(EmitArgs e, BitGeom g) {
   const long long t = (blockIdx.x * 256ll + threadIdx.x) >> 6;
   if (t >= g.words) return;
   const int lane = threadIdx.x & 63;
@@ -284,10 +165,9 @@ __global__ void __launch_bounds__(256) mesh_emit_kernel(EmitArgs e, MeshGeom g) 
 
   int cfg;
   const int n = cell_triangles(c, lane, cfg);
-  const u64 b0 = __ballot(n & 1), b1 = __ballot(n & 2), b2 = __ballot(n & 4);
-  if ((b0 | b1 | b2) == 0ull) return;
-  const long long first = (long long)(e.fblk[t / kScanBlock] + e.fcnt[t]) + __popcll(b0 & below) + 2 * __popcll(b1 & below) +
-                          4 * __popcll(b2 & below);
+  const BitPlanes<3> nb = ballot_planes<3>(n);
+  if ((nb.b[0] | nb.b[1] | nb.b[2]) == 0ull) return;
+  const long long first = (long long)(e.fblk[t / kScanBlock] + e.fcnt[t]) + plane_sum(nb, below);
   for (int q = 0; q < n; ++q) {
     const long long f = first + q;
     if (f >= e.nfaces) break;                                // (cannot happen with the totals of the count pass)
@@ -297,12 +177,6 @@ __global__ void __launch_bounds__(256) mesh_emit_kernel(EmitArgs e, MeshGeom g) 
 }
 
 // ---- skeleton centre: exact integer sums ----------------------------------------------------------------------------------------
-__device__ __forceinline__ u64 wave_sum_u64(u64 v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += shfl_xor_settled(v, off);
-  return v;
-}
-
 __global__ void __launch_bounds__(256) mesh_coord_sums_kernel(const unsigned char* __restrict__ mask, long long n, int n1, int n2, u64* out) {
   u64 cnt = 0ull, s0 = 0ull, s1 = 0ull, s2 = 0ull;
   for (long long v = blockIdx.x * 256ll + threadIdx.x; v < n; v += gridDim.x * 256ll)
@@ -311,7 +185,7 @@ __global__ void __launch_bounds__(256) mesh_coord_sums_kernel(const unsigned cha
       ++cnt;
       s0 += (u64)p.i0; s1 += (u64)p.i1; s2 += (u64)p.i2;
     }
-  cnt = wave_sum_u64(cnt); s0 = wave_sum_u64(s0); s1 = wave_sum_u64(s1); s2 = wave_sum_u64(s2);
+  cnt = wave_sum(cnt); s0 = wave_sum(s0); s1 = wave_sum(s1); s2 = wave_sum(s2);
   if ((threadIdx.x & 63) == 0 && cnt != 0ull) {              // integer additions: the order of the atomics cannot matter
     atomicAdd(&out[0], cnt); atomicAdd(&out[1], s0); atomicAdd(&out[2], s1); atomicAdd(&out[3], s2);
   }
@@ -455,13 +329,6 @@ mesh_stl_kernel(const float* __restrict__ x, unsigned V, const int* __restrict__
   p[24] = 0;
 }
 
-MeshGeom mesh_geom(int n0, int n1, int n2) {
-  MeshGeom g;
-  g.n0 = n0; g.n1 = n1; g.n2 = n2; g.W = (n2 + 63) / 64;
-  g.words = (long long)n0 * n1 * g.W;
-  return g;
-}
-
 int make_affine(const float* centre, const float* scale, Affine* a) {
   for (int q = 0; q < 3; ++q) {
     a->c[q] = centre ? centre[q] : 0.f;
@@ -488,9 +355,9 @@ int launch_mesh_count(const unsigned char* vol, int n0, int n1, int n2, long lon
   WsCarver carve(workspace);
   const MeshWs w = mesh_ws(carve, n0, n1, n2);
   SEUNET_CHECK(ws_bytes >= carve.bytes(), "mesh_count: workspace too small (%zu bytes, %zu needed)", ws_bytes, carve.bytes());
-  const MeshGeom g = mesh_geom(n0, n1, n2);
+  const BitGeom g = bit_geom(n0, n1, n2);
   const unsigned word_blocks = (unsigned)((g.words + 3) / 4);
-  mesh_pack_kernel<<<word_blocks, 256, 0, s>>>(vol, g, w.bits);
+  pack_bits(vol, nullptr, g, w.bits, nullptr, s);
   mesh_count_kernel<<<word_blocks, 256, 0, s>>>(w.bits, g, w.a0, w.a1, w.a2, w.vcnt, w.fcnt);
   if (int e = run_scan(w.vcnt, w.fcnt, g.words, w.vblk, w.fblk, &w.rec->nverts, s)) return e;
   MeshRec host;                                                // the one synchronisation of the extraction: the output sizes
@@ -516,7 +383,7 @@ int launch_mesh_emit(int n0, int n1, int n2, double level, long long nverts, lon
   WsCarver carve(const_cast<void*>(workspace));
   const MeshWs w = mesh_ws(carve, n0, n1, n2);
   SEUNET_CHECK(ws_bytes >= carve.bytes(), "mesh_emit: workspace too small (%zu bytes, %zu needed)", ws_bytes, carve.bytes());
-  const MeshGeom g = mesh_geom(n0, n1, n2);
+  const BitGeom g = bit_geom(n0, n1, n2);
   EmitArgs e;
   e.bits = w.bits; e.a0s = w.a0; e.a1s = w.a1; e.a2s = w.a2;
   e.vcnt = w.vcnt; e.fcnt = w.fcnt; e.vblk = w.vblk; e.fblk = w.fblk;
@@ -553,12 +420,12 @@ int launch_mesh_adjacency(const int* faces, long long nfaces, long long nverts, 
   SEUNET_HIP(hipMemsetAsync(w.deg, 0, (size_t)(nverts + 1) * sizeof(unsigned), s));
   if (nfaces > 0) adj_degree_kernel<<<blocks_256(nfaces), 256, 0, s>>>(faces, nfaces, V, w.deg, status_dev);
   if (int e = run_scan(w.deg, nullptr, nverts, w.blk, nullptr, w.total, s)) return e;
-  scan_add_kernel<<<blocks_256(nverts + 1), 256, 0, s>>>(w.deg, w.blk, nverts, w.total, w.rawptr);
+  scan_add(w.deg, w.blk, nverts, w.total, w.rawptr, s);
   SEUNET_HIP(hipMemsetAsync(w.deg, 0, (size_t)(nverts + 1) * sizeof(unsigned), s));     // now the fill cursors
   if (nfaces > 0) adj_fill_kernel<<<blocks_256(nfaces), 256, 0, s>>>(faces, nfaces, V, w.rawptr, w.deg, w.raw);
   if (nverts > 0) adj_sort_kernel<<<blocks_256(nverts), 256, 0, s>>>(V, w.rawptr, w.raw, w.deg, boundary);   // deg: the final degrees
   if (int e = run_scan(w.deg, nullptr, nverts, w.blk, nullptr, w.total, s)) return e;
-  scan_add_kernel<<<blocks_256(nverts + 1), 256, 0, s>>>(w.deg, w.blk, nverts, w.total, reinterpret_cast<unsigned*>(indptr));
+  scan_add(w.deg, w.blk, nverts, w.total, reinterpret_cast<unsigned*>(indptr), s);
   if (nverts > 0 && nfaces > 0) adj_compact_kernel<<<blocks_256(nverts), 256, 0, s>>>(V, w.rawptr, w.raw, indptr, indices, capacity);
   SEUNET_LAUNCH_CHECK();
   return 0;

@@ -6,7 +6,8 @@
 // mesh.hip's marching_cubes(L == k) (tests/mesh_oracle.py): same positions, same numbering, same orientation; the
 // result is the concatenation over k = 1 .. num (tests/mesh_label_oracle.py), and every byte equals that oracle.
 //
-// One wavefront works on one 64-voxel word of a row, one lane per voxel / cell, as in mesh.hip, but on the labels themselves:
+// One wavefront works on one 64-voxel word of a row (the word grid of bitvol.h), one lane per voxel / cell, as in mesh.hip, but on
+// the labels themselves:
 //   count  a lane reads the 8 corners of its cell.  Its voxel owns, per axis with a +1 neighbour of another label, one vertex
 //          item for each of the two labels that is not 0 (low-end label first): at most 3 x 2 = 6.  Its cell owns, for every
 //          distinct non-zero label among the corners, the table's triangles of the configuration "corner == label": at most 8
@@ -15,7 +16,7 @@
 //          and is marked, so that the two later passes over the words leave it after one byte.
 //          Items per label are summed over the wavefront and added with one integer atomic per distinct label (a count does
 //          not depend on the order of its additions; no atomic ever hands out a position).
-//   scan   mesh.hip's run_scan over the per-word counts (item numbering in raster order) and over the per-label counts
+//   scan   run_scan (bitvol.h) over the per-word counts (item numbering in raster order) and over the per-label counts
 //          (vert_ptr / face_ptr).  The host reads V, F, the largest label and the status once.
 //   keys   the label of every item, in raster order.
 //   sort   stable LSD radix sort of (label, raster index), 8-bit digits, one pass for num < 256 and two otherwise: per-block
@@ -31,23 +32,9 @@ namespace seunet {
 
 namespace {
 
-struct LabelTable {
-  unsigned char count[256];
-  unsigned char edges[256][3 * SEUNET_MESH_MAX_TRIS];
-};
-constexpr LabelTable make_label_table() {
-  LabelTable t{};
-  for (int c = 0; c < 256; ++c) {
-    t.count[c] = kMeshTriCount[c];
-    for (int k = 0; k < 3 * SEUNET_MESH_MAX_TRIS; ++k) t.edges[c][k] = kMeshTriEdges[c][k];
-  }
-  return t;
-}
-__constant__ LabelTable kLabelTable = make_label_table();
+__constant__ MeshTable kLabelTable = make_mesh_table();
 
-struct LabelGeom {
-  int n0, n1, n2, W;          // W = words per row
-  long long words;            // n0 * n1 * W
+struct LabelGeom : BitGeom {  // the word grid of the label volume's rows: no packed volume is stored, the lanes read the labels
   int limit;                  // the largest label accepted: num, or kMeshLabelMax when the call finds num itself
   int cells;                  // 0: an extent of 1, no cell and by definition no vertex either
 };
@@ -142,15 +129,6 @@ __device__ __forceinline__ int lane_triangles(const Lane& a) {
   return n;
 }
 
-__device__ __forceinline__ int wave_max_int(int v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const int o = shfl_xor_settled(v, off);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-
 // hist[label] += n over the wavefront, one atomic per distinct label: a branch's surface puts most of a word's items on one label,
 // and a single word of memory takes atomics far more slowly than the waves produce them.  n <= 8.  Called by all 64 lanes.
 __device__ __forceinline__ void wave_add(unsigned* __restrict__ hist, int lane, int label, unsigned n) {
@@ -159,8 +137,7 @@ __device__ __forceinline__ void wave_add(unsigned* __restrict__ hist, int lane, 
     const int leader = __ffsll((long long)pending) - 1;
     const int lab = __shfl(label, leader, 64);
     const bool same = n != 0u && label == lab;
-    const unsigned total = (unsigned)(__popcll(__ballot(same && (n & 1u))) + 2 * __popcll(__ballot(same && (n & 2u))) +
-                                      4 * __popcll(__ballot(same && (n & 4u))) + 8 * __popcll(__ballot(same && (n & 8u))));
+    const unsigned total = (unsigned)ballot_sum<4>(same ? (int)n : 0);
     if (lane == leader) atomicAdd(&hist[lab], total);
     pending &= ~__ballot(same);
   }
@@ -175,15 +152,14 @@ label_count_kernel(const int* __restrict__ L, LabelGeom g, MeshLabelWs w) {
   const bool flat = wave_flat(a) || !g.cells;
   // every voxel is the c[0] of exactly one lane: the label check and the largest label ride on the loads
   const u64 negative = __ballot(a.raw < 0), large = __ballot(a.raw > g.limit);
-  const int top = flat && g.cells ? a.c[0] : wave_max_int(a.c[0]);
+  const int top = flat && g.cells ? a.c[0] : wave_max(a.c[0]);
   unsigned nv = 0u, nf = 0u;
-  u64 v0 = 0ull, v1 = 0ull, v2 = 0ull;
+  BitPlanes<3> vb = {};
   if (!flat) {                                                 // uniform; most words of a CT carry one value
     const int mv = lane_vertices(a), mf = lane_triangles(a);
-    v0 = __ballot(mv & 1); v1 = __ballot(mv & 2); v2 = __ballot(mv & 4);
-    nv = (unsigned)(__popcll(v0) + 2 * __popcll(v1) + 4 * __popcll(v2));
-    nf = (unsigned)(__popcll(__ballot(mf & 1)) + 2 * __popcll(__ballot(mf & 2)) + 4 * __popcll(__ballot(mf & 4)) +
-                    8 * __popcll(__ballot(mf & 8)));
+    vb = ballot_planes<3>(mv);
+    nv = (unsigned)plane_sum(vb);
+    nf = (unsigned)ballot_sum<4>(mf);
     // items per label.  Labels are clean: 0 .. limit <= kMeshLabelMax, inside the two arrays.  Every call below is made by the
     // whole wavefront (n = 0: nothing to add).
     const int p = a.c[0];
@@ -206,7 +182,7 @@ label_count_kernel(const int* __restrict__ L, LabelGeom g, MeshLabelWs w) {
     }
   }
   if (lane == 0) {
-    w.vb0[t] = v0; w.vb1[t] = v1; w.vb2[t] = v2;
+    w.vb0[t] = vb.b[0]; w.vb1[t] = vb.b[1]; w.vb2[t] = vb.b[2];
     w.vcnt[t] = nv;
     w.fcnt[t] = nf;
     w.active[t] = flat ? 0 : 1;
@@ -248,9 +224,8 @@ struct ItemArgs {
 
 // raster index of the first vertex item of the voxel at bit `bit` of word tw
 __device__ __forceinline__ unsigned voxel_vertex_base(const MeshLabelWs& w, long long tw, int bit) {
-  const u64 below = (1ull << bit) - 1ull;
-  return w.vblk[tw / kScanBlock] + w.vcnt[tw] +
-         (unsigned)(__popcll(w.vb0[tw] & below) + 2 * __popcll(w.vb1[tw] & below) + 4 * __popcll(w.vb2[tw] & below));
+  const BitPlanes<3> vb = {{w.vb0[tw], w.vb1[tw], w.vb2[tw]}};
+  return w.vblk[tw / kScanBlock] + w.vcnt[tw] + (unsigned)plane_sum(vb, lanes_below(bit));
 }
 
 // Raster index of the vertex item (grid edge, label): the grid edge is cube edge `edge` of the cell at (i, j, k), which exists, so
@@ -281,7 +256,6 @@ template <bool KEYS> __global__ void __launch_bounds__(256) label_items_kernel(I
   const int lane = threadIdx.x & 63;
   if (e.w.active[t] == 0) return;                              // uniform: the count pass found the word flat (99 % of a CT)
   const Lane a = load_lane(e.labels, g, t, lane);
-  const u64 below = (1ull << lane) - 1ull;
 
   if (lane_vertices(a) != 0) {
     long long idx = (long long)voxel_vertex_base(e.w, t, lane);
@@ -312,10 +286,9 @@ template <bool KEYS> __global__ void __launch_bounds__(256) label_items_kernel(I
   }
 
   const int mf = lane_triangles(a);
-  const u64 b0 = __ballot(mf & 1), b1 = __ballot(mf & 2), b2 = __ballot(mf & 4), b3 = __ballot(mf & 8);
-  if ((b0 | b1 | b2 | b3) == 0ull) return;
-  long long f = (long long)(e.w.fblk[t / kScanBlock] + e.w.fcnt[t]) + __popcll(b0 & below) + 2 * __popcll(b1 & below) +
-                4 * __popcll(b2 & below) + 8 * __popcll(b3 & below);
+  const BitPlanes<4> fb = ballot_planes<4>(mf);
+  if ((fb.b[0] | fb.b[1] | fb.b[2] | fb.b[3]) == 0ull) return;
+  long long f = (long long)(e.w.fblk[t / kScanBlock] + e.w.fcnt[t]) + plane_sum(fb, lanes_below(lane));
   for_each_cell_label(a, [&](int l, int cfg) {
     const int n = kLabelTable.count[cfg];
     for (int q = 0; q < n; ++q, ++f) {
@@ -426,9 +399,7 @@ int sort_by_label(const unsigned short* key, long long n, int passes, const Mesh
 }
 
 LabelGeom label_geom(int n0, int n1, int n2, int num) {
-  LabelGeom g;
-  g.n0 = n0; g.n1 = n1; g.n2 = n2; g.W = (n2 + 63) / 64;
-  g.words = (long long)n0 * n1 * g.W;
+  LabelGeom g{bit_geom(n0, n1, n2)};
   g.limit = num < 0 ? kMeshLabelMax : num;
   g.cells = n0 >= 2 && n1 >= 2 && n2 >= 2;
   return g;

@@ -245,12 +245,7 @@ slice_moments_kernel(const unsigned char* __restrict__ mask, int n0, int n1, int
       s1 += (u64)(r % n1);
     }
   }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    cnt += shfl_xor_settled(cnt, off);
-    s0 += shfl_xor_settled(s0, off);
-    s1 += shfl_xor_settled(s1, off);
-  }
+  cnt = wave_sum(cnt); s0 = wave_sum(s0); s1 = wave_sum(s1);
   if ((threadIdx.x & 63) == 0 && cnt) {
     atomicAdd(&out[0], cnt);
     atomicAdd(&out[1], s0);

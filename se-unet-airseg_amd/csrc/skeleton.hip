@@ -9,7 +9,7 @@
 //   26-connected component; (2) the candidates in raster order: delete iff the one-component test still holds on the image with
 //   the deletions made so far.
 //
-// Storage: the volume as bits along the last axis, 64 voxels per word (bit b of word w of a row = voxel 64 w + b), with one zero
+// Storage: the padded form of the bit-packed volume (bitvol.h): 64 voxels of a row per word, with one zero
 // row on each side of axes 0 and 1 and one zero word on each side of a row, so that no neighbour access needs a bounds test.
 // One wavefront works on one word, one lane per voxel.  The 27 words around a word are fetched by 27 lanes with one vector load
 // and handed round with v_readlane; the 3 x 3 x 3 neighbourhood of a lane is 27 bits, bit (di+1)*9 + (dj+1)*3 + (dk+1).
@@ -72,13 +72,6 @@ constexpr SkelTables make_tables() {
 constexpr SkelTables kHostTables = make_tables();
 __constant__ SkelTables kTables = make_tables();
 
-struct SkelGeom {
-  int n0, n1, n2, W;          // W = words per row
-  long long row_stride;       // W + 2 words
-  long long plane_stride;     // (n1 + 2) rows
-  long long words;            // n0 * n1 * W words that hold voxels
-};
-
 struct SkelCtl {              // zeroed before every pass, read back after it
   int changed[6];             // sub-iteration s of the pass deleted a voxel
   unsigned count[6];          // words with candidates in sub-iteration s
@@ -86,20 +79,13 @@ struct SkelCtl {              // zeroed before every pass, read back after it
   int pad[3];
 };
 
-__device__ __forceinline__ long long padded_word(const SkelGeom& g, long long t) {   // t-th voxel word -> index in the padded array
-  const int w = (int)(t % g.W);
-  const long long r = t / g.W;
-  const long long j = r % g.n1, i = r / g.n1;
-  return ((i + 1) * g.plane_stride + (j + 1)) * g.row_stride + (w + 1);
-}
-
 // Device-scope loads and stores on the vector path: words written by other wavefronts of the same launch are read again in
 // later rounds of the single-workgroup loop, so they must come neither from the scalar cache nor from a stale L1 line.
 __device__ __forceinline__ u64 ld(const u64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void st(u64* p, u64 v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // lane t < 27 fetches the word at (row t / 3 of the 3x3 rows around the word, word t % 3 - 1); the other lanes fetch nothing
-__device__ __forceinline__ u64 fetch_block(const u64* a, long long p, const SkelGeom& g, int lane, int lanes) {
+__device__ __forceinline__ u64 fetch_block(const u64* a, long long p, const BitGeom& g, int lane, int lanes) {
   if (lane >= lanes) return 0;
   const int r = lane / 3, c = lane % 3;
   return ld(a + p + (r / 3 - 1) * g.plane_stride * g.row_stride + (r % 3 - 1) * g.row_stride + (c - 1));
@@ -159,35 +145,15 @@ __device__ __forceinline__ bool one_component(unsigned nb) {
   return comp == nb;
 }
 
-__global__ void __launch_bounds__(256)
-skel_pack_kernel(const unsigned char* __restrict__ vol, SkelGeom g, u64* __restrict__ bits) {
-  const long long t = (blockIdx.x * 256ll + threadIdx.x) >> 6;
-  if (t >= g.words) return;
-  const int lane = threadIdx.x & 63;
-  const int k = (int)(t % g.W) * 64 + lane;
-  const bool fg = k < g.n2 && vol[(t / g.W) * g.n2 + k] != 0;
-  const u64 m = __ballot(fg);
-  if (lane == 0) bits[padded_word(g, t)] = m;
-}
-
-__global__ void __launch_bounds__(256)
-skel_unpack_kernel(const u64* __restrict__ bits, SkelGeom g, unsigned char* __restrict__ out) {
-  const long long t = (blockIdx.x * 256ll + threadIdx.x) >> 6;
-  if (t >= g.words) return;
-  const int lane = threadIdx.x & 63;
-  const int k = (int)(t % g.W) * 64 + lane;
-  if (k < g.n2) out[(t / g.W) * g.n2 + k] = (unsigned char)((bits[padded_word(g, t)] >> lane) & 1ull);
-}
-
 // step 1 of a sub-iteration: the candidate mask of every word into BOTH undecided buffers, the words that have candidates into
 // the list.  `border` = the neighbourhood bit that must be background.
 __global__ void __launch_bounds__(256)
-skel_candidates_kernel(const u64* __restrict__ bits, SkelGeom g, unsigned border, u64* __restrict__ und0, u64* __restrict__ und1,
+skel_candidates_kernel(const u64* __restrict__ bits, BitGeom g, unsigned border, u64* __restrict__ und0, u64* __restrict__ und1,
                        unsigned* __restrict__ list, unsigned* __restrict__ count) {
   const long long t = (blockIdx.x * 256ll + threadIdx.x) >> 6;
   if (t >= g.words) return;                                  // whole wavefronts leave together
   const int lane = threadIdx.x & 63;
-  const long long p = padded_word(g, t);
+  const long long p = word_index(g, t);
   u64 cand = 0;
   if (bits[p] != 0ull) {                                     // uniform; most words of a volume are empty
     const unsigned nb = neighbourhood<9>(fetch_block(bits, p, g, lane, 27), lane);
@@ -212,7 +178,7 @@ skel_candidates_kernel(const u64* __restrict__ bits, SkelGeom g, unsigned border
 // voxel.  Two candidates decided in one step are never adjacent; the eight other rows do not change where an eligible candidate
 // looks.  Deletes the decided candidates whose neighbours still form one component and writes the word's remaining undecided
 // mask to `next`.  Returns that mask.  All 64 lanes call; every mask below is uniform.
-__device__ __forceinline__ u64 recheck_word(u64* bits, const u64* prev, u64* next, long long p, const SkelGeom& g, int lane,
+__device__ __forceinline__ u64 recheck_word(u64* bits, const u64* prev, u64* next, long long p, const BitGeom& g, int lane,
                                             int* changed) {
   const u64 mine = fetch_block(prev, p, g, lane, 14);        // rows (-1,-1) (-1,0) (-1,+1) (0,-1) and the own row's words -1, 0
   const u64 own = from_lane<13>(mine);
@@ -248,7 +214,7 @@ __device__ __forceinline__ u64 recheck_word(u64* bits, const u64* prev, u64* nex
 
 __global__ void __launch_bounds__(256)
 skel_round_kernel(u64* bits, const u64* prev, u64* next, const unsigned* __restrict__ list, const unsigned* __restrict__ count,
-                  SkelGeom g, int* changed) {
+                  BitGeom g, int* changed) {
   const unsigned n = *count;
   const int lane = threadIdx.x & 63;
   const unsigned waves = gridDim.x * 4u;
@@ -260,7 +226,7 @@ skel_round_kernel(u64* bits, const u64* prev, u64* next, const unsigned* __restr
 // after at most 64 * (open words) rounds; the bound is enforced, and `stuck` reports a violation instead of hanging the card.
 __global__ void __launch_bounds__(1024)
 skel_finish_kernel(u64* bits, u64* und_a, u64* und_b, const unsigned* __restrict__ list, unsigned* open_list,
-                   const unsigned* __restrict__ count, SkelGeom g, int* changed, int* stuck) {
+                   const unsigned* __restrict__ count, BitGeom g, int* changed, int* stuck) {
   __shared__ unsigned n_open;
   __shared__ int remaining;
   const unsigned n = *count;
@@ -304,7 +270,7 @@ __global__ void skel_set_int_kernel(int* p, int v) {
 }
 
 struct SkelLayout {
-  SkelGeom g;
+  BitGeom g;
   SkelCtl* ctl;
   u64* bits;                  // the image, then the two undecided masks: planes_bytes from `bits` on hold the three padded volumes
   u64* und[2];
@@ -317,12 +283,8 @@ bool skel_layout(WsCarver& c, int n0, int n1, int n2, SkelLayout* L) {
   if (n0 < 1 || n1 < 1 || n2 < 1) return false;
   const unsigned long long n = (unsigned long long)n0 * n1 * n2;
   if (n > 0x7fffffffull) return false;
-  SkelGeom& g = L->g;
-  g.n0 = n0; g.n1 = n1; g.n2 = n2; g.W = (n2 + 63) / 64;
-  g.row_stride = g.W + 2;
-  g.plane_stride = (long long)n1 + 2;
-  g.words = (long long)n0 * n1 * g.W;
-  const unsigned long long padded = (unsigned long long)(n0 + 2ll) * g.plane_stride * g.row_stride;
+  const BitGeom g = L->g = bit_geom(n0, n1, n2, 1);
+  const unsigned long long padded = padded_words(g);
   if (padded > 0xffffffffull) return false;                  // the word lists hold 32-bit indices
   static_assert(sizeof(SkelCtl) <= 256, "SkelCtl outgrew its slot");
   L->ctl = c.take<SkelCtl>(1);
@@ -360,13 +322,13 @@ int launch_skeletonize(const unsigned char* vol, int n0, int n1, int n2, unsigne
   u64* bits = L.bits;
   u64* const* und = L.und;
   unsigned *list = L.list, *open_list = L.open_list;
-  const SkelGeom g = L.g;
+  const BitGeom g = L.g;
   const unsigned word_blocks = (unsigned)((g.words + 3) / 4);
   const unsigned round_blocks = std::min(word_blocks, 2048u);
   static const int order[6] = {4, 3, 2, 1, 5, 6};
 
   SEUNET_HIP(hipMemsetAsync(bits, 0, L.planes_bytes, s));    // the zero borders of the image and of both undecided masks
-  skel_pack_kernel<<<word_blocks, 256, 0, s>>>(vol, g, bits);
+  pack_bits(vol, nullptr, g, bits, nullptr, s);
   int passes = 0;
   for (;;) {
     ++passes;
@@ -387,7 +349,7 @@ int launch_skeletonize(const unsigned char* vol, int n0, int n1, int n2, unsigne
     for (int i = 0; i < 6; ++i) any = any || host.changed[i] != 0;
     if (!any) break;
   }
-  skel_unpack_kernel<<<word_blocks, 256, 0, s>>>(bits, g, out);
+  unpack_bits(bits, g, out, s);
   if (passes_dev) skel_set_int_kernel<<<1, 64, 0, s>>>(passes_dev, passes);
   SEUNET_LAUNCH_CHECK();
   return 0;

@@ -2,10 +2,10 @@
 // symmetric surface distance and the surface Dice at a tolerance.  The reference computes none of them; the
 // definition is include/seunet_hip.h, restated in numpy by tests/surface_oracle.py.
 //
-//   count    both masks are bit-packed along axis 2 (bit j of word w of a row = voxel 64 w + j, zero tails, as morph.hip); one pass
-//            on the packed words forms both border masks (set, and one of the six neighbours unset or outside), counts their bits
-//            per word and reduces the bounding box of A | B; run_scan (mesh.hip) scans the two count arrays in one launch.  The
-//            host reads the two totals and the box once.
+//   count    both masks are bit-packed along axis 2 by one pack_bits launch (bitvol.h); one pass on the
+//            packed words forms both border masks (set, and one of the six neighbours unset or outside: load_cross6 with outside
+//            = 0), counts their bits per word and reduces the bounding box of A | B; run_scan scans the two count arrays in one
+//            launch.  The host reads the two totals and the box once.
 //   emit     per direction, inside the box only: the other mask's border becomes the zero voxels of a byte volume, the EDT with
 //            spacing (edt_sampling.hip, as it is) gives every box voxel the linear index of its feature, and every border bit of
 //            this mask writes sqrt((dt0^2 + dt1^2) + dt2^2) at the position the scan gives it: raster order, A's then B's.  All
@@ -35,48 +35,26 @@ constexpr int kSelectPasses = 64 / kSelectBits;
 constexpr int kSelectMaxBlocks = 512;
 
 // ---- count -------------------------------------------------------------------------------------------------------------------
-// bytes -> bits of both masks: one wave per word, lane j reads voxel 64 w + j of the row, the ballot is the word
-__global__ void __launch_bounds__(256)
-surface_pack_kernel(const unsigned char* __restrict__ a, const unsigned char* __restrict__ b, long long rows, int n2, int nw,
-                    u64* __restrict__ pa, u64* __restrict__ pb) {
-  const long long word = blockIdx.x * 4ll + (threadIdx.x >> 6);      // wave-uniform
-  if (word >= rows * nw) return;
-  const int lane = threadIdx.x & 63;
-  const long long row = word / nw;
-  const int k = (int)(word % nw) * 64 + lane;
-  const bool in = k < n2;
-  const long long v = row * n2 + k;
-  const u64 ma = __ballot(in && a[v] != 0), mb = __ballot(in && b[v] != 0);
-  if (lane == 0) { pa[word] = ma; pb[word] = mb; }
-}
-
-// the border bits of word idx: set, and not all six neighbours set; outside the volume and the tail of a row read as 0
-__device__ __forceinline__ u64 border_word(const u64* __restrict__ in, long long idx, int m, int i0, int i1, int n0, int n1, int nw) {
+// the border bits of word idx: set, and not all six neighbours set (morph.hip's erosion with outside = 0, then x & ~eroded)
+__device__ __forceinline__ u64 border_word(const u64* __restrict__ in, const BitGeom& g, long long idx) {
   const u64 x = in[idx];
   if (!x) return 0ull;
-  const long long plane = (long long)n1 * nw;
-  const u64 lo = m > 0 ? in[idx - 1] >> 63 : 0ull;
-  const u64 hi = m + 1 < nw ? in[idx + 1] << 63 : 0ull;
-  const u64 r0 = i1 > 0 ? in[idx - nw] : 0ull;
-  const u64 r1 = i1 + 1 < n1 ? in[idx + nw] : 0ull;
-  const u64 p0 = i0 > 0 ? in[idx - plane] : 0ull;
-  const u64 p1 = i0 + 1 < n0 ? in[idx + plane] : 0ull;
-  return x & ~(((x << 1) | lo) & ((x >> 1) | hi) & r0 & r1 & p0 & p1);
+  return x & ~and6(load_cross6(in, g, idx, 0ull));
 }
 
 // one thread per word: both borders, their bit counts, and the box of A | B as six maxima (exclusive high ends, and extent - low
 // end), so that a zeroed record is the empty box.  Wave and workgroup maxima first, then at most six integer atomics per workgroup (none for a workgroup of empty words).
 __global__ void __launch_bounds__(256)
-surface_border_kernel(const u64* __restrict__ pa, const u64* __restrict__ pb, int n0, int n1, int n2, int nw, u64* __restrict__ ba,
-                      u64* __restrict__ bb, unsigned* __restrict__ ca, unsigned* __restrict__ cb, SurfaceRec* __restrict__ rec) {
+surface_border_kernel(const u64* __restrict__ pa, const u64* __restrict__ pb, BitGeom g, u64* __restrict__ ba, u64* __restrict__ bb,
+                      unsigned* __restrict__ ca, unsigned* __restrict__ cb, SurfaceRec* __restrict__ rec) {
   __shared__ int part[4][6];
   const long long idx = blockIdx.x * 256ll + threadIdx.x;
   int v[6] = {0, 0, 0, 0, 0, 0};
-  if (idx < (long long)n0 * n1 * nw) {
-    const long long row = idx / nw;
-    const int m = (int)(idx % nw);
-    const int i1 = (int)(row % n1), i0 = (int)(row / n1);
-    const u64 xa = border_word(pa, idx, m, i0, i1, n0, n1, nw), xb = border_word(pb, idx, m, i0, i1, n0, n1, nw);
+  if (idx < g.words) {
+    const long long row = idx / g.W;
+    const int m = (int)(idx % g.W);
+    const int i1 = (int)(row % g.n1), i0 = (int)(row / g.n1);
+    const u64 xa = border_word(pa, g, idx), xb = border_word(pb, g, idx);
     ba[idx] = xa;
     bb[idx] = xb;
     ca[idx] = (unsigned)__popcll(xa);
@@ -86,9 +64,9 @@ surface_border_kernel(const u64* __restrict__ pa, const u64* __restrict__ pb, in
       v[0] = i0 + 1;
       v[1] = i1 + 1;
       v[2] = 64 * m + 64 - __clzll((long long)any);
-      v[3] = n0 - i0;
-      v[4] = n1 - i1;
-      v[5] = n2 - (64 * m + __ffsll((unsigned long long)any) - 1);
+      v[3] = g.n0 - i0;
+      v[4] = g.n1 - i1;
+      v[5] = g.n2 - (64 * m + __ffsll((unsigned long long)any) - 1);
     }
   }
 #pragma unroll
@@ -111,19 +89,19 @@ struct SurfaceBox { int lo[3], ext[3]; };
 
 // the EDT's input on the box: 0 (a site) at the border voxels of the other mask, 1 elsewhere
 __global__ void __launch_bounds__(256)
-surface_sites_kernel(const u64* __restrict__ border, int n1, int nw, SurfaceBox bx, long long nbox, unsigned char* __restrict__ sites) {
+surface_sites_kernel(const u64* __restrict__ border, BitGeom g, SurfaceBox bx, long long nbox, unsigned char* __restrict__ sites) {
   const long long i = blockIdx.x * 256ll + threadIdx.x;
   if (i >= nbox) return;
   const Vox3 p = vox3(i, bx.ext[1], bx.ext[2]);
-  const long long row = (long long)(p.i0 + bx.lo[0]) * n1 + (p.i1 + bx.lo[1]);
+  const long long row = (long long)(p.i0 + bx.lo[0]) * g.n1 + (p.i1 + bx.lo[1]);
   const int k = p.i2 + bx.lo[2];
-  sites[i] = (unsigned char)(((border[row * nw + (k >> 6)] >> (k & 63)) & 1ull) ^ 1ull);
+  sites[i] = (unsigned char)(((border[row * g.W + (k >> 6)] >> (k & 63)) & 1ull) ^ 1ull);
 }
 
 // one wave per word of the box's rows, lane j = bit j.  A border bit writes its distance at the position the scan gives it.
 __global__ void __launch_bounds__(256)
-surface_gather_kernel(const u64* __restrict__ border, const unsigned* __restrict__ cnt, const unsigned* __restrict__ blk, int n1, int n2,
-                      int nw, SurfaceBox bx, int w_lo, int w_span, long long items, const int* __restrict__ lin, double s0, double s1,
+surface_gather_kernel(const u64* __restrict__ border, const unsigned* __restrict__ cnt, const unsigned* __restrict__ blk, BitGeom g,
+                      SurfaceBox bx, int w_lo, int w_span, long long items, const int* __restrict__ lin, double s0, double s1,
                       double s2, long long count, double* __restrict__ dist, int* __restrict__ voxel) {
   const long long t = (blockIdx.x * 256ll + threadIdx.x) >> 6;      // wave-uniform
   if (t >= items) return;
@@ -132,7 +110,7 @@ surface_gather_kernel(const u64* __restrict__ border, const unsigned* __restrict
   const int wi = (int)(t % w_span) + w_lo;
   const int c1 = (int)(r % bx.ext[1]), c0 = (int)(r / bx.ext[1]);      // box coordinates of the row
   const int i0 = c0 + bx.lo[0], i1 = c1 + bx.lo[1];
-  const long long idx = ((long long)i0 * n1 + i1) * nw + wi;
+  const long long idx = ((long long)i0 * g.n1 + i1) * g.W + wi;
   const u64 bits = border[idx];
   if (!((bits >> lane) & 1ull)) return;
   const long long pos = (long long)cnt[idx] + blk[idx / kScanBlock] + __popcll(bits & ((1ull << lane) - 1ull));
@@ -148,7 +126,7 @@ surface_gather_kernel(const u64* __restrict__ border, const unsigned* __restrict
     d = sqrt((t0 * t0 + t1 * t1) + t2 * t2);
   }
   dist[pos] = d;
-  if (voxel) voxel[pos] = (int)(((long long)i0 * n1 + i1) * n2 + k);
+  if (voxel) voxel[pos] = (int)(((long long)i0 * g.n1 + i1) * g.n2 + k);
 }
 
 // ---- summary -----------------------------------------------------------------------------------------------------------------
@@ -163,14 +141,11 @@ __host__ __device__ constexpr int summary_rec_words(int ntol) { return 2 * (3 + 
 __device__ __forceinline__ void summary_block_reduce(double& sum, u64& mx, u64 (&le)[kSurfaceMaxTol], int ntol) {
   __shared__ double s_sum[4];
   __shared__ u64 s_max[4], s_le[4][kSurfaceMaxTol];
-  sum = stride_sum_d<1>(sum);
+  sum = wave_sum(sum);
   mx = wave_max(mx);
 #pragma unroll
   for (int q = 0; q < kSurfaceMaxTol; ++q) {
-    if (q < ntol) {                                                  // uniform
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1) le[q] += shfl_xor_settled(le[q], off);
-    }
+    if (q < ntol) le[q] = wave_sum(le[q]);                           // uniform
   }
   const int wave = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0) {
@@ -347,13 +322,11 @@ int launch_surface_count(const unsigned char* a, const unsigned char* b, int n0,
   WsCarver carve(workspace);
   const SurfaceWs w = surface_ws(carve, n0, n1, n2);
   SEUNET_CHECK(ws_bytes >= carve.bytes(), "surface_count: workspace too small (%zu bytes, %zu needed)", ws_bytes, carve.bytes());
-  const int nw = (n2 + 63) / 64;
-  const long long rows = (long long)n0 * n1, words = rows * nw;
+  const BitGeom g = bit_geom(n0, n1, n2);
   SEUNET_HIP(hipMemsetAsync(w.rec, 0, sizeof(SurfaceRec), s));
-  surface_pack_kernel<<<(unsigned)((words + 3) / 4), 256, 0, s>>>(a, b, rows, n2, nw, w.bits_a, w.bits_b);
-  surface_border_kernel<<<blocks_256(words), 256, 0, s>>>(w.bits_a, w.bits_b, n0, n1, n2, nw, w.border_a, w.border_b, w.cnt_a, w.cnt_b,
-                                                         w.rec);
-  if (int e = run_scan(w.cnt_a, w.cnt_b, words, w.blk_a, w.blk_b, &w.rec->n_a, s)) return e;
+  pack_bits(a, b, g, w.bits_a, w.bits_b, s);
+  surface_border_kernel<<<blocks_256(g.words), 256, 0, s>>>(w.bits_a, w.bits_b, g, w.border_a, w.border_b, w.cnt_a, w.cnt_b, w.rec);
+  if (int e = run_scan(w.cnt_a, w.cnt_b, g.words, w.blk_a, w.blk_b, &w.rec->n_a, s)) return e;
   SurfaceRec host;                                             // the one synchronisation: the output sizes and the box
   SEUNET_HIP(hipMemcpyAsync(&host, w.rec, sizeof(SurfaceRec), hipMemcpyDeviceToHost, s));
   SEUNET_HIP(hipStreamSynchronize(s));
@@ -390,18 +363,18 @@ int launch_surface_emit(int n0, int n1, int n2, const int* box, double s0, doubl
   WsCarver ecarve(emit_workspace);
   const SurfaceEmitWs e = surface_emit_ws(ecarve, bx.ext[0], bx.ext[1], bx.ext[2]);
   SEUNET_CHECK(emit_bytes >= ecarve.bytes(), "surface_emit: emit workspace too small (%zu bytes, %zu needed)", emit_bytes, ecarve.bytes());
-  const int nw = (n2 + 63) / 64;
+  const BitGeom g = bit_geom(n0, n1, n2);
   const long long nbox = (long long)bx.ext[0] * bx.ext[1] * bx.ext[2];
   const int w_lo = bx.lo[2] / 64, w_span = (bx.lo[2] + bx.ext[2] - 1) / 64 - w_lo + 1;
   const long long items = (long long)bx.ext[0] * bx.ext[1] * w_span;
   for (int dir = 0; dir < 2; ++dir) {                          // 0: A's border against B's, 1: the mirror image
     const u64* mine = dir ? w.border_b : w.border_a;
     const u64* other = dir ? w.border_a : w.border_b;
-    surface_sites_kernel<<<blocks_256(nbox), 256, 0, s>>>(other, n1, nw, bx, nbox, e.sites);
+    surface_sites_kernel<<<blocks_256(nbox), 256, 0, s>>>(other, g, bx, nbox, e.sites);
     if (int err = launch_edt_sampling(e.sites, bx.ext[0], bx.ext[1], bx.ext[2], s0, s1, s2, EdtSamplingOut{nullptr, nullptr, e.lin}, nullptr,
                                       e.edt.f0, e.edt_bytes, s))
       return err;
-    surface_gather_kernel<<<(unsigned)((items + 3) / 4), 256, 0, s>>>(mine, dir ? w.cnt_b : w.cnt_a, dir ? w.blk_b : w.blk_a, n1, n2, nw, bx,
+    surface_gather_kernel<<<(unsigned)((items + 3) / 4), 256, 0, s>>>(mine, dir ? w.cnt_b : w.cnt_a, dir ? w.blk_b : w.blk_a, g, bx,
                                                                      w_lo, w_span, items, e.lin, s0, s1, s2, dir ? n_b : n_a,
                                                                      dist + (dir ? n_a : 0), voxel ? voxel + (dir ? n_a : 0) : nullptr);
   }

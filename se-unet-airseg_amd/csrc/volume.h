@@ -1,5 +1,7 @@
-// Shared layer of the volume operations (components.hip, lung.hip, edt.hip, edt_sampling.hip, parse.hip, skeleton.hip, dti.hip, morph.hip, mesh.hip, mesh_label.hip, morphometry.hip, cldice.hip, surface.hip): their launcher
-// prototypes, ONE workspace layout per operation, the extent check and the voxel / wave helpers their kernels share.
+// Shared layer of the volume operations (components.hip, lung.hip, edt.hip, edt_sampling.hip, parse.hip, skeleton.hip, dti.hip,
+// morph.hip, mesh.hip, mesh_label.hip, morphometry.hip, cldice.hip, surface.hip): their launcher prototypes, ONE workspace layout
+// per operation, the extent check and the voxel / wave helpers their kernels share.  The bit-packed representation six of them
+// work on -- geometry, packing, neighbour words, the scan, wave counts -- is bitvol.h / bitvol.hip.
 //
 // Workspace contract: every operation has a layout struct filled by one function that walks a WsCarver.  Over a null base
 // the walk measures (`X_workspace_bytes`), over the caller's workspace it carves (the launcher); no launcher computes an
@@ -7,11 +9,10 @@
 // to tests/test_volume_layout_host.py, which pins the byte counts.
 #pragma once
 #include "seunet_common.h"
+#include "bitvol.h"
 #include <algorithm>
 
 namespace seunet {
-
-typedef unsigned long long u64;
 
 // workgroups of a one-thread-per-item pass of 256-thread blocks (grid_for clamps to 4096 workgroups for grid-stride passes)
 static inline unsigned blocks_256(long long n) { return (unsigned)((n + 255) / 256); }
@@ -228,8 +229,8 @@ int launch_scatter_labels(const long long* lin_index, const int* value, long lon
 // ---- binary morphology with the 6-neighbour cross (morph.hip) ---------------------------------------------------------------
 struct MorphWs { u64 *a, *b; };   // the packed volume and one step's result; rows of ceil(n2 / 64) words
 static inline MorphWs morph_ws(WsCarver& c, int n0, int n1, int n2) {
-  const size_t words = (size_t)n0 * n1 * ((n2 + 63) / 64);
-  return MorphWs{c.take<u64>(words), c.take<u64>(words)};
+  const size_t nwords = words(n0, n1, n2);
+  return MorphWs{c.take<u64>(nwords), c.take<u64>(nwords)};
 }
 size_t binary_morph_workspace_bytes(int n0, int n1, int n2);
 int launch_binary_morph(const unsigned char* vol, int n0, int n1, int n2, int op, unsigned char* out, void* workspace, size_t ws_bytes,
@@ -267,8 +268,8 @@ int launch_crop3d(const void* src, int elem_bytes, int H, int W, int Z, const in
 // ---- double threshold (dti.hip) -------------------------------------------------------------------------------------------
 struct DtiWs { u64 *g, *weak; };   // strong mask (swept in place into the result), weak mask; rows of ceil(z / 64) words
 static inline DtiWs dti_ws(WsCarver& c, int h, int w, int z) {
-  const size_t words = (size_t)h * w * ((z + 63) / 64);
-  return DtiWs{c.take<u64>(words, 8), c.take<u64>(words, 8)};   // the two halves have never been padded: word alignment only
+  const size_t nwords = words(h, w, z);
+  return DtiWs{c.take<u64>(nwords, 8), c.take<u64>(nwords, 8)};   // the two halves have never been padded: word alignment only
 }
 size_t dti_workspace_bytes(int h, int w, int z);
 int launch_dti(const double* pred, int h, int w, int z, double h_thresh, double l_thresh, int pred_dtype, unsigned char* out,
@@ -284,9 +285,9 @@ struct MeshWs {
   unsigned *vblk, *fblk;          // per block: its total, then the exclusive scan of the totals
 };
 static inline MeshWs mesh_ws(WsCarver& c, int n0, int n1, int n2) {
-  const size_t words = (size_t)n0 * n1 * ((n2 + 63) / 64), blocks = (words + 1023) / 1024;
-  return MeshWs{c.take<MeshRec>(1), c.take<u64>(words), c.take<u64>(words), c.take<u64>(words), c.take<u64>(words),
-                c.take<unsigned>(words), c.take<unsigned>(words), c.take<unsigned>(blocks), c.take<unsigned>(blocks)};
+  const size_t nwords = words(n0, n1, n2), blocks = (nwords + kScanBlock - 1) / kScanBlock;
+  return MeshWs{c.take<MeshRec>(1), c.take<u64>(nwords), c.take<u64>(nwords), c.take<u64>(nwords), c.take<u64>(nwords),
+                c.take<unsigned>(nwords), c.take<unsigned>(nwords), c.take<unsigned>(blocks), c.take<unsigned>(blocks)};
 }
 struct MeshAdjWs {
   u64* total;                     // the scan's grand total (two slots)
@@ -300,11 +301,6 @@ static inline MeshAdjWs mesh_adj_ws(WsCarver& c, long long nverts, long long nfa
   return MeshAdjWs{c.take<u64>(2), c.take<unsigned>(v1), c.take<unsigned>(v1), c.take<unsigned>((size_t)nfaces * 6),
                    c.take<unsigned>((v1 + 1023) / 1024)};
 }
-// Exclusive scan of a (and b, null: none) over n elements (mesh.hip): in place inside blocks of kScanBlock elements, the blocks'
-// totals to blk_a / blk_b and scanned there, the grand totals in 64 bits to total[0] / total[1].  Element i's scan value is
-// a[i] + blk_a[i / kScanBlock].  No atomics.
-constexpr int kScanBlock = 1024;          // elements per workgroup of the block scan: 256 threads x 4
-int run_scan(unsigned* a, unsigned* b, long long n, unsigned* blk_a, unsigned* blk_b, u64* total, hipStream_t s);
 size_t mesh_workspace_bytes(int n0, int n1, int n2);
 size_t mesh_adjacency_workspace_bytes(long long nverts, long long nfaces);
 // count: pack, count, scan; synchronises once to return the totals.  emit: verts (V, 3) and faces (F, 3) from the same workspace.
@@ -335,10 +331,10 @@ struct MeshLabelWs {
   u64* htotal;                    // their grand totals (two slots)
 };
 static inline MeshLabelWs mesh_label_ws(WsCarver& c, int n0, int n1, int n2) {
-  const size_t words = (size_t)n0 * n1 * ((n2 + 63) / 64), blocks = (words + kScanBlock - 1) / kScanBlock;
+  const size_t nwords = words(n0, n1, n2), blocks = (nwords + kScanBlock - 1) / kScanBlock;
   const size_t labels = kMeshLabelMax + 1, label_blocks = labels / kScanBlock;
-  return MeshLabelWs{c.take<MeshLabelRec>(1), c.take<u64>(words), c.take<u64>(words), c.take<u64>(words),
-                     c.take<unsigned>(words), c.take<unsigned>(words), c.take<unsigned char>(words), c.take<unsigned>(blocks),
+  return MeshLabelWs{c.take<MeshLabelRec>(1), c.take<u64>(nwords), c.take<u64>(nwords), c.take<u64>(nwords),
+                     c.take<unsigned>(nwords), c.take<unsigned>(nwords), c.take<unsigned char>(nwords), c.take<unsigned>(blocks),
                      c.take<unsigned>(blocks), c.take<unsigned>(labels), c.take<unsigned>(labels), c.take<unsigned>(label_blocks),
                      c.take<unsigned>(label_blocks), c.take<u64>(2)};
 }
@@ -436,9 +432,9 @@ struct SurfaceWs {
   unsigned *blk_a, *blk_b;                // per block: its total, then the exclusive scan of the totals
 };
 static inline SurfaceWs surface_ws(WsCarver& c, int n0, int n1, int n2) {
-  const size_t words = (size_t)n0 * n1 * ((n2 + 63) / 64), blocks = (words + kScanBlock - 1) / kScanBlock;
-  return SurfaceWs{c.take<SurfaceRec>(1), c.take<u64>(words), c.take<u64>(words), c.take<u64>(words), c.take<u64>(words),
-                   c.take<unsigned>(words), c.take<unsigned>(words), c.take<unsigned>(blocks), c.take<unsigned>(blocks)};
+  const size_t nwords = words(n0, n1, n2), blocks = (nwords + kScanBlock - 1) / kScanBlock;
+  return SurfaceWs{c.take<SurfaceRec>(1), c.take<u64>(nwords), c.take<u64>(nwords), c.take<u64>(nwords), c.take<u64>(nwords),
+                   c.take<unsigned>(nwords), c.take<unsigned>(nwords), c.take<unsigned>(blocks), c.take<unsigned>(blocks)};
 }
 struct SurfaceEmitWs {                    // on the extents of the box; used by one direction after the other
   unsigned char* sites;                   // 0 at the other mask's border voxels, 1 elsewhere: the EDT's input
@@ -510,6 +506,12 @@ template <typename V> __device__ __forceinline__ V wave_max(V v) {
     const V o = shfl_xor_settled(v, off);
     v = o > v ? o : v;
   }
+  return v;
+}
+// sum over the 64 lanes, in every lane: the butterfly 32, 16, .. 1, so a floating-point sum is a tree of one fixed shape
+template <typename V> __device__ __forceinline__ V wave_sum(V v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += shfl_xor_settled(v, off);
   return v;
 }
 

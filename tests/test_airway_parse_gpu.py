@@ -14,7 +14,8 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 Z = np.load(os.path.join(GOLDEN, "topology_known.npz"))
 NCASE = int(Z["ncase"])
 FLAT_KEYS = ("index", "fatherindex", "start", "has_end", "end", "member_count", "members")
-MORPH_SHAPES = [(1, 1, 1), (1, 1, 70), (3, 4, 5), (5, 6, 64), (4, 5, 65), (7, 9, 129), (20, 24, 134)]
+# (2, 3, 1) and (1, 2, 64): one word per row with and without a tail, and fewer words than one workgroup of the pack holds
+MORPH_SHAPES = [(1, 1, 1), (1, 1, 70), (3, 4, 5), (5, 6, 64), (4, 5, 65), (7, 9, 129), (20, 24, 134), (2, 3, 1), (1, 2, 64)]
 
 
 @pytest.fixture(scope="module")
