@@ -2,7 +2,8 @@
 every buffer (tests/guarded_alloc.py), as the sibling files run the other volume operations: three runs -- workspaces and outputs
 pre-filled with 0x00, 0xFF and seeded random bytes, inputs copied into red-zoned buffers -- must leave every red zone as it was,
 give the same bits, and equal the numpy oracle (tests/mesh_oracle.py), never another run of the code under test.  The shapes
-cross a 64-voxel word and fill more than one block of the scan."""
+cross a 64-voxel word and fill more than one block of the scan; one extraction (tests/volume_large_cases.py) fills more than
+one chunk of the scan's top level."""
 import numpy as np
 import pytest
 import torch
@@ -10,6 +11,7 @@ import torch
 from guarded_alloc import guard, three_fills
 
 import mesh_oracle as mo
+import volume_large_cases as vc
 
 pytestmark = pytest.mark.gpu
 
@@ -52,6 +54,14 @@ def bits(a):
 def test_extraction(A, shape):
     v, verts, faces = want(shape)
     got_v, got_f = three_fills(lambda: A.marching_cubes(dev(v)), "mesh extraction")
+    assert np.array_equal(bits(host(got_v)), bits(verts)) and np.array_equal(host(got_f), faces)
+
+
+def test_extraction_past_the_first_chunk_of_the_top_scan(A):
+    """``ragged`` of tests/volume_large_cases.py: 1026 block totals, so the top scan runs a second chunk whose last block is not
+    full.  The block-total arrays past their end and the 64-bit totals are what a wrong guard there would read uninitialised."""
+    v, verts, faces = vc.mesh("ragged")
+    got_v, got_f = three_fills(lambda: A.marching_cubes(dev(v), vc.LEVEL), "mesh extraction")
     assert np.array_equal(bits(host(got_v)), bits(verts)) and np.array_equal(host(got_f), faces)
 
 

@@ -48,7 +48,8 @@ def _same():
 # name -> (maker of (a, b), spacing)
 CASES = {
     "tail_3x4x130": (lambda: _random_pair((3, 4, 130), 0.5, 130), ANISO),             # rows of 3 words, 2-bit tail
-    "flat_40x30x1": (lambda: _random_pair((40, 30, 1), 0.6, 4030), ANISO),            # 1200 words: the scan crosses a block
+    # 1200 words: the scan crosses a block (the block scan only; the chunk loop of the top scan: tests/test_volume_large_gpu.py)
+    "flat_40x30x1": (lambda: _random_pair((40, 30, 1), 0.6, 4030), ANISO),
     "line_1x9x70": (lambda: _random_pair((1, 9, 70), 0.5, 1970), ANISO),
     "line_9x1x70": (lambda: _random_pair((9, 1, 70), 0.5, 9170), ANISO),
     "dense_20x20x70": (lambda: _random_pair((20, 20, 70), 0.8, 8070), UNIT),          # 35 534 distances, 3 distinct: ties
