@@ -1,5 +1,6 @@
 // extern "C" entry points of libseunet_hip.so (per-op part; the whole-network calls live in net.cpp).
-// Thin argument marshalling only: every function validates, forwards to a launcher and returns a status.
+// Thin argument marshalling only: every function validates, forwards to a launcher -- the convolutions and weight gradients
+// to their family's dispatch by kernel (conv.h run_conv / launch_conv_pack, wgrad.h run_wgrad) -- and returns a status.
 #include "seunet_common.h"
 #include "epilogue.h"
 #include "volume.h"
@@ -11,11 +12,19 @@ using namespace seunet;
 static inline Dims D(seunet_dims d) { return Dims{d.n, d.d, d.h, d.w}; }
 static inline hipStream_t S(seunet_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
-static int make_src(int nsrc, const void* const* src, const int* src_c, SrcList& l) {
-  SEUNET_CHECK(nsrc >= 1 && nsrc <= 3 && src && src_c, "bad source list");
+// the lists of a conv call; without pointers (channels_only, dst null) the form a *_supported query takes
+static int make_src(int nsrc, const void* const* src, const int* src_c, SrcList& l, bool channels_only = false) {
+  SEUNET_CHECK(nsrc >= 1 && nsrc <= 3 && (src || channels_only) && src_c, "bad source list");
   l = SrcList{};
   l.n = nsrc;
-  for (int i = 0; i < nsrc; ++i) { l.ptr[i] = src[i]; l.C[i] = src_c[i]; }
+  for (int i = 0; i < nsrc; ++i) { l.ptr[i] = src ? src[i] : nullptr; l.C[i] = src_c[i]; }
+  return 0;
+}
+static int make_dst(int ndst, void* const* dst, const int* dst_c, const int* dst_acc, DstList& dl) {
+  SEUNET_CHECK(ndst >= 1 && ndst <= 3 && dst_c, "bad destination list");
+  dl = DstList{};
+  dl.n = ndst;
+  for (int i = 0; i < ndst; ++i) { dl.ptr[i] = dst ? dst[i] : nullptr; dl.C[i] = dst_c[i]; dl.acc[i] = dst_acc ? dst_acc[i] : 0; }
   return 0;
 }
 
@@ -89,64 +98,63 @@ int seunet_unpack_cl(int dtype, const void* in, int c, float* out, seunet_dims d
   return launch_unpack_cl(dtype, in, c, out, D(dims), S(s));
 }
 
-size_t seunet_conv_wpack_bytes(int dtype, int taps, int cin, int cout) { return conv_wpack_bytes(dtype, taps, cin, cout); }
+// the forward convs: validate, build the lists, run on the kernel the entry point names (conv.h)
+static inline ConvKernel fwd_kernel(int impl) { return impl == SEUNET_CONV_NAIVE ? ConvKernel::Naive : ConvKernel::Tiled; }
+// one weight packed for kernel k: a list of one job
+static int pack_one(ConvKernel k, int dtype, const float* w, int taps, int cin_w, int cout_w, int tflip, int src_c, int dst_c,
+                    void* wpack, seunet_stream_t s) {
+  const ConvPackJob j{k, w, wpack, taps, cin_w, cout_w, tflip, src_c, dst_c};
+  return launch_conv_pack(dtype, &j, 1, S(s));
+}
+size_t seunet_conv_wpack_bytes(int dtype, int taps, int cin, int cout) { return conv_igemm_wpack_bytes(dtype, taps, cin, cout); }
 int seunet_conv_pack_weights(int dtype, const float* w, int taps, int cin, int cout, int tflip, void* wpack, seunet_stream_t s) {
   SEUNET_CHECK(w && wpack, "conv_pack_weights: null tensor");
-  return launch_conv_pack_weights(dtype, w, taps, cin, cout, tflip, wpack, S(s));
+  return pack_one(ConvKernel::Tiled, dtype, w, taps, cin, cout, tflip, 0, 0, wpack, s);
 }
 int seunet_conv_stats_slots(int impl, int taps, int dilation, seunet_dims dims) {
-  return impl == SEUNET_CONV_NAIVE ? epi_partials(D(dims)) : conv_stats_tiles(D(dims), taps, dilation);
+  return conv_slots(fwd_kernel(impl), D(dims), taps, dilation, 0, 0);
 }
 int seunet_conv3d_fwd(int dtype, int impl, int taps, int dilation, int nsrc, const void* const* src, const int* src_c, int cin,
                       const void* weights, int tflip, const float* bias, int ndst, void* const* dst, const int* dst_c,
                       const int* dst_acc, double* stats_partial, seunet_dims dims, seunet_stream_t s) {
-  SrcList sl;
+  SrcList sl; DstList dl;
   if (int e = make_src(nsrc, src, src_c, sl)) return e;
   SEUNET_CHECK(ndst >= 1 && ndst <= 3 && dst && dst_c && weights, "conv3d_fwd: bad destination list / weights");
-  DstList dl{};
-  dl.n = ndst;
-  for (int i = 0; i < ndst; ++i) { dl.ptr[i] = dst[i]; dl.C[i] = dst_c[i]; dl.acc[i] = dst_acc ? dst_acc[i] : 0; }
-  if (impl == SEUNET_CONV_NAIVE) {
-    if (int e = launch_conv_naive(dtype, taps, dilation, sl, cin, (const float*)weights, tflip, bias, dl, D(dims), S(s))) return e;
-    if (stats_partial) {
-      SEUNET_CHECK(ndst == 1, "conv3d_fwd: statistics need a single destination");
-      return launch_channel_stats(dtype, dst[0], dst_c[0], stats_partial, D(dims), S(s));
-    }
-    return 0;
+  if (int e = make_dst(ndst, dst, dst_c, dst_acc, dl)) return e;
+  const ConvKernel k = fwd_kernel(impl);   // weights: the PyTorch tensor (naive) or the packed one
+  if (int e = run_conv(k, dtype, taps, dilation, sl, cin, (const float*)weights, tflip, weights, bias, dl, stats_partial, D(dims), S(s)))
+    return e;
+  if (k == ConvKernel::Naive && stats_partial) {   // (the naive conv leaves the statistics to a pass of their own)
+    SEUNET_CHECK(ndst == 1, "conv3d_fwd: statistics need a single destination");
+    return launch_channel_stats(dtype, dst[0], dst_c[0], stats_partial, D(dims), S(s));
   }
-  return launch_conv_igemm(dtype, taps, dilation, sl, cin, weights, bias, dl, stats_partial, D(dims), S(s));
+  return 0;
 }
 int seunet_conv3d_stream_supported(int dtype, int dilation, int src_c, int dst_c) { return conv_stream_supported(dtype, 27, dilation, src_c, dst_c) ? 1 : 0; }
 size_t seunet_conv3d_stream_wpack_bytes(int src_c) { return conv_stream_wpack_bytes(src_c); }
 int seunet_conv3d_stream_slots(int dilation, seunet_dims dims) { return conv_stream_slots(D(dims), dilation); }
 int seunet_conv3d_stream_pack(int dtype, const float* w, int cin_w, int cout_w, int transpose_flip, int src_c, int dst_c, void* wpack,
                               seunet_stream_t s) {
-  return launch_conv_stream_pack(dtype, w, cin_w, cout_w, transpose_flip, src_c, dst_c, wpack, S(s));
+  return pack_one(ConvKernel::Stream, dtype, w, 27, cin_w, cout_w, transpose_flip, src_c, dst_c, wpack, s);
 }
 int seunet_conv3d_stream(int dtype, int dilation, const void* src, int src_c, const void* wpack, const float* bias, void* dst, int dst_c,
                          int dst_accumulate, double* stats_partial, seunet_dims dims, seunet_stream_t s) {
-  return launch_conv_stream(dtype, dilation, src, src_c, wpack, bias, dst, dst_c, dst_accumulate, stats_partial, D(dims), S(s));
-}
-static int make_dst(int ndst, void* const* dst, const int* dst_c, const int* dst_acc, DstList& dl) {
-  SEUNET_CHECK(ndst >= 1 && ndst <= 3 && dst_c, "bad destination list");
-  dl = DstList{};
-  dl.n = ndst;
-  for (int i = 0; i < ndst; ++i) { dl.ptr[i] = dst ? dst[i] : nullptr; dl.C[i] = dst_c[i]; dl.acc[i] = dst_acc ? dst_acc[i] : 0; }
-  return 0;
+  const SrcList sl{{src}, {src_c}, 1};
+  const DstList dl{{dst}, {dst_c}, {dst_accumulate}, 1};
+  return run_conv(ConvKernel::Stream, dtype, 27, dilation, sl, src_c, nullptr, 0, wpack, bias, dl, stats_partial, D(dims), S(s));
 }
 int seunet_conv3d_march_supported(int dtype, int dilation, int nsrc, const int* src_c, int ndst, const int* dst_c) {
-  if (nsrc < 1 || nsrc > 3 || ndst < 1 || ndst > 3 || !src_c || !dst_c) return 0;
-  SrcList sl{}; DstList dl{};
-  sl.n = nsrc; dl.n = ndst;
-  for (int i = 0; i < nsrc; ++i) sl.C[i] = src_c[i];
-  for (int i = 0; i < ndst; ++i) dl.C[i] = dst_c[i];
-  return conv_march_supported(dtype, 27, dilation, sl, dl) ? 1 : 0;
+  if (nsrc < 1 || nsrc > 3 || ndst < 1 || ndst > 3 || !src_c || !dst_c) return 0;   // (a query sets no error)
+  SrcList sl; DstList dl;
+  make_src(nsrc, nullptr, src_c, sl, true);
+  make_dst(ndst, nullptr, dst_c, nullptr, dl);
+  return conv_supported(ConvKernel::March, dtype, 27, dilation, sl, dl) ? 1 : 0;
 }
 size_t seunet_conv3d_march_wpack_bytes(int cin, int cout) { return conv_march_wpack_bytes(cin, cout); }
 int seunet_conv3d_march_slots(int dilation, int cin, int cout, seunet_dims dims) { return conv_march_slots(D(dims), dilation, cin, cout); }
 int seunet_conv3d_march_pack(int dtype, const float* w, int cin_w, int cout_w, int transpose_flip, int cin, int cout, void* wpack,
                              seunet_stream_t s) {
-  return launch_conv_march_pack(dtype, w, cin_w, cout_w, transpose_flip, cin, cout, wpack, S(s));
+  return pack_one(ConvKernel::March, dtype, w, 27, cin_w, cout_w, transpose_flip, cin, cout, wpack, s);
 }
 int seunet_conv3d_march(int dtype, int dilation, int nsrc, const void* const* src, const int* src_c, const void* wpack, const float* bias,
                         int ndst, void* const* dst, const int* dst_c, const int* dst_accumulate, double* stats_partial, seunet_dims dims,
@@ -155,7 +163,7 @@ int seunet_conv3d_march(int dtype, int dilation, int nsrc, const void* const* sr
   if (int e = make_src(nsrc, src, src_c, sl)) return e;
   SEUNET_CHECK(dst != nullptr, "conv3d_march: null destination list");
   if (int e = make_dst(ndst, dst, dst_c, dst_accumulate, dl)) return e;
-  return launch_conv_march(dtype, dilation, sl, wpack, bias, dl, stats_partial, D(dims), S(s));
+  return run_conv(ConvKernel::March, dtype, 27, dilation, sl, sl.total(), nullptr, 0, wpack, bias, dl, stats_partial, D(dims), S(s));
 }
 int seunet_conv3d_wgrad_stream_supported(int dtype, int dilation, int x_c, int dy_c) { return wgrad_stream_supported(dtype, 27, dilation, x_c, dy_c) ? 1 : 0; }
 size_t seunet_conv3d_wgrad_stream_workspace_bytes(int x_c, int dy_c, int dilation, seunet_dims dims) {

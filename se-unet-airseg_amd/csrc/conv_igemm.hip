@@ -29,7 +29,7 @@
 //                 optionally += (gradient accumulation) and split over up to three destination tensors (backward of
 //                 the fused concatenation)
 //   grid          blockIdx.x is remapped so that each XCD (private L2) owns a contiguous run of tiles
-#include "seunet_common.h"
+#include "conv.h"
 #include "lds_dma.h"
 #include "mfma.h"
 
@@ -590,12 +590,6 @@ __device__ __forceinline__ void conv_pack_body(const float* __restrict__ w, int 
     out[i] = from_f32<T>(v);
   }
 }
-template <typename T>
-__global__ void conv_pack_kernel(const float* __restrict__ w, int taps, int cin_w, int cout_w, int tflip,
-                                 T* __restrict__ out, int cin_e, int cout_e, int nchunks, int ncol,
-                                 long long total) {
-  conv_pack_body<T>(w, taps, cin_w, cout_w, tflip, out, cin_e, cout_e, nchunks, ncol, total);
-}
 // all the weight tensors of a forward (or backward) pass in one launch: blockIdx.y = list entry
 struct PackEntry { const float* w; void* out; int taps, cin_w, cout_w, tflip, cin_e, cout_e, nchunks, ncol; long long total; };
 struct PackList { PackEntry e[24]; };
@@ -614,40 +608,26 @@ static constexpr int CV_NCOL = 32;
 unsigned long long* g_conv_debug = nullptr;   // set by seunet_debug_set_buffer (diagnostic builds)
 static inline int conv_kc(int dtype) { return dtype_size(dtype) == 2 ? 16 : 8; }
 
-size_t conv_wpack_bytes(int dtype, int taps, int cin, int cout) {
+size_t conv_igemm_wpack_bytes(int dtype, int taps, int cin, int cout) {
   const int ntiles = cdiv(cout, CV_NCOL), nchunks = cdiv(cin, conv_kc(dtype));
   return (size_t)ntiles * nchunks * taps * CV_NCOL * 32;
 }
 
-int launch_conv_pack_weights(int dtype, const float* w, int taps, int cin_w, int cout_w, int tflip,
-                             void* wpack, hipStream_t s) {
-  SEUNET_CHECK(taps == 27 || taps == 1, "conv pack: taps=%d unsupported", taps);
-  const int cin_e = tflip ? cout_w : cin_w, cout_e = tflip ? cin_w : cout_w;
-  const int nchunks = cdiv(cin_e, conv_kc(dtype));
-  const long long total = (long long)(conv_wpack_bytes(dtype, taps, cin_e, cout_e) / dtype_size(dtype));
-  const int grid = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
-  SEUNET_DTYPE_SWITCH(dtype, conv_pack_kernel<T><<<grid, 256, 0, s>>>(w, taps, cin_w, cout_w, tflip, (T*)wpack, cin_e, cout_e, nchunks, CV_NCOL, total));
-  SEUNET_LAUNCH_CHECK();
-  return 0;
-}
-
-int launch_conv_pack_weights_multi(int dtype, const ConvPackJob* jobs, int n, hipStream_t s) {
-  for (int base = 0; base < n; base += 24) {
+int launch_conv_igemm_pack(int dtype, const ConvPackJob* jobs, int n, hipStream_t s) {
+  return conv_pack_chunks(jobs, n, 24, [&](const ConvPackJob* job, int m) {
     PackList l{};
-    const int m = n - base < 24 ? n - base : 24;
     for (int i = 0; i < m; ++i) {
-      const ConvPackJob& j = jobs[base + i];
+      const ConvPackJob& j = job[i];
       SEUNET_CHECK(j.taps == 27 || j.taps == 1, "conv pack: taps=%d unsupported", j.taps);
       PackEntry& e = l.e[i];
       e.w = j.w; e.out = j.wpack; e.taps = j.taps; e.cin_w = j.cin_w; e.cout_w = j.cout_w; e.tflip = j.tflip;
       e.cin_e = j.tflip ? j.cout_w : j.cin_w; e.cout_e = j.tflip ? j.cin_w : j.cout_w;
       e.ncol = CV_NCOL; e.nchunks = cdiv(e.cin_e, conv_kc(dtype));
-      e.total = (long long)(conv_wpack_bytes(dtype, j.taps, e.cin_e, e.cout_e) / dtype_size(dtype));
+      e.total = (long long)(conv_igemm_wpack_bytes(dtype, j.taps, e.cin_e, e.cout_e) / dtype_size(dtype));
     }
     SEUNET_DTYPE_SWITCH(dtype, conv_pack_multi_kernel<T><<<dim3(64, m), 256, 0, s>>>(l));
-  }
-  SEUNET_LAUNCH_CHECK();
-  return 0;
+    return 0;
+  });
 }
 
 // partial-stat slots per sample == workgroups per sample (tiles x parity classes of the dilation)
@@ -677,37 +657,38 @@ static int launch_t(int taps, int dil, const ConvKArgs& a, dim3 grid, hipStream_
   return launch_one<T, 27, 2>(a, grid, s);
 }
 
-static int check_lists(const SrcList& src, const DstList& dst) {
+// the lists, checked, as both kernels of this file take them: the channel concatenation of the sources, the channel split of
+// the output, the extents
+static int conv_list_args(const SrcList& src, int cin_logical, const DstList& dst, Dims d, ConvKArgs& a) {
   SEUNET_CHECK(src.n >= 1 && src.n <= 3 && dst.n >= 1 && dst.n <= 3, "conv: 1..3 sources/destinations");
   for (int i = 0; i < src.n; ++i)
     SEUNET_CHECK(src.C[i] > 0 && src.C[i] % 8 == 0 && src.ptr[i], "conv: source %d needs C %% 8 == 0 (got %d)", i, src.C[i]);
   for (int i = 0; i < dst.n; ++i)
     SEUNET_CHECK(dst.C[i] > 0 && dst.C[i] % 8 == 0, "conv: destination %d needs C %% 8 == 0 (got %d)", i, dst.C[i]);
-  return 0;
-}
-
-int launch_conv_igemm(int dtype, int taps, int dil, const SrcList& src, int cin_logical, const void* wpack,
-                      const float* bias, const DstList& dst, double* stats, Dims d, hipStream_t s) {
-  if (int e = check_lists(src, dst)) return e;
   SEUNET_CHECK(cin_logical >= 1 && cin_logical <= src.total(), "conv: cin=%d exceeds the source channels %d", cin_logical, src.total());
-  SEUNET_CHECK(taps == 27 || taps == 1, "conv: taps=%d unsupported", taps);
-  SEUNET_CHECK(taps == 1 || dil == 1 || dil == 2, "conv: dilation %d unsupported", dil);
-  ConvKArgs a{};
   a.src0 = src.ptr[0]; a.srcC0 = src.C[0];
   a.src1 = src.n > 1 ? src.ptr[1] : nullptr; a.srcC1 = src.n > 1 ? src.C[1] : 0;
   a.src2 = src.n > 2 ? src.ptr[2] : nullptr; a.srcC2 = src.n > 2 ? src.C[2] : 0;
   a.cin = cin_logical;
   a.cum1 = src.n > 1 ? src.C[0] : src.total();
   a.cum2 = src.n > 2 ? src.C[0] + src.C[1] : src.total();
-  a.wpack = wpack; a.bias = bias;
   a.dst0 = dst.ptr[0]; a.dstC0 = dst.C[0]; a.dacc0 = dst.acc[0];
   a.dst1 = dst.n > 1 ? dst.ptr[1] : nullptr; a.dstC1 = dst.n > 1 ? dst.C[1] : 0; a.dacc1 = dst.n > 1 ? dst.acc[1] : 0;
   a.dst2 = dst.n > 2 ? dst.ptr[2] : nullptr; a.dstC2 = dst.n > 2 ? dst.C[2] : 0; a.dacc2 = dst.n > 2 ? dst.acc[2] : 0;
   a.cout = dst.total();
   a.dcum1 = dst.n > 1 ? dst.C[0] : a.cout;
   a.dcum2 = dst.n > 2 ? dst.C[0] + dst.C[1] : a.cout;
-  a.stats = stats;
   a.N = d.N; a.D = d.D; a.H = d.H; a.W = d.W;
+  return 0;
+}
+
+int launch_conv_igemm(int dtype, int taps, int dil, const SrcList& src, int cin_logical, const void* wpack,
+                      const float* bias, const DstList& dst, double* stats, Dims d, hipStream_t s) {
+  ConvKArgs a{};
+  if (int e = conv_list_args(src, cin_logical, dst, d, a)) return e;
+  SEUNET_CHECK(taps == 27 || taps == 1, "conv: taps=%d unsupported", taps);
+  SEUNET_CHECK(taps == 1 || dil == 1 || dil == 2, "conv: dilation %d unsupported", dil);
+  a.wpack = wpack; a.bias = bias; a.stats = stats;
   const int st = taps == 27 ? dil : 1;
   a.tx = cdiv(cdiv(d.W, st), CV_TX); a.ty = cdiv(cdiv(d.H, st), CV_TY); a.tz = cdiv(cdiv(d.D, st), CV_TZ);
   a.nchunks = cdiv(a.cin, conv_kc(dtype));
@@ -781,23 +762,9 @@ __global__ void conv_naive_kernel(ConvKArgs a, const float* __restrict__ w, int 
 // tensors may be zero-padded beyond it (the packed network input).
 int launch_conv_naive(int dtype, int taps, int dil, const SrcList& src, int cin_logical, const float* w,
                       int tflip, const float* bias, const DstList& dst, Dims d, hipStream_t s) {
-  if (int e = check_lists(src, dst)) return e;
-  SEUNET_CHECK(cin_logical >= 1 && cin_logical <= src.total(), "conv: cin=%d exceeds the source channels %d", cin_logical, src.total());
   ConvKArgs a{};
-  a.src0 = src.ptr[0]; a.srcC0 = src.C[0];
-  a.src1 = src.n > 1 ? src.ptr[1] : nullptr; a.srcC1 = src.n > 1 ? src.C[1] : 0;
-  a.src2 = src.n > 2 ? src.ptr[2] : nullptr; a.srcC2 = src.n > 2 ? src.C[2] : 0;
-  a.cin = cin_logical;
-  a.cum1 = src.n > 1 ? src.C[0] : src.total();
-  a.cum2 = src.n > 2 ? src.C[0] + src.C[1] : src.total();
+  if (int e = conv_list_args(src, cin_logical, dst, d, a)) return e;
   a.bias = bias;
-  a.dst0 = dst.ptr[0]; a.dstC0 = dst.C[0]; a.dacc0 = dst.acc[0];
-  a.dst1 = dst.n > 1 ? dst.ptr[1] : nullptr; a.dstC1 = dst.n > 1 ? dst.C[1] : 0; a.dacc1 = dst.n > 1 ? dst.acc[1] : 0;
-  a.dst2 = dst.n > 2 ? dst.ptr[2] : nullptr; a.dstC2 = dst.n > 2 ? dst.C[2] : 0; a.dacc2 = dst.n > 2 ? dst.acc[2] : 0;
-  a.cout = dst.total();
-  a.dcum1 = dst.n > 1 ? dst.C[0] : a.cout;
-  a.dcum2 = dst.n > 2 ? dst.C[0] + dst.C[1] : a.cout;
-  a.N = d.N; a.D = d.D; a.H = d.H; a.W = d.W;
   const long long total = (long long)d.N * d.vox() * a.cout;
   const int grid = (int)((total + 255) / 256 > 65535 ? 65535 : (total + 255) / 256);
   const int cin_w = tflip ? a.cout : cin_logical;  // the PyTorch weight's Cin extent

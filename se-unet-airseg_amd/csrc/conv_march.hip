@@ -27,7 +27,7 @@
 //   * InstanceNorm partial sums per lane in f32 inside a plane, in f64 (LDS slots) across the march and across lanes, one
 //     record per workgroup.
 // One workgroup per CU: a 4 x 128^3 batch at 64 -> 32 channels is exactly 256 marches of 128 planes.
-#include "seunet_common.h"
+#include "conv.h"
 #include "lds_dma.h"
 #include "mfma.h"
 
@@ -487,9 +487,6 @@ __device__ __forceinline__ void conv_march_pack_body(const MarchPackArgs& p, uns
     out[j] = from_f32<T>(v);
   }
 }
-template <typename T>
-__global__ void __launch_bounds__(64)
-conv_march_pack_kernel(MarchPackArgs p) { conv_march_pack_body<T>(p, blockIdx.x); }
 
 // all the weight tensors of a pass in one launch: blockIdx.y = list entry
 struct MarchPackList { MarchPackArgs e[12]; int blocks[12]; };
@@ -560,41 +557,28 @@ int conv_march_slots(Dims d, int dil, int cin_e, int cout_e) {
 }
 
 // one packing job, validated: the kernel's arguments and its workgroup count
-static int march_pack_args(int dtype, const float* w, int cin_w, int cout_w, int tflip, int cin_e, int cout_e, void* wpack,
-                           MarchPackArgs& p, int& blocks) {
+// (the job's src_c -> dst_c are the conv's effective channels, cin_e -> cout_e)
+static int march_pack_args(int dtype, const ConvPackJob& j, MarchPackArgs& p, int& blocks) {
   MarchCfg c;
-  SEUNET_CHECK(march_cfg(dtype, 27, 1, cin_e, cout_e, 0, c) && w && wpack, "conv_march_pack: unsupported shape (%d -> %d channels)", cin_e, cout_e);
-  const int we_in = tflip ? cout_w : cin_w, we_out = tflip ? cin_w : cout_w;
-  SEUNET_CHECK(we_in <= cin_e && we_out <= cout_e, "conv_march_pack: weight (%d -> %d) exceeds the tensors (%d -> %d)", we_in, we_out, cin_e, cout_e);
-  p = MarchPackArgs{w, wpack, cin_w, cout_w, tflip, we_in, we_out, c.ks};
-  blocks = (cout_e / 16) * 27 * c.ks;
+  SEUNET_CHECK(march_cfg(dtype, 27, 1, j.src_c, j.dst_c, 0, c) && j.w && j.wpack, "conv_march_pack: unsupported shape (%d -> %d channels)", j.src_c, j.dst_c);
+  const int we_in = j.tflip ? j.cout_w : j.cin_w, we_out = j.tflip ? j.cin_w : j.cout_w;
+  SEUNET_CHECK(we_in <= j.src_c && we_out <= j.dst_c, "conv_march_pack: weight (%d -> %d) exceeds the tensors (%d -> %d)", we_in, we_out, j.src_c, j.dst_c);
+  p = MarchPackArgs{j.w, j.wpack, j.cin_w, j.cout_w, j.tflip, we_in, we_out, c.ks};
+  blocks = (j.dst_c / 16) * 27 * c.ks;
   return 0;
 }
-int launch_conv_march_pack(int dtype, const float* w, int cin_w, int cout_w, int tflip, int cin_e, int cout_e, void* wpack, hipStream_t s) {
-  MarchPackArgs p{};
-  int blocks = 0;
-  if (int e = march_pack_args(dtype, w, cin_w, cout_w, tflip, cin_e, cout_e, wpack, p, blocks)) return e;
-  if (dtype == SEUNET_F16) conv_march_pack_kernel<f16_t><<<blocks, 64, 0, s>>>(p);
-  else conv_march_pack_kernel<bf16_t><<<blocks, 64, 0, s>>>(p);
-  SEUNET_LAUNCH_CHECK();
-  return 0;
-}
-
-int launch_conv_march_pack_multi(int dtype, const MarchPackJob* jobs, int n, hipStream_t s) {
-  for (int base = 0; base < n; base += 12) {
+int launch_conv_march_pack(int dtype, const ConvPackJob* jobs, int n, hipStream_t s) {
+  return conv_pack_chunks(jobs, n, 12, [&](const ConvPackJob* job, int m) {
     MarchPackList l{};
-    const int m = n - base < 12 ? n - base : 12;
     int maxb = 0;
     for (int i = 0; i < m; ++i) {
-      const MarchPackJob& j = jobs[base + i];
-      if (int e = march_pack_args(dtype, j.w, j.cin_w, j.cout_w, j.tflip, j.cin_e, j.cout_e, j.wpack, l.e[i], l.blocks[i])) return e;
+      if (int e = march_pack_args(dtype, job[i], l.e[i], l.blocks[i])) return e;
       maxb = l.blocks[i] > maxb ? l.blocks[i] : maxb;
     }
     if (dtype == SEUNET_F16) conv_march_pack_multi_kernel<f16_t><<<dim3(maxb, m), 64, 0, s>>>(l);
     else conv_march_pack_multi_kernel<bf16_t><<<dim3(maxb, m), 64, 0, s>>>(l);
-  }
-  SEUNET_LAUNCH_CHECK();
-  return 0;
+    return 0;
+  });
 }
 
 template <typename T, int KS, int NGW, int RYW, int DIL, int MODE, bool BUF>

@@ -27,7 +27,7 @@
 // Dilation 2 marches each z-parity class separately (planes z, z+2, ...) and keeps the natural layout in the plane (halo 2).
 // LDS image of a plane: planar [16-B piece of the channels][voxel of the halo patch][16 B]; fragment reads are ds_read_b128
 // of consecutive voxels (conflict-free), DMA instructions write 1 KB contiguous.
-#include "seunet_common.h"
+#include "conv.h"
 #include "lds_dma.h"
 #include "mfma.h"
 
@@ -529,9 +529,6 @@ __device__ __forceinline__ void conv_stream_pack_body(const StreamPackArgs& p, i
     out[j] = from_f32<T>(v);
   }
 }
-template <typename T>
-__global__ void __launch_bounds__(64)
-conv_stream_pack_kernel(StreamPackArgs p) { conv_stream_pack_body<T>(p, blockIdx.x); }
 // every streaming layer of a pass in one launch: blockIdx.y = layer
 template <typename T>
 __global__ void __launch_bounds__(64)
@@ -548,7 +545,7 @@ static int stream_variant(int dtype, int taps, int dil, int src_c, int dst_c) {
 }
 bool conv_stream_supported(int dtype, int taps, int dil, int src_c, int dst_c) { return stream_variant(dtype, taps, dil, src_c, dst_c) != 0; }
 
-size_t conv_stream_wpack_bytes(int src_c) { return (size_t)27 * 64 * 16; (void)src_c; }
+size_t conv_stream_wpack_bytes(int) { return (size_t)27 * 64 * 16; }
 
 // The launch cut of one sample: patches, z segments per parity class, output planes per segment.  conv_stream_slots() and
 // launch_conv_stream() both take it from stream_cut(); the grid and the statistics records follow from it alone.
@@ -583,36 +580,25 @@ static StreamCut stream_cut(Dims d, int dil) {
 }
 int conv_stream_slots(Dims d, int dil) { return stream_cut(d, dil).slots(); }
 
-static int stream_pack_args(int dtype, const float* w, int cin_w, int cout_w, int tflip, int src_c, int dst_c, void* wpack, StreamPackArgs& p) {
-  const int cin_e = tflip ? cout_w : cin_w, cout_e = tflip ? cin_w : cout_w;
-  const int var = stream_variant(dtype, 27, 1, src_c, dst_c);
-  SEUNET_CHECK(var != 0 && w && wpack, "conv_stream_pack: unsupported shape (%d -> %d channels)", src_c, dst_c);
-  SEUNET_CHECK(cin_e <= src_c && cout_e <= dst_c, "conv_stream_pack: weight (%d -> %d) exceeds the tensors (%d -> %d)", cin_e, cout_e, src_c, dst_c);
-  p = StreamPackArgs{w, wpack, cin_w, cout_w, tflip, cin_e, cout_e, var == 1 ? 32 : 16, (var == 3 || var == 4) ? 1 : 0, src_c / 8};
-  return 0;
-}
-int launch_conv_stream_pack(int dtype, const float* w, int cin_w, int cout_w, int tflip, int src_c, int dst_c, void* wpack, hipStream_t s) {
-  StreamPackArgs p{};
-  if (int e = stream_pack_args(dtype, w, cin_w, cout_w, tflip, src_c, dst_c, wpack, p)) return e;
-  if (dtype == SEUNET_F16) conv_stream_pack_kernel<f16_t><<<27, 64, 0, s>>>(p);
-  else conv_stream_pack_kernel<bf16_t><<<27, 64, 0, s>>>(p);
-  SEUNET_LAUNCH_CHECK();
+static int stream_pack_args(int dtype, const ConvPackJob& j, StreamPackArgs& p) {
+  const int cin_e = j.tflip ? j.cout_w : j.cin_w, cout_e = j.tflip ? j.cin_w : j.cout_w;
+  const int var = stream_variant(dtype, 27, 1, j.src_c, j.dst_c);
+  SEUNET_CHECK(var != 0 && j.w && j.wpack, "conv_stream_pack: unsupported shape (%d -> %d channels)", j.src_c, j.dst_c);
+  SEUNET_CHECK(cin_e <= j.src_c && cout_e <= j.dst_c, "conv_stream_pack: weight (%d -> %d) exceeds the tensors (%d -> %d)", cin_e, cout_e, j.src_c, j.dst_c);
+  p = StreamPackArgs{j.w, j.wpack, j.cin_w, j.cout_w, j.tflip, cin_e, cout_e, var == 1 ? 32 : 16, (var == 3 || var == 4) ? 1 : 0, j.src_c / 8};
   return 0;
 }
 // all streaming layers of a pass in one launch (the weights change every step; seven 6-us launches per step otherwise)
-int launch_conv_stream_pack_multi(int dtype, const StreamPackJob* jobs, int n, hipStream_t s) {
-  for (int i0 = 0; i0 < n; i0 += ST_PACK_MAX) {
+int launch_conv_stream_pack(int dtype, const ConvPackJob* jobs, int n, hipStream_t s) {
+  return conv_pack_chunks(jobs, n, ST_PACK_MAX, [&](const ConvPackJob* job, int m) {
     StreamPackList l{};
-    l.n = n - i0 < ST_PACK_MAX ? n - i0 : ST_PACK_MAX;
-    for (int i = 0; i < l.n; ++i) {
-      const StreamPackJob& j = jobs[i0 + i];
-      if (int e = stream_pack_args(dtype, j.w, j.cin_w, j.cout_w, j.tflip, j.src_c, j.dst_c, j.wpack, l.j[i])) return e;
-    }
-    if (dtype == SEUNET_F16) conv_stream_pack_multi_kernel<f16_t><<<dim3(27, l.n), 64, 0, s>>>(l);
-    else conv_stream_pack_multi_kernel<bf16_t><<<dim3(27, l.n), 64, 0, s>>>(l);
-    SEUNET_LAUNCH_CHECK();
-  }
-  return 0;
+    l.n = m;
+    for (int i = 0; i < m; ++i)
+      if (int e = stream_pack_args(dtype, job[i], l.j[i])) return e;
+    if (dtype == SEUNET_F16) conv_stream_pack_multi_kernel<f16_t><<<dim3(27, m), 64, 0, s>>>(l);
+    else conv_stream_pack_multi_kernel<bf16_t><<<dim3(27, m), 64, 0, s>>>(l);
+    return 0;
+  });
 }
 
 template <typename T, int CIN, int COUTP, bool XFOLD, int DIL, bool FWD, bool DACC>

@@ -175,16 +175,6 @@ inline bool march_level(const Dims& d, int dil) {
   return d.W >= 32 && (d.vox() >= 48LL * 48 * 48 || (dil == 2 && d.vox() >= 32LL * 32 * 32));
 }
 
-// statistics slots per sample of a forward conv on kernel k
-int conv_slots(ConvKernel k, const Dims& dm, int taps, int dil, int cin, int cout) {
-  switch (k) {
-    case ConvKernel::Stream: return conv_stream_slots(dm, dil);
-    case ConvKernel::March: return conv_march_slots(dm, dil, cin, cout);
-    case ConvKernel::Naive: return epi_partials(dm);
-    default: return conv_stats_tiles(dm, taps, dil);
-  }
-}
-
 // ---------------------------------------------------------------------------------------------------
 // workspace plan
 // ---------------------------------------------------------------------------------------------------
@@ -258,29 +248,21 @@ struct Plan {
     // small-channel 3x3x3 layers with one source tensor (ec1 / ec2 / ec3 / dc6 at width 1) run on the streaming kernel
     // (the streaming kernels address one sample through 32-bit buffer offsets; a sample of 4 GB or more takes the general kernels)
     const bool stream_ok = o.kind == OP_GATED && x.n == 1 && (long long)dm.D * dm.H * dm.W * 32 * (long long)esz < 0xFFFFFFFFll;
-    const bool stream_f = stream_ok && conv_stream_supported(d.dtype, 27, o.dil, c0, r.cout);
-    const bool stream_d = stream_ok && conv_stream_supported(d.dtype, 27, o.dil, r.cout, c0);
+    const bool stream_f = stream_ok && conv_supported(ConvKernel::Stream, d.dtype, 27, o.dil, x, y);
+    const bool stream_d = stream_ok && conv_supported(ConvKernel::Stream, d.dtype, 27, o.dil, gy, gx);
     // 32 / 64-input-channel 3x3x3 layers of the levels that fill the chip with 32-voxel rows run on the marching kernel
     // (one workgroup per CU, weights in registers): dc5, dc4, ec4..ec6 and the data gradients of those and of dc3
     const bool march_ok = o.kind == OP_GATED && !stream_f && march_level(dm, o.dil);
     r.fwd = stream_f ? ConvKernel::Stream
-          : march_ok && conv_march_supported(d.dtype, 27, o.dil, x, y) ? ConvKernel::March : ConvKernel::Tiled;
+          : march_ok && conv_supported(ConvKernel::March, d.dtype, 27, o.dil, x, y) ? ConvKernel::March : ConvKernel::Tiled;
     r.dgrad = stream_d ? ConvKernel::Stream
-            : march_ok && conv_march_supported(d.dtype, 27, o.dil, gy, gx) ? ConvKernel::March : ConvKernel::Tiled;
+            : march_ok && conv_supported(ConvKernel::March, d.dtype, 27, o.dil, gy, gx) ? ConvKernel::March : ConvKernel::Tiled;
     r.wgrad = stream_ok && wgrad_stream_supported(d.dtype, 27, o.dil, c0, r.cout)
                   ? ConvKernel::Stream : wgrad_kernel(d.dtype, r.taps, o.dil, x, r.cin, r.cout, dm, src_dist(i));
     if (o.xname) {   // the x-branch: 1x1x1 conv of the 8-channel padded input
       const SrcList xs{{}, {8}, 1};
       r.x_fwd = ConvKernel::Tiled;
       r.x_wgrad = wgrad_kernel(d.dtype, 1, 1, xs, d.in_channel, r.cout, dm, 0);
-    }
-  }
-  // bytes of a packed weight for kernel k: src_c channels in the single source tensor (Stream), cin -> cout channels
-  size_t wpack_bytes(ConvKernel k, int taps, int src_c, int cin, int cout) const {
-    switch (k) {
-      case ConvKernel::Stream: return conv_stream_wpack_bytes(src_c);
-      case ConvKernel::March: return conv_march_wpack_bytes(cin, cout);
-      default: return conv_wpack_bytes(d.dtype, taps, cin, cout);   // (the naive kernels read the PyTorch weight: same slot)
     }
   }
 
@@ -333,8 +315,8 @@ struct Plan {
       r.mean = take((size_t)d.batch * r.cout * 4, "mean", o.name);
       r.rstd = take((size_t)d.batch * r.cout * 4, "rstd", o.name);
       route(i);
-      r.wp_f = take(wpack_bytes(r.fwd, r.taps, C[o.src[0]], r.cin, r.cout), "wp_f", o.name);
-      if (r.need_dgrad) r.wp_d = take(wpack_bytes(r.dgrad, r.taps, r.cout, r.cout, r.cin), "wp_d", o.name);
+      r.wp_f = take(conv_wpack_bytes(r.fwd, d.dtype, r.taps, C[o.src[0]], r.cin, r.cout), "wp_f", o.name);
+      if (r.need_dgrad) r.wp_d = take(conv_wpack_bytes(r.dgrad, d.dtype, r.taps, r.cout, r.cout, r.cin), "wp_d", o.name);
       slots_max = std::max(slots_max, conv_slots(r.fwd, dm, r.taps, o.dil, r.cin, r.cout));
       if (r.wgrad == ConvKernel::Stream) wg_max = std::max(wg_max, wgrad_stream_workspace_bytes(C[o.src[0]], r.cout, o.dil, dm));
       wg_max = std::max(wg_max, wgrad_workspace_bytes(r.taps, r.cin, r.cout));
@@ -347,7 +329,7 @@ struct Plan {
           xmom_max = std::max(xmom_max, (size_t)d.batch * xbranch_moment_slots(dm) * 5 * 8);
         } else {
           r.raw2 = take(act, "raw", o.xname);
-          r.wp_x = take(wpack_bytes(r.x_fwd, 1, 8, d.in_channel, r.cout), "wp_f", o.xname);
+          r.wp_x = take(conv_wpack_bytes(r.x_fwd, d.dtype, 1, 8, d.in_channel, r.cout), "wp_f", o.xname);
           gx_max = std::max(gx_max, act);
           wg_max = std::max(wg_max, wgrad_workspace_bytes(1, d.in_channel, r.cout));
         }
@@ -443,27 +425,13 @@ struct Exec {
     return l;
   }
 
-  // one forward or data-gradient conv on kernel k.  w: the PyTorch weight (naive kernels, tflip 1 = data gradient); wp: the weight
-  // packed for k by pack_all_weights
-  int run_conv(ConvKernel k, int taps, int dil, const SrcList& src, int cin, const float* w, int tflip, const void* wp,
-               const float* bias, const DstList& dst, double* stats, const Dims& dm) const {
-    switch (k) {
-      case ConvKernel::Naive: return launch_conv_naive(p.d.dtype, taps, dil, src, cin, w, tflip, bias, dst, dm, s);
-      case ConvKernel::Tiled: return launch_conv_igemm(p.d.dtype, taps, dil, src, cin, wp, bias, dst, stats, dm, s);
-      case ConvKernel::Stream:
-        return launch_conv_stream(p.d.dtype, dil, src.ptr[0], src.C[0], wp, bias, dst.ptr[0], dst.C[0], dst.acc[0], stats, dm, s);
-      case ConvKernel::March: return launch_conv_march(p.d.dtype, dil, src, wp, bias, dst, stats, dm, s);
-      default: return fail("net: internal: kernel %d runs no convolution", (int)k);
-    }
-  }
-
   // conv (+ InstanceNorm statistics) of one block: raw <- conv(src), (mean, rstd) <- stats(raw)
   int conv_and_stats(const char* nm, ConvKernel k, int taps, int dil, const SrcList& src, int cin, const float* w,
                      const float* bias, size_t wp_off, size_t raw_off, int cout, size_t mean_off, size_t rstd_off, const Dims& dm) {
     DstList dst{};
     dst.n = 1; dst.ptr[0] = at(raw_off); dst.C[0] = cout; dst.acc[0] = 0;
     mark("conv_fwd:", nm);
-    if (int e = run_conv(k, taps, dil, src, cin, w, 0, at(wp_off), bias, dst, dat(p.stats), dm)) return e;
+    if (int e = run_conv(k, p.d.dtype, taps, dil, src, cin, w, 0, at(wp_off), bias, dst, dat(p.stats), dm, s)) return e;
     if (k == ConvKernel::Naive) {   // (the naive conv leaves the statistics to a pass of their own)
       mark("stats");
       if (int e = launch_channel_stats(p.d.dtype, at(raw_off), cout, dat(p.stats), dm, s)) return e;
@@ -537,20 +505,15 @@ struct Exec {
     return 0;
   }
 
-  // every conv weight of a pass repacked into its MFMA layout by one or two launches (the parameters change every step)
+  // every conv weight of a pass repacked into its MFMA layout by one launch per kernel (the parameters change every step)
   int pack_all_weights(bool dgrad) {
     if (p.d.conv_impl == SEUNET_CONV_NAIVE) return 0;
     mark("pack_w");
     std::vector<ConvPackJob> jobs;
-    std::vector<MarchPackJob> mjobs;
-    std::vector<StreamPackJob> sjobs;
     // PyTorch weight w (cout, cin, k,k,k), read transposed / mirrored by the data gradient; src_c -> dst_c: the channels of the
     // conv's source and destination tensors
-    const int tf = dgrad ? 1 : 0;
     auto add = [&](ConvKernel k, const float* w, size_t wp, int taps, int cin, int cout, int src_c, int dst_c) {
-      if (k == ConvKernel::Stream) sjobs.push_back({w, at(wp), cin, cout, tf, src_c, dst_c});
-      else if (k == ConvKernel::March) mjobs.push_back({w, at(wp), cin, cout, tf, src_c, dst_c});
-      else jobs.push_back({w, at(wp), taps, cin, cout, tf});
+      jobs.push_back({k, w, at(wp), taps, cin, cout, dgrad ? 1 : 0, src_c, dst_c});
     };
     for (int i = 0; i < kNumOps; ++i) {
       const OpDesc& o = kOps[i];
@@ -564,11 +527,7 @@ struct Exec {
         add(r.dgrad, par(i, P_CONV1_W), r.wp_d, r.taps, r.cin, r.cout, r.cout, ctot);
       }
     }
-    if (!sjobs.empty())
-      if (int e = launch_conv_stream_pack_multi(p.d.dtype, sjobs.data(), (int)sjobs.size(), s)) return e;
-    if (!mjobs.empty())
-      if (int e = launch_conv_march_pack_multi(p.d.dtype, mjobs.data(), (int)mjobs.size(), s)) return e;
-    return launch_conv_pack_weights_multi(p.d.dtype, jobs.data(), (int)jobs.size(), s);
+    return launch_conv_pack(p.d.dtype, jobs.data(), (int)jobs.size(), s);
   }
 
   // ---- forward: one step per op kind --------------------------------------------------------------------------------------
@@ -707,7 +666,7 @@ struct Exec {
       if (!is_input(t)) written[t] = true;
     }
     mark("dgrad:", o.name);
-    return run_conv(r.dgrad, r.taps, o.dil, gsrc, r.cout, par(c.i, P_CONV1_W), 1, at(r.wp_d), nullptr, gd, nullptr, c.dm);
+    return run_conv(r.dgrad, p.d.dtype, r.taps, o.dil, gsrc, r.cout, par(c.i, P_CONV1_W), 1, at(r.wp_d), nullptr, gd, nullptr, c.dm, s);
   }
 
   // heads: level gradients = transposed interpolation of the logit gradients

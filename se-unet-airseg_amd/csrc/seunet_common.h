@@ -272,44 +272,8 @@ int launch_pack_input(int dtype, const float* x_ncdhw, int in_channel, void* out
 int launch_unpack_cl(int dtype, const void* in_cl, int C, float* out_ncdhw, Dims d, hipStream_t s);
 int launch_pack_cl(int dtype, const float* in_ncdhw, int C, void* out_cl, int Cpad, Dims d, hipStream_t s);
 
-// convolution (conv_igemm.hip)
-size_t conv_wpack_bytes(int dtype, int taps, int cin, int cout);
-int launch_conv_pack_weights(int dtype, const float* w_torch, int taps, int cin_w, int cout_w,
-                             int transpose_flip, void* wpack, hipStream_t s);
-int conv_stats_tiles(Dims d, int taps, int dil);   // partial-stat slots per sample written by the igemm kernel
-struct ConvPackJob { const float* w; void* wpack; int taps, cin_w, cout_w, tflip; };
-int launch_conv_pack_weights_multi(int dtype, const ConvPackJob* jobs, int n, hipStream_t s);
-int launch_conv_igemm(int dtype, int taps, int dil, const SrcList& src, int cin_logical,
-                      const void* wpack, const float* bias, const DstList& dst,
-                      double* stats_partial, Dims d, hipStream_t s);
-int launch_conv_naive(int dtype, int taps, int dil, const SrcList& src, int cin_logical,
-                      const float* w_torch, int transpose_flip, const float* bias,
-                      const DstList& dst, Dims d, hipStream_t s);
-
-// streaming small-channel 3x3x3 convolution (conv_stream.hip): bf16, 8/16/32 source channels, <= 32 destination channels
-bool conv_stream_supported(int dtype, int taps, int dil, int src_c, int dst_c);
-size_t conv_stream_wpack_bytes(int src_c);
-int conv_stream_slots(Dims d, int dil);
-int launch_conv_stream_pack(int dtype, const float* w, int cin_w, int cout_w, int tflip, int src_c, int dst_c, void* wpack, hipStream_t s);
-struct StreamPackJob { const float* w; void* wpack; int cin_w, cout_w, tflip, src_c, dst_c; };
-int launch_conv_stream_pack_multi(int dtype, const StreamPackJob* jobs, int n, hipStream_t s);
-int launch_conv_stream(int dtype, int dil, const void* src, int src_c, const void* wpack, const float* bias, void* dst, int dst_c,
-                       int dst_accumulate, double* stats, Dims d, hipStream_t s);
-
-// marching 3x3x3 convolution for 32 / 64 source channels (conv_march.hip): bf16 | f16, one or two equal sources, destinations
-// in multiples of 16 channels; forward (bias, statistics) and data gradient (optionally accumulating)
-bool conv_march_supported(int dtype, int taps, int dil, const SrcList& src, const DstList& dst);
-size_t conv_march_wpack_bytes(int cin_e, int cout_e);
-int conv_march_slots(Dims d, int dil, int cin_e, int cout_e);
-int launch_conv_march_pack(int dtype, const float* w, int cin_w, int cout_w, int tflip, int cin_e, int cout_e, void* wpack, hipStream_t s);
-struct MarchPackJob { const float* w; void* wpack; int cin_w, cout_w, tflip, cin_e, cout_e; };
-int launch_conv_march_pack_multi(int dtype, const MarchPackJob* jobs, int n, hipStream_t s);   // every layer of a pass in one launch
-int launch_conv_march(int dtype, int dil, const SrcList& src, const void* wpack, const float* bias, const DstList& dst, double* stats,
-                      Dims d, hipStream_t s);
-
+// forward / data-gradient convolutions (conv_igemm.hip, conv_stream.hip, conv_march.hip): conv.h
 // weight gradients (wgrad.hip, wgrad_march.hip, wgrad_1x1.hip, wgrad_stream.hip): wgrad.h
-// the kernel of each conv pass: chosen in one place, net.cpp (kernel routing)
-enum class ConvKernel { Naive, Tiled, Stream, March, Wgrad1x1 };
 
 // normalisation / gates / cat (epilogue.hip, gate.hip, cat.hip): epilogue.h
 

@@ -5,13 +5,13 @@
 // launch cut and nothing else of this; its Map -- where element e of a slab lies in dW -- is here too, since the reduction
 // travels as one struct (WgReduceJob).
 #pragma once
-#include "seunet_common.h"
+#include "conv.h"
 
 namespace seunet {
 
 struct WgReduceJob;   // the reduction of a launch's slabs, as data (below)
 
-// ---- the family (ConvKernel, the enum the routing speaks in, is in seunet_common.h: the forward convs use it too) ----
+// ---- the family (ConvKernel: conv.h) ----
 // streaming small-channel weight gradient (wgrad_stream.hip)
 bool wgrad_stream_supported(int dtype, int taps, int dil, int x_c, int dy_c);
 size_t wgrad_stream_workspace_bytes(int x_c, int dy_c, int dil, Dims d);

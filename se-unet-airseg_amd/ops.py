@@ -66,37 +66,74 @@ def pack_weights(w: torch.Tensor, code: int, transpose_flip: bool = False) -> to
     return buf
 
 
+def _conv(kernel: str, srcs, weight, bias, dilation, transpose_flip, dsts, dst_channels, accumulate, want_stats,
+          impl: int = _lib.CONV_MFMA, cin: Optional[int] = None):
+    """One convolution (with transpose_flip: data gradient) on ``kernel`` -- "tiled" (or, with impl CONV_NAIVE, naive), "stream",
+    "march": pack the weight, run, optionally with the InstanceNorm partial sums.
+    Returns (list of destination tensors, stats_partial or None, slots)."""
+    lib = _lib.load()
+    x = srcs[0]
+    code, dims = _code(x), _dims_cl(x)
+    co_w, ci_w = weight.shape[0], weight.shape[1]
+    taps = weight.shape[2] * weight.shape[3] * weight.shape[4]
+    cin_e, cout_e = (co_w, ci_w) if transpose_flip else (ci_w, co_w)
+    src_c = [t.shape[4] for t in srcs]
+    if dsts is None:
+        dst_channels = list(dst_channels or [cout_e if kernel == "march" else (cout_e + 7) // 8 * 8])
+        dsts = [torch.empty(tuple(x.shape[:4]) + (c,), dtype=x.dtype, device=x.device) for c in dst_channels]
+        accumulate = [0] * len(dsts)
+    else:
+        dst_channels = list(dst_channels or [t.shape[4] for t in dsts])
+        accumulate = list(accumulate or [0] * len(dsts))
+    ctot, cout, tf = sum(src_c), sum(dst_channels), int(transpose_flip)
+    w = weight.contiguous().float()
+    b = None if bias is None else bias.contiguous().float()
+    # per kernel: whether it serves the shape, the packed weight, the statistics slots, the call
+    if kernel == "tiled":
+        served = True
+        wbuf = w if impl == _lib.CONV_NAIVE else pack_weights(weight, code, transpose_flip)
+        nslots = lambda: lib.seunet_conv_stats_slots(impl, taps, dilation, dims)
+        run = lambda st: lib.seunet_conv3d_fwd(code, impl, taps, dilation, len(srcs), _lib.ptr_array(list(srcs)), _lib.int_array(src_c),
+                                               cin or cin_e, wbuf.data_ptr(), tf, _lib.ptr(b), len(dsts), _lib.ptr_array(list(dsts)),
+                                               _lib.int_array(dst_channels), _lib.int_array(accumulate), _lib.ptr(st), dims, _s())
+    elif kernel == "stream":
+        served, shape = lib.seunet_conv3d_stream_supported(code, dilation, ctot, cout), f"{ctot} -> {cout}"
+        wbytes = lambda: lib.seunet_conv3d_stream_wpack_bytes(ctot)
+        pack = lambda: lib.seunet_conv3d_stream_pack(code, w.data_ptr(), ci_w, co_w, tf, ctot, cout, wbuf.data_ptr(), _s())
+        nslots = lambda: lib.seunet_conv3d_stream_slots(dilation, dims)
+        run = lambda st: lib.seunet_conv3d_stream(code, dilation, x.data_ptr(), ctot, wbuf.data_ptr(), _lib.ptr(b), dsts[0].data_ptr(),
+                                                  cout, accumulate[0], _lib.ptr(st), dims, _s())
+    else:
+        served, shape = conv3d_march_supported(srcs, dst_channels, dilation), f"{src_c} -> {dst_channels}"
+        wbytes = lambda: lib.seunet_conv3d_march_wpack_bytes(ctot, cout)
+        pack = lambda: lib.seunet_conv3d_march_pack(code, w.data_ptr(), ci_w, co_w, tf, ctot, cout, wbuf.data_ptr(), _s())
+        nslots = lambda: lib.seunet_conv3d_march_slots(dilation, ctot, cout, dims)
+        run = lambda st: lib.seunet_conv3d_march(code, dilation, len(srcs), _lib.ptr_array(list(srcs)), _lib.int_array(src_c),
+                                                 wbuf.data_ptr(), _lib.ptr(b), len(dsts), _lib.ptr_array(list(dsts)),
+                                                 _lib.int_array(dst_channels), _lib.int_array(accumulate), _lib.ptr(st), dims, _s())
+    if not served:
+        raise RuntimeError(f"conv3d_{kernel}: {shape} channels, dilation {dilation}, dtype {x.dtype} is not served by this kernel")
+    if kernel != "tiled":
+        wbuf = torch.empty(wbytes(), dtype=torch.uint8, device=x.device)
+        _lib.check(pack(), f"conv3d_{kernel}_pack")
+        if bias is not None:   # these kernels read a bias for every destination channel
+            b = torch.zeros(cout, dtype=torch.float32, device=x.device)
+            b[:bias.numel()] = bias.float()
+    stats, slots = None, 0
+    if want_stats:
+        slots = nslots()
+        stats = torch.zeros((dims.n, slots, cout, 2), dtype=torch.float64, device=x.device)
+    _lib.check(run(stats), "conv3d_fwd" if kernel == "tiled" else f"conv3d_{kernel}")
+    return list(dsts), stats, slots
+
+
 def conv3d(srcs: Sequence[torch.Tensor], weight: torch.Tensor, bias: Optional[torch.Tensor] = None, dilation: int = 1,
            impl: int = _lib.CONV_MFMA, transpose_flip: bool = False, cin: Optional[int] = None,
            dsts: Optional[Sequence[Optional[torch.Tensor]]] = None, dst_channels: Optional[Sequence[int]] = None,
            accumulate: Optional[Sequence[int]] = None, want_stats: bool = False):
     """Convolution (or, with transpose_flip, its data gradient) of the channel concatenation of ``srcs``.
     Returns (list of destination tensors, stats_partial or None, slots)."""
-    lib = _lib.load()
-    code = _code(srcs[0])
-    dims = _dims_cl(srcs[0])
-    taps = weight.shape[2] * weight.shape[3] * weight.shape[4]
-    co_w, ci_w = weight.shape[0], weight.shape[1]
-    cin_e, cout_e = (co_w, ci_w) if transpose_flip else (ci_w, co_w)
-    cin = cin or cin_e
-    if dsts is None:
-        dst_channels = dst_channels or [(cout_e + 7) // 8 * 8]
-        dsts = [torch.empty(tuple(srcs[0].shape[:4]) + (c,), dtype=srcs[0].dtype, device=srcs[0].device) for c in dst_channels]
-        accumulate = [0] * len(dsts)
-    else:
-        dst_channels = dst_channels or [t.shape[4] for t in dsts]
-        accumulate = list(accumulate or [0] * len(dsts))
-    wbuf = weight.contiguous().float() if impl == _lib.CONV_NAIVE else pack_weights(weight, code, transpose_flip)
-    stats, slots = None, 0
-    if want_stats:
-        slots = lib.seunet_conv_stats_slots(impl, taps, dilation, dims)
-        stats = torch.zeros((dims.n, slots, sum(dst_channels), 2), dtype=torch.float64, device=srcs[0].device)
-    b = None if bias is None else bias.contiguous().float()
-    _lib.check(lib.seunet_conv3d_fwd(code, impl, taps, dilation, len(srcs), _lib.ptr_array(list(srcs)),
-                                     _lib.int_array([t.shape[4] for t in srcs]), cin, wbuf.data_ptr(), int(transpose_flip),
-                                     _lib.ptr(b), len(dsts), _lib.ptr_array(list(dsts)), _lib.int_array(list(dst_channels)),
-                                     _lib.int_array(list(accumulate)), _lib.ptr(stats), dims, _s()), "conv3d_fwd")
-    return list(dsts), stats, slots
+    return _conv("tiled", srcs, weight, bias, dilation, transpose_flip, dsts, dst_channels, accumulate, want_stats, impl, cin)
 
 
 def conv3d_stream(src: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, dilation: int = 1,
@@ -104,31 +141,9 @@ def conv3d_stream(src: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.
                   accumulate: bool = False, want_stats: bool = False):
     """The streaming small-channel 3x3x3 convolution (csrc/conv_stream.hip): one bf16 source of 8 / 16 / 32 channels.
     Returns (destination, stats_partial or None, slots)."""
-    lib = _lib.load()
-    code, dims = _code(src), _dims_cl(src)
-    co_w, ci_w = weight.shape[0], weight.shape[1]
-    cout_e = ci_w if transpose_flip else co_w
-    src_c = src.shape[4]
-    dst_c = dst.shape[4] if dst is not None else (dst_channels or (cout_e + 7) // 8 * 8)
-    if not lib.seunet_conv3d_stream_supported(code, dilation, src_c, dst_c):
-        raise RuntimeError(f"conv3d_stream: {src_c} -> {dst_c} channels, dilation {dilation}, dtype {src.dtype} is not served by this kernel")
-    wbuf = torch.empty(lib.seunet_conv3d_stream_wpack_bytes(src_c), dtype=torch.uint8, device=src.device)
-    w = weight.contiguous().float()
-    _lib.check(lib.seunet_conv3d_stream_pack(code, w.data_ptr(), ci_w, co_w, int(transpose_flip), src_c, dst_c, wbuf.data_ptr(), _s()),
-               "conv3d_stream_pack")
-    if dst is None:
-        dst = torch.empty(tuple(src.shape[:4]) + (dst_c,), dtype=src.dtype, device=src.device)
-    stats, slots = None, 0
-    if want_stats:
-        slots = lib.seunet_conv3d_stream_slots(dilation, dims)
-        stats = torch.zeros((dims.n, slots, dst_c, 2), dtype=torch.float64, device=src.device)
-    b = None
-    if bias is not None:
-        b = torch.zeros(dst_c, dtype=torch.float32, device=src.device)
-        b[:bias.numel()] = bias.float()
-    _lib.check(lib.seunet_conv3d_stream(code, dilation, src.data_ptr(), src_c, wbuf.data_ptr(), _lib.ptr(b), dst.data_ptr(), dst_c,
-                                        int(accumulate), _lib.ptr(stats), dims, _s()), "conv3d_stream")
-    return dst, stats, slots
+    dsts, stats, slots = _conv("stream", [src], weight, bias, dilation, transpose_flip, None if dst is None else [dst],
+                               [dst_channels] if dst is None and dst_channels else None, [int(accumulate)], want_stats)
+    return dsts[0], stats, slots
 
 
 def conv3d_march_supported(srcs: Sequence[torch.Tensor], dst_channels: Sequence[int], dilation: int = 1) -> bool:
@@ -141,39 +156,7 @@ def conv3d_march(srcs: Sequence[torch.Tensor], weight: torch.Tensor, bias: Optio
                  dst_channels: Optional[Sequence[int]] = None, accumulate: Optional[Sequence[int]] = None, want_stats: bool = False):
     """The marching 3x3x3 convolution (csrc/conv_march.hip): 32 or 64 source channels (one or two tensors), bf16 / fp16.
     Returns (list of destination tensors, stats_partial or None, slots)."""
-    lib = _lib.load()
-    code, dims = _code(srcs[0]), _dims_cl(srcs[0])
-    co_w, ci_w = weight.shape[0], weight.shape[1]
-    cout_e = ci_w if transpose_flip else co_w
-    cin = sum(t.shape[4] for t in srcs)
-    if dsts is None:
-        dst_channels = list(dst_channels or [cout_e])
-        dsts = [torch.empty(tuple(srcs[0].shape[:4]) + (c,), dtype=srcs[0].dtype, device=srcs[0].device) for c in dst_channels]
-        accumulate = [0] * len(dsts)
-    else:
-        dst_channels = list(dst_channels or [t.shape[4] for t in dsts])
-        accumulate = list(accumulate or [0] * len(dsts))
-    if not conv3d_march_supported(srcs, dst_channels, dilation):
-        raise RuntimeError(f"conv3d_march: {[t.shape[4] for t in srcs]} -> {dst_channels} channels, dilation {dilation}, "
-                           f"dtype {srcs[0].dtype} is not served by this kernel")
-    cout = sum(dst_channels)
-    wbuf = torch.empty(lib.seunet_conv3d_march_wpack_bytes(cin, cout), dtype=torch.uint8, device=srcs[0].device)
-    w = weight.contiguous().float()
-    _lib.check(lib.seunet_conv3d_march_pack(code, w.data_ptr(), ci_w, co_w, int(transpose_flip), cin, cout, wbuf.data_ptr(), _s()),
-               "conv3d_march_pack")
-    stats, slots = None, 0
-    if want_stats:
-        slots = lib.seunet_conv3d_march_slots(dilation, cin, cout, dims)
-        stats = torch.zeros((dims.n, slots, cout, 2), dtype=torch.float64, device=srcs[0].device)
-    b = None
-    if bias is not None:
-        b = torch.zeros(cout, dtype=torch.float32, device=srcs[0].device)
-        b[:bias.numel()] = bias.float()
-    _lib.check(lib.seunet_conv3d_march(code, dilation, len(srcs), _lib.ptr_array(list(srcs)), _lib.int_array([t.shape[4] for t in srcs]),
-                                       wbuf.data_ptr(), _lib.ptr(b), len(dsts), _lib.ptr_array(list(dsts)),
-                                       _lib.int_array(dst_channels), _lib.int_array(accumulate), _lib.ptr(stats), dims, _s()),
-               "conv3d_march")
-    return list(dsts), stats, slots
+    return _conv("march", srcs, weight, bias, dilation, transpose_flip, dsts, dst_channels, accumulate, want_stats)
 
 
 def conv3d_wgrad(srcs: Sequence[torch.Tensor], dy: torch.Tensor, cin: int, cout: int, taps: int, dilation: int = 1,
