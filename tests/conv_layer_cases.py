@@ -1,9 +1,10 @@
 """The machinery of the per-layer convolution tests: every convolution pass of a plan, at the layer's own shape and on the kernel
 the plan routes it to, BITWISE.  ``Config(batch, extent, width)`` holds what ``SE_UNet.conv_plan`` gives for one descriptor
-(batch x 2 x extent^3, that channel width) in bf16 and fp16 storage, and the case lists generated from it; the test modules
-(tests/test_conv_layers_gpu.py: the benchmarked 4 x 2 x 128^3 at width 1, and two small plans; tests/test_conv_layers_config4_gpu.py:
-160^3 at width 2) parametrise over those lists and call ``forward_case`` / ``dgrad_case`` / ``wgrad_case``, so a layer that is
-added or re-routed later is covered without editing a test.
+(batch x 2 x extent^3, or batch x 2 x D x H x W for an extent given as a tuple, that channel width) in bf16 and fp16 storage, and
+the case lists generated from it; the test modules (tests/test_conv_layers_gpu.py: the benchmarked 4 x 2 x 128^3 at width 1, and
+two small plans; tests/test_conv_layers_config4_gpu.py: 160^3 at width 2; tests/test_conv_layers_ragged_gpu.py: non-cubic extents
+that leave every tile of the kernel family ragged) parametrise over those lists and call ``forward_case`` / ``dgrad_case`` /
+``wgrad_case``, so a layer that is added or re-routed later is covered without editing a test.
 
 Why equality and not a tolerance: the operands are small integers.  With x, w, bias in {-3..3} every product and every partial
 sum of a 3x3x3 convolution with up to 256 input channels is an integer of magnitude at most 27 * 256 * 9 + 3 = 62 211 < 2^24,
@@ -26,6 +27,12 @@ import torch.nn.functional as F
 DTYPES = ("bf16", "fp16")
 
 
+def extents(extent):
+    """(D, H, W) of an extent given as one int (a cube) or as a (D, H, W) tuple."""
+    d, h, w = (extent,) * 3 if isinstance(extent, int) else extent
+    return int(d), int(h), int(w)
+
+
 def plan_of(dtype, batch, extent, width):
     import seunet_amd  # noqa: F401
     from seunet_amd import _lib
@@ -33,17 +40,20 @@ def plan_of(dtype, batch, extent, width):
     if not os.path.exists(_lib.LIB_PATH):
         import __graft_entry__
         __graft_entry__.build()
-    return conv_plan(make_desc(batch, 2, 1, extent, extent, extent, width, _lib.dtype_code(dtype), 0, 0.01))
+    return conv_plan(make_desc(batch, 2, 1, *extents(extent), width, _lib.dtype_code(dtype), 0, 0.01))
 
 
 class Config:
-    """The plan of batch x 2 x extent^3 at channel width `width` per storage type, and the cases generated from it."""
+    """The plan of batch x 2 x extent^3 (extent: an int) or batch x 2 x D x H x W (extent: a tuple) at channel width `width` per
+    storage type, and the cases generated from it.  `levels` keeps only the layers of those plan levels in LAYERS, CASES and
+    DGRAD_CASES (PLANS and ROUTED stay whole: they describe the plan)."""
 
-    def __init__(self, batch, extent, width, dtypes=DTYPES):
+    def __init__(self, batch, extent, width, dtypes=DTYPES, levels=None):
         self.batch, self.extent, self.width, self.dtypes = batch, extent, width, tuple(dtypes)
+        self.levels = None if levels is None else tuple(levels)
         self.key = (batch, extent, width)
         self.PLANS = {dt: {c["name"]: c for c in plan_of(dt, batch, extent, width)} for dt in self.dtypes}
-        self.LAYERS = list(self.PLANS[self.dtypes[0]])
+        self.LAYERS = [n for n, c in self.PLANS[self.dtypes[0]].items() if self.levels is None or c["level"] in self.levels]
         # (kernel, pass) pairs the plan routes: a plan that silently routed everything to one kernel would make the cases pass
         # vacuously, so the test modules assert what they expect to find here
         self.ROUTED = {(c[p], p) for dt in self.dtypes for c in self.PLANS[dt].values() for p in ("fwd", "dgrad", "wgrad") if c[p]}

@@ -382,7 +382,7 @@ def test_bf16_mode_no_worse_than_bf16_autocast(A, orc):
     assert not worse, worse
 
 
-@pytest.mark.parametrize("batch,size", [(2, 32), (1, 64)])
+@pytest.mark.parametrize("batch,size", [(2, 32), (1, 64), (1, (72, 56, 88))], ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else None)
 @pytest.mark.parametrize("dtype,med_bar,max_bar,dc5_bar", [("bf16", 1e-1, 1.5e-1, 5e-2), ("fp16", 1.5e-2, 2.5e-2, 1e-2)])
 def test_16bit_modes_against_same_choice_float64(A, orc, dtype, med_bar, max_bar, dc5_bar, batch, size):
     """The 16-bit storage modes against FLOAT64 (not against another 16-bit implementation): with the LeakyReLU-sign and max-pool
@@ -393,10 +393,13 @@ def test_16bit_modes_against_same_choice_float64(A, orc, dtype, med_bar, max_bar
     / max 8.5e-2 over the large tensors (dc5.conv1.weight 3.2e-2), fp16 6.4e-3 / 1.0e-2 (3.9e-3): the error is the 8- (11-) bit
     rounding of the stored activations and activation gradients, amplified ~13 x by the InstanceNorm backward's cancellation.
     Bars = ~2 x measured.  The 1 x 64^3 case runs the full-resolution level on the marching kernels (conv_march.hip,
-    wgrad_march.hip: levels of >= 48^3 voxels with rows of >= 32), the 2 x 32^3 case on the tiled / streaming ones."""
+    wgrad_march.hip: levels of >= 48^3 voxels with rows of >= 32), the 2 x 32^3 case on the tiled / streaming ones.  The
+    1 x (72, 56, 88) case is configuration A of tests/conv_ragged_cases.py: a non-cubic shape that marches at full resolution and,
+    for the dilation-2 layers, on level 1, with every x block, row patch and axis ragged (`size` is an int or a (D, H, W) tuple);
+    it keeps the same bars -- the error they bound is the per-element storage rounding, not a property of the extents."""
     import forced_oracle as FO
     m = build(A, orc, 2, dtype)
-    b = orc.synthetic_batch(batch, (size,) * 3, 2, seed=3)
+    b = orc.synthetic_batch(batch, (size,) * 3 if isinstance(size, int) else size, 2, seed=3)
     _, _, inter = m.forward_with_intermediates(b["image"].cuda(), FO.LRELU_ORDER)
     ge, gd = m(b["image"].cuda())
     A.fused_stage_loss(1, ge, gd, b["label"].cuda()).backward()
