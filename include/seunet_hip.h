@@ -675,6 +675,49 @@ size_t seunet_select_ranks_workspace_bytes(int nranks);
 int seunet_select_ranks(const double* values, long long n, const long long* seg_begin, const long long* seg_end, const long long* rank,
                         int nranks, double* out_dev, void* workspace, size_t workspace_bytes, seunet_stream_t s);
 
+/* ---- component labelling, Euler number, Betti numbers ----------------------------------------------------
+ * The reference labels components with skimage.measure.label / scipy.ndimage.label (util.py, tree_parsing.py,
+ * atm22_skel_parse.py) and computes no topological number; the definitions are this comment, restated in numpy / scipy by
+ * tests/betti_oracle.py.  mask: bytes, non-zero = foreground, C-contiguous (n0, n1, n2), extents >= 1, fewer than 2^31 voxels.
+ * connectivity 1, 2, 3 = 6, 18, 26 neighbours (scipy's generate_binary_structure(3, connectivity)).  Integer work only: every
+ * result is independent of the order in which the device executes anything.
+ *
+ * seunet_label: labels (n0 n1 n2 int32) = 0 on the background and 1 .. N on the components, numbered in raster order of each
+ *   component's first voxel: scipy.ndimage.label(mask, generate_binary_structure(3, connectivity)) bit for bit.  num_dev (device
+ *   int, optional) = N.  workspace: seunet_label_workspace_bytes(n0, n1, n2), caller-owned.  Does not synchronise.
+ * seunet_component_table: for the labels and the UNCHANGED workspace of a seunet_label call and its N = num >= 1: size[k] (int64) =
+ *   voxels of component k + 1, first[k] (int64) = linear index of its first voxel, box[6 k ..] (int32) = {min0, max0, min1, max1,
+ *   min2, max2} of its voxels' coordinates, maxima inclusive.  No cap on N.  Does not synchronise.
+ * seunet_remove_small_objects: out (bytes 0 / 1; may alias mask) = the voxels of the components with at least min_size voxels.
+ *   workspace: seunet_cc_workspace_bytes(n0, n1, n2).  Does not synchronise.
+ *
+ * The tile calls take a patch (p0, p1, p2), every extent >= 1 (an extent past the volume's is the volume's): the volume is cut
+ * into t0 t1 t2 tiles of that size from the origin, t_k = ceil(n_k / p_k), the last tile of an axis ragged; a tile's numbers are
+ * those of the tile cropped out as a volume of its own, and all tiles are done by one fixed set of launches.  The patch
+ * (n0, n1, n2) is the whole volume.  connectivity: 3 or 1 (18 neighbours have no dual).
+ * seunet_euler: chi_dev (t0 t1 t2 device int64, raster tile order) = the Euler characteristic.  connectivity 3: of the union of
+ *   the closed unit cubes of the foreground voxels, V - E + F - C with C the voxels and F, E, V the lattice faces, edges and
+ *   vertices that touch at least one of them.  connectivity 1: of the complex whose vertices are the voxels, V' - E' + F' - C' with
+ *   the voxels, the face-adjacent pairs, the 2 x 2 squares and the 2 x 2 x 2 cubes that are all foreground.
+ *   workspace: seunet_euler_workspace_bytes(n0, n1, n2, p0, p1, p2).
+ * seunet_betti: table_dev (t0 t1 t2 x 3 device int32) = (b0, b1, b2) per tile.  b0 = components at `connectivity`; b2 = components
+ *   of the complement at the dual connectivity (3 <-> 1) that touch no face of the tile; b1 = b0 + b2 - chi.
+ *   workspace: seunet_betti_workspace_bytes(n0, n1, n2, p0, p1, p2).
+ * Neither synchronises; all work is ordered on s.  Extent, patch and connectivity errors return before any device work. */
+size_t seunet_label_workspace_bytes(int n0, int n1, int n2);
+int seunet_label(const unsigned char* mask, int n0, int n1, int n2, int connectivity, int* labels, int* num_dev, void* workspace,
+                 size_t workspace_bytes, seunet_stream_t s);
+int seunet_component_table(const int* labels, int n0, int n1, int n2, long long num, long long* size, long long* first, int* box,
+                           void* workspace, size_t workspace_bytes, seunet_stream_t s);
+int seunet_remove_small_objects(const unsigned char* mask, int n0, int n1, int n2, long long min_size, int connectivity,
+                                unsigned char* out, void* workspace, size_t workspace_bytes, seunet_stream_t s);
+size_t seunet_euler_workspace_bytes(int n0, int n1, int n2, int p0, int p1, int p2);
+int seunet_euler(const unsigned char* mask, int n0, int n1, int n2, int p0, int p1, int p2, int connectivity, long long* chi_dev,
+                 void* workspace, size_t workspace_bytes, seunet_stream_t s);
+size_t seunet_betti_workspace_bytes(int n0, int n1, int n2, int p0, int p1, int p2);
+int seunet_betti(const unsigned char* mask, int n0, int n1, int n2, int p0, int p1, int p2, int connectivity, int* table_dev,
+                 void* workspace, size_t workspace_bytes, seunet_stream_t s);
+
 /* ---- CT preprocessing: preprocessing.py:26-130 with util.py:95-152 -----------------------------
  * CT volumes are int16, C-contiguous (h, w, z) on the device (the reference's orientation after its transposes), fewer than 2^31
  * voxels; masks are bytes, non-zero = 1.

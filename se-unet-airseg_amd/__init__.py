@@ -5,7 +5,7 @@ hand-written HIP kernels behind a C ABI (``include/seunet_hip.h``).  The directo
 Python identifier; import it as ``seunet_amd`` (alias module at the repo root) or via
 ``importlib.import_module("se-unet-airseg_amd")``.
 """
-from . import _lib, ddp, mesh, morphometry, online, ops, optim, pipeline, postprocess, prep, preprocess, topology
+from . import _lib, components, ddp, mesh, morphometry, online, ops, optim, pipeline, postprocess, prep, preprocess, topology
 from .SE_UNet import CapturedForward, CATConv, DropLayer, SE_UNet, SSEConv, SSEConv2, get_model, load_reference_checkpoint
 from .optim import AdamW
 from .pipeline import (AirwayHMData3GPU, AirwayHMDataGPU, CropSegDataGPU, aug_code, crop_batch, draw_stage1_plan, draw_stage2_plan,
@@ -19,6 +19,7 @@ from .morphometry import BranchTable, branch_morphometry, branch_stats, branch_t
 from .preprocess import cut_mask, get_l, large_connected_domain26, preprocess_ct, th_2t
 from .postprocess import (MetricSums, SurfaceMetrics, cldice_score, double_threshold_iteration, evaluation_case, largest_component,
                           maximum_3d, order_statistics, postprocess_prediction, surface_distances, surface_metrics, zero_borders)
+from .components import (BettiError, ComponentTable, betti_error, betti_numbers, euler_number, label, remove_small_objects)
 from .losses import atr_loss, dice_loss, fused_logit_loss, fused_stage_loss, general_union_loss_lib, per_sample_loss, soft_cldice_loss, soft_skeleton
 from .online import OnlineHardPool
 from .sliding_window import sliding_window_predict, sliding_window_validate, two_channel, window_starts, window_table
@@ -31,4 +32,5 @@ __all__ = ["SE_UNet", "SSEConv", "SSEConv2", "CATConv", "DropLayer", "get_model"
            "binary_erosion", "binary_closing", "binary_fill_holes", "preprocess_ct", "th_2t", "get_l", "large_connected_domain26", "cut_mask",
            "marching_cubes", "smooth_mesh", "write_stl", "prediction_mesh", "mesh_adjacency", "stl_records", "transform_mesh",
            "label_meshes", "branch_meshes", "LabelMeshes", "branch_stats", "branch_tree", "branch_morphometry", "BranchTable", "branch_wall_distance",
-           "soft_skeleton", "soft_cldice_loss", "cldice_score", "surface_distances", "order_statistics", "surface_metrics", "SurfaceMetrics"]
+           "soft_skeleton", "soft_cldice_loss", "cldice_score", "surface_distances", "order_statistics", "surface_metrics", "SurfaceMetrics",
+           "label", "remove_small_objects", "euler_number", "betti_numbers", "betti_error", "ComponentTable", "BettiError"]

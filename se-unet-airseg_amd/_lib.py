@@ -174,6 +174,14 @@ PROTOTYPES = {
     "seunet_surface_summary": (_i, [_vp, _ll, _ll, C.POINTER(_d), _i, _vp, _vp]),
     "seunet_select_ranks_workspace_bytes": (_sz, [_i]),
     "seunet_select_ranks": (_i, [_vp, _ll, C.POINTER(_ll), C.POINTER(_ll), C.POINTER(_ll), _i, _vp, _vp, _sz, _vp]),
+    "seunet_label_workspace_bytes": (_sz, [_i, _i, _i]),
+    "seunet_label": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "seunet_component_table": (_i, [_vp, _i, _i, _i, _ll, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "seunet_remove_small_objects": (_i, [_vp, _i, _i, _i, _ll, _i, _vp, _vp, _sz, _vp]),
+    "seunet_euler_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "seunet_euler": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "seunet_betti_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "seunet_betti": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "seunet_mesh_coord_sums": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "seunet_mesh_adjacency_workspace_bytes": (_sz, [_ll, _ll]),
     "seunet_mesh_adjacency": (_i, [_vp, _ll, _ll, _vp, _vp, _ll, _vp, _vp, _vp, _sz, _vp]),

@@ -40,7 +40,8 @@ int seunet_debug_upsample2_form(int dtype, int c, seunet_dims dims, int backward
 
 // diagnostic hook (not part of the public header, host only): the workspace layout of a volume operation as its launcher
 // carves it.  op: 0 cc, 1 get_l, 2 edt, 3 lib_weight, 4 break_weight, 5 skeleton_branches, 6 dti, 7 skeleton, 8 parse_assign,
-// 9 binary_morph, 10 mesh, 11 mesh_label, 12 edt_sampling, 13 surface (count), 14 surface_emit (extents of the box).
+// 9 binary_morph, 10 mesh, 11 mesh_label, 12 edt_sampling, 13 surface (count), 14 surface_emit (extents of the box), 15 label,
+// 16 euler, 17 betti (the last two for the whole volume: one tile).
 // Returns the number of sub-buffers (0: extents the op rejects, -1: no such op) and writes (offset, bytes up to the next
 // sub-buffer or the end) of the first `cap`.
 int seunet_debug_volume_layout(int op, int n0, int n1, int n2, size_t* offsets, int cap) {
@@ -64,6 +65,9 @@ int seunet_debug_volume_layout(int op, int n0, int n1, int n2, size_t* offsets, 
     case 12: edt_sampling_ws(c, n0, n1, n2); break;
     case 13: if ((long long)n0 * n1 * n2 >= (1ll << 31)) return 0; surface_ws(c, n0, n1, n2); break;
     case 14: if ((long long)n0 * n1 * n2 >= (1ll << 31)) return 0; surface_emit_ws(c, n0, n1, n2); break;
+    case 15: if ((long long)n0 * n1 * n2 >= (1ll << 31)) return 0; label_ws(c, n0, n1, n2); break;
+    case 16: if ((long long)n0 * n1 * n2 >= (1ll << 31)) return 0; euler_ws(c, n0, n1, n2, 1); break;
+    case 17: if ((long long)n0 * n1 * n2 >= (1ll << 31)) return 0; betti_ws(c, n0, n1, n2, 1); break;
     default: return -1;
   }
   if (c.taken > c.log_cap) return -1;
@@ -618,6 +622,46 @@ size_t seunet_select_ranks_workspace_bytes(int nranks) {
 int seunet_select_ranks(const double* values, long long n, const long long* seg_begin, const long long* seg_end, const long long* rank,
                         int nranks, double* out_dev, void* workspace, size_t workspace_bytes, seunet_stream_t s) {
   return launch_select_ranks(values, n, seg_begin, seg_end, rank, nranks, out_dev, workspace, workspace_bytes, S(s));
+}
+size_t seunet_label_workspace_bytes(int n0, int n1, int n2) {
+  if (volume_check("label_workspace_bytes", n0, n1, n2, 0)) return 0;
+  return label_workspace_bytes(n0, n1, n2);
+}
+int seunet_label(const unsigned char* mask, int n0, int n1, int n2, int connectivity, int* labels, int* num_dev, void* workspace,
+                 size_t workspace_bytes, seunet_stream_t s) {
+  return launch_label(mask, n0, n1, n2, connectivity, labels, num_dev, workspace, workspace_bytes, S(s));
+}
+int seunet_component_table(const int* labels, int n0, int n1, int n2, long long num, long long* size, long long* first, int* box,
+                           void* workspace, size_t workspace_bytes, seunet_stream_t s) {
+  return launch_component_table(labels, n0, n1, n2, num, size, first, box, workspace, workspace_bytes, S(s));
+}
+int seunet_remove_small_objects(const unsigned char* mask, int n0, int n1, int n2, long long min_size, int connectivity,
+                                unsigned char* out, void* workspace, size_t workspace_bytes, seunet_stream_t s) {
+  return launch_remove_small(mask, n0, n1, n2, min_size, connectivity, out, workspace, workspace_bytes, S(s));
+}
+// the patch of the tile calls: at least 1 per axis; an extent past the volume's is the volume's
+static int patch_check(const char* what, int n0, int n1, int n2, int p0, int p1, int p2) {
+  if (volume_check(what, n0, n1, n2, 0)) return 1;
+  SEUNET_CHECK(p0 >= 1 && p1 >= 1 && p2 >= 1, "%s: bad patch (%d, %d, %d)", what, p0, p1, p2);
+  return 0;
+}
+size_t seunet_euler_workspace_bytes(int n0, int n1, int n2, int p0, int p1, int p2) {
+  if (patch_check("euler_workspace_bytes", n0, n1, n2, p0, p1, p2)) return 0;
+  return euler_workspace_bytes(n0, n1, n2, tile_cut(n0, n1, n2, p0, p1, p2));
+}
+int seunet_euler(const unsigned char* mask, int n0, int n1, int n2, int p0, int p1, int p2, int connectivity, long long* chi_dev,
+                 void* workspace, size_t workspace_bytes, seunet_stream_t s) {
+  if (patch_check("euler", n0, n1, n2, p0, p1, p2)) return 1;
+  return launch_euler(mask, n0, n1, n2, tile_cut(n0, n1, n2, p0, p1, p2), connectivity, chi_dev, workspace, workspace_bytes, S(s));
+}
+size_t seunet_betti_workspace_bytes(int n0, int n1, int n2, int p0, int p1, int p2) {
+  if (patch_check("betti_workspace_bytes", n0, n1, n2, p0, p1, p2)) return 0;
+  return betti_workspace_bytes(n0, n1, n2, tile_cut(n0, n1, n2, p0, p1, p2));
+}
+int seunet_betti(const unsigned char* mask, int n0, int n1, int n2, int p0, int p1, int p2, int connectivity, int* table_dev,
+                 void* workspace, size_t workspace_bytes, seunet_stream_t s) {
+  if (patch_check("betti", n0, n1, n2, p0, p1, p2)) return 1;
+  return launch_betti(mask, n0, n1, n2, tile_cut(n0, n1, n2, p0, p1, p2), connectivity, table_dev, workspace, workspace_bytes, S(s));
 }
 int seunet_mesh_coord_sums(const unsigned char* mask, int n0, int n1, int n2, long long* sums_dev, seunet_stream_t s) {
   return launch_mesh_coord_sums(mask, n0, n1, n2, sums_dev, S(s));

@@ -1,5 +1,5 @@
-// The bit-packed volume layer that morph.hip, dti.hip, skeleton.hip, mesh.hip, mesh_label.hip and
-// surface.hip share: geometry, byte <-> bit packing, neighbour words, the exclusive scan and the wave counts by bit planes.
+// The bit-packed volume layer that morph.hip, dti.hip, skeleton.hip, mesh.hip, mesh_label.hip,
+// surface.hip and betti.hip share: geometry, byte <-> bit packing, neighbour words, the exclusive scan and the wave counts by bit planes.
 //
 // Representation: 64 voxels of a row (axis 2) per u64, bit b of word w of a row = voxel 64 w + b.  Zero-tail rule: the bits of a
 // row's last word past the row's end are 0 in every packed volume, and every kernel that writes one keeps them 0.  The padded form

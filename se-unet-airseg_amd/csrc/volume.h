@@ -1,7 +1,7 @@
 // Shared layer of the volume operations (components.hip, lung.hip, edt.hip, edt_sampling.hip, parse.hip, skeleton.hip, dti.hip,
-// morph.hip, mesh.hip, mesh_label.hip, morphometry.hip, cldice.hip, surface.hip): their launcher prototypes, ONE workspace layout
-// per operation, the extent check and the voxel / wave helpers their kernels share.  The bit-packed representation six of them
-// work on -- geometry, packing, neighbour words, the scan, wave counts -- is bitvol.h / bitvol.hip.
+// morph.hip, mesh.hip, mesh_label.hip, morphometry.hip, cldice.hip, surface.hip, betti.hip): their launcher prototypes, ONE
+// workspace layout per operation, the extent check and the voxel / wave helpers their kernels share.  The bit-packed
+// representation seven of them work on -- geometry, packing, neighbour words, the scan, wave counts -- is bitvol.h / bitvol.hip.
 //
 // Workspace contract: every operation has a layout struct filled by one function that walks a WsCarver.  Over a null base
 // the walk measures (`X_workspace_bytes`), over the caller's workspace it carves (the launcher); no launcher computes an
@@ -472,6 +472,73 @@ int launch_surface_emit(int n0, int n1, int n2, const int* box, double s0, doubl
 int launch_surface_summary(const double* dist, long long n_a, long long n_b, const double* tol, int ntol, void* out_dev, hipStream_t s);
 int launch_select_ranks(const double* values, long long n, const long long* seg_begin, const long long* seg_end, const long long* rank,
                         int nranks, double* out_dev, void* workspace, size_t ws_bytes, hipStream_t s);
+
+// ---- component labelling, Euler number, Betti numbers (betti.hip) -----------------------------------------------------------------
+// connectivity 1 / 2 / 3 = 6 / 18 / 26 neighbours.  A patch (p0, p1, p2) cuts the volume into tiles from the origin (the last tile of
+// an axis may be ragged); a tile's numbers are those of the tile cropped out as a volume of its own.  The whole volume is the one
+// tile whose patch is the extents.
+struct TileCut {
+  int p0, p1, p2;         // patch extents, 1 .. n_k
+  int t0, t1, t2;         // tiles per axis: ceil(n_k / p_k)
+  long long tiles() const { return (long long)t0 * t1 * t2; }
+};
+static inline TileCut tile_cut(int n0, int n1, int n2, int p0, int p1, int p2) {
+  p0 = std::min(std::max(p0, 1), n0); p1 = std::min(std::max(p1, 1), n1); p2 = std::min(std::max(p2, 1), n2);
+  return TileCut{p0, p1, p2, (n0 + p0 - 1) / p0, (n1 + p1 - 1) / p1, (n2 + p2 - 1) / p2};
+}
+struct LabelWs {
+  int* labels;            // minimum linear index of every voxel's component, -1 off (handed unchanged to the table call)
+  unsigned* counts;       // voxels per root (the table call)
+  u64* roots;             // the packed mask of the roots; rows of ceil(n2 / 64) words, zero tails
+  unsigned* cnt;          // per word: roots, then their exclusive scan inside a block of 1024 words
+  unsigned* blk;          // per block: its total, then the exclusive scan of the totals
+  unsigned* base;         // words + 1: the plain exclusive scan; the last entry is the number of components
+  u64* total;             // the scan's grand total (two slots)
+};
+static inline LabelWs label_ws(WsCarver& c, int n0, int n1, int n2) {
+  const size_t n = (size_t)n0 * n1 * n2, nwords = words(n0, n1, n2), blocks = (nwords + kScanBlock - 1) / kScanBlock;
+  return LabelWs{c.take<int>(n), c.take<unsigned>(n), c.take<u64>(nwords), c.take<unsigned>(nwords), c.take<unsigned>(blocks),
+                 c.take<unsigned>(nwords + 1), c.take<u64>(2)};
+}
+constexpr int kCellClasses = 4;           // cell counts per tile, by the number of axes a cell spans two voxels along
+struct EulerWs {
+  u64* bits;              // the packed volume; rows of ceil(n2 / 64) words, zero tails
+  u64* cells;             // tiles x kCellClasses
+};
+static inline EulerWs euler_ws(WsCarver& c, int n0, int n1, int n2, long long tiles) {
+  return EulerWs{c.take<u64>(words(n0, n1, n2)), c.take<u64>((size_t)tiles * kCellClasses)};
+}
+struct BettiWs {
+  int* labels;            // the foreground's labels, then the complement's
+  unsigned char* flag;    // per root of the complement: 1 = its component reaches a face of its tile
+  EulerWs euler;
+};
+static inline BettiWs betti_ws(WsCarver& c, int n0, int n1, int n2, long long tiles) {
+  const size_t n = (size_t)n0 * n1 * n2;
+  BettiWs w;
+  w.labels = c.take<int>(n);
+  w.flag = c.take<unsigned char>(n);
+  w.euler = euler_ws(c, n0, n1, n2, tiles);
+  return w;
+}
+size_t label_workspace_bytes(int n0, int n1, int n2);
+size_t euler_workspace_bytes(int n0, int n1, int n2, TileCut t);
+size_t betti_workspace_bytes(int n0, int n1, int n2, TileCut t);
+// labels_out: 0 off, 1 .. N in raster order of each component's first voxel; num_dev (optional): N.  Does not synchronise.
+int launch_label(const unsigned char* vol, int n0, int n1, int n2, int connectivity, int* labels_out, int* num_dev, void* workspace,
+                 size_t ws_bytes, hipStream_t s);
+// size / first (num int64 each) and box (num x {min0, max0, min1, max1, min2, max2}) from the label call's output and workspace
+int launch_component_table(const int* labels, int n0, int n1, int n2, long long num, long long* size, long long* first, int* box,
+                           void* workspace, size_t ws_bytes, hipStream_t s);
+// out = the voxels of the components with at least min_size voxels; workspace: cc_ws
+int launch_remove_small(const unsigned char* vol, int n0, int n1, int n2, long long min_size, int connectivity, unsigned char* out,
+                        void* workspace, size_t ws_bytes, hipStream_t s);
+// chi_dev: one int64 per tile, raster tile order
+int launch_euler(const unsigned char* vol, int n0, int n1, int n2, TileCut t, int connectivity, long long* chi_dev, void* workspace,
+                 size_t ws_bytes, hipStream_t s);
+// table_dev: int32 (tiles, 3) = (b0, b1, b2) per tile, raster tile order
+int launch_betti(const unsigned char* vol, int n0, int n1, int n2, TileCut t, int connectivity, int* table_dev, void* workspace,
+                 size_t ws_bytes, hipStream_t s);
 
 // ---- device helpers -------------------------------------------------------------------------------------------------------
 // raster index -> coordinates of an (n0, n1, n2) volume (n0 is not needed)
