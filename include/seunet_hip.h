@@ -203,7 +203,9 @@ int seunet_upsample2_bwd(int dtype, const void* g_out, int c, void* g_in, int ac
 int seunet_side_upsample(const float* side, int c, int scale, float* out_ncdhw, int c_total, int c_off,
                          seunet_dims low_dims, seunet_stream_t s);
 
-/* ---- heads: dc0_0 / dc0_1 over the DropLayer-scaled side stack; SE_UNet.py:150-153,232-233 ------------ */
+/* ---- heads: dc0_0 / dc0_1 over the DropLayer-scaled side stack; SE_UNet.py:150-153,232-233 ------------
+ * level l has extents (D >> l, H >> l, W >> l): D, H and W must be multiples of 2^(nlevels - 1) (W of 4 as well);
+ * other extents are refused with an error and nothing is launched. */
 int seunet_head_fwd(const float* const* level_maps, int nlevels, const float* bias, float* pred, seunet_dims dims,
                     seunet_stream_t s);
 size_t seunet_head_bwd_tmp_floats(seunet_dims dims);

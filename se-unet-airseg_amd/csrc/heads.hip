@@ -186,6 +186,12 @@ head_fwd_rows_kernel(HeadLevels lv, const float* __restrict__ bias, float* __res
 // summation order as the axis pass, up_transpose_axis_multi_kernel (bitwise identical results).
 // HB_K: weights per table row, and the register taps of a lane's second entry (the level-3 ones, ~20 taps), read out of those rows
 constexpr int HB_ROWS = 32, HB_K = 24, HB_PAD = 24, HB_KA = 8;
+// A table row keeps HB_K weights and no more.  For every W <= 1024 that 2^l divides, an output of level l has at most 6 (l = 1),
+// 12 (l = 2, W = 20) and 23 (l = 3, W = 24) taps after its leading zero weights; a width that 2^(nlevels - 1) does not divide can
+// have more (W = 28 with 4 levels: 27), and launch_head_bwd refuses it (head_extents_check).  The enumeration is repeated in
+// float32 on the host by tests/test_epilogue_ragged_host.py.
+constexpr int HB_MAX_TAPS = 23;
+static_assert(HB_K >= HB_MAX_TAPS, "a table row of head_bwd_x_multi_kernel must hold every tap of a level-3 output");
 __global__ void __launch_bounds__(256)
 head_bwd_x_multi_kernel(const float* __restrict__ g, float* __restrict__ t1a, float* __restrict__ t1b, float* __restrict__ t1c,
                         int nl, int W, long long rows, double* __restrict__ bias_part) {
@@ -361,6 +367,15 @@ __device__ __forceinline__ void sum_stage2_wide_by_256(const double* __restrict_
 }
 
 // ---------------- launchers -----------------------------------------------------------------------
+// Level l of a head has extents (D >> l, H >> l, W >> l) and is interpolated by exactly 2^l: every extent has to be a multiple
+// of 2^(nlevels - 1).  (The x pass of the backward relies on it: see HB_K.)
+static int head_extents_check(const char* what, Dims d0, int nlevels) {
+  const int m = (1 << (nlevels - 1)) - 1;
+  SEUNET_CHECK((d0.D & m) == 0 && (d0.H & m) == 0 && (d0.W & m) == 0,
+               "%s: extents (%d, %d, %d) must be multiples of %d for %d levels", what, d0.D, d0.H, d0.W, m + 1, nlevels);
+  return 0;
+}
+
 int launch_side_upsample(const float* side, int C, int scale, float* out, int c_total, int c_off, Dims dl,
                          hipStream_t s) {
   const long long total = (long long)dl.N * dl.vox() * scale * scale * scale;
@@ -377,6 +392,7 @@ int launch_head_fwd(const float* const* level_maps, int nlevels, const float* bi
   for (int l = 1; l < nlevels; ++l)
     SEUNET_CHECK((d0.D >> l) >= 1 && (d0.H >> l) >= 1 && (d0.W >> l) >= 1, "head: volume too small for level %d", l);
   SEUNET_CHECK(d0.W % 4 == 0, "head: W=%d must be a multiple of 4", d0.W);
+  if (int e = head_extents_check("head_fwd", d0, nlevels)) return e;
   if (d0.W % 8 == 0 && d0.W <= 2048 && (long long)d0.D * d0.H * d0.W < (1ll << 31)) {   // row form: whole level rows, LDS rows fit, 32-bit in-sample offsets
     const size_t lds = (size_t)4 * HF_RPW * ((d0.W >> 1) + (d0.W >> 2) + (d0.W >> 3)) * sizeof(float);
     const int ybl = (d0.H + 4 * HF_RPW - 1) / (4 * HF_RPW);
@@ -451,6 +467,8 @@ size_t head_bwd_tmp_floats(Dims d0) { return (size_t)head_bwd_layout(d0, 4).tota
 int launch_head_bwd(const float* g_pred, float* const* g_levels, int nlevels, float* tmp, float* g_bias,
                     Dims d0, hipStream_t s) {
   SEUNET_CHECK(nlevels >= 1 && nlevels <= 4, "head: nlevels=%d out of range", nlevels);
+  // (a width that 2^(nlevels - 1) does not divide can give an output more than HB_K taps, which the x pass would drop)
+  if (int e = head_extents_check("head_bwd", d0, nlevels)) return e;
   const long long rows = (long long)d0.N * d0.D * d0.H;
   const long long V = rows * d0.W;
   const HeadBwdLayout m = head_bwd_layout(d0, nlevels);

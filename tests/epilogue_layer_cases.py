@@ -2,12 +2,13 @@
 shape and storage type a configuration runs it with, against a float64 restatement (tests/epilogue_ref.py) under DERIVED bounds
 -- and bitwise wherever the operation only selects or rounds once.
 
-``Config(batch, extent, width)`` generates the cases from ``SE_UNet.conv_plan`` for batch x 2 x extent^3 at that channel width
-and from the module's own blocks (one or two gates, head and head slot, the block a max-pool follows), so a block that is added
-later is covered without editing a test; the test modules (tests/test_epilogue_layers_gpu.py: the benchmarked 4 x 2 x 128^3 at
-width 1; tests/test_epilogue_layers_config4_gpu.py: 2 x 2 x 160^3 at width 2) parametrise over its lists and call the case
-functions below.  Inputs are seeded, already rounded to the storage type, with a per-(sample, channel) offset and scale (a
-lane-group or sample mix-up changes the answer); the parameters are the module's seeded initial values, level gradients / head
+``Config(batch, extent, width, levels=None, dtypes=None)`` generates the cases from ``SE_UNet.conv_plan`` for batch x 2 x
+extent^3 (an int) or batch x 2 x D x H x W (a tuple) at that channel width and from the module's own blocks (one or two gates,
+head and head slot, the block a max-pool follows), so a block that is added later is covered without editing a test; the test
+modules (tests/test_epilogue_layers_gpu.py: the benchmarked 4 x 2 x 128^3 at width 1; tests/test_epilogue_layers_config4_gpu.py:
+2 x 2 x 160^3 at width 2; tests/test_epilogue_layers_ragged_gpu.py: the non-cubic configurations of
+tests/epilogue_ragged_cases.py) parametrise over its lists and call the case functions below.  Inputs are seeded, already
+rounded to the storage type, with a per-(sample, channel) offset and scale (a lane-group or sample mix-up changes the answer); the parameters are the module's seeded initial values, level gradients / head
 weights / DropLayer scales random f32.  One block's tensors live at a time.
 
 Tolerances (u = 2^-24; the counts are justified in tests/epilogue_ref.py and next to each use):
@@ -28,7 +29,7 @@ import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import epilogue_ref as R  # noqa: E402
-from conv_layer_cases import _cache, ops_or_skip, shared  # noqa: E402,F401  (one cache: a module's tensors go when the next starts)
+from conv_layer_cases import _cache, extents, ops_or_skip, shared  # noqa: E402,F401  (one cache: a module's tensors go when the next starts)
 
 # eps and the LeakyReLU slope reach the kernels as C floats: the reference takes the same two numbers
 EPS, SLOPE = float(torch.tensor(1e-5, dtype=torch.float32)), float(torch.tensor(0.01, dtype=torch.float32))
@@ -44,40 +45,47 @@ NONPOW2 = [("np2-32", 32, (3, 6, 10, 14)), ("np2-16", 16, (3, 12, 20, 24)), ("np
 
 
 class Config:
-    """The plan of batch x 2 x extent^3 at channel width `width`, the module with its seeded initial parameters, the slot count
-    of every level, what each block is, and the case lists."""
+    """The plan of batch x 2 x extent^3 (extent: an int) or batch x 2 x D x H x W (extent: a tuple) at channel width `width`, the
+    module with its seeded initial parameters, the slot count of every level, what each block is, and the case lists.  `levels`
+    keeps only the cases whose tensor lives on one of those plan levels (a block's own level; the level an up-sampling reads and
+    a max-pool reads -- for the packed input of POOLS_X that is the level above the block's); `dtypes` keeps only those storage
+    types.  PLAN, BLOCKS and SLOTS stay whole: they describe the plan."""
 
-    def __init__(self, batch, extent, width):
+    def __init__(self, batch, extent, width, levels=None, dtypes=None):
         import seunet_amd  # noqa: F401
         from seunet_amd import _lib
         from seunet_amd.SE_UNet import SE_UNet, conv_plan, make_desc
         if not os.path.exists(_lib.LIB_PATH):
             import __graft_entry__
             __graft_entry__.build()
-        self.batch, self.extent, self.width = batch, extent, width
+        self.batch, self.extent, self.width = batch, extents(extent), width
+        self.levels = None if levels is None else tuple(levels)
+        self.dtypes = None if dtypes is None else tuple(dtypes)
         self.key = (batch, extent, width)
-        self.PLAN_LIST = conv_plan(make_desc(batch, 2, 1, extent, extent, extent, width, _lib.BF16, 0, SLOPE))
+        self.PLAN_LIST = conv_plan(make_desc(batch, 2, 1, *self.extent, width, _lib.BF16, 0, SLOPE))
         with torch.random.fork_rng(devices=[]):      # seeded initial values without touching the session's generator
             torch.default_generator.manual_seed(1234)     # (the CPU generator only: parameters are drawn on the CPU)
             self.NET = SE_UNet(2, 1, width_mult=width, act_dtype="bf16", negative_slope=SLOPE)
         self.SLOTS = {c["level"]: slots_of(c["dims"]) for c in self.PLAN_LIST}
         self.PLAN = {c["name"]: c for c in self.PLAN_LIST}
         self.BLOCKS = B = self._blocks()
-        self.GATED = [n for n, b in B.items() if b["gated"]]
-        self.AGG = [n for n, b in B.items() if not b["gated"]]
+        on = lambda level: self.levels is None or level in self.levels
+        dts = lambda level=0: tuple(dt for dt in dtypes_for(level) if self.dtypes is None or dt in self.dtypes)
+        self.GATED = [n for n, b in B.items() if b["gated"] and on(b["level"])]
+        self.AGG = [n for n, b in B.items() if not b["gated"] and on(b["level"])]
         self.AGG_X = [n for n in self.AGG if B[n]["xr"]]
         self.AGG_1 = [n for n in self.AGG if not B[n]["xr"]]
         self.max_C = max(b["C"] for b in B.values())
-        self.UPS = [(n, B[b["up_from"]]["C"], B[b["up_from"]]["dims"]) for n, b in B.items() if b["up_from"]]
+        self.UPS = [(n, B[b["up_from"]]["C"], B[b["up_from"]]["dims"]) for n, b in B.items() if b["up_from"] and on(b["level"] + 1)]
         self.POOLS = [(n, B[n]["C"], B[n]["dims"]) for n in self.AGG_X]                            # pool0 / pool1 / pool2
         self.POOLS_X = [(self.PLAN[n]["x_name"], 8, self.PLAN_LIST[[c["level"] for c in self.PLAN_LIST].index(B[n]["level"] - 1)]["dims"])
-                        for n in self.AGG_X if B[n]["level"] >= 1]                                 # pool0x / pool1x: the packed input
-        self.GATE_CASES = [(n, dt) for n in self.GATED for dt in dtypes_for(B[n]["level"])]
-        self.X_CASES = [(n, dt, kind) for n in self.AGG_X for dt in dtypes_for(B[n]["level"]) for kind in ("random", "ties")]
-        self.AGG1_CASES = [(n, dt) for n in self.AGG_1 for dt in dtypes_for(B[n]["level"])]
-        self.POOL_FWD_CASES = [(n, c, dims, dt) for n, c, dims in self.POOLS + self.POOLS_X for dt in ("bf16", "fp16")]
-        self.POOL_BWD_CASES = [(n, c, dims, dt, acc) for n, c, dims in self.POOLS for dt in ("bf16", "fp16") for acc in (0, 1)]
-        self.UP_CASES = [(n, c, dims, dt) for n, c, dims in self.UPS for dt in ("bf16", "fp16")]
+                        for n, b in B.items() if not b["gated"] and b["xr"] and b["level"] >= 1 and on(b["level"] - 1)]   # pool0x / pool1x: the packed input
+        self.GATE_CASES = [(n, dt) for n in self.GATED for dt in dts(B[n]["level"])]
+        self.X_CASES = [(n, dt, kind) for n in self.AGG_X for dt in dts(B[n]["level"]) for kind in ("random", "ties")]
+        self.AGG1_CASES = [(n, dt) for n in self.AGG_1 for dt in dts(B[n]["level"])]
+        self.POOL_FWD_CASES = [(n, c, dims, dt) for n, c, dims in self.POOLS + self.POOLS_X for dt in dts()]
+        self.POOL_BWD_CASES = [(n, c, dims, dt, acc) for n, c, dims in self.POOLS for dt in dts() for acc in (0, 1)]
+        self.UP_CASES = [(n, c, dims, dt) for n, c, dims in self.UPS for dt in dts()]
         self.UP_BWD_CASES = [c + (acc,) for c in self.UP_CASES for acc in (0, 1)]
 
     def _blocks(self):
@@ -575,9 +583,9 @@ def upsample_backward(S, case, grad_scale=None, store_check=None):
 def head_forward(S, cfg, nlevels):
     """pred = bias + level 0 + sum_l interpolation_{2^l}(level l).  Per coarse term 10 roundings (as the up-sampling forward:
     two weights, their product, 4 products and 3 additions, then 1 - lx, a product, an addition); the chain adds <= 4 terms."""
-    n, D = cfg.batch, cfg.extent
+    n, (D, H, W) = cfg.batch, cfg.extent
     g = gen(seed_of("head", nlevels))
-    maps = [torch.randn((n, D >> l, D >> l, D >> l), generator=g, device="cuda") * (1 + l) + 0.3 for l in range(nlevels)]
+    maps = [torch.randn((n, D >> l, H >> l, W >> l), generator=g, device="cuda") * (1 + l) + 0.3 for l in range(nlevels)]
     bias = torch.randn(1, generator=g, device="cuda")
     pred = S.head_fwd(maps, bias)
     for i in range(n):
@@ -593,20 +601,20 @@ def head_forward(S, cfg, nlevels):
 
 
 def head_backward(S, cfg, nlevels, grad_scale=None):
-    """Three axis passes per level, each a chain of up to T_l taps (weight 2 roundings, product 1): L = 3 T_l, K = 9.  The bias
-    gradient's partials are all f64: 1 ulp of f32 at the float64 sum."""
-    n, D = cfg.batch, cfg.extent
-    g_pred = scale_grad(torch.randn((n, 1, D, D, D), generator=gen(seed_of("headb", nlevels)), device="cuda") + 0.1, grad_scale)
+    """Three axis passes per level, each a chain of up to T taps of its own axis (weight 2 roundings, product 1): L = T_x + T_y +
+    T_z (3 T_l on a cube), K = 9.  The bias gradient's partials are all f64: 1 ulp of f32 at the float64 sum."""
+    n, (D, H, W) = cfg.batch, cfg.extent
+    g_pred = scale_grad(torch.randn((n, 1, D, H, W), generator=gen(seed_of("headb", nlevels)), device="cuda") + 0.1, grad_scale)
     lv, gb = S.head_bwd(g_pred, nlevels)
     tot = g_pred.double().sum()
     report(gb, tot.reshape(1), R.ulp32(tot).reshape(1) + g_pred.numel() * 2.0 ** -53 * g_pred.double().abs().sum().reshape(1), "head_bwd bias gradient")
     for l in range(1, nlevels):
-        taps = R.max_taps(D >> l, 2 ** l, "cuda")
+        taps = sum(R.max_taps(e >> l, 2 ** l, "cuda") for e in (D, H, W))
         for i in range(n):
             x = g_pred[i, 0].double()[..., None]
             ref = R.upsample(x, 2 ** l, transpose=True)[..., 0]
             S_ = R.upsample(x.abs(), 2 ** l, transpose=True)[..., 0]
-            report(lv[l][i], ref, R.sum_bound(S_, 3 * taps, 9) + U * R.lambda_term(x.abs(), 2 ** l, transpose=True)[..., 0], f"head_bwd {nlevels} levels, level {l} [{i}]")
+            report(lv[l][i], ref, R.sum_bound(S_, taps, 9) + U * R.lambda_term(x.abs(), 2 ** l, transpose=True)[..., 0], f"head_bwd {nlevels} levels, level {l} [{i}]")
 
 
 # ---- one forward of the real network, block by block -----------------------------------------------------------------------------
@@ -627,13 +635,14 @@ def network_forward_block_by_block(S, cfg, dtype):
         net = SE_UNet(2, 1, width_mult=cfg.width, act_dtype=dtype, negative_slope=SLOPE)
     net = net.cuda().eval()
     g = gen(seed_of("net", dtype))
-    x = torch.randn((cfg.batch, 2, cfg.extent, cfg.extent, cfg.extent), generator=g, device="cuda")
+    D, H, W = cfg.extent
+    x = torch.randn((cfg.batch, 2, D, H, W), generator=g, device="cuda")
     x = x * torch.tensor([1.0, 0.6], device="cuda").view(1, 2, 1, 1, 1) + 0.4 * torch.randn((cfg.batch, 2, 1, 1, 1), generator=g, device="cuda")
     x_lv = [x.to(R.storage(dtype)).float()]                       # the network's rounded copy of the input, pooled per level
     for _ in range(2):
         x_lv.append(F.max_pool3d(x_lv[-1], 2))
-    D = cfg.extent
-    lvl = {(hd, l): torch.zeros((cfg.batch, (D >> l) ** 3), dtype=torch.float64, device="cuda") for hd in (0, 1) for l in range(4 - hd)}
+    ext = lambda l: (D >> l, H >> l, W >> l)           # the level maps are (N, 1, D_l, H_l, W_l)
+    lvl = {(hd, l): torch.zeros((cfg.batch, (D >> l) * (H >> l) * (W >> l)), dtype=torch.float64, device="cuda") for hd in (0, 1) for l in range(4 - hd)}
     lvl_S = {k: torch.zeros_like(v) for k, v in lvl.items()}
     heads = (net.dc0_0, net.dc0_1)
     groups = [[n] for n in cfg.PLAN if cfg.BLOCKS[n]["level"] == 0] + [[n for n in cfg.PLAN if cfg.BLOCKS[n]["level"] == l] for l in (1, 2, 3)]
@@ -680,12 +689,12 @@ def network_forward_block_by_block(S, cfg, dtype):
     for hd, pred in ((0, pred0), (1, pred1)):
         bias = f64(heads[hd].bias)
         for i in range(cfg.batch):
-            ref = bias + lvl[(hd, 0)][i].reshape(D, D, D)
-            S_ = bias.abs() + lvl_S[(hd, 0)][i].reshape(D, D, D)
+            ref = bias + lvl[(hd, 0)][i].reshape(D, H, W)
+            S_ = bias.abs() + lvl_S[(hd, 0)][i].reshape(D, H, W)
             lam = 0.0
             for l in range(1, 4 - hd):
-                m = lvl[(hd, l)][i].reshape(D >> l, D >> l, D >> l, 1)
-                ms = lvl_S[(hd, l)][i].reshape(D >> l, D >> l, D >> l, 1)
+                m = lvl[(hd, l)][i].reshape(*ext(l), 1)
+                ms = lvl_S[(hd, l)][i].reshape(*ext(l), 1)
                 ref = ref + R.upsample(m, 2 ** l)[..., 0]
                 S_ = S_ + R.upsample(ms, 2 ** l)[..., 0]
                 lam = lam + U * R.lambda_term(ms, 2 ** l)[..., 0]

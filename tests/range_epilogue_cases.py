@@ -187,8 +187,8 @@ def upsample_backward_nonfinite(S, case):
 
 
 def head_backward_nonfinite(S, cfg, nlevels):
-    n, D = cfg.batch, cfg.extent
-    g_pred = torch.randn((n, 1, D, D, D), generator=E.gen(E.seed_of("headb", nlevels, "nf")), device="cuda") + 0.1
+    n, (D, H, W) = cfg.batch, cfg.extent
+    g_pred = torch.randn((n, 1, D, H, W), generator=E.gen(E.seed_of("headb", nlevels, "nf")), device="cuda") + 0.1
 
     def run(gg):
         lv, gb = S.head_bwd(gg, nlevels)
