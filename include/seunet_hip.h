@@ -634,6 +634,40 @@ int seunet_branch_wall_stats(const int* parsing, const unsigned char* skeleton, 
                              double s0, double s1, double s2, long long* wall_count, long long* offset_sq_sum, double* wall_sq_min,
                              double* wall_sq_max, int* status_dev, seunet_stream_t s);
 
+/* ---- airway cross-sections: the lumen section perpendicular to the centreline at every centreline point ---------
+ * The reference measures nothing of the kind; the definition is this comment, restated operation by operation in numpy by
+ * tests/cross_section_oracle.py, and every output equals that oracle bit for bit.  parsing, skeleton, num: as seunet_branch_stats.
+ * A point is a labelled skeleton voxel (skeleton != 0, 1 <= parsing <= num); points are numbered in raster order.
+ *
+ * seunet_cross_section_count marks and numbers the points (no atomics in the numbering) and synchronises the stream once to
+ * return *m, their number, and *status: 1 if a parsing value outside 0..num was met (that voxel is no point), 0 otherwise.
+ * workspace: seunet_cross_section_workspace_bytes(n0, n1, n2) bytes, handed unchanged to the emit call.
+ *
+ * seunet_cross_section_emit (m >= 1, the count call's) writes per point, without synchronising and with no launch or pass per
+ * point or per label: lin int32[m], its linear index; tangent float64[m][3]; table int32[m][12] = i0, i1, i2, label, support,
+ * count, sum i, sum j, sum i^2, sum j^2, sum ij, rim.  All float64 operations are single IEEE operations in the order written,
+ * none contracted into a fused multiply-add.  With p the point, k its label, (s0, s1, s2) the spacing, h = step, W = window (1..7):
+ *   tangent  over the skeleton voxels q of label k with |q - p|_inf <= W (p included; support = n, their number), d = q - p:
+ *            S_ab = n sum d_a d_b - sum d_a sum d_b in int64; C_ab = ((double)S_ab * s_a) * s_b for a <= b, C_ba = C_ab.  Invalid
+ *            (tangent 0, count, moments and rim 0) when n < 3 or max |C_ab| is not positive.  A = C / max |C_ab|; six times
+ *            B_ab = (A_a0 A_0b + A_a1 A_1b) + A_a2 A_2b, A = B / max |B_ab|.  The column c of largest (A_0c^2 + A_1c^2) + A_2c^2
+ *            (the lowest on a tie) divided by the root of that sum is t; t is negated when its component of largest magnitude
+ *            (the lowest on a tie) is negative.
+ *   basis    a = the index of smallest |t_a| (the lowest on a tie); w_b = [a == b] - t_a t_b; u = w / sqrt((w_0^2 + w_1^2) + w_2^2);
+ *            v = t x u, v_0 = t_1 u_2 - t_2 u_1 and cyclically.
+ *   samples  column i and row j in -31..31: x_a = (p_a s_a + (i h) u_a) + (j h) v_a, voxel_a = floor(x_a / s_a + 0.5).  A sample is
+ *            inside when its voxel lies in the volume and parsing there equals k (same_label != 0) or is non-zero (same_label == 0).
+ *   section  the 4-connected set of inside samples that contains (0, 0); count, the moments and rim (the section's samples with
+ *            |i| = 31 or |j| = 31; > 0: the section is cut by the grid) are taken over it.
+ * seunet_cross_section_sweep_points: the points one grid sweep of the section pass takes (tests put more points than that). */
+size_t seunet_cross_section_workspace_bytes(int n0, int n1, int n2);
+int seunet_cross_section_sweep_points(void);
+int seunet_cross_section_count(const int* parsing, const unsigned char* skeleton, int n0, int n1, int n2, int num, long long* m, int* status,
+                               void* workspace, size_t workspace_bytes, seunet_stream_t s);
+int seunet_cross_section_emit(const int* parsing, const unsigned char* skeleton, int n0, int n1, int n2, double s0, double s1, double s2,
+                              double step, int window, int same_label, long long m, int* lin, double* tangent, int* table,
+                              const void* workspace, size_t workspace_bytes, seunet_stream_t s);
+
 /* ---- surface distances: Hausdorff distance, its percentiles, ASSD and surface Dice in the units of the spacing --
  * The reference computes none of them; the definition is this comment, restated in numpy by tests/surface_oracle.py.
  * a, b: two 0/1 volumes (bytes, non-zero = 1, C-contiguous (n0, n1, n2), extents <= 32767, fewer than 2^31 voxels).

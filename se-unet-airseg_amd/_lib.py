@@ -166,6 +166,10 @@ PROTOTYPES = {
     "seunet_mesh_label_emit": (_i, [_vp, _i, _i, _i, _i, _d, _ll, _ll, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "seunet_branch_stats": (_i, [_vp, _vp, _vp, _i, _i, _i, _i] + [_vp] * 11 + [_vp]),
     "seunet_branch_wall_stats": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _d, _d, _d, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "seunet_cross_section_workspace_bytes": (_sz, [_i, _i, _i]),
+    "seunet_cross_section_sweep_points": (_i, []),
+    "seunet_cross_section_count": (_i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(_ll), _ip, _vp, _sz, _vp]),
+    "seunet_cross_section_emit": (_i, [_vp, _vp, _i, _i, _i, _d, _d, _d, _d, _i, _i, _ll, _vp, _vp, _vp, _vp, _sz, _vp]),
     "seunet_surface_workspace_bytes": (_sz, [_i, _i, _i]),
     "seunet_surface_count": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(_ll), C.POINTER(_ll), _ip, _vp, _sz, _vp]),
     "seunet_surface_emit_workspace_bytes": (_sz, [_i, _i, _i]),

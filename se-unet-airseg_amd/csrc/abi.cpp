@@ -41,7 +41,7 @@ int seunet_debug_upsample2_form(int dtype, int c, seunet_dims dims, int backward
 // diagnostic hook (not part of the public header, host only): the workspace layout of a volume operation as its launcher
 // carves it.  op: 0 cc, 1 get_l, 2 edt, 3 lib_weight, 4 break_weight, 5 skeleton_branches, 6 dti, 7 skeleton, 8 parse_assign,
 // 9 binary_morph, 10 mesh, 11 mesh_label, 12 edt_sampling, 13 surface (count), 14 surface_emit (extents of the box), 15 label,
-// 16 euler, 17 betti (the last two for the whole volume: one tile).
+// 16 euler, 17 betti (the last two for the whole volume: one tile), 18 cross_section.
 // Returns the number of sub-buffers (0: extents the op rejects, -1: no such op) and writes (offset, bytes up to the next
 // sub-buffer or the end) of the first `cap`.
 int seunet_debug_volume_layout(int op, int n0, int n1, int n2, size_t* offsets, int cap) {
@@ -68,6 +68,7 @@ int seunet_debug_volume_layout(int op, int n0, int n1, int n2, size_t* offsets, 
     case 15: if ((long long)n0 * n1 * n2 >= (1ll << 31)) return 0; label_ws(c, n0, n1, n2); break;
     case 16: if ((long long)n0 * n1 * n2 >= (1ll << 31)) return 0; euler_ws(c, n0, n1, n2, 1); break;
     case 17: if ((long long)n0 * n1 * n2 >= (1ll << 31)) return 0; betti_ws(c, n0, n1, n2, 1); break;
+    case 18: if ((long long)n0 * n1 * n2 >= (1ll << 31)) return 0; cross_section_ws(c, n0, n1, n2); break;
     default: return -1;
   }
   if (c.taken > c.log_cap) return -1;
@@ -588,6 +589,21 @@ int seunet_branch_wall_stats(const int* parsing, const unsigned char* skeleton, 
                              double* wall_sq_max, int* status_dev, seunet_stream_t s) {
   return launch_branch_wall_stats(parsing, skeleton, indices, n0, n1, n2, num, s0, s1, s2,
                                   BranchWallOut{wall_count, offset_sq_sum, wall_sq_min, wall_sq_max, status_dev}, S(s));
+}
+size_t seunet_cross_section_workspace_bytes(int n0, int n1, int n2) {
+  if (volume_check("cross_section_workspace_bytes", n0, n1, n2, 0)) return 0;
+  return cross_section_workspace_bytes(n0, n1, n2);
+}
+int seunet_cross_section_sweep_points(void) { return cross_section_sweep_points(); }
+int seunet_cross_section_count(const int* parsing, const unsigned char* skeleton, int n0, int n1, int n2, int num, long long* m, int* status,
+                               void* workspace, size_t workspace_bytes, seunet_stream_t s) {
+  return launch_cross_section_count(parsing, skeleton, n0, n1, n2, num, m, status, workspace, workspace_bytes, S(s));
+}
+int seunet_cross_section_emit(const int* parsing, const unsigned char* skeleton, int n0, int n1, int n2, double s0, double s1, double s2,
+                              double step, int window, int same_label, long long m, int* lin, double* tangent, int* table,
+                              const void* workspace, size_t workspace_bytes, seunet_stream_t s) {
+  return launch_cross_section_emit(parsing, skeleton, n0, n1, n2, s0, s1, s2, step, window, same_label, m, lin, tangent, table, workspace,
+                                   workspace_bytes, S(s));
 }
 size_t seunet_surface_workspace_bytes(int n0, int n1, int n2) {
   if (volume_check("surface_workspace_bytes", n0, n1, n2, kEdtMaxExtent)) return 0;

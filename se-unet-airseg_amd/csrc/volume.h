@@ -1,5 +1,5 @@
 // Shared layer of the volume operations (components.hip, lung.hip, edt.hip, edt_sampling.hip, parse.hip, skeleton.hip, dti.hip,
-// morph.hip, mesh.hip, mesh_label.hip, morphometry.hip, cldice.hip, surface.hip, betti.hip): their launcher prototypes, ONE
+// morph.hip, mesh.hip, mesh_label.hip, morphometry.hip, cldice.hip, surface.hip, betti.hip, cross_section.hip): their launcher prototypes, ONE
 // workspace layout per operation, the extent check and the voxel / wave helpers their kernels share.  The bit-packed
 // representation seven of them work on -- geometry, packing, neighbour words, the scan, wave counts -- is bitvol.h / bitvol.hip.
 //
@@ -387,6 +387,28 @@ struct BranchWallOut {
 };
 int launch_branch_wall_stats(const int* parsing, const unsigned char* skeleton, const int* indices, int n0, int n1, int n2, int num,
                              double s0, double s1, double s2, BranchWallOut out, hipStream_t s);
+
+// ---- airway cross-sections (cross_section.hip): the lumen section perpendicular to the centreline at every labelled skeleton voxel --
+struct CrossRec { u64 total[2]; int status, pad; };   // what the host reads once: the scan's grand total, the label status
+struct CrossWs {
+  CrossRec* rec;
+  u64* bits;                      // the point mask: one word per 64 voxels in raster order (not per row)
+  unsigned* cnt;                  // per word: points, then their exclusive scan inside a block of 1024 words
+  unsigned* blk;                  // per block: its total, then the exclusive scan of the totals
+};
+static inline CrossWs cross_section_ws(WsCarver& c, int n0, int n1, int n2) {
+  const size_t nwords = ((size_t)n0 * n1 * n2 + 63) / 64, blocks = (nwords + kScanBlock - 1) / kScanBlock;
+  return CrossWs{c.take<CrossRec>(1), c.take<u64>(nwords), c.take<unsigned>(nwords), c.take<unsigned>(blocks)};
+}
+size_t cross_section_workspace_bytes(int n0, int n1, int n2);
+int cross_section_sweep_points();         // points one grid sweep of the section pass takes (one wave each)
+// count: mark, scan; synchronises once to return the number of points and the label status (1: a label outside 0 .. num).
+// emit: lin (m int32), tangent (m x 3 float64) and table (m x 12 int32) from the same workspace; does not synchronise.
+int launch_cross_section_count(const int* parsing, const unsigned char* skeleton, int n0, int n1, int n2, int num, long long* m, int* status,
+                               void* workspace, size_t ws_bytes, hipStream_t s);
+int launch_cross_section_emit(const int* parsing, const unsigned char* skeleton, int n0, int n1, int n2, double s0, double s1, double s2,
+                              double step, int window, int same_label, long long m, int* lin, double* tangent, int* table,
+                              const void* workspace, size_t ws_bytes, hipStream_t s);
 
 // ---- soft skeleton / soft clDice loss / hard clDice counts (cldice.hip) -----------------------------------------------------
 // `volumes` independent (n0, n1, n2) volumes back to back; n = volumes n0 n1 n2 voxels.  A forward that keeps no state needs

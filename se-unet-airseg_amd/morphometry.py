@@ -8,9 +8,15 @@ include/seunet_hip.h, restated in plain numpy by tests/morphometry_oracle.py, an
 
 ``branch_wall_distance`` reduces the feature transform of the EDT with voxel spacing over the skeleton in one
 more streaming pass: the distance from the centreline to the wall per branch as a length, which ``branch_morphometry(...,
-inscribed="physical")`` puts into the table; its tables equal tests/wall_distance_oracle.py bit for bit."""
+inscribed="physical")`` puts into the table; its tables equal tests/wall_distance_oracle.py bit for bit.
+
+``cross_sections`` (csrc/cross_section.hip) measures the lumen section perpendicular to the centreline at every
+labelled skeleton voxel, one wave per point: its sample count, five integer moments and the samples on the grid's rim, from which
+area and major / minor diameter follow on the host; ``branch_morphometry(..., cross_sections=True)`` reduces them per branch.  Its
+integer columns and its float64 tangents equal tests/cross_section_oracle.py bit for bit."""
 from __future__ import annotations
 
+import ctypes as C
 import dataclasses
 from typing import Dict, Optional, Sequence, Tuple
 
@@ -206,6 +212,172 @@ def branch_wall_distance(parsing, skeleton, spacing, num: Optional[int] = None, 
     return _branch_wall(vol, skel, ind, s, num)
 
 
+SECTION_HALF = 31                                            # the sample plane is 63 x 63: columns and rows -31 .. 31
+SECTION_COLUMNS = ("section_count", "area_mean", "area_min", "area_max", "area_median", "diameter_major_mean", "diameter_minor_mean")
+
+
+@dataclasses.dataclass
+class CrossSections:
+    """One row per labelled skeleton voxel (``skeleton != 0``, ``1 <= parsing <= num``) in raster order.  Integer columns, from the
+    device: ``coord`` int32[m, 3]; ``label`` int32[m]; ``support`` int32[m], the same-label skeleton voxels in the tangent window;
+    ``count`` int32[m], the samples in the section; ``moments`` int32[m, 5], the sums of i, j, i^2, j^2 and ij over the section's
+    samples (column i, row j in -31 .. 31); ``rim`` int32[m], the section's samples on the outermost ring of the grid (> 0: the
+    section is cut off by the grid).  ``tangent`` float64[m, 3]: the unit tangent, zeros where it is invalid (then ``count`` is 0).
+    float64 columns derived on the host: ``area = count * step^2``; ``diameter_major`` / ``diameter_minor = 4 step sqrt(lambda)``
+    with lambda the larger / smaller eigenvalue of the samples' 2 x 2 covariance, 1/12 added on its diagonal so that a sample
+    stands for a step x step square (the diameters of the ellipse with those second moments; nan where ``count`` is 0);
+    ``valid = (count > 0) & (rim == 0)``.  Lengths are in the units of ``spacing``."""
+    num: int
+    spacing: Tuple[float, float, float]
+    step: float
+    window: int
+    same_label: bool
+    coord: np.ndarray
+    label: np.ndarray
+    support: np.ndarray
+    tangent: np.ndarray
+    count: np.ndarray
+    moments: np.ndarray
+    rim: np.ndarray
+    area: np.ndarray
+    diameter_major: np.ndarray
+    diameter_minor: np.ndarray
+    valid: np.ndarray
+
+    def __len__(self) -> int:
+        return int(self.label.shape[0])
+
+    def to_dict(self) -> dict:
+        return {f.name: getattr(self, f.name) for f in dataclasses.fields(self)}
+
+    @classmethod
+    def from_columns(cls, coord, label, support, tangent, count, moments, rim, step: float, num: Optional[int] = None,
+                     spacing: Sequence[float] = (1.0, 1.0, 1.0), window: int = 4, same_label: bool = True) -> "CrossSections":
+        """The derived columns from the integer ones; host only."""
+        step = float(step)
+        if not (np.isfinite(step) and step > 0):
+            raise ValueError(f"{_PREFIX}: step must be positive and finite, got {step}")
+        label = np.asarray(label, dtype=np.int32).reshape(-1)
+        m = label.size
+        count = np.asarray(count, dtype=np.int32).reshape(m)
+        moments = np.asarray(moments, dtype=np.int32).reshape(m, 5)
+        rim = np.asarray(rim, dtype=np.int32).reshape(m)
+        c = count.astype(np.float64)
+        mo = moments.astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            mean_i, mean_j = mo[:, 0] / c, mo[:, 1] / c
+            var_i = mo[:, 2] / c - mean_i * mean_i + 1.0 / 12.0
+            var_j = mo[:, 3] / c - mean_j * mean_j + 1.0 / 12.0
+            cov = mo[:, 4] / c - mean_i * mean_j
+            mid = 0.5 * (var_i + var_j)
+            rad = np.sqrt(0.25 * (var_i - var_j) * (var_i - var_j) + cov * cov)
+            major = 4.0 * step * np.sqrt(mid + rad)
+            minor = 4.0 * step * np.sqrt(np.maximum(mid - rad, 0.0))
+        empty = count <= 0
+        return cls(num=int(label.max()) if num is None and m else int(num or 0), spacing=tuple(float(v) for v in spacing), step=step,
+                   window=int(window), same_label=bool(same_label), coord=np.asarray(coord, dtype=np.int32).reshape(m, 3), label=label,
+                   support=np.asarray(support, dtype=np.int32).reshape(m), tangent=np.asarray(tangent, dtype=np.float64).reshape(m, 3),
+                   count=count, moments=moments, rim=rim, area=c * (step * step), diameter_major=np.where(empty, np.nan, major),
+                   diameter_minor=np.where(empty, np.nan, minor), valid=(count > 0) & (rim == 0))
+
+    def per_branch(self, num: Optional[int] = None) -> Dict[str, np.ndarray]:
+        """Per label 1..num (row k - 1 = label k) over its ``valid`` rows: ``section_count`` int64[num]; ``area_mean``, ``area_min``,
+        ``area_max``, ``area_median``, ``diameter_major_mean``, ``diameter_minor_mean`` float64[num], nan for a label without one."""
+        num = self.num if num is None else int(num)
+        out = {"section_count": np.zeros(num, np.int64)}
+        for k in SECTION_COLUMNS[1:]:
+            out[k] = np.full(num, np.nan, np.float64)
+        rows = np.flatnonzero(self.valid & (self.label >= 1) & (self.label <= num))
+        if rows.size == 0:
+            return out
+        rows = rows[np.lexsort((self.area[rows], self.label[rows]))]       # by label, a label's rows by area
+        labels, start, n = np.unique(self.label[rows], return_index=True, return_counts=True)
+        at = labels - 1
+        area = self.area[rows]
+        out["section_count"][at] = n
+        out["area_mean"][at] = np.add.reduceat(area, start) / n
+        out["area_min"][at] = area[start]
+        out["area_max"][at] = area[start + n - 1]
+        out["area_median"][at] = 0.5 * (area[start + (n - 1) // 2] + area[start + n // 2])
+        out["diameter_major_mean"][at] = np.add.reduceat(self.diameter_major[rows], start) / n
+        out["diameter_minor_mean"][at] = np.add.reduceat(self.diameter_minor[rows], start) / n
+        return out
+
+
+def _cross_sections(vol, skel, s, step: float, window: int, same_label: bool, num: int) -> CrossSections:
+    """``cross_sections`` for device inputs and parameters that are already checked."""
+    lib = _lib.load()
+    cap = int(lib.seunet_label_stats_max_num())
+    if not 0 <= num <= cap:
+        raise ValueError(f"{_PREFIX}: labels up to {cap} are supported, got num = {num}")
+    shape = tuple(int(v) for v in vol.shape)
+    m, host = 0, None
+    if vol.numel():
+        dev = vol.device
+        with torch.cuda.device(dev):
+            ws_bytes = int(lib.seunet_cross_section_workspace_bytes(*shape))
+            if ws_bytes == 0:
+                raise ValueError(f"{_PREFIX}: {_lib.last_error()}")
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            n_points, status = C.c_longlong(0), C.c_int(0)
+            _lib.check(lib.seunet_cross_section_count(vol.data_ptr(), skel.data_ptr(), *shape, num, C.byref(n_points), C.byref(status),
+                                                      ws.data_ptr(), ws_bytes, _lib.stream_ptr()), "cross_section_count")
+            if status.value != 0:
+                raise ValueError(f"{_PREFIX}: the volume holds a label outside 0..{num}")
+            m = int(n_points.value)                           # the one host read that sizes the outputs
+            if m:
+                # one buffer of 8-byte words: tangent (3 per point), table (12 int32 per point), lin (one int32 per point)
+                buf = torch.empty(3 * m + 6 * m + (m + 1) // 2, dtype=torch.int64, device=dev)
+                base = buf.data_ptr()
+                _lib.check(lib.seunet_cross_section_emit(vol.data_ptr(), skel.data_ptr(), *shape, s[0], s[1], s[2], step, window,
+                                                         int(same_label), m, base + 8 * 9 * m, base, base + 8 * 3 * m, ws.data_ptr(),
+                                                         ws_bytes, _lib.stream_ptr()), "cross_section_emit")
+                host = buf.cpu().numpy()                         # the one copy back
+    if m == 0:
+        tangent, table = np.zeros((0, 3), np.float64), np.zeros((0, 12), np.int32)
+    else:
+        tangent = host[:3 * m].view(np.float64).reshape(m, 3).copy()
+        table = host[3 * m:9 * m].view(np.int32).reshape(m, 12)
+    return CrossSections.from_columns(table[:, 0:3].copy(), table[:, 3].copy(), table[:, 4].copy(), tangent, table[:, 5].copy(),
+                                      table[:, 6:11].copy(), table[:, 11].copy(), step, num, s, window, same_label)
+
+
+def _section_args(spacing, step, window):
+    s = prep.normalize_sampling(spacing, "spacing")
+    step = min(s) / 2.0 if step is None else float(step)
+    if not (np.isfinite(step) and step > 0):
+        raise ValueError(f"{_PREFIX}: step must be positive and finite, got {step}")
+    if int(window) != window or not 1 <= int(window) <= 7:
+        raise ValueError(f"{_PREFIX}: window must be an integer in 1..7, got {window!r}")
+    return s, step, int(window)
+
+
+def cross_sections(parsing, skeleton, spacing: Sequence[float] = (1.0, 1.0, 1.0), step: Optional[float] = None, window: int = 4,
+                   same_label: bool = True, num: Optional[int] = None) -> CrossSections:
+    """The lumen cross-section perpendicular to the centreline at every labelled skeleton voxel: ``CrossSections``, one row per point.
+
+    At a point p of label k the tangent is the dominant direction of the physical scatter of the label's skeleton voxels within
+    ``window`` voxels (Chebyshev) of p; a plane of 63 x 63 samples of pitch ``step`` (``None``: ``min(spacing) / 2``; in the units
+    of ``spacing``) through p perpendicular to it is sampled by nearest voxel; a sample is inside when its voxel carries label k
+    (``same_label=False``: any label); the section is the 4-connected set of inside samples that contains p.  A section that
+    reaches the outermost ring of the grid is cut off (``rim > 0``, ``valid`` False): choose a larger ``step``.  A point with fewer
+    than 3 same-label skeleton voxels in its window has no tangent (``tangent`` 0, ``count`` 0).  The exact definition, operation by
+    operation, is include/seunet_hip.h and tests/cross_section_oracle.py.
+
+    ``parsing``: integer labels 0..num; ``skeleton``: 0/1 mask; ``spacing``: a positive number or three; ``window``: 1..7.  CUDA
+    tensors or numpy arrays; the inputs are not modified.  One host read of the number of points sizes the outputs and carries the
+    label status; after it there is no launch, pass or synchronise per point or per label, and the call ends in one copy back.
+    ``num=None`` takes ``int(parsing.max())``, which reads the device once more.  ValueError: a label outside 0..num, ``num`` above
+    4095, mismatched shapes, a bad ``spacing``, ``step`` or ``window``."""
+    s, step, window = _section_args(spacing, step, window)
+    vol, skel, _, _ = _inputs(parsing, skeleton, None)
+    if skel is None:
+        raise ValueError(f"{_PREFIX}: cross_sections needs the skeleton")
+    if num is None:
+        num = max(int(vol.max()), 0) if vol.numel() else 0
+    return _cross_sections(vol, skel, s, step, window, bool(same_label), int(num))
+
+
 def branch_tree(counts, adjacency) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """The branch tree from the face adjacency, on the host.  ``counts``: voxels of the labels 1..num; ``adjacency``: (num, num),
     non-zero where two labels meet across a face (both as ``label_adjacency`` returns them).  The root is the label with the most
@@ -284,16 +456,26 @@ class BranchTable:
     offset_sq_sum: Optional[np.ndarray] = None
     wall_sq_min: Optional[np.ndarray] = None
     wall_sq_max: Optional[np.ndarray] = None
+    section_count: Optional[np.ndarray] = None
+    area_mean: Optional[np.ndarray] = None
+    area_min: Optional[np.ndarray] = None
+    area_max: Optional[np.ndarray] = None
+    area_median: Optional[np.ndarray] = None
+    diameter_major_mean: Optional[np.ndarray] = None
+    diameter_minor_mean: Optional[np.ndarray] = None
 
     def to_dict(self) -> dict:
-        return {f.name: getattr(self, f.name) for f in dataclasses.fields(self)}
+        """Every column by name; the cross-section columns only where they were computed, so the keys without them are unchanged."""
+        return {f.name: getattr(self, f.name) for f in dataclasses.fields(self)
+                if f.name not in SECTION_COLUMNS or getattr(self, f.name) is not None}
 
     @classmethod
     def from_stats(cls, stats: Dict[str, np.ndarray], adjacency, spacing: Sequence[float] = (1.0, 1.0, 1.0),
-                   wall: Optional[Dict[str, np.ndarray]] = None) -> "BranchTable":
+                   wall: Optional[Dict[str, np.ndarray]] = None, sections: Optional["CrossSections"] = None) -> "BranchTable":
         """The derived columns from the integer tables of ``branch_stats`` and a (num, num) face adjacency; host only.  ``wall``: the
         tables of ``branch_wall_distance`` for the same ``spacing``; the inscribed radii are then ``sqrt((s0^2 sum d0^2 + s1^2 sum d1^2
-        + s2^2 sum d2^2) / wall_count)``, ``sqrt(wall_sq_min)`` and ``sqrt(wall_sq_max)``, nan where ``wall_count`` is 0."""
+        + s2^2 sum d2^2) / wall_count)``, ``sqrt(wall_sq_min)`` and ``sqrt(wall_sq_max)``, nan where ``wall_count`` is 0.
+        ``sections``: a ``CrossSections`` of the same volume; its ``per_branch`` columns are added (None otherwise)."""
         s = np.asarray(spacing, dtype=np.float64).reshape(3)
         if not (np.all(np.isfinite(s)) and np.all(s > 0)):
             raise ValueError(f"{_PREFIX}: spacing must be three positive numbers, got {tuple(spacing)}")
@@ -326,11 +508,12 @@ class BranchTable:
                    volume=volume, centroid=centroid, length=length, radius_equivalent=radius_equivalent, radius_inscribed_rms=rms,
                    radius_inscribed_min=rmin, radius_inscribed_max=rmax, parent=parent, generation=generation, n_children=n_children,
                    is_leaf=is_leaf, n_branches=int((voxels > 0).sum()), n_leaves=int(is_leaf.sum()), total_length=float(length.sum()),
-                   max_generation=max_generation, branches_per_generation=per_generation, **(wall or {}))
+                   max_generation=max_generation, branches_per_generation=per_generation, **(wall or {}),
+                   **(sections.per_branch(num) if sections is not None else {}))
 
 
 def branch_morphometry(parsing, skeleton=None, spacing: Sequence[float] = (1.0, 1.0, 1.0), num: Optional[int] = None,
-                       sqdist=None, inscribed: str = "voxel") -> BranchTable:
+                       sqdist=None, inscribed: str = "voxel", cross_sections=None) -> BranchTable:
     """The per-branch table of a ``parsing`` volume (``tree_parsing`` or ``airway_parse``): ``BranchTable``.
 
     ``volume = voxels * s0 s1 s2``; ``centroid = coord_sum / voxels * spacing`` (nan for a label without voxels);
@@ -349,6 +532,11 @@ def branch_morphometry(parsing, skeleton=None, spacing: Sequence[float] = (1.0, 
     ``offset_sq_sum``, ``wall_sq_min`` and ``wall_sq_max`` (None in voxel mode); ``r2_sum`` / ``r2_min`` / ``r2_max`` keep their
     empty values (0, INT32_MAX, -1), and passing ``sqdist`` is a ValueError.
 
+    ``cross_sections``: a ``CrossSections`` of the same volume, or True to compute one with ``cross_sections(parsing, skeleton,
+    spacing, num=num)`` at its defaults; the table then carries, per label over its valid sections, ``section_count``, ``area_mean``,
+    ``area_min``, ``area_max``, ``area_median``, ``diameter_major_mean`` and ``diameter_minor_mean`` (nan for a label without a valid
+    section; None by default).
+
     ``skeleton=None`` thins ``parsing != 0`` with ``skeletonize_3d``; ``sqdist=None`` takes the squared EDT of ``parsing != 0`` (a
     volume without a background voxel has none: ValueError).  ``num=None``: ``int(parsing.max())``.  CUDA tensors or numpy arrays in,
     numpy columns out; the inputs are not modified."""
@@ -358,6 +546,8 @@ def branch_morphometry(parsing, skeleton=None, spacing: Sequence[float] = (1.0, 
     if physical and sqdist is not None:
         raise ValueError(f"{_PREFIX}: `sqdist` is the unit-sampling squared distance; it is not used with inscribed='physical'")
     s = prep.normalize_sampling(spacing, "spacing") if physical else None
+    if cross_sections is not None and cross_sections is not True and not isinstance(cross_sections, CrossSections):
+        raise TypeError(f"{_PREFIX}: cross_sections must be None, True or a CrossSections, got {type(cross_sections).__name__}")
     vol, skel, sq, _ = _inputs(parsing, skeleton, sqdist)
     if num is None:
         num = max(int(vol.max()), 0) if vol.numel() else 0
@@ -374,4 +564,7 @@ def branch_morphometry(parsing, skeleton=None, spacing: Sequence[float] = (1.0, 
     stats = _branch_stats(vol, skel, sq, num)
     wall = _branch_wall(vol, skel, ind, s, num) if physical else None
     _, adjacency = prep._label_stats(vol, num)
-    return BranchTable.from_stats(stats, adjacency[1:, 1:], spacing, wall)
+    sections = cross_sections
+    if sections is True:
+        sections = _cross_sections(vol, skel, *_section_args(spacing, None, 4), True, num)
+    return BranchTable.from_stats(stats, adjacency[1:, 1:], spacing, wall, sections)
