@@ -668,6 +668,57 @@ int seunet_cross_section_emit(const int* parsing, const unsigned char* skeleton,
                               double step, int window, int same_label, long long m, int* lin, double* tangent, int* table,
                               const void* workspace, size_t workspace_bytes, seunet_stream_t s);
 
+/* ---- airway walls: FWHM wall edges on 64 rays in the section plane of every centreline point ---------------------
+ * The reference measures nothing of the kind; the definition is this comment, restated operation by operation in numpy by
+ * tests/airway_wall_oracle.py, and every output equals that oracle bit for bit.  All float64 and float32 operations are single
+ * IEEE operations in the order written, none contracted into a fused multiply-add.
+ *
+ * seunet_airway_walls: one launch on stream s, no workspace, no synchronise, no launch or pass per point, per label or per ray.
+ * ct: the CT, int16 (ct_dtype = SEUNET_IMG_I16) or finite float32 (SEUNET_IMG_F32), C-contiguous (n0, n1, n2) like parsing (int32
+ * labels); a constant shift of the CT (such as +1024) moves an edge by float32 rounding only.  (s0, s1, s2): the spacing; h = step: the section step of
+ * the rows; dr = ray_step > 0; n = n_search in 1..31; c = min_contrast > 0 (float32), all finite.  table int32[m][12], tangent
+ * float64[m][3]: the rows of seunet_cross_section_emit (i0, i1, i2, label, support, count, sum i, sum j, ..., rim), m >= 1.
+ * A point with count == 0 or rim > 0 is not measured: every ray gets code 6, mask 0, sums 0.  Otherwise, with p the point:
+ *   frame    u, v from the tangent as in seunet_cross_section_emit's basis.  c_i = (double)sum_i / (double)count, c_j likewise;
+ *            the origin is the lumen centroid o_a = (p_a s_a + (c_i h) u_a) + (c_j h) v_a.
+ *   rays     r = 0..63 with e_a = C_r u_a + S_r v_a, (C_r, S_r) the committed table of seunet_airway_wall_directions.
+ *   samples  k = 0..63 at rho_k = (double)k dr: x_a = o_a + rho_k e_a, g_a = x_a / s_a, f_a = floor(g_a), w_a = (float)(g_a - f_a).
+ *            A sample is usable when 0 <= f_a and f_a + 1 <= n_a - 1 on every axis; L = the first unusable k, or 64.  P[k] is the
+ *            float32 trilinear value of the CT (corners converted to float32) along axis 2, then 1, then 0, each step
+ *            a + w (b - a).  The label g_k is parsing at floor(g_a + 0.5); a sample is inside when g_k == label (same_label != 0)
+ *            or g_k != 0 (same_label == 0).
+ *   per ray  the first rule that fails gives the code, 0 = measured:
+ *            1 no boundary: L == 0, sample 0 not inside, or no k in 1..L-1 that is not inside; k_b = the smallest such k.
+ *            2 no peak: k_p = argmax P over max(k_b - 1, 0) .. min(k_b + n, L - 1), the lowest k on a tie; fails when k_p + 1 >= L,
+ *              or when k_p is the window's last index and P[k_p + 1] >= P[k_p].
+ *            3 no inner contrast: P_l = min P[0..k_p], P_p = P[k_p]; fails when P_p - P_l < c.
+ *            4 another lumen: walk k from k_p while k < min(k_p + n, L - 1) and P[k + 1] <= P[k]; k_o = where it stops,
+ *              P_o = P[k_o]; fails when g_k != 0 for some k in k_b..k_o.
+ *            5 no outer contrast: P_p - P_o < c.
+ *            measured: H_in = 0.5f (P_l + P_p); k_i = the largest k < k_p with P[k] <= H_in;
+ *              rho_in = ((double)k_i + ((double)H_in - P[k_i]) / ((double)P[k_i + 1] - P[k_i])) dr;
+ *              H_out = 0.5f (P_p + P_o); k_e = the smallest k in k_p..k_o - 1 with P[k + 1] <= H_out;
+ *              rho_out = ((double)k_e + ((double)P[k_e] - H_out) / ((double)P[k_e] - P[k_e + 1])) dr.
+ *            Both denominators are positive: P_l <= H_in < P_p and P_o <= H_out < P_p, because P_p exceeds P_l and P_o by at
+ *            least c > 0 (c no smaller than the spacing of float32 at these values, so that the half sum rounds strictly below
+ *            P_p); k_i + 1 is then either k_p or an index whose value exceeds H_in >= P[k_i], and P[k_e] is either P_p or a
+ *            value above H_out >= P[k_e + 1].  CT magnitudes are below 2^126, so that no difference or sum overflows.
+ *   outputs  mask uint64[m]: bit r set when ray r has code 0.  sums float64[m][6]: the sums over the rays of rho_in, rho_out,
+ *            rho_in^2, rho_out^2, rho_out - rho_in and (double)P_p, a ray with a non-zero code contributing +0.0, each by the fixed
+ *            tree T_{l+1}[r] = T_l[r] + T_l[r ^ (1 << l)], l = 0..5, result T_6[0].  codes uint8[m][64] and edges
+ *            float64[m][64][2] = (rho_in, rho_out), 0 for a ray that is not measured: either may be NULL.
+ * A ray needs no sample past min(L, k_b + 2 n + 2); the device evaluates none, which changes no result.
+ * Host only, usable without a GPU: seunet_airway_wall_rays and _samples return 64; _sweep_points the points one grid sweep takes
+ * (one wave per point; tests put more points than that); _directions writes the table, out[2 r] = C_r, out[2 r + 1] = S_r. */
+int seunet_airway_wall_rays(void);
+int seunet_airway_wall_samples(void);
+int seunet_airway_wall_sweep_points(void);
+int seunet_airway_wall_directions(double out[128]);
+int seunet_airway_walls(const void* ct, int ct_dtype, const int* parsing, int n0, int n1, int n2, double s0, double s1, double s2,
+                        double step, double ray_step, int n_search, float min_contrast, int same_label, long long m, const int* table,
+                        const double* tangent, unsigned long long* mask, double* sums, unsigned char* codes, double* edges,
+                        seunet_stream_t s);
+
 /* ---- surface distances: Hausdorff distance, its percentiles, ASSD and surface Dice in the units of the spacing --
  * The reference computes none of them; the definition is this comment, restated in numpy by tests/surface_oracle.py.
  * a, b: two 0/1 volumes (bytes, non-zero = 1, C-contiguous (n0, n1, n2), extents <= 32767, fewer than 2^31 voxels).

@@ -15,7 +15,8 @@ from .prep import (CandidateSet, airway_parse, binary_closing, binary_dilation, 
                    tree_parsing, tree_parsing_func)
 from .mesh import (LabelMeshes, branch_meshes, label_meshes, marching_cubes, mesh_adjacency, prediction_mesh, smooth_mesh, stl_records,
                    transform_mesh, write_stl)
-from .morphometry import BranchTable, CrossSections, branch_morphometry, branch_stats, branch_tree, branch_wall_distance, cross_sections
+from .morphometry import (AirwayWalls, BranchTable, CrossSections, airway_walls, branch_morphometry, branch_stats, branch_tree,
+                          branch_wall_distance, cross_sections)
 from .preprocess import cut_mask, get_l, large_connected_domain26, preprocess_ct, th_2t
 from .postprocess import (MetricSums, SurfaceMetrics, cldice_score, double_threshold_iteration, evaluation_case, largest_component,
                           maximum_3d, order_statistics, postprocess_prediction, surface_distances, surface_metrics, zero_borders)
@@ -32,6 +33,6 @@ __all__ = ["SE_UNet", "SSEConv", "SSEConv2", "CATConv", "DropLayer", "get_model"
            "binary_erosion", "binary_closing", "binary_fill_holes", "preprocess_ct", "th_2t", "get_l", "large_connected_domain26", "cut_mask",
            "marching_cubes", "smooth_mesh", "write_stl", "prediction_mesh", "mesh_adjacency", "stl_records", "transform_mesh",
            "label_meshes", "branch_meshes", "LabelMeshes", "branch_stats", "branch_tree", "branch_morphometry", "BranchTable", "branch_wall_distance",
-           "cross_sections", "CrossSections",
+           "cross_sections", "CrossSections", "airway_walls", "AirwayWalls",
            "soft_skeleton", "soft_cldice_loss", "cldice_score", "surface_distances", "order_statistics", "surface_metrics", "SurfaceMetrics",
            "label", "remove_small_objects", "euler_number", "betti_numbers", "betti_error", "ComponentTable", "BettiError"]

@@ -170,6 +170,11 @@ PROTOTYPES = {
     "seunet_cross_section_sweep_points": (_i, []),
     "seunet_cross_section_count": (_i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(_ll), _ip, _vp, _sz, _vp]),
     "seunet_cross_section_emit": (_i, [_vp, _vp, _i, _i, _i, _d, _d, _d, _d, _i, _i, _ll, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "seunet_airway_wall_rays": (_i, []),
+    "seunet_airway_wall_samples": (_i, []),
+    "seunet_airway_wall_sweep_points": (_i, []),
+    "seunet_airway_wall_directions": (_i, [C.POINTER(_d)]),
+    "seunet_airway_walls": (_i, [_vp, _i, _vp, _i, _i, _i, _d, _d, _d, _d, _d, _i, _f, _i, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "seunet_surface_workspace_bytes": (_sz, [_i, _i, _i]),
     "seunet_surface_count": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(_ll), C.POINTER(_ll), _ip, _vp, _sz, _vp]),
     "seunet_surface_emit_workspace_bytes": (_sz, [_i, _i, _i]),

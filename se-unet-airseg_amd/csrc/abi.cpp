@@ -605,6 +605,21 @@ int seunet_cross_section_emit(const int* parsing, const unsigned char* skeleton,
   return launch_cross_section_emit(parsing, skeleton, n0, n1, n2, s0, s1, s2, step, window, same_label, m, lin, tangent, table, workspace,
                                    workspace_bytes, S(s));
 }
+int seunet_airway_wall_rays(void) { return airway_wall_rays(); }
+int seunet_airway_wall_samples(void) { return airway_wall_samples(); }
+int seunet_airway_wall_sweep_points(void) { return airway_wall_sweep_points(); }
+int seunet_airway_wall_directions(double* out) {
+  SEUNET_CHECK(out, "airway_wall_directions: null argument");
+  airway_wall_directions(out);
+  return 0;
+}
+int seunet_airway_walls(const void* ct, int ct_dtype, const int* parsing, int n0, int n1, int n2, double s0, double s1, double s2,
+                        double step, double ray_step, int n_search, float min_contrast, int same_label, long long m, const int* table,
+                        const double* tangent, unsigned long long* mask, double* sums, unsigned char* codes, double* edges,
+                        seunet_stream_t s) {
+  return launch_airway_walls(ct, ct_dtype, parsing, n0, n1, n2, s0, s1, s2, step, ray_step, n_search, min_contrast, same_label, m, table,
+                             tangent, mask, sums, codes, edges, S(s));
+}
 size_t seunet_surface_workspace_bytes(int n0, int n1, int n2) {
   if (volume_check("surface_workspace_bytes", n0, n1, n2, kEdtMaxExtent)) return 0;
   return surface_workspace_bytes(n0, n1, n2);

@@ -21,6 +21,7 @@
 //                     popcounts of f under the six index-bit masks, summed over the wave by settled butterflies.
 // No LDS, no atomics, no floating-point reduction: nothing depends on the launch shape.
 #include "volume.h"
+#include "cross_basis.h"
 #include <cmath>
 
 // the tangent, the basis and the sample positions are the oracle's float64 arithmetic operation by operation
@@ -147,24 +148,6 @@ __device__ __forceinline__ bool cross_tangent(long long n, const long long (&sd)
     for (int q = 0; q < 3; ++q) t[q] = -t[q];
   }
   return true;
-}
-
-// u = normalise(e_a - t_a t) with a the index of smallest |t_a| (the lowest on a tie), v = t x u
-__device__ __forceinline__ void cross_basis(const double (&t)[3], double (&u)[3], double (&v)[3]) {
-  int a = 0;
-  double least = fabs(t[0]);
-  if (fabs(t[1]) < least) { a = 1; least = fabs(t[1]); }
-  if (fabs(t[2]) < least) a = 2;
-  const double ta = a == 0 ? t[0] : a == 1 ? t[1] : t[2];
-  double w[3];
-#pragma unroll
-  for (int q = 0; q < 3; ++q) w[q] = (q == a ? 1.0 : 0.0) - ta * t[q];
-  const double len = sqrt((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2]);
-#pragma unroll
-  for (int q = 0; q < 3; ++q) u[q] = w[q] / len;
-  v[0] = t[1] * u[2] - t[2] * u[1];
-  v[1] = t[2] * u[0] - t[0] * u[2];
-  v[2] = t[0] * u[1] - t[1] * u[0];
 }
 
 // one wave per point, grid-stride.  table: 12 int32 per point (i0, i1, i2, label, support, count, sum i, sum j, sum i^2,

@@ -410,6 +410,17 @@ int launch_cross_section_emit(const int* parsing, const unsigned char* skeleton,
                               double step, int window, int same_label, long long m, int* lin, double* tangent, int* table,
                               const void* workspace, size_t ws_bytes, hipStream_t s);
 
+// ---- airway walls (airway_wall.hip): 64 FWHM rays in the section plane of every centreline point, one wave per point ------------
+int airway_wall_rays();
+int airway_wall_samples();
+int airway_wall_sweep_points();           // points one grid sweep takes (one wave each)
+void airway_wall_directions(double* out); // the committed table: (C_r, S_r) for r = 0 .. 63
+// one launch, no workspace, no synchronise; table / tangent: the rows of launch_cross_section_emit; codes and edges may be null
+int launch_airway_walls(const void* ct, int ct_dtype, const int* parsing, int n0, int n1, int n2, double s0, double s1, double s2,
+                        double step, double ray_step, int n_search, float min_contrast, int same_label, long long m, const int* table,
+                        const double* tangent, unsigned long long* mask, double* sums, unsigned char* codes, double* edges,
+                        hipStream_t s);
+
 // ---- soft skeleton / soft clDice loss / hard clDice counts (cldice.hip) -----------------------------------------------------
 // `volumes` independent (n0, n1, n2) volumes back to back; n = volumes n0 n1 n2 voxels.  A forward that keeps no state needs
 // the two E buffers only.  A saving forward (the loss's prediction branch) also fills the chains the backward reads; the

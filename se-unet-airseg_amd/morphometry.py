@@ -13,7 +13,12 @@ inscribed="physical")`` puts into the table; its tables equal tests/wall_distanc
 ``cross_sections`` (csrc/cross_section.hip) measures the lumen section perpendicular to the centreline at every
 labelled skeleton voxel, one wave per point: its sample count, five integer moments and the samples on the grid's rim, from which
 area and major / minor diameter follow on the host; ``branch_morphometry(..., cross_sections=True)`` reduces them per branch.  Its
-integer columns and its float64 tangents equal tests/cross_section_oracle.py bit for bit."""
+integer columns and its float64 tangents equal tests/cross_section_oracle.py bit for bit.
+
+``airway_walls`` (csrc/airway_wall.hip) reads the CT again: 64 rays in the section plane of every such point,
+one wave per point and one ray per lane, find the wall's inner and outer edge by the full-width-at-half-maximum rule; thickness,
+wall area percentage and ``AirwayWalls.pi10`` follow on the host, ``branch_morphometry(..., walls=)`` reduces them per branch.  Its
+mask, codes, edges and sums equal tests/airway_wall_oracle.py bit for bit."""
 from __future__ import annotations
 
 import ctypes as C
@@ -304,14 +309,15 @@ class CrossSections:
         return out
 
 
-def _cross_sections(vol, skel, s, step: float, window: int, same_label: bool, num: int) -> CrossSections:
-    """``cross_sections`` for device inputs and parameters that are already checked."""
+def _cross_sections(vol, skel, s, step: float, window: int, same_label: bool, num: int, keep: bool = False):
+    """``cross_sections`` for device inputs and parameters that are already checked.  ``keep``: -> (CrossSections, the device
+    buffer of its rows: 3 m words of tangents, then 6 m words of table rows; None without a point)."""
     lib = _lib.load()
     cap = int(lib.seunet_label_stats_max_num())
     if not 0 <= num <= cap:
         raise ValueError(f"{_PREFIX}: labels up to {cap} are supported, got num = {num}")
     shape = tuple(int(v) for v in vol.shape)
-    m, host = 0, None
+    m, host, buf = 0, None, None
     if vol.numel():
         dev = vol.device
         with torch.cuda.device(dev):
@@ -338,8 +344,9 @@ def _cross_sections(vol, skel, s, step: float, window: int, same_label: bool, nu
     else:
         tangent = host[:3 * m].view(np.float64).reshape(m, 3).copy()
         table = host[3 * m:9 * m].view(np.int32).reshape(m, 12)
-    return CrossSections.from_columns(table[:, 0:3].copy(), table[:, 3].copy(), table[:, 4].copy(), tangent, table[:, 5].copy(),
-                                      table[:, 6:11].copy(), table[:, 11].copy(), step, num, s, window, same_label)
+    sections = CrossSections.from_columns(table[:, 0:3].copy(), table[:, 3].copy(), table[:, 4].copy(), tangent, table[:, 5].copy(),
+                                          table[:, 6:11].copy(), table[:, 11].copy(), step, num, s, window, same_label)
+    return (sections, buf) if keep else sections
 
 
 def _section_args(spacing, step, window):
@@ -376,6 +383,256 @@ def cross_sections(parsing, skeleton, spacing: Sequence[float] = (1.0, 1.0, 1.0)
     if num is None:
         num = max(int(vol.max()), 0) if vol.numel() else 0
     return _cross_sections(vol, skel, s, step, window, bool(same_label), int(num))
+
+
+WALL_RAYS = 64                                               # rays per point, one per lane; bit r of ``mask`` = ray r
+WALL_CODES = ("measured", "no boundary", "no peak", "no inner contrast", "another lumen", "no outer contrast", "point not measured")
+WALL_COLUMNS = ("wall_sections", "wall_thickness_mean", "wall_thickness_median", "wall_area_percent_mean", "wall_area_percent_median")
+
+
+def _label_rows(label, valid, num):
+    """(rows, labels, start, n): the valid rows with a label in 1..num grouped by label (rows in their given order)."""
+    rows = np.flatnonzero(valid & (label >= 1) & (label <= num))
+    rows = rows[np.argsort(label[rows], kind="stable")]
+    labels, start, n = np.unique(label[rows], return_index=True, return_counts=True)
+    return rows, labels, start, n
+
+
+def _label_medians(values, rows, start, n):
+    """The median of ``values[rows]`` per group of ``_label_rows``."""
+    v = values[rows]
+    group = np.repeat(np.arange(start.size), n)
+    v = v[np.lexsort((v, group))]
+    return 0.5 * (v[start + (n - 1) // 2] + v[start + n // 2])
+
+
+@dataclasses.dataclass
+class AirwayWalls:
+    """One row per row of the ``CrossSections`` it was measured on.  From the device: ``mask`` uint64[m], bit r set when ray r was
+    measured; ``rays_valid`` int32[m], its popcount; ``sums`` float64[m, 6], the sums over the measured rays of rho_in, rho_out,
+    rho_in^2, rho_out^2, rho_out - rho_in and the peak value; with ``return_rays`` also ``codes`` uint8[m, 64] (``WALL_CODES``) and
+    ``edges`` float64[m, 64, 2] = (rho_in, rho_out), the distances of the wall's inner and outer half-maximum crossing from the
+    lumen centroid (None otherwise).  ``coord`` and ``label`` are the sections'.  float64 columns derived on the host with
+    n = ``rays_valid``, nan where n < ``min_rays``: ``inner_radius = sum rho_in / n``; ``outer_radius``; ``wall_thickness =
+    sum (rho_out - rho_in) / n``; ``inner_area = pi sum rho_in^2 / n``; ``outer_area``; ``wall_area = outer_area - inner_area``;
+    ``wall_area_percent = 100 wall_area / outer_area``; ``inner_perimeter = 2 pi inner_radius``; ``peak``, the mean peak value;
+    ``valid = n >= min_rays``.  Lengths are in the units of ``spacing``."""
+    num: int
+    spacing: Tuple[float, float, float]
+    step: float
+    ray_step: float
+    n_search: int
+    min_contrast: float
+    same_label: bool
+    min_rays: int
+    coord: np.ndarray
+    label: np.ndarray
+    mask: np.ndarray
+    rays_valid: np.ndarray
+    sums: np.ndarray
+    codes: Optional[np.ndarray]
+    edges: Optional[np.ndarray]
+    inner_radius: np.ndarray
+    outer_radius: np.ndarray
+    wall_thickness: np.ndarray
+    inner_area: np.ndarray
+    outer_area: np.ndarray
+    wall_area: np.ndarray
+    wall_area_percent: np.ndarray
+    inner_perimeter: np.ndarray
+    peak: np.ndarray
+    valid: np.ndarray
+
+    def __len__(self) -> int:
+        return int(self.label.shape[0])
+
+    def to_dict(self) -> dict:
+        return {f.name: getattr(self, f.name) for f in dataclasses.fields(self)}
+
+    @classmethod
+    def from_columns(cls, coord, label, mask, sums, codes=None, edges=None, num: Optional[int] = None,
+                     spacing: Sequence[float] = (1.0, 1.0, 1.0), step: float = 0.5, ray_step: Optional[float] = None, n_search: int = 10,
+                     min_contrast: float = 100.0, same_label: bool = True, min_rays: int = 32) -> "AirwayWalls":
+        """The derived columns from the device's; host only."""
+        if int(min_rays) != min_rays or not 1 <= int(min_rays) <= WALL_RAYS:
+            raise ValueError(f"{_PREFIX}: min_rays must be an integer in 1..{WALL_RAYS}, got {min_rays!r}")
+        label = np.asarray(label, dtype=np.int32).reshape(-1)
+        m = label.size
+        mask = np.ascontiguousarray(mask, dtype=np.uint64).reshape(m)
+        sums = np.asarray(sums, dtype=np.float64).reshape(m, 6)
+        n = np.unpackbits(mask.view(np.uint8).reshape(m, 8), axis=1).sum(axis=1).astype(np.int32)
+        valid = n >= int(min_rays)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            c = n.astype(np.float64)
+            inner_radius, outer_radius, thickness = sums[:, 0] / c, sums[:, 1] / c, sums[:, 4] / c
+            inner_area, outer_area, peak = np.pi * sums[:, 2] / c, np.pi * sums[:, 3] / c, sums[:, 5] / c
+            wall_area = outer_area - inner_area
+            percent = 100.0 * wall_area / outer_area
+            perimeter = 2.0 * np.pi * inner_radius
+        cols = [np.where(valid, v, np.nan) for v in (inner_radius, outer_radius, thickness, inner_area, outer_area, wall_area, percent,
+                                                     perimeter, peak)]
+        return cls(int(label.max()) if num is None and m else int(num or 0), tuple(float(v) for v in spacing), float(step),
+                   float(step if ray_step is None else ray_step), int(n_search), float(min_contrast), bool(same_label), int(min_rays),
+                   np.asarray(coord, dtype=np.int32).reshape(m, 3), label, mask, n, sums,
+                   None if codes is None else np.asarray(codes, dtype=np.uint8).reshape(m, WALL_RAYS),
+                   None if edges is None else np.asarray(edges, dtype=np.float64).reshape(m, WALL_RAYS, 2), *cols, valid)
+
+    def per_branch(self, num: Optional[int] = None) -> Dict[str, np.ndarray]:
+        """Per label 1..num (row k - 1 = label k) over its ``valid`` rows: ``wall_sections`` int64[num]; ``wall_thickness_mean``,
+        ``wall_thickness_median``, ``wall_area_percent_mean``, ``wall_area_percent_median`` float64[num], nan for a label without
+        one."""
+        num = self.num if num is None else int(num)
+        out = {"wall_sections": np.zeros(num, np.int64)}
+        for k in WALL_COLUMNS[1:]:
+            out[k] = np.full(num, np.nan, np.float64)
+        rows, labels, start, n = _label_rows(self.label, self.valid, num)
+        if rows.size == 0:
+            return out
+        at = labels - 1
+        out["wall_sections"][at] = n
+        out["wall_thickness_mean"][at] = np.add.reduceat(self.wall_thickness[rows], start) / n
+        out["wall_thickness_median"][at] = _label_medians(self.wall_thickness, rows, start, n)
+        out["wall_area_percent_mean"][at] = np.add.reduceat(self.wall_area_percent[rows], start) / n
+        out["wall_area_percent_median"][at] = _label_medians(self.wall_area_percent, rows, start, n)
+        return out
+
+    def pi10(self, perimeter_range: Sequence[float] = (6.0, 20.0)) -> Dict[str, float]:
+        """Pi10: the square root of the wall area of a hypothetical airway with an inner perimeter of 10 (in the units of
+        ``spacing``: millimetres).  The least-squares line of ``sqrt(median wall_area)`` on ``median inner_perimeter`` over the
+        branches (labels, over their valid rows) whose median perimeter lies in ``perimeter_range`` (ends included) ->
+        ``{"intercept", "slope", "pi10": intercept + 10 slope, "branches"}``; nan with fewer than two branches, or when they all
+        have the same perimeter."""
+        lo, hi = (float(v) for v in perimeter_range)
+        nan = {"intercept": float("nan"), "slope": float("nan"), "pi10": float("nan"), "branches": 0}
+        rows, _, start, n = _label_rows(self.label, self.valid, max(self.num, int(self.label.max()) if len(self) else 0))
+        if rows.size == 0:
+            return nan
+        x = _label_medians(self.inner_perimeter, rows, start, n)
+        y = np.sqrt(np.maximum(_label_medians(self.wall_area, rows, start, n), 0.0))
+        keep = (x >= lo) & (x <= hi) & np.isfinite(y)
+        x, y = x[keep], y[keep]
+        nan["branches"] = int(x.size)
+        if x.size < 2:
+            return nan
+        dx = x - x.mean()
+        sxx = float((dx * dx).sum())
+        if sxx == 0.0:
+            return nan
+        slope = float((dx * (y - y.mean())).sum() / sxx)
+        intercept = float(y.mean() - slope * x.mean())
+        return {"intercept": intercept, "slope": slope, "pi10": intercept + 10.0 * slope, "branches": int(x.size)}
+
+
+def _ct_in(ct, vol):
+    """The CT argument -> an int16 or float32 CUDA tensor of ``vol``'s shape, used where it lies when it is contiguous."""
+    if isinstance(ct, np.ndarray):
+        if ct.dtype not in (np.int16, np.float32):
+            raise TypeError(f"{_PREFIX}: `ct` has dtype {ct.dtype}; expected int16 or float32")
+        ct = torch.from_numpy(np.ascontiguousarray(ct)).to(vol.device)
+    if not isinstance(ct, torch.Tensor) or not ct.is_cuda:
+        raise RuntimeError(f"{_PREFIX}: `ct` must be a CUDA tensor resident on the GPU (there is no CPU path)")
+    if ct.dtype not in (torch.int16, torch.float32):
+        raise TypeError(f"{_PREFIX}: `ct` has dtype {ct.dtype}; expected int16 or float32")
+    if tuple(ct.shape) != tuple(vol.shape):
+        raise ValueError(f"{_PREFIX}: `ct` shape {tuple(ct.shape)} differs from `parsing`'s {tuple(vol.shape)}")
+    if ct.device != vol.device:
+        raise ValueError(f"{_PREFIX}: `ct` is on {ct.device}, `parsing` on {vol.device}")
+    return ct.contiguous()
+
+
+def wall_search(ray_step: float, max_wall: float) -> int:
+    """``n_search``: the smallest integer n with ``n * ray_step >= max_wall``; ValueError outside 1..31."""
+    ray_step, max_wall = float(ray_step), float(max_wall)
+    if not (np.isfinite(ray_step) and ray_step > 0):
+        raise ValueError(f"{_PREFIX}: ray_step must be positive and finite, got {ray_step}")
+    if not (np.isfinite(max_wall) and max_wall > 0):
+        raise ValueError(f"{_PREFIX}: max_wall must be positive and finite, got {max_wall}")
+    ratio = max_wall / ray_step
+    if not ratio < 64:
+        raise ValueError(f"{_PREFIX}: max_wall / ray_step = {ratio:g}: the wall is searched over 1..31 samples")
+    n = int(np.ceil(ratio))
+    while n > 0 and (n - 1) * ray_step >= max_wall:
+        n -= 1
+    while n * ray_step < max_wall:
+        n += 1
+    if not 1 <= n <= 31:
+        raise ValueError(f"{_PREFIX}: max_wall / ray_step = {ratio:g}: the wall is searched over 1..31 samples, got n_search = {n}")
+    return n
+
+
+def airway_walls(ct, parsing, skeleton=None, spacing: Sequence[float] = (1.0, 1.0, 1.0), sections: Optional[CrossSections] = None,
+                 ray_step: Optional[float] = None, max_wall: Optional[float] = None, min_contrast: float = 100.0, min_rays: int = 32,
+                 return_rays: bool = False) -> AirwayWalls:
+    """The airway wall at every centreline point, from the CT: ``AirwayWalls``, one row per row of ``sections``.
+
+    From the centroid of a point's lumen section 64 rays are cast in the section plane; along each the CT is sampled every
+    ``ray_step`` (``None``: the sections' step) by trilinear interpolation, and ``parsing`` by nearest voxel.  A ray finds where it
+    leaves the lumen, the brightest sample within ``max_wall`` (``None``: ``5 min(spacing)``) of it, and the half-maximum crossings
+    on both sides of that peak: the wall's inner and outer edge.  A ray is dropped when it finds no boundary or peak, when either
+    side of the peak is less than ``min_contrast`` above the darkest sample on that side (an abutting vessel), or when it meets
+    another labelled voxel on the way out (a junction, a neighbouring airway).  A point whose section is empty or cut by the sample
+    grid is not measured; a point with fewer than ``min_rays`` measured rays has nan columns.  The exact definition, operation by
+    operation, is include/seunet_hip.h and tests/airway_wall_oracle.py.
+
+    ``ct``: int16 or float32, the shape of ``parsing`` (``preprocess_ct``'s ``data_cut``; a constant shift moves an edge by float32 rounding only);
+    ``sections``: a ``CrossSections`` of the same volume and ``spacing``, whose rows are uploaded in one copy and whose ``same_label``
+    the rays follow; ``None`` computes it from ``skeleton`` with the defaults of ``branch_morphometry(cross_sections=True)`` and uses
+    its device buffer where it lies.  One launch for all points and rays, and the call ends in one copy back.  ``return_rays`` adds
+    ``codes`` and ``edges``.  CUDA tensors or numpy arrays; the inputs are not modified.  ValueError: mismatched shapes, a bad
+    ``spacing``, ``ray_step``, ``max_wall`` (``n_search`` outside 1..31), ``min_contrast`` or ``min_rays``."""
+    s = prep.normalize_sampling(spacing, "spacing")
+    if sections is not None and not isinstance(sections, CrossSections):
+        raise TypeError(f"{_PREFIX}: sections must be None or a CrossSections, got {type(sections).__name__}")
+    if sections is None and skeleton is None:
+        raise ValueError(f"{_PREFIX}: airway_walls needs `sections` or the skeleton to compute them from")
+    mc = float(np.float32(min_contrast))
+    if not (np.isfinite(mc) and mc > 0):
+        raise ValueError(f"{_PREFIX}: min_contrast must be positive and finite in float32, got {min_contrast}")
+    if int(min_rays) != min_rays or not 1 <= int(min_rays) <= WALL_RAYS:
+        raise ValueError(f"{_PREFIX}: min_rays must be an integer in 1..{WALL_RAYS}, got {min_rays!r}")
+    vol, skel, _, _ = _inputs(parsing, skeleton if sections is None else None, None)
+    vox = _ct_in(ct, vol)
+    rows = None
+    if sections is None:
+        num = max(int(vol.max()), 0) if vol.numel() else 0
+        sections, rows = _cross_sections(vol, skel, *_section_args(s, None, 4), True, num, keep=True)
+    elif tuple(sections.spacing) != s:
+        raise ValueError(f"{_PREFIX}: `sections` were measured with spacing {tuple(sections.spacing)}, not {s}")
+    dr = sections.step if ray_step is None else float(ray_step)
+    n = wall_search(dr, 5.0 * min(s) if max_wall is None else max_wall)
+    m = len(sections)
+    mask, sums = np.zeros(m, np.uint64), np.zeros((m, 6), np.float64)
+    codes = np.zeros((m, WALL_RAYS), np.uint8) if return_rays else None
+    edges = np.zeros((m, WALL_RAYS, 2), np.float64) if return_rays else None
+    if m:
+        if not vol.numel():
+            raise ValueError(f"{_PREFIX}: `sections` has {m} rows but the volume is empty")
+        lib = _lib.load()
+        dev = vol.device
+        with torch.cuda.device(dev):
+            if rows is None:                                  # the one upload: tangents (3 m words), then table rows (6 m words)
+                host = np.empty(9 * m, np.int64)
+                host[:3 * m].view(np.float64)[:] = sections.tangent.reshape(-1)
+                table = host[3 * m:].view(np.int32).reshape(m, 12)
+                table[:, 0:3], table[:, 3], table[:, 4], table[:, 5] = sections.coord, sections.label, sections.support, sections.count
+                table[:, 6:11], table[:, 11] = sections.moments, sections.rim
+                rows = torch.from_numpy(host).to(dev)
+            # one buffer of 8-byte words: mask (m), sums (6 m), then edges (128 m) and codes (8 m) where they are wanted
+            buf = torch.empty(7 * m + (136 * m if return_rays else 0), dtype=torch.int64, device=dev)
+            base = buf.data_ptr()
+            _lib.check(lib.seunet_airway_walls(vox.data_ptr(), 0 if vox.dtype == torch.int16 else 1, vol.data_ptr(),
+                                               *(int(v) for v in vol.shape), s[0], s[1], s[2], sections.step, dr, n, mc,
+                                               int(sections.same_label), m, rows.data_ptr() + 8 * 3 * m, rows.data_ptr(), base,
+                                               base + 8 * m, base + 8 * 135 * m if return_rays else None,
+                                               base + 8 * 7 * m if return_rays else None, _lib.stream_ptr()), "airway_walls")
+            host = buf.cpu().numpy()                          # the one copy back
+        mask = host[:m].view(np.uint64).copy()
+        sums = host[m:7 * m].view(np.float64).reshape(m, 6).copy()
+        if return_rays:
+            edges = host[7 * m:135 * m].view(np.float64).reshape(m, WALL_RAYS, 2).copy()
+            codes = host[135 * m:].view(np.uint8).reshape(m, WALL_RAYS).copy()
+    return AirwayWalls.from_columns(sections.coord, sections.label, mask, sums, codes, edges, sections.num, s, sections.step, dr, n, mc,
+                                    sections.same_label, int(min_rays))
 
 
 def branch_tree(counts, adjacency) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -463,19 +720,27 @@ class BranchTable:
     area_median: Optional[np.ndarray] = None
     diameter_major_mean: Optional[np.ndarray] = None
     diameter_minor_mean: Optional[np.ndarray] = None
+    wall_sections: Optional[np.ndarray] = None
+    wall_thickness_mean: Optional[np.ndarray] = None
+    wall_thickness_median: Optional[np.ndarray] = None
+    wall_area_percent_mean: Optional[np.ndarray] = None
+    wall_area_percent_median: Optional[np.ndarray] = None
 
     def to_dict(self) -> dict:
-        """Every column by name; the cross-section columns only where they were computed, so the keys without them are unchanged."""
+        """Every column by name; the cross-section and airway-wall columns only where they were computed, so the keys without them
+        are unchanged."""
         return {f.name: getattr(self, f.name) for f in dataclasses.fields(self)
-                if f.name not in SECTION_COLUMNS or getattr(self, f.name) is not None}
+                if f.name not in SECTION_COLUMNS + WALL_COLUMNS or getattr(self, f.name) is not None}
 
     @classmethod
     def from_stats(cls, stats: Dict[str, np.ndarray], adjacency, spacing: Sequence[float] = (1.0, 1.0, 1.0),
-                   wall: Optional[Dict[str, np.ndarray]] = None, sections: Optional["CrossSections"] = None) -> "BranchTable":
+                   wall: Optional[Dict[str, np.ndarray]] = None, sections: Optional["CrossSections"] = None,
+                   walls: Optional["AirwayWalls"] = None) -> "BranchTable":
         """The derived columns from the integer tables of ``branch_stats`` and a (num, num) face adjacency; host only.  ``wall``: the
         tables of ``branch_wall_distance`` for the same ``spacing``; the inscribed radii are then ``sqrt((s0^2 sum d0^2 + s1^2 sum d1^2
         + s2^2 sum d2^2) / wall_count)``, ``sqrt(wall_sq_min)`` and ``sqrt(wall_sq_max)``, nan where ``wall_count`` is 0.
-        ``sections``: a ``CrossSections`` of the same volume; its ``per_branch`` columns are added (None otherwise)."""
+        ``sections``: a ``CrossSections`` of the same volume; its ``per_branch`` columns are added (None otherwise).  ``walls``: an
+        ``AirwayWalls`` of the same volume, likewise."""
         s = np.asarray(spacing, dtype=np.float64).reshape(3)
         if not (np.all(np.isfinite(s)) and np.all(s > 0)):
             raise ValueError(f"{_PREFIX}: spacing must be three positive numbers, got {tuple(spacing)}")
@@ -509,11 +774,12 @@ class BranchTable:
                    radius_inscribed_min=rmin, radius_inscribed_max=rmax, parent=parent, generation=generation, n_children=n_children,
                    is_leaf=is_leaf, n_branches=int((voxels > 0).sum()), n_leaves=int(is_leaf.sum()), total_length=float(length.sum()),
                    max_generation=max_generation, branches_per_generation=per_generation, **(wall or {}),
-                   **(sections.per_branch(num) if sections is not None else {}))
+                   **(sections.per_branch(num) if sections is not None else {}),
+                   **(walls.per_branch(num) if walls is not None else {}))
 
 
 def branch_morphometry(parsing, skeleton=None, spacing: Sequence[float] = (1.0, 1.0, 1.0), num: Optional[int] = None,
-                       sqdist=None, inscribed: str = "voxel", cross_sections=None) -> BranchTable:
+                       sqdist=None, inscribed: str = "voxel", cross_sections=None, walls: Optional[AirwayWalls] = None) -> BranchTable:
     """The per-branch table of a ``parsing`` volume (``tree_parsing`` or ``airway_parse``): ``BranchTable``.
 
     ``volume = voxels * s0 s1 s2``; ``centroid = coord_sum / voxels * spacing`` (nan for a label without voxels);
@@ -537,6 +803,9 @@ def branch_morphometry(parsing, skeleton=None, spacing: Sequence[float] = (1.0, 
     ``area_min``, ``area_max``, ``area_median``, ``diameter_major_mean`` and ``diameter_minor_mean`` (nan for a label without a valid
     section; None by default).
 
+    ``walls``: an ``AirwayWalls`` of the same volume (``airway_walls``); the table then carries, per label over its valid rows,
+    ``wall_sections``, ``wall_thickness_mean`` / ``_median`` and ``wall_area_percent_mean`` / ``_median`` (None by default).
+
     ``skeleton=None`` thins ``parsing != 0`` with ``skeletonize_3d``; ``sqdist=None`` takes the squared EDT of ``parsing != 0`` (a
     volume without a background voxel has none: ValueError).  ``num=None``: ``int(parsing.max())``.  CUDA tensors or numpy arrays in,
     numpy columns out; the inputs are not modified."""
@@ -548,6 +817,8 @@ def branch_morphometry(parsing, skeleton=None, spacing: Sequence[float] = (1.0, 
     s = prep.normalize_sampling(spacing, "spacing") if physical else None
     if cross_sections is not None and cross_sections is not True and not isinstance(cross_sections, CrossSections):
         raise TypeError(f"{_PREFIX}: cross_sections must be None, True or a CrossSections, got {type(cross_sections).__name__}")
+    if walls is not None and not isinstance(walls, AirwayWalls):
+        raise TypeError(f"{_PREFIX}: walls must be None or an AirwayWalls, got {type(walls).__name__}")
     vol, skel, sq, _ = _inputs(parsing, skeleton, sqdist)
     if num is None:
         num = max(int(vol.max()), 0) if vol.numel() else 0
@@ -567,4 +838,4 @@ def branch_morphometry(parsing, skeleton=None, spacing: Sequence[float] = (1.0, 
     sections = cross_sections
     if sections is True:
         sections = _cross_sections(vol, skel, *_section_args(spacing, None, 4), True, num)
-    return BranchTable.from_stats(stats, adjacency[1:, 1:], spacing, wall, sections)
+    return BranchTable.from_stats(stats, adjacency[1:, 1:], spacing, wall, sections, walls)
