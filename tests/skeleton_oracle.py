@@ -9,7 +9,12 @@ Definition.  The volume is padded with one layer of background.  One pass is six
 sub-iteration every voxel is first judged on the image as it stands: it is a candidate when it is foreground (a), its
 d-neighbour is background (b), it does not have exactly one foreground 26-neighbour (c), removing it keeps the Euler
 characteristic (d) and its foreground 26-neighbours form exactly one 26-connected component (e).  Then the candidates are
-visited in raster order, and one is deleted iff (e) still holds on the image with the deletions made so far."""
+visited in raster order, and one is deleted iff (e) still holds on the image with the deletions made so far.
+
+skeletonize() is that definition word for word.  skeletonize_memo() is the same definition for volumes of tens of thousands of
+voxels: neighbourhoods as 27-bit integers, the verdicts of euler_delta / neighbour_components remembered per integer.  It also
+numbers the re-check rounds in which csrc/skeleton.hip would decide each candidate (round_model) and runs re-checks that are
+wrong on purpose, so that tests/test_skeleton_host.py can show what each test volume is able to tell apart."""
 import hashlib
 import itertools
 
@@ -98,6 +103,168 @@ def skeletonize(volume, recheck: str = "raster"):
         if deleted == 0:
             break
     return img[1:-1, 1:-1, 1:-1].astype(np.uint8), passes
+
+
+# ---- the same definition, fast enough for 50 000 voxels -----------------------------------------------------------------------
+# A neighbourhood is a 27-bit integer, bit a*9 + b*3 + c for the cell (a, b, c) of the 3x3x3 block.  The two verdicts a voxel
+# needs -- "candidate by (c), (d), (e)" and "(e) alone" -- are remembered per integer.  A verdict is computed by decoding the
+# integer back into a block and calling euler_delta / neighbour_components above, so the memo holds nothing but their answers.
+_CELL_BITS = [(a, b, c, a * 9 + b * 3 + c) for a, b, c in itertools.product(range(3), repeat=3)]
+_CENTRE = 1 << 13
+_BEFORE_IN_ROW = 1 << 12                                                 # the cell (1, 1, 0): the voxel before this one in its row
+_one_memo = {}
+_candidate_memo = {}
+
+# How csrc/skeleton.hip schedules the re-check ("Re-check in rounds"); round_model() counts in these units.
+ROUND_LAUNCHES = 32      # kRoundLaunches (skeleton.hip:34): rounds run as grid-wide launches of skel_round_kernel (:338-339)
+ROUND_WAVES = 2048 * 4   # round_blocks = min(word_blocks, 2048u) (:327) workgroups of 4 wavefronts, `waves` in skel_round_kernel
+                         # (:220-221): a sub-iteration with more candidate words runs the grid-stride loop a second time
+FINISH_WAVES = 16        # skel_finish_kernel (:227): 1024 threads, the `i += 16u` strides of its two loops (:237, :255)
+WORD = 64                # voxels of a row per word: one wavefront, one lane per voxel
+
+RECHECKS = ("raster", "none", "reverse", "late_unchecked", "late_dropped", "no_carry")
+
+
+def _block(code):
+    return np.array([(code >> b) & 1 for b in range(27)], dtype=bool).reshape(3, 3, 3)
+
+
+def _one_component(code) -> bool:
+    code &= ~_CENTRE
+    v = _one_memo.get(code)
+    if v is None:
+        v = _one_memo[code] = neighbour_components(_block(code)) == 1     # (e)
+    return v
+
+
+def _is_candidate(code) -> bool:
+    code &= ~_CENTRE
+    v = _candidate_memo.get(code)
+    if v is None:
+        v = _candidate_memo[code] = bin(code).count("1") != 1 and euler_delta(_block(code)) == 0 and _one_component(code)
+    return v
+
+
+class SubIteration:
+    """One sub-iteration as the kernels would schedule it (round_model)."""
+    __slots__ = ("pass_", "direction", "candidates", "words", "rounds", "open_words", "deleted")
+
+    def __repr__(self):
+        return (f"pass {self.pass_} direction {self.direction}: {self.candidates} candidates in {self.words} words, "
+                f"{self.rounds} rounds, {self.open_words} words open after round {ROUND_LAUNCHES}, {self.deleted} deleted")
+
+
+class Trace:
+    """What skeletonize_memo(volume, trace=Trace()) records: `subiterations`, one SubIteration per sub-iteration run, and per
+    voxel the LAST time it was a candidate: `kind` (0 never, 1 kept by the re-check, 2 deleted), `pass_`, `direction` and
+    `round` (the re-check round that decides it, see round_model)."""
+
+    def __init__(self):
+        self.subiterations = []
+        self.kind = self.pass_ = self.direction = self.round = None
+
+
+def skeletonize_memo(volume, recheck: str = "raster", trace: Trace = None):
+    """skeletonize() again: the same definition, raster order and return value (skeleton uint8 0/1, passes), with each 3x3x3
+    neighbourhood encoded as a 27-bit integer and the verdicts of euler_delta / neighbour_components memoised per integer.
+
+    `recheck` other than "raster" is wrong on purpose.  "none" and "reverse" as in skeletonize().  The other three are the ways
+    the kernels' round schedule could go wrong (each candidate's round is the one of round_model):
+      "late_unchecked"  a candidate of a round after ROUND_LAUNCHES is deleted without the re-check;
+      "late_dropped"    such a candidate is never deleted;
+      "no_carry"        the first voxel of a word is judged as if the last voxel of the word before it still had its value
+                        from the start of the sub-iteration (the carry `own_prev >> 63` of recheck_word dropped)."""
+    if recheck not in RECHECKS:
+        raise ValueError(f"recheck must be one of {RECHECKS}")
+    vol = np.asarray(volume)
+    if vol.ndim != 3:
+        raise ValueError("skeletonize_memo expects a 3-D volume")
+    shape = tuple(s + 2 for s in vol.shape)
+    img = np.zeros(shape, dtype=bool)
+    img[1:-1, 1:-1, 1:-1] = vol != 0
+    flat = img.reshape(-1)                                               # a view: the loops below index it by padded offset
+    s0, s1 = shape[1] * shape[2], shape[2]
+    around = np.array([(a - 1) * s0 + (b - 1) * s1 + (c - 1) for a, b, c, _ in _CELL_BITS])
+    weights = np.array([1 << bit for _, _, _, bit in _CELL_BITS], dtype=np.int64)
+    # the 12 raster-earlier neighbours in other rows: the plane before (9) and the row before in the own plane (3)
+    earlier_rows = np.array([-s0 + b * s1 + c for b in (-1, 0, 1) for c in (-1, 0, 1)] + [-s1 + c for c in (-1, 0, 1)])
+    rounds = np.zeros(flat.size, dtype=np.int32)                         # of this sub-iteration's candidates, 0 elsewhere
+    words_per_row = (vol.shape[2] + WORD - 1) // WORD
+    if trace is not None:
+        trace.kind, trace.pass_, trace.direction, trace.round = (np.zeros(flat.size, dtype=np.int32) for _ in range(4))
+    passes = 0
+    while True:
+        passes += 1
+        deleted = 0
+        for d in ORDER:
+            di, dj, dk = DIRECTIONS[d]
+            border = np.flatnonzero(flat & ~np.roll(flat, -(di * s0 + dj * s1 + dk)))   # (a), (b); the padding keeps the roll honest
+            codes = np.zeros(border.size, dtype=np.int64)
+            for off, w in zip(around, weights):
+                codes |= flat[border + off] * w
+            uniq, inverse = np.unique(codes, return_inverse=True)
+            verdict = np.array([_is_candidate(int(c)) for c in uniq], dtype=bool)
+            cand = border[verdict[inverse]] if border.size else border                # flatnonzero is raster order
+            k_of = cand % s1 - 1                                                      # index along the last axis, unpadded
+            for p, k in zip(cand.tolist(), k_of.tolist()):
+                r = int(rounds[p + earlier_rows].max()) + 1
+                before = int(rounds[p - 1])
+                if before:
+                    r = max(r, before + 1 if k % WORD == 0 else before)
+                rounds[p] = r
+            r_of = rounds[cand]
+            at_start = flat.copy() if recheck == "no_carry" else None
+            order = cand[::-1] if recheck == "reverse" else cand
+            gone = 0
+            kept = []
+            for p in order.tolist():
+                late = rounds[p] > ROUND_LAUNCHES
+                if recheck == "none" or (recheck == "late_unchecked" and late):
+                    ok = True
+                elif recheck == "late_dropped" and late:
+                    ok = False
+                else:
+                    code = int(flat[p + around] @ weights)
+                    if recheck == "no_carry" and (p % s1 - 1) % WORD == 0:
+                        code = (code & ~_BEFORE_IN_ROW) | (_BEFORE_IN_ROW if at_start[p - 1] else 0)
+                    ok = _one_component(code)
+                if ok:
+                    flat[p] = False
+                    gone += 1
+                else:
+                    kept.append(p)
+            deleted += gone
+            if trace is not None:
+                word_of = (cand // s1) * words_per_row + k_of // WORD
+                sub = SubIteration()
+                sub.pass_, sub.direction, sub.candidates, sub.deleted = passes, d, int(cand.size), gone
+                sub.words = int(np.unique(word_of).size)
+                sub.rounds = int(r_of.max()) if cand.size else 0
+                sub.open_words = int(np.unique(word_of[r_of > ROUND_LAUNCHES]).size)
+                trace.subiterations.append(sub)
+                trace.kind[cand] = 2
+                trace.kind[kept] = 1
+                trace.pass_[cand], trace.direction[cand], trace.round[cand] = passes, d, r_of
+            rounds[cand] = 0
+        if deleted == 0:
+            break
+    if trace is not None:
+        for name in ("kind", "pass_", "direction", "round"):
+            setattr(trace, name, getattr(trace, name).reshape(shape)[1:-1, 1:-1, 1:-1].copy())
+    return img[1:-1, 1:-1, 1:-1].astype(np.uint8), passes
+
+
+def round_model(volume):
+    """The sub-iterations of thinning `volume` as csrc/skeleton.hip would schedule them: a list of SubIteration with the
+    candidates, the words (64 voxels of a row) that hold candidates, the re-check rounds needed and the words still open after
+    ROUND_LAUNCHES rounds, which is what skel_finish_kernel starts from.
+
+    The round of a candidate: 1 + the largest round among the candidates in its 12 raster-earlier neighbours in other rows and,
+    for the first voxel of a word, the last voxel of the word before; the round of the candidate before it in its own word,
+    if that is larger (recheck_word walks a word's chain inside one round); 1 if there is none of these."""
+    t = Trace()
+    skeletonize_memo(volume, trace=t)
+    return t.subiterations
 
 
 def digest(skel) -> str:

@@ -39,7 +39,10 @@ def test_equals_the_oracle_bitwise(A, name):
 
 
 def test_word_aligned_rows_and_carries(A):
-    """A last axis of exactly two words: the carries at k = 63/64 and a full last word, on a dense random volume."""
+    """A last axis of exactly two words with a full last word, on a dense random volume: it exercises two-word rows.  It does
+    NOT pin the carry at k = 63/64 of the re-check: the oracle with that carry dropped gives the same bits on this volume
+    (test_skeleton_host.py::test_the_dense_two_word_volume_does_not_see_the_carry).  The `plate` and `plate_noise` cases of
+    test_skeleton_rounds_gpu.py pin it."""
     v = (np.random.default_rng(7).random((5, 6, 128)) < 0.7).astype(np.uint8)
     want, passes = so.skeletonize(v)
     got, got_passes = A.skeletonize_3d(dev(v), return_passes=True)
